@@ -550,6 +550,23 @@ def side_legs(torch, fmrx, synth, args, pl, step, d_iq, n_bytes, stream) -> dict
     return legs
 
 
+DUMP_MAX_BLOCKS = 256               # --dump-outputs: at most 256 blocks x 20,480 float32 samples = 21 MB
+DUMP_SEED = 0x3D74
+
+
+def dump_outputs(path: str, pcm, blocks: int) -> None:
+    """--dump-outputs: the s16 PCM the timed call returned, as float32 [blocks, samples per block]; above
+    DUMP_MAX_BLOCKS blocks a fixed sample of DUMP_MAX_BLOCKS of them (seeded, sorted, indices stored beside)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    pcm = pcm.reshape(blocks, -1)
+    if blocks > DUMP_MAX_BLOCKS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(blocks, DUMP_MAX_BLOCKS, replace=False))
+        pcm = pcm[idx]
+        np.save(os.path.join(path, "pcm16_blocks.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "pcm16.npy"), pcm.astype(np.float32))
+
+
 def run_stub(args) -> int:
     """Test hook (tests/test_multiproc_cpu.py): the launcher, the rank environment and the timing /
     aggregation logic without a GPU -- a step is a sleep of stub_ms * (rank + 1)."""
@@ -590,8 +607,15 @@ def main() -> int:
     ap.add_argument("--dist-backend", default="gloo", choices=["gloo", "nccl"],
                     help="control-plane backend for N>1 (barrier + max of the elapsed time only; gloo: RCCL stays unused as the north star says)")
     ap.add_argument("--all-on-device0", action="store_true", help="rehearsal: every rank uses GPU 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's s16 PCM) as float32 "
+                         f"DIR/pcm16.npy, shape [blocks, {BLOCK_SAMPLES // 50}]: every block, or above {DUMP_MAX_BLOCKS} "
+                         f"blocks a fixed seeded sample of {DUMP_MAX_BLOCKS} (their indices in DIR/pcm16_blocks.npy, float64)")
     ap.add_argument("--stub-ms", type=float, default=0.0, help=argparse.SUPPRESS)   # test hook: see run_stub
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        print(json.dumps({"error": "--steps must be >= 1 and --warmup >= 0"}))
+        return 2
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
@@ -659,6 +683,8 @@ def main() -> int:
                            device="cuda" if args.dist_backend == "nccl" else "cpu",
                            on_start=ev[0].record, on_stop=ev[1].record)
     fe_ms = ev[0].elapsed_time(ev[1]) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_pcm.cpu().numpy(), B)
     fused = args.fe_variant == "mfma"
     if not fused:   # vector-ALU variant: the step is two kernels; the front end's share from the handle's event brackets
         pl.set_profiling(4)

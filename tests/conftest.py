@@ -29,6 +29,23 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def ref():
+    """The reference's answers to tests/test_oracle_vs_ref.py: stored in tests/golden/ref_calls.npz, and checked call
+    for call against oracle/_ref/libfmref.so where that is built.  FMRX_RECORD_REF=<path> records them from the
+    compiled reference instead (tests/golden/make_golden_ref.py)."""
+    from _oracle import RecordingRef, Ref, StoredRef
+    live = Ref() if Ref.available() else None
+    record = os.environ.get("FMRX_RECORD_REF")
+    if not record:
+        yield StoredRef(live=live)
+        return
+    assert live is not None, "FMRX_RECORD_REF needs oracle/_ref/libfmref.so"
+    rec = RecordingRef(live)
+    yield rec
+    rec.save(record)
+
+
+@pytest.fixture(scope="session")
+def compiled_ref():
     from _oracle import Ref
     if not Ref.available():
         pytest.skip("oracle/_ref/libfmref.so not built (reference sources absent)")

@@ -71,3 +71,56 @@ def test_bench_json_contract(fmrx):
     hb = out["legs"]["host_buffers"]
     assert "error" not in hb and hb["h2d_GBs"] > 5 and hb["value"] > 1000, hb
     assert out["legs"]["cli_stdin_stdout"]["rc"] == 0 and out["legs"]["cli_stdin_stdout"]["output_bytes"] * 50 == out["legs"]["cli_stdin_stdout"]["input_bytes"]
+
+
+def test_dump_outputs_writes_every_block_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: the s16 PCM as float32 [blocks, 20480]; above bench.DUMP_MAX_BLOCKS blocks the same seeded sample of
+    blocks every time (indices beside it), at most 64 MB in all."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    per = bench.BLOCK_SAMPLES // 50
+    small = (np.arange(6 * per) % 65536 - 32768).astype(np.int16)
+    bench.dump_outputs(str(tmp_path / "s"), small, 6)
+    got = np.load(tmp_path / "s" / "pcm16.npy")
+    assert got.dtype == np.float32 and got.shape == (6, per) and np.array_equal(got.ravel(), small.astype(np.float32))
+    assert not (tmp_path / "s" / "pcm16_blocks.npy").exists()
+    blocks = 1024
+    big = (np.arange(blocks * per, dtype=np.int64) % 65536 - 32768).astype(np.int16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, blocks)
+    idx = np.load(tmp_path / "a" / "pcm16_blocks.npy")
+    got = np.load(tmp_path / "a" / "pcm16.npy")
+    assert idx.dtype == np.float64 and len(idx) == bench.DUMP_MAX_BLOCKS and np.all(np.diff(idx) > 0) and idx[-1] < blocks
+    assert got.shape == (bench.DUMP_MAX_BLOCKS, per)
+    assert np.array_equal(got, big.reshape(blocks, per)[idx.astype(np.int64)].astype(np.float32))
+    for f in ("pcm16.npy", "pcm16_blocks.npy"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+
+
+def test_bench_rejects_zero_steps():
+    rc, out, err = _run("--steps", "0")
+    assert rc != 0 and out is not None and "--steps" in out["error"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(fmrx, tmp_path):
+    """Two runs dump the same PCM, and it is what the oracle computes for the bench's stream (within 1 LSB, as smoke()).
+    Each step continues the stream with the same bytes, so the last step's output is the oracle's second pass over them."""
+    import numpy as np
+    from _oracle import Oracle
+    synth = __import__("software-defined-radio_amd.synth", fromlist=["synth_fm_u8"])
+    dumps = []
+    for d in ("a", "b"):
+        rc, out, err = _run("--steps", "3", "--warmup", "1", "--blocks", "8", "--settle-ms", "0", "--no-side-legs",
+                            "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d))
+        assert rc == 0 and out["steps"] == 3 and out["ms_per_step"] > 0, err
+        dumps.append(np.load(tmp_path / d / "pcm16.npy"))
+    assert dumps[0].shape == (8, 20480) and np.array_equal(dumps[0], dumps[1])
+    iq = np.tile(synth.synth_fm_u8(4 * 1_024_000, 2.4e6, seed=0x3D74), 2)
+    o = Oracle()
+    pl = o.pipeline(0, 1)
+    pl.process(iq)
+    want = o.pcm16(pl.process(iq)["audio"]).astype(np.int32)
+    assert np.abs(dumps[0].ravel().astype(np.int32) - want).max() <= 1
