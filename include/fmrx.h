@@ -65,7 +65,8 @@ FMRX_API int fmrx_device_count(void);
 /* select the device used by the host-pointer stage functions of this thread */
 FMRX_API int fmrx_set_device(int device);
 
-/* Run-time options (tuning and A/B knobs; none is needed in normal use).  The process-wide defaults are
+/* Run-time options (reference variants and A/B knobs; none is needed in normal use; any other name is rejected
+ * with FMRX_EINVAL).  The process-wide defaults are
  * the built-in values, overridden ONCE, when the library first needs them, by the environment variable
  * FMRX_<NAME IN CAPITALS>; fmrx_set_option changes the defaults afterwards.  A pipeline handle copies the
  * defaults when it is created and keeps its own set (fmrx_pipeline_set_option); the stage functions use the
@@ -80,22 +81,14 @@ FMRX_API int fmrx_set_device(int device);
  *                      complete when the call is made; the stages of consecutive calls then run on internal streams, a call
  *                      apart (1: the next call's front end under this call's PLL and output stage; 2: three lanes).  Outputs
  *                      stay complete in the order of the stream passed to the call; results are bit-identical.  Default 0
- *   "fe_wgs_per_cu"    cap on resident workgroups per CU of the front-end kernels (0 = auto)
- *   "pll_warmup", "pll_segment", "pll_head"   lane shape of the parallel-in-time PLL (-1 = built-in)
+ *   "pll_warmup", "pll_segment"               lane shape of the parallel-in-time PLL (-1 = built-in)
  *   "pll_start"        where the parallel PLL's lanes start: 1 (default) = the locked loop solved as a linear system of the
  *                      input's signs + 64 true steps, 0 = the block's initial state plus drift + 512 true steps
- *   "pll_align"        1 = lanes of the parallel PLL (pll_start 0) start on a multiple of the loop's period, 0 (default) = exactly pll_warmup early
  *   "pll_mode"         stereo PLL of the specialised pipeline: 0 = parallel in time, fast math (default),
  *                      1 = serial, fast math, 2 = serial, glibc's functions (cause-by-cause variants)
  *   "demod"            0 (default) = the C++ reference's discriminator fmDemod (src/filter.cpp:248-266); 1 = the Python model's
  *                      arctangent demodulator fmDemodArctan (model/fmSupportLib.py:502-531, float64 atan2 + unwrap): the pipeline
- *                      then runs its unfused kernels (front end -> IF stream -> arctan -> audio / stereo stages)
- *   "bank_streams"     fast stereo banks (fmrx_channels_create_ex, exact = 0): internal streams of a call: 3 (default) = front end |
- *                      band-pass pair + output stage | PLL lanes; 2 = the front end with the other wide kernels; 4 = the output stage apart too
- *   "bank_fused"       fast stereo banks: 1 = front end + band-pass pair in ONE kernel (f32 matrix cores; measured slower: default 0)
- *   "bank_fe_wgs", "bank_fe_wgs_fused"        workgroups per CU of the bank's matrix-core front end (1) / of the fused kernel (2)
- *   "fused_tune", "fe_mfma_tune"              ablation kernels (timing only, WRONG results): FMRX_EINVAL unless the
- *                                            library was built with -DFMRX_TUNING (make TUNING=1; never shipped) */
+ *                      then runs its unfused kernels (front end -> IF stream -> arctan -> audio / stereo stages) */
 FMRX_API int fmrx_set_option(const char *name, long value);
 FMRX_API int fmrx_get_option(const char *name, long *value);
 

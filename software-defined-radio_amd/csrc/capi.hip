@@ -52,22 +52,13 @@ bool option_ref(Options &o, const char *name, long **as_long, int **as_int)
     else if (n == "fe_variant") *as_int = &o.fe_variant;
     else if (n == "resample_l2") *as_int = &o.resample_l2;
     else if (n == "resample_exact") *as_int = &o.resample_exact;
-    else if (n == "fe_wgs_per_cu") *as_int = &o.fe_wgs_per_cu;
     else if (n == "pll_warmup") *as_int = &o.pll_warmup;
     else if (n == "pll_segment") *as_int = &o.pll_segment;
-    else if (n == "pll_head") *as_int = &o.pll_head;
     else if (n == "pll_start") *as_int = &o.pll_start;
-    else if (n == "pll_align") *as_int = &o.pll_align;
     else if (n == "pll_mode") *as_int = &o.pll_mode;
     else if (n == "demod") *as_int = &o.demod;
-    else if (n == "bank_streams") *as_int = &o.bank_streams;
-    else if (n == "bank_fe_wgs") *as_int = &o.bank_fe_wgs;
-    else if (n == "bank_fused") *as_int = &o.bank_fused;
-    else if (n == "bank_fe_wgs_fused") *as_int = &o.bank_fe_wgs_fused;
     else if (n == "resample_chains") *as_int = &o.resample_chains;
     else if (n == "overlap_calls") *as_int = &o.overlap_calls;
-    else if (n == "fused_tune") *as_int = &o.fused_tune;
-    else if (n == "fe_mfma_tune") *as_int = &o.fe_mfma_tune;
     else return false;
     return true;
 }
@@ -83,21 +74,11 @@ Options &default_options()
         if (const char *e = std::getenv("FMRX_RESAMPLE_EXACT")) d.resample_exact = std::atoi(e);
         if (const char *e = std::getenv("FMRX_RESAMPLE_CHAINS")) d.resample_chains = std::atoi(e);
         if (const char *e = std::getenv("FMRX_OVERLAP_CALLS")) d.overlap_calls = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_FE_WGS_PER_CU")) d.fe_wgs_per_cu = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_WARMUP")) d.pll_warmup = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_SEGMENT")) d.pll_segment = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_PLL_HEAD")) d.pll_head = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_START")) d.pll_start = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_PLL_ALIGN")) d.pll_align = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_MODE")) d.pll_mode = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_BANK_STREAMS")) d.bank_streams = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_BANK_FE_WGS")) d.bank_fe_wgs = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_BANK_FUSED")) d.bank_fused = std::atoi(e);
         if (const char *e = std::getenv("FMRX_DEMOD")) d.demod = std::strcmp(e, "arctan") == 0 ? 1 : std::atoi(e);
-#ifdef FMRX_TUNING
-        if (const char *e = std::getenv("FMRX_FUSED_TUNE")) d.fused_tune = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_FE_MFMA_TUNE")) d.fe_mfma_tune = std::atoi(e);
-#endif
         return d;
     }();
     return o;
@@ -120,10 +101,6 @@ int set_option_in(Options &o, const char *name, long value)
     long *pl = nullptr;
     int *pi = nullptr;
     if (!option_ref(o, name, &pl, &pi)) return fail(FMRX_EINVAL, "unknown option '%s'", name ? name : "(null)");
-#ifndef FMRX_TUNING
-    if ((pi == &o.fused_tune || pi == &o.fe_mfma_tune) && value != 0)
-        return fail(FMRX_EINVAL, "option '%s': ablation kernels exist only in a -DFMRX_TUNING build of libfmrx", name);
-#endif
     if (pi == &o.fe_variant && value != 0 && value != 1) return fail(FMRX_EINVAL, "option fe_variant: 0 (mfma) or 1 (valu)");
     if (pi == &o.pll_mode && (value < 0 || value > 2)) return fail(FMRX_EINVAL, "option pll_mode: 0, 1 or 2");
     if (pi == &o.demod && value != 0 && value != 1) return fail(FMRX_EINVAL, "option demod: 0 (the C++ reference's discriminator) or 1 (arctan)");
@@ -173,11 +150,7 @@ extern "C" {
 
 const char *fmrx_version(void)
 {
-#ifdef FMRX_TUNING
-    return "fmrx 0.3 (gfx950, TUNING build: ablation kernels included) src:" FMRX_SRC_HASH;
-#else
     return "fmrx 0.3 (gfx950) src:" FMRX_SRC_HASH;
-#endif
 }
 
 // The process-wide defaults may be changed by one thread while another creates a handle (which copies them): writers and the

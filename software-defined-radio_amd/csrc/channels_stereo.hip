@@ -860,8 +860,6 @@ struct StereoBank {
     DevBuf<uint8_t> slots;
     DevBuf<float> fe_table, bpf_table, out_table;
     FePlan fe;                      // fast banks: the matrix-core front end's tap image
-    DevBuf<float> st_img, car_img;  // fast banks: the band-pass filters' Toeplitz images for the f32 matrix cores (fe_bpf_bank_kernel)
-    bool fused_front = false;       // front end + band-pass pair in one kernel
     Options opt;
     DevBuf<float> demod, carrier, bpf, trig, pll, nco0, mixtail[2];
     DevBuf<int8_t> carrier8;        // fast banks: the sign of the pilot band-pass output, one byte per IF sample
@@ -883,11 +881,10 @@ struct StereoBank {
     int max_chunks = kMaxChunks;
     hipStream_t wide = nullptr, lanes = nullptr;
     hipStream_t front = nullptr;    // fast banks: the HBM-bound front end runs on its own stream, next to the vector-ALU-bound kernels
-    hipStream_t post = nullptr;     // fast banks, option bank_streams = 4: the output stage on a stream of its own too
     hipEvent_t ev_bpf[kMaxChunks] = {}, ev_pll[kMaxChunks] = {}, ev_fe[kMaxChunks] = {}, ev_fork = nullptr, ev_join = nullptr;
     ~StereoBank()
     {
-        for (hipStream_t st : {wide, lanes, front, post})
+        for (hipStream_t st : {wide, lanes, front})
             if (st) {
                 (void)hipStreamSynchronize(st);
                 (void)hipStreamDestroy(st);
@@ -1203,10 +1200,6 @@ int stereo_bank_create(StereoBank **out, const fmrx_params &p, int n_channels, i
 #define X(T_) if (p.stereo_taps == T_) FMRX_TRY(bpf_table_init<T_>(*b, hs.data(), hc.data()));
             CHS_BPF_CASES(X)
 #undef X
-            if (!b->exact && !b->resample && fe_bpf_bank_available(b->fe, p.stereo_taps)) {
-                FMRX_TRY(fe_bpf_tables_init(b->st_img, b->car_img, hs.data(), hc.data(), p.stereo_taps));
-                b->fused_front = true;
-            }
             if (b->exact) {
                 FMRX_TRY(b->carrier.alloc(b->ypitch * N + 64));
                 FMRX_HIP(hipMemset(b->carrier.p, 0, b->carrier.bytes()));
@@ -1234,7 +1227,6 @@ int stereo_bank_create(StereoBank **out, const fmrx_params &p, int n_channels, i
             FMRX_HIP(hipStreamCreateWithFlags(&b->wide, hipStreamNonBlocking));
             FMRX_HIP(hipStreamCreateWithFlags(&b->lanes, hipStreamNonBlocking));
             FMRX_HIP(hipStreamCreateWithFlags(&b->front, hipStreamNonBlocking));
-            FMRX_HIP(hipStreamCreateWithFlags(&b->post, hipStreamNonBlocking));
             for (auto &e : b->ev_fe) FMRX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             for (auto &e : b->ev_bpf) FMRX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             for (auto &e : b->ev_pll) FMRX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1293,8 +1285,7 @@ int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int w
     auto fe = [&](long k_lo, long k_hi, hipStream_t st) -> int {
         if (!b->exact)
             return fe_mfma_bank_launch(b->fe, b->slots.p, static_cast<long>(b->slots.n), static_cast<long>(b->slot_bytes),
-                                       static_cast<long>(b->hist_bytes), b->n_channels, k_lo, k_hi, b->demod.p, b->dpitch, b->Hd,
-                                       b->opt.bank_fe_wgs, st);
+                                       static_cast<long>(b->hist_bytes), b->n_channels, k_lo, k_hi, b->demod.p, b->dpitch, b->Hd, st);
 #define X(T_, D_) if (p.rf_taps == T_ && p.rf_decim == D_) return launch_fe<T_, D_>(*b, k_lo, k_hi, st);
         CHS_FE_CASES(X)
 #undef X
@@ -1328,19 +1319,14 @@ int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int w
         const int K = static_cast<int>((b->n_audio + per - 1) / per);
         hipStream_t sw = K > 1 ? b->wide : s, sl = K > 1 ? b->lanes : s;
         // fast banks: the front end is HBM-bound on the matrix cores, the band-pass pair and the output stage are bound by the
-        // vector ALUs: on two streams they run side by side (option bank_streams = 2: everything but the PLL on one stream)
-        const bool split = K > 1 && !b->exact && b->opt.bank_streams >= 3;
+        // vector ALUs: on two streams they run side by side
+        const bool split = K > 1 && !b->exact;
         hipStream_t sf = split ? b->front : sw;
-        // bank_streams = 4: the output stage (bound by the latency of its staging, not by the vector ALUs) on a fourth stream, next to
-        // the band-pass pair instead of behind it
-        const bool split_out = split && b->opt.bank_streams >= 4;
-        hipStream_t so = split_out ? b->post : sw;
         if (K > 1) {   // whatever the caller's stream did before the call (loading the slots, reading the last output) comes first
             FMRX_HIP(hipEventRecord(b->ev_fork, s));
             FMRX_HIP(hipStreamWaitEvent(sw, b->ev_fork, 0));
             FMRX_HIP(hipStreamWaitEvent(sl, b->ev_fork, 0));
             if (split) FMRX_HIP(hipStreamWaitEvent(sf, b->ev_fork, 0));
-            if (split_out) FMRX_HIP(hipStreamWaitEvent(so, b->ev_fork, 0));
         }
         // The output stage of chunk c follows the band-pass pair of chunk c + lag on the wide stream.  Exact banks: lag 1 (the PLL is
         // the longest stage; nothing on the wide stream is waited for).  Fast banks: lag 2 -- the PLL of chunk c starts when its
@@ -1356,31 +1342,18 @@ int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int w
             if (c < K) {
                 const long a_lo = c * per, a_hi = a_lo + per < b->n_audio ? a_lo + per : b->n_audio;
                 const long k_lo = if_of(a_lo), k_hi = if_of(a_hi);
-                const bool fused = b->fused_front && b->opt.bank_fused != 0;
-                if (fused) {
-                    // fast banks: front end + band-pass pair in ONE kernel (int8 + f32 matrix cores), on the front stream
-                    FMRX_TRY(fe_bpf_bank_launch(b->fe, p.stereo_taps, b->st_img.p, b->car_img.p, b->slots.p, static_cast<long>(b->slots.n),
-                                                static_cast<long>(b->slot_bytes), static_cast<long>(b->hist_bytes), b->n_channels, k_lo, k_hi,
-                                                b->demod.p, b->dpitch, b->Hd, b->bpf.p, b->ypitch, b->carrier8.p, b->cpitch,
-                                                b->opt.bank_fe_wgs_fused, sf));
-                    if (K > 1) {   // read-after-write: the PLL's lanes read the sign bytes this kernel wrote
-                        FMRX_HIP(hipEventRecord(b->ev_bpf[c], sf));
-                        FMRX_HIP(hipStreamWaitEvent(sl, b->ev_bpf[c], 0));
-                    }
-                } else {
-                    long fe_hi = (k_hi + fe_tile - 1) / fe_tile * fe_tile;
-                    if (fe_hi > b->n_if || c == K - 1) fe_hi = b->n_if;
-                    if (fe_hi > fe_done) FMRX_TRY(fe(fe_done, fe_hi, sf));
-                    fe_done = fe_hi;
-                    if (split) {   // read-after-write: the band-pass pair reads the discriminator rows the front end wrote on its own stream
-                        FMRX_HIP(hipEventRecord(b->ev_fe[c], sf));
-                        FMRX_HIP(hipStreamWaitEvent(sw, b->ev_fe[c], 0));
-                    }
-                    FMRX_TRY(bpf(k_lo, k_hi, sw));
-                    if (K > 1) {
-                        FMRX_HIP(hipEventRecord(b->ev_bpf[c], sw));
-                        FMRX_HIP(hipStreamWaitEvent(sl, b->ev_bpf[c], 0));
-                    }
+                long fe_hi = (k_hi + fe_tile - 1) / fe_tile * fe_tile;
+                if (fe_hi > b->n_if || c == K - 1) fe_hi = b->n_if;
+                if (fe_hi > fe_done) FMRX_TRY(fe(fe_done, fe_hi, sf));
+                fe_done = fe_hi;
+                if (split) {   // read-after-write: the band-pass pair reads the discriminator rows the front end wrote on its own stream
+                    FMRX_HIP(hipEventRecord(b->ev_fe[c], sf));
+                    FMRX_HIP(hipStreamWaitEvent(sw, b->ev_fe[c], 0));
+                }
+                FMRX_TRY(bpf(k_lo, k_hi, sw));
+                if (K > 1) {
+                    FMRX_HIP(hipEventRecord(b->ev_bpf[c], sw));
+                    FMRX_HIP(hipStreamWaitEvent(sl, b->ev_bpf[c], 0));
                 }
                 // fmPLL(carrier_filt, 19 kHz, if_Fs, ncoScale 2, phaseAdjust 0, normBandwidth 0.01): src/project.cpp:237
                 if (b->exact)
@@ -1396,14 +1369,14 @@ int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int w
             }
             if (c >= lag) {   // the output stage of an earlier chunk, behind this chunk's band-pass pair on the wide stream
                 const long a_lo = (c - lag) * per, a_hi = a_lo + per < b->n_audio ? a_lo + per : b->n_audio;
-                if (K > 1) FMRX_HIP(hipStreamWaitEvent(so, b->ev_pll[c - lag], 0));   // (the PLL followed this chunk's band-pass pair: both are done)
+                if (K > 1) FMRX_HIP(hipStreamWaitEvent(sw, b->ev_pll[c - lag], 0));   // (the PLL followed this chunk's band-pass pair: both are done)
                 // fast banks, modes 0/1: inside the output stage; the resampling modes materialise the mixer rows from finished NCO values
-                if (b->exact || b->resample) FMRX_TRY(launch_nco(*b, if_of(a_lo), if_of(a_hi), so));
-                FMRX_TRY(out(a_lo, a_hi, if_of(a_hi), so));
+                if (b->exact || b->resample) FMRX_TRY(launch_nco(*b, if_of(a_lo), if_of(a_hi), sw));
+                FMRX_TRY(out(a_lo, a_hi, if_of(a_hi), sw));
             }
         }
         if (K > 1) {
-            FMRX_HIP(hipEventRecord(b->ev_join, so));               // the last output stage follows everything else of the call
+            FMRX_HIP(hipEventRecord(b->ev_join, sw));               // the last output stage follows everything else of the call
             FMRX_HIP(hipStreamWaitEvent(s, b->ev_join, 0));
         }
         b->mix_cur ^= 1;

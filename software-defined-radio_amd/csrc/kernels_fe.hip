@@ -442,7 +442,7 @@ __global__ __launch_bounds__(256, (FeWaveCfg<T, D, R>::MINW)) void fe_demod_kern
 
 template <int T, int D, int R>
 int launch_fused(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, const uint8_t *d_hist, const float *d_prev_override,
-                 float *d_demod, float *d_if, float *d_prev_out, uint8_t *d_hist_next, const Options &o, hipStream_t stream)
+                 float *d_demod, float *d_if, float *d_prev_out, uint8_t *d_hist_next, hipStream_t stream)
 {
     using W = FeWaveCfg<T, D, R>;
     if (d_hist) d_hist += pl.hist_bytes - W::HBX;   // the kernel reads the last HBX bytes of the history
@@ -452,7 +452,6 @@ int launch_fused(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, const 
     long per_cu = (160 * 1024) / lds_wg;
     if (per_cu > 4) per_cu = 4;
     if (per_cu < 1) per_cu = 1;
-    if (o.fe_wgs_per_cu >= 1 && o.fe_wgs_per_cu < per_cu) per_cu = o.fe_wgs_per_cu;   // tuning knob
     const long want = (n_wtiles + 3) / 4;
     const unsigned grid = static_cast<unsigned>(want < 256 * per_cu ? want : 256 * per_cu);
     hipLaunchKernelGGL((fe_demod_kernel<T, D, R>), dim3(grid), dim3(256), static_cast<size_t>(lds_wg), stream, d_iq, d_hist,
@@ -575,7 +574,7 @@ int fe_demod_launch(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, con
 #define X(T_, D_) \
     if (pl.taps == T_ && pl.decim == D_) \
         return launch_fused<T_, D_, 8>(pl, d_iq, n_samples, d_hist, d_prev_override, d_demod, d_if, d_prev_out, \
-                                       d_hist_next, o, stream);
+                                       d_hist_next, stream);
     FMRX_FE_CASES(X)
 #undef X
     return fail(FMRX_EINVAL, "fe_demod_launch: no specialised kernel for taps=%d decim=%d", pl.taps, pl.decim);

@@ -426,17 +426,8 @@ __device__ __forceinline__ float pll_integ_tol(float base, const float *state, l
 constexpr int kSegThreads = 64;
 // seg[s*16 + 0..5]  state at the END of segment s      (after sample a_s + L - 1; fbI/fbQ/last finished)
 // seg[s*16 + 8..9]  (integ, phase) this lane had at the START of segment s (after its warm-up)
-//
-// Where a lane starts.  A locked loop is not just "near a constant": its phase carries the ripple of the
-// phase detector (a sawtooth per pilot half cycle, +-0.07 rad), and on a pilot that is on frequency that
-// ripple repeats with the pilot: every P = Fs / gcd(Fs, freq) samples (240 at 240 kHz: 19 pilot cycles)
-// the loop is in the same state again, up to its slow drift.  So a lane does not start "W samples early"
-// but at the last multiple of P (counted from the block start, where the true state is known) that is at
-// least W samples early, from the block's initial state plus the drift: its guess is then already within a
-// few grid steps of the true trajectory, and W only has to cover what the drift estimate misses (64
-// samples instead of the 768 it takes to forget a guess that ignores the ripple).  P = 0: no alignment.
 __global__ __launch_bounds__(kSegThreads) void pll_segments_kernel(const float *__restrict__ in, long n, float *__restrict__ out,
-                                    const float *__restrict__ state, PllCoef c, int L, int W, int P, long nseg,
+                                    const float *__restrict__ state, PllCoef c, int L, int W, long nseg,
                                     float *__restrict__ seg, float *hdr, const double *__restrict__ lti_rec,
                                     const double *__restrict__ lti_wgtot, unsigned long long *__restrict__ badmask,
                                     float tol_phase_base, float tol_integ_base)
@@ -453,11 +444,7 @@ __global__ __launch_bounds__(kSegThreads) void pll_segments_kernel(const float *
     const long sgc = sg < nseg ? sg : nseg - 1;
     const long a = sgc * L;
     const long b = a + L < n ? a + L : n;
-    long k = 0;
-    if (a > W) {
-        k = a - W;
-        if (P > 0) k -= k % P;
-    }
+    long k = a > W ? a - W : 0;                                // a lane starts W samples early
     typedef float f4 __attribute__((ext_vector_type(4)));
     const f4 *in4 = reinterpret_cast<const f4 *>(in);
     const long last4 = (n + 3) / 4 + 1;                   // last group that is safe to read (floats up to n+10)
@@ -996,14 +983,6 @@ int k_fm_pll_parallel(const float *d_in, size_t n, float *d_out, float *d_state,
         return k_fm_pll(d_in, n, d_out, d_state, freq, Fs, ncoScale, phaseAdjust, normBandwidth, 1, s);
     }
     PllCoef c = make_coef(freq, Fs, ncoScale, phaseAdjust, normBandwidth);
-    // the loop's state repeats every P samples on an on-frequency pilot: Fs / gcd(Fs, freq), when both are whole Hz
-    int P = 0;
-    if (o.pll_align != 0 && !lti && Fs == static_cast<float>(static_cast<long>(Fs)) && freq == static_cast<float>(static_cast<long>(freq)) && freq > 0) {
-        long x = static_cast<long>(Fs), y = static_cast<long>(freq);
-        while (y) { const long t = x % y; x = y; y = t; }
-        const long p = static_cast<long>(Fs) / x;
-        if (p > 0 && p <= 4096 && p % 4 == 0) P = static_cast<int>(p);
-    }
     const long nseg = static_cast<long>((n + L - 1) / L);
     // scratch: [2] repaired-segment counter (u32), [3],[4] largest accepted |dphase|,|dinteg| (diagnostics),
     // [5..7] previous call's start phase / length / valid; [8..] per-segment records, then the mismatch bitmask
@@ -1029,7 +1008,7 @@ int k_fm_pll_parallel(const float *d_in, size_t n, float *d_out, float *d_state,
         lti_wgtot = wgtot;
     }
     if (!(phases & 2)) return FMRX_OK;
-    hipLaunchKernelGGL(pll_segments_kernel, dim3(grid), dim3(kSegThreads), 0, s, d_in, static_cast<long>(n), d_out, d_state, c, L, W, P,
+    hipLaunchKernelGGL(pll_segments_kernel, dim3(grid), dim3(kSegThreads), 0, s, d_in, static_cast<long>(n), d_out, d_state, c, L, W,
                        nseg, seg, d_scratch, lti_rec, lti_wgtot, badmask, kPllTolPhase, kPllTolInteg);
     FMRX_LAUNCH_CHECK("pll_segments");
     hipLaunchKernelGGL(pll_repair_kernel, dim3(1), dim3(kRepairThreads), 0, s, d_in, static_cast<long>(n), d_out, d_state, c, L, nseg, seg,

@@ -599,10 +599,7 @@ int fmrx_pipeline_process_dev(fmrx_pipeline *pl, const uint8_t *d_iq, size_t n_b
             // a stream's first block starts unlocked: walk its first samples serially so that the
             // segment lanes extrapolate from a locked state; later blocks start locked already
             size_t head = 0;
-            if (!pl->pll_warm) {
-                const size_t head_len = pl->opt.pll_head >= 0 ? static_cast<size_t>(pl->opt.pll_head) : kPllHead;
-                head = n_if < head_len ? n_if : head_len;
-            }
+            if (!pl->pll_warm) head = n_if < static_cast<size_t>(kPllHead) ? n_if : static_cast<size_t>(kPllHead);
             // what depends on the input alone (the linear system's chunk records) belongs to the front
             float *lti = ovl ? pl->lti_rec[cur].p : nullptr;
             if (ovl && n_if > head)

@@ -127,29 +127,27 @@ def test_bank_other_block_sizes(fmrx, oracle):
         fmrx.Channels(2, 4, audio_channels=2, exact=True, block_bytes=16160)     # 808 IF samples: a block must end on an output boundary (n_if * U % D == 0)
 
 
-@pytest.mark.parametrize("fused", [0, 1], ids=["two kernels", "front end + band-pass pair in one kernel"])
-def test_stereo_bank_fast_error_envelope(fmrx, oracle, fused):
+@pytest.mark.parametrize("N, per_call", [(24, 1), (65, 4)], ids=["24 receivers, one block per call", "65 receivers, four blocks per call"])
+def test_stereo_bank_fast_error_envelope(fmrx, oracle, N, per_call):
     """The FAST stereo bank (exact = 0: matrix-core front end, one fma per tap in the band-pass pair and the audio FIRs, the
     PLL's fast recurrence walked by one lane per channel) promises what the default single-stream path promises
     (tests/test_gpu_parity.py: ENVELOPE_FACTOR): per channel and 0.1 s window, audio RMS error <= max(1e-4, 0.06
     ulp(trigArg(t))) against the oracle, <= 1e-4 in the first window, mono sum (L+R)/2 <= 2e-6 throughout -- checked for
-    each of 24 receivers with distinct signals over 2.13 s, one call per reference block."""
+    each of N receivers with distinct signals over 2.13 s.  One reference block per call walks the call in two chunks;
+    four per call (bench.py's stereo_channels leg) in eight, output stage two chunks behind, front end on a stream of its
+    own, and 65 receivers take two PLL waves: the form in which the bank's cross-stream ordering is exercised."""
     from test_gpu_parity import ENVELOPE_FACTOR, stereo_error_envelope, trig_arg_ulp
     p = oracle.mode_params(0, 101, 101, 101)
-    N, nblk, bb = 24, 100, p.block_bytes
+    nblk, bb, na = 100 // per_call, per_call * p.block_bytes, per_call * 1024
     with ProcessPoolExecutor(max_workers=min(12, os.cpu_count() or 1)) as ex:
         res = sorted(ex.map(_oracle_channel, [(c, nblk, bb, float(p.rf_Fs)) for c in range(N)], chunksize=2), key=lambda r: r[0])
-    fmrx.set_option("bank_fused", fused)                    # a bank copies the process-wide options when it is created
-    try:
-        ch = fmrx.Channels(0, N, audio_channels=2, exact=False)
-    finally:
-        fmrx.set_option("bank_fused", 0)
-    L = np.zeros((N, nblk * 1024), np.float32)
-    R = np.zeros((N, nblk * 1024), np.float32)
+    ch = fmrx.Channels(0, N, audio_channels=2, exact=False, block_bytes=bb)
+    L = np.zeros((N, nblk * na), np.float32)
+    R = np.zeros((N, nblk * na), np.float32)
     for b in range(nblk):
         out = ch.process(np.stack([r[1][b * bb:(b + 1) * bb] for r in res]), want_pcm=(b == 0))
-        L[:, b * 1024:(b + 1) * 1024] = out["audio_l"]
-        R[:, b * 1024:(b + 1) * 1024] = out["audio_r"]
+        L[:, b * na:(b + 1) * na] = out["audio_l"]
+        R[:, b * na:(b + 1) * na] = out["audio_r"]
         if b == 0:
             # the fast bank's NCO tap (it keeps trigArg; the tap runs the NCO pass on a copy of the row): n_if + 1 values, PLL[0] = the
             # incoming state's lastOut, a 38 kHz cosine after lock
@@ -161,7 +159,7 @@ def test_stereo_bank_fast_error_envelope(fmrx, oracle, fused):
                 bits_equal(out["pcm16"][c, :, 0], oracle.pcm16(out["audio_l"][c]), f"pcm left, channel {c}")
                 bits_equal(out["pcm16"][c, :, 1], oracle.pcm16(out["audio_r"][c]), f"pcm right, channel {c}")
     win = 4800
-    t_end = (np.arange(nblk * 1024 // win) + 1) * 0.1
+    t_end = (np.arange(nblk * na // win) + 1) * 0.1
     bound = np.maximum(1e-4, ENVELOPE_FACTOR * trig_arg_ulp(t_end))
     worst = 0.0
     for c in range(N):

@@ -1,16 +1,20 @@
 #!/bin/bash
-# per-kernel split of a bank configuration: args are passed to tools/bank_bench.py
+# per-kernel split of a bank configuration: args are passed to tools/bank_bench.py (stops at the first failing step).
+# Output under $OUT_DIR (default build/prof_bank).
+set -eo pipefail
 export TMPDIR=/tmp
-rm -rf gpurun_out/prof_bank; mkdir -p gpurun_out/prof_bank
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_bank -o bank -- python3 tools/bank_bench.py "$@" > gpurun_out/prof_bank/run.log 2>&1 < /dev/null; echo rc=$?
-cat gpurun_out/prof_bank/run.log | grep channels
-python3 - <<'PY'
-import csv,glob
-for f in glob.glob('gpurun_out/prof_bank/**/*kernel_stats.csv', recursive=True):
+OUT=${OUT_DIR:-build/prof_bank}
+rm -rf "$OUT"; mkdir -p "$OUT"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o bank -- python3 tools/bank_bench.py "$@" > "$OUT/run.log" 2>&1 < /dev/null
+grep channels "$OUT/run.log"
+timeout -k 10 60 python3 - "$OUT" <<'PY'
+import csv,glob,sys
+out=sys.argv[1]
+for f in glob.glob(out + '/**/*kernel_stats.csv', recursive=True):
     for r in list(csv.DictReader(open(f)))[:12]:
         print(f"{r['Name'][:90]:90s} calls {r['Calls']:>5s} avg_us {float(r['AverageNs'])/1e3:10.1f} pct {r['Percentage']}")
 rows=[]
-for f in glob.glob('gpurun_out/prof_bank/**/*kernel_trace.csv', recursive=True):
+for f in glob.glob(out + '/**/*kernel_trace.csv', recursive=True):
     rows=list(csv.DictReader(open(f)))
 ks=[r for r in rows if 'chs_' in r['Kernel_Name'] or 'pll_channels' in r['Kernel_Name'] or 'fe_mfma_bank' in r['Kernel_Name']]
 if ks:
