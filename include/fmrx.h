@@ -405,6 +405,40 @@ FMRX_API int fmrx_rds_diff_decode(const uint8_t *in, size_t n, uint8_t *out);
 FMRX_API int fmrx_rds_frame_sync(const uint8_t *bits, size_t n, char *offset_type, size_t *next_index);
 
 /* ------------------------------------------------------------------ */
+/* RDS banks: the RDS chain of N channels per device call               */
+/* ------------------------------------------------------------------ */
+/* fmrx_rds for N independent stations at once, in a fixed number of kernel launches per call whatever N: the float64 chain
+ * with one lane per channel for its PLL, clock and data recovery on the device (one lane per channel), frame synchronisation on
+ * the host.  Per channel every result equals, bit for bit, what an fmrx_rds handle reports for the same discriminator stream.
+ * Rows are channel-major.
+ *   block: IF samples per channel and call; block*upsamp % decim == 0 and block >= every history (as fmrx_rds_process_dev).
+ *   9 600 IF samples (block_bytes 192 000 of a receiver bank) serve both RDS modes and the banks of modes 0 and 2.
+ * Every frame-sync report depends on the bits of every earlier call: a second process_dev (or a reset) before the previous
+ * call's collect returns FMRX_EINVAL; bits are never dropped. */
+typedef struct fmrx_rds_bank fmrx_rds_bank;
+FMRX_API int fmrx_rds_bank_create(fmrx_rds_bank **out, const fmrx_rds_params *p, int n_channels, size_t block, int device);
+FMRX_API int fmrx_rds_bank_destroy(fmrx_rds_bank *b);
+FMRX_API int fmrx_rds_bank_reset(fmrx_rds_bank *b, int channel);            /* channel < 0: all */
+FMRX_API size_t fmrx_rds_bank_n_out(const fmrx_rds_bank *b);               /* block*upsamp/decim */
+FMRX_API size_t fmrx_rds_bank_max_bits(const fmrx_rds_bank *b);            /* per channel and call */
+/* device rows: channel c's block at d_demod + c*pitch (floats); async on `stream` */
+FMRX_API int fmrx_rds_bank_process_dev(fmrx_rds_bank *b, const float *d_demod, size_t pitch, void *stream);
+/* waits for the last process_dev; rrc_i / rrc_q [n_channels][n_out] (either may be NULL), bits [n_channels][max_bits],
+ * n_bits [n_channels], offset_type [n_channels][8]: per channel exactly what fmrx_rds_process reports */
+FMRX_API int fmrx_rds_bank_collect(fmrx_rds_bank *b, double *rrc_i, double *rrc_q, uint8_t *bits, size_t *n_bits,
+                                   char *offset_type);
+/* host rows [n_channels][block]: H2D + process_dev + collect */
+FMRX_API int fmrx_rds_bank_process(fmrx_rds_bank *b, const float *demod, double *rrc_i, double *rrc_q, uint8_t *bits,
+                                   size_t *n_bits, char *offset_type);
+FMRX_API int fmrx_rds_bank_read_tap(fmrx_rds_bank *b, int channel, int which, double *out, size_t *n);  /* FMRX_RDS_TAP_* */
+/* Receiver banks that keep discriminator rows (stereo banks, exact banks, the resampling modes' banks): where the last
+ * call's rows are, for fmrx_rds_bank_process_dev on the same stream.  FMRX_EINVAL for the fused mono bank of modes 0/1.
+ * A call leaves its rows intact (only the history in front of each row is rewritten) until the next fmrx_channels_process*;
+ * the bank forks from and joins back into the caller's stream, so work enqueued on that stream after
+ * fmrx_channels_process_dev sees finished rows.  n_if = block_bytes / (2*rf_decim): the RDS bank's block. */
+FMRX_API int fmrx_channels_demod_layout(const fmrx_channels *c, const float **d_row0, size_t *pitch, size_t *n_if);
+
+/* ------------------------------------------------------------------ */
 /* fused front end (the hot kernel) as a stage of its own               */
 /* ------------------------------------------------------------------ */
 /* Fused: u8 I/Q -> (u8-128)/128 -> rf low-pass FIR -> decimate, I and Q

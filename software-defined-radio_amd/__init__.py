@@ -147,6 +147,16 @@ _sig("fmrx_rds_rrc", [C.c_double, _int, _f64p])
 _sig("fmrx_rds_cdr", [_f64p, _sz, _int, _int, _f64p, _u8p, C.POINTER(_sz)])
 _sig("fmrx_rds_diff_decode", [_u8p, _sz, _u8p])
 _sig("fmrx_rds_frame_sync", [_u8p, _sz, C.c_char_p, C.POINTER(_sz)])
+_sig("fmrx_rds_bank_create", [C.POINTER(_vp), C.POINTER(RdsParams), _int, _sz, _int])
+_sig("fmrx_rds_bank_destroy", [_vp])
+_sig("fmrx_rds_bank_reset", [_vp, _int])
+_sig("fmrx_rds_bank_n_out", [_vp], _sz)
+_sig("fmrx_rds_bank_max_bits", [_vp], _sz)
+_sig("fmrx_rds_bank_process_dev", [_vp, _vp, _sz, _vp])
+_sig("fmrx_rds_bank_collect", [_vp, _vp, _vp, _vp, _vp, _vp])
+_sig("fmrx_rds_bank_process", [_vp, _f32p, _vp, _vp, _vp, _vp, _vp])
+_sig("fmrx_rds_bank_read_tap", [_vp, _int, _int, _vp, C.POINTER(_sz)])
+_sig("fmrx_channels_demod_layout", [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz)])
 _sig("fmrx_fe_fir_decim_u8", [_u8p, _sz, _f32p, _sz, _uint, _vp, _vp, _vp, _int])
 _sig("fmrx_fe_plan_create", [C.POINTER(_vp), _f32p, _sz, _uint])
 _sig("fmrx_fe_plan_destroy", [_vp])
@@ -568,6 +578,13 @@ class Channels:
         _check(lib.fmrx_channels_read_tap(self._h, channel, TAPS[name], out.ctypes.data, C.byref(n)))
         return out
 
+    def demod_layout(self):
+        """(device address of channel 0's discriminator row of the last call, pitch in floats, IF samples per row): the input
+        of RdsBank.process_dev on the same stream.  Not for the fused mono bank of modes 0/1 (FmrxError)."""
+        ptr, pitch, n_if = _vp(), _sz(0), _sz(0)
+        _check(lib.fmrx_channels_demod_layout(self._h, C.byref(ptr), C.byref(pitch), C.byref(n_if)))
+        return ptr.value, pitch.value, n_if.value
+
     def load_dev(self, d_iq_ptr, stream=None):
         """Device-resident [n_channels, block_bytes] blocks -> the channels' slots (async on `stream`)."""
         _check(lib.fmrx_channels_load_dev(self._h, d_iq_ptr, stream))
@@ -661,6 +678,71 @@ class Rds:
         _check(lib.fmrx_rds_read_tap(self._h, RDS_TAPS[name], None, C.byref(n)))
         out = np.zeros(n.value)
         _check(lib.fmrx_rds_read_tap(self._h, RDS_TAPS[name], out.ctypes.data, C.byref(n)))
+        return out
+
+
+class RdsBank:
+    """The RDS chain of N channels per device call (fmrx_rds_bank_*): per channel, bit for bit what an Rds handle reports for
+    the same discriminator stream.  block: IF samples per channel and call (9600 = the receiver banks' block_bytes 192000)."""
+
+    def __init__(self, mode=0, n_channels=1, block=9600, device=0, params: RdsParams | None = None):
+        self.params = params if params is not None else RdsParams()
+        if params is None:
+            _check(lib.fmrx_rds_mode_params(mode, C.byref(self.params)))
+        self.n_channels, self.block = int(n_channels), int(block)
+        self._h = _vp()
+        _check(lib.fmrx_rds_bank_create(C.byref(self._h), C.byref(self.params), self.n_channels, self.block, device))
+        self.n_out = lib.fmrx_rds_bank_n_out(self._h)
+        self.max_bits = lib.fmrx_rds_bank_max_bits(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_rds_bank_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, channel=-1):
+        _check(lib.fmrx_rds_bank_reset(self._h, channel))
+
+    def _outputs(self, want_rrc=True):
+        n = self.n_channels
+        yi = np.zeros((n, self.n_out)) if want_rrc else None
+        yq = np.zeros((n, self.n_out)) if want_rrc else None
+        bits, nb, off = np.zeros((n, self.max_bits), np.uint8), np.zeros(n, np.uint64), C.create_string_buffer(8 * n)
+        return yi, yq, bits, nb, off
+
+    def _result(self, yi, yq, bits, nb, off):
+        raw = off.raw
+        return {"rrc_i": list(yi) if yi is not None else None, "rrc_q": list(yq) if yq is not None else None,
+                "diff_bits": [bits[c, :int(nb[c])].copy() for c in range(self.n_channels)],
+                "offset_type": [raw[8 * c:8 * c + 8].split(b"\0", 1)[0].decode() for c in range(self.n_channels)]}
+
+    def process(self, demod):
+        """demod: [n_channels, block] (host) -> dict(rrc_i, rrc_q, diff_bits: per-channel lists of arrays, offset_type: list of str)."""
+        x = _f32(demod).reshape(self.n_channels, self.block)
+        out = self._outputs()
+        yi, yq, bits, nb, off = out
+        _check(lib.fmrx_rds_bank_process(self._h, x.reshape(-1), yi.ctypes.data, yq.ctypes.data, bits.ctypes.data, nb.ctypes.data, off))
+        return self._result(*out)
+
+    def process_dev(self, d_demod_ptr, pitch, stream=None):
+        """Device rows: channel c's block at d_demod_ptr + c*pitch floats (Channels.demod_layout()); async on `stream`."""
+        _check(lib.fmrx_rds_bank_process_dev(self._h, d_demod_ptr, pitch, stream))
+
+    def collect(self, want_rrc=True):
+        """Waits for the last process_dev -> the same dict as process()."""
+        out = self._outputs(want_rrc)
+        yi, yq, bits, nb, off = out
+        _check(lib.fmrx_rds_bank_collect(self._h, yi.ctypes.data if want_rrc else None, yq.ctypes.data if want_rrc else None,
+                                         bits.ctypes.data, nb.ctypes.data, off))
+        return self._result(*out)
+
+    def read_tap(self, channel, name) -> np.ndarray:
+        n = _sz(0)
+        _check(lib.fmrx_rds_bank_read_tap(self._h, channel, RDS_TAPS[name], None, C.byref(n)))
+        out = np.zeros(n.value)
+        _check(lib.fmrx_rds_bank_read_tap(self._h, channel, RDS_TAPS[name], out.ctypes.data, C.byref(n)))
         return out
 
 

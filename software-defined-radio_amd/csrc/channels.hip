@@ -212,6 +212,14 @@ int fmrx_channels_input_layout(const fmrx_channels *c, uint8_t **d_first_block, 
     return FMRX_OK;
 }
 
+int fmrx_channels_demod_layout(const fmrx_channels *c, const float **d_row0, size_t *pitch, size_t *n_if)
+{
+    if (!c || !d_row0 || !pitch || !n_if) return fail(FMRX_EINVAL, "channels_demod_layout: null argument");
+    if (!c->bank) return fail(FMRX_EINVAL, "channels_demod_layout: the fused mono bank of modes 0/1 keeps no discriminator rows");
+    stereo_bank_demod_layout(c->bank, d_row0, pitch, n_if);
+    return FMRX_OK;
+}
+
 int fmrx_channels_reset(fmrx_channels *c, int channel)
 {
     if (!c) return fail(FMRX_EINVAL, "channels_reset: null handle");

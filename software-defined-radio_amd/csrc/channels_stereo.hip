@@ -1248,6 +1248,12 @@ int stereo_bank_create(StereoBank **out, const fmrx_params &p, int n_channels, i
 size_t stereo_bank_n_audio(const StereoBank *b) { return static_cast<size_t>(b->n_audio); }
 uint8_t *stereo_bank_first_block(const StereoBank *b) { return b->slots.p + b->hist_bytes; }
 size_t stereo_bank_pitch(const StereoBank *b) { return b->slot_bytes; }
+void stereo_bank_demod_layout(const StereoBank *b, const float **d_row0, size_t *pitch, size_t *n_if)
+{
+    *d_row0 = b->demod.p + b->Hd;   // the finish kernel rewrites only the history in front of each row
+    *pitch = static_cast<size_t>(b->dpitch);
+    *n_if = static_cast<size_t>(b->n_if);
+}
 
 // back to the start-of-stream state (src/project.cpp:61-65, 446-458): one channel, or all of them (channel < 0)
 int stereo_bank_reset(StereoBank *b, int channel)

@@ -301,6 +301,7 @@ void stereo_bank_destroy(StereoBank *b);
 size_t stereo_bank_n_audio(const StereoBank *b);
 uint8_t *stereo_bank_first_block(const StereoBank *b);
 size_t stereo_bank_pitch(const StereoBank *b);
+void stereo_bank_demod_layout(const StereoBank *b, const float **d_row0, size_t *pitch, size_t *n_if);
 int stereo_bank_reset(StereoBank *b, int channel);
 int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStream_t s);
 int stereo_bank_read_tap(StereoBank *b, int channel, int which, float *out, size_t *n);

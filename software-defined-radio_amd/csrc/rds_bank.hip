@@ -1,0 +1,588 @@
+// rds_bank.hip -- the RDS chain of N channels per device call (include/fmrx.h: fmrx_rds_bank_*).
+//
+// The single-stream handle (rds.hip) runs one station's chain in 17 launches per block, its float64 PLL in one lane of one wave
+// and its bit recovery on the host.  A receiver bank (channels.hip, channels_stereo.hip) demodulates 10^4 - 10^5 stations per
+// call; this file gives each of them its RDS chain in a FIXED number of launches, whatever the number of channels, with the
+// arithmetic of rds.hip unchanged -- every channel's results equal, bit for bit, what an fmrx_rds handle produces from the same
+// discriminator stream:
+//   rdsb_cvt_kernel         f32 demod rows (caller's pitch) -> f64 rows behind their histories       (rds_cvt_kernel)
+//   rdsb_fir_kernel<0>      54-60 kHz channel band-pass, 151 taps                                     (rds_fir_kernel)
+//   rdsb_fir_kernel<1>      113.5-114.5 kHz band-pass of the squared channel row                      (rds_fir_kernel, square)
+//   rdsb_pll_lanes_kernel   the 114 kHz PLL, ONE LANE PER CHANNEL (64 channels per wave)              (rds_pll_kernel, rds_nco_state_kernel)
+//   rdsb_mix_kernel         NCO pair, I / Q mixers                                                    (rds_nco_kernel, rds_mix_kernel)
+//   rdsb_resample_kernel    rational resampler U/D, 101*U taps, gain U, I and Q                       (rds_resample_kernel x 2)
+//   rdsb_fir_kernel<0>      root-raised-cosine matched filter, I and Q (grid z)                      (rds_fir_kernel x 2)
+//   rdsb_cdr_kernel         clock and data recovery, Manchester and differential decoding, one lane per channel (host cdr())
+//   rdsb_tail_kernel        carried state: every row's tail -> its history                            (rds_tail_kernel x 6)
+// Frame synchronisation stays on the host (fmrx_rds_bank_collect), ~190 new bits per channel and call.
+//
+// Data layout: channel-major float64 rows, the carried history (raw samples, as rds.hip keeps them) in front of the block and
+// a few samples of padding behind it (the register-window FIRs read up to kR - 2 samples past the block; results discarded):
+//   x      [N][Hx | n | pad]     converted discriminator output          ch     [N][Hc | n | pad]    channel band-pass
+//   car    [N][n | pad]          carrier band-pass (squared input)       arg    [N][n | pad]         raw trigArg of every PLL step
+//   nco_i, nco_q [N][n+1 | pad]  NCO pair, [0] = previous call's last    mi, mq [N][Hm | n | pad]    mixer rows
+//   ri, rq [N][Hr | n_out | pad] resampler output                        yi, yq [N][n_out | pad]     matched-filter output
+//   state  [N][8]                rds_pll_kernel's layout {integ, phase, fI, fQ, nco_i[n], off, nco_q[n], trigArg}
+//   bits   u8 [N][max_bits], n_bits u32 [N], blk i32 [N] (0 until a channel's first call: the CDR's block_count != 0 test)
+#include "fmrx_internal.hpp"
+#include "rds_common.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+using namespace fmrx;
+using namespace fmrx::rds;
+
+namespace {
+
+constexpr int kR = 4;        // consecutive outputs per thread of the FIR kernels
+constexpr int kPllB = 32;    // samples per lane and batch of the PLL lanes (two 128-byte lines of a double row)
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(256) void rdsb_cvt_kernel(const float *__restrict__ in, long in_pitch, long n, double *__restrict__ x, long xpitch)
+{
+    const long c = blockIdx.x, i = static_cast<long>(blockIdx.y) * blockDim.x + threadIdx.x;
+    if (i < n) x[c * xpitch + i] = static_cast<double>(in[c * in_pitch + i]);
+}
+
+// y[k] = sum_j h[j] * f(x[k-j]), f = identity or square, in rds_fir_kernel's order (acc = h[j]*v + acc, j from taps-1 down to 0).
+// A thread owns kR consecutive outputs and slides one register window over x: the window of step j is x[k0-j .. k0-j+kR-1],
+// one new sample per step, so every sample is loaded (and squared) once for all kR outputs while each output still meets its
+// taps in the single-stream order.  x, y: the block's first sample of channel 0's row (blockIdx.x = channel); blockIdx.z
+// selects the second (x, y) pair (the matched filter runs I and Q in one launch).  Reads x[-(taps-1) .. n+kR-2].
+template <bool SQUARE>
+__global__ __launch_bounds__(256) void rdsb_fir_kernel(const double *__restrict__ x0, const double *__restrict__ x1, long xpitch, long n,
+                                                       const double *__restrict__ h, int taps, double *__restrict__ y0, double *__restrict__ y1,
+                                                       long ypitch)
+{
+    const long c = blockIdx.x, k0 = (static_cast<long>(blockIdx.y) * blockDim.x + threadIdx.x) * kR;
+    if (k0 >= n) return;
+    const double *x = (blockIdx.z ? x1 : x0) + c * xpitch + k0;
+    double *y = (blockIdx.z ? y1 : y0) + c * ypitch + k0;
+    double w[kR], acc[kR];
+#pragma unroll
+    for (int r = 0; r < kR; r++) {
+        const double v = x[r - (taps - 1)];
+        w[r] = SQUARE ? v * v : v;
+        acc[r] = 0.0;
+    }
+    for (int j = taps - 1; j >= 0; j--) {
+        const double hj = h[j];
+#pragma unroll
+        for (int r = 0; r < kR; r++) acc[r] = hj * w[r] + acc[r];
+        if (j) {
+#pragma unroll
+            for (int r = 0; r + 1 < kR; r++) w[r] = w[r + 1];
+            const double v = x[kR - j];
+            w[kR - 1] = SQUARE ? v * v : v;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kR; r++)
+        if (k0 + r < n) y[r] = acc[r];
+}
+
+// The recurrence of fmPll (fmSupportLib.py:297-353) in float64, rds_pll_kernel's step, ONE LANE PER CHANNEL.  The carrier row
+// arrives a batch ahead through registers into LDS and the chain touches LDS only; the state stays in
+// registers (the step is written out in the loop: no call, nothing in scratch).  Also: nco[0] <- the incoming state's last NCO
+// pair, and the outgoing one computed from the last trigArg (what rds_nco_kernel / rds_nco_state_kernel do for one stream).
+// Rows are 16-byte aligned (even pitches).
+__global__ __launch_bounds__(64) void rdsb_pll_lanes_kernel(const double *__restrict__ car, long apitch, long n, int n_ch, double *__restrict__ arg,
+                                                            double *__restrict__ state, double *__restrict__ nco_i, double *__restrict__ nco_q,
+                                                            long npitch, double freq, double Fs, double normBandwidth, double ncoScale,
+                                                            double phaseAdjust)
+{
+    __shared__ double lin[kPllB * 64], lout[kPllB * 64];     // [sample][lane]: every lane reads and writes its own column
+    const int lane = threadIdx.x;
+    const long ch = static_cast<long>(blockIdx.x) * 64 + lane;
+    if (ch >= n_ch) return;
+    const double Kp = normBandwidth * 2.666, Ki = normBandwidth * normBandwidth * 3.555;
+    const double w = 2 * kPi * (freq / Fs);
+    double *st = state + 8 * ch;
+    double integ = st[0], phase = st[1], fI = st[2], fQ = st[3], off = st[5], last = 0.0;
+    nco_i[ch * npitch] = st[4];
+    nco_q[ch * npitch] = st[6];
+    const double *in = car + ch * apitch;
+    double *out = arg + ch * apitch;
+    const d2 *in2 = reinterpret_cast<const d2 *>(in);
+    d2 *out2 = reinterpret_cast<d2 *>(out);
+    const long nb = n / kPllB;
+    d2 pre[kPllB / 2];
+    if (nb > 0) {
+#pragma unroll
+        for (int g = 0; g < kPllB / 2; g++) pre[g] = in2[g];
+    }
+    for (long b = 0; b < nb; b++) {
+        // (1) this batch's input -> LDS (requested a batch ago); (2) request the next batch
+#pragma unroll
+        for (int g = 0; g < kPllB / 2; g++) {
+            lin[(2 * g) * 64 + lane] = pre[g].x;
+            lin[(2 * g + 1) * 64 + lane] = pre[g].y;
+        }
+        if (b + 1 < nb) {
+#pragma unroll
+            for (int g = 0; g < kPllB / 2; g++) pre[g] = in2[(b + 1) * (kPllB / 2) + g];
+        }
+        // (3) the previous batch's output -> memory (its stores have this whole batch to complete)
+        if (b > 0) {
+#pragma unroll
+            for (int g = 0; g < kPllB / 2; g++) out2[(b - 1) * (kPllB / 2) + g] = (d2){lout[(2 * g) * 64 + lane], lout[(2 * g + 1) * 64 + lane]};
+        }
+        // (4) the chain: LDS in, LDS out
+#pragma unroll 1
+        for (int j = 0; j < kPllB; j++) {
+            const double xk = lin[j * 64 + lane];
+            const double eD = atan2(xk * (-fQ), xk * (+fI));
+            integ = integ + Ki * eD;
+            phase = phase + Kp * eD + integ;
+            off += 1;
+            last = w * off + phase;
+            sincos(last, &fQ, &fI);
+            lout[j * 64 + lane] = last;
+        }
+    }
+    if (nb > 0) {
+#pragma unroll
+        for (int g = 0; g < kPllB / 2; g++) out2[(nb - 1) * (kPllB / 2) + g] = (d2){lout[(2 * g) * 64 + lane], lout[(2 * g + 1) * 64 + lane]};
+    }
+    for (long k = nb * kPllB; k < n; k++) {                   // what is left of a block that is not a multiple of the batch
+        const double xk = in[k];
+        const double eD = atan2(xk * (-fQ), xk * (+fI));
+        integ = integ + Ki * eD;
+        phase = phase + Kp * eD + integ;
+        off += 1;
+        last = w * off + phase;
+        sincos(last, &fQ, &fI);
+        out[k] = last;
+    }
+    double s, cs;
+    sincos(last * ncoScale + phaseAdjust, &s, &cs);          // = nco[n] of this call, the next call's nco[0]
+    st[0] = integ; st[1] = phase; st[2] = fI; st[3] = fQ; st[4] = cs; st[5] = off; st[6] = s; st[7] = last;
+}
+
+// NCO pair and mixers: nco[i+1] = cos / sin(arg[i]*ncoScale + phaseAdjust); mixer[i] = nco[i] * allpass[i] * 2, allpass = the
+// channel row delayed by `delay`.  Thread i computes nco[i+1] and mixer[i+1]; thread 0 also mixer[0] (nco[0]: the PLL lanes).
+// ch, mi, mq: the block's first sample of channel 0's row.
+__global__ __launch_bounds__(256) void rdsb_mix_kernel(const double *__restrict__ arg, long apitch, long n, const double *__restrict__ ch, long cpitch,
+                                                       int delay, double ncoScale, double phaseAdjust, double *__restrict__ nco_i,
+                                                       double *__restrict__ nco_q, long npitch, double *__restrict__ mi, double *__restrict__ mq,
+                                                       long mpitch)
+{
+    const long c = blockIdx.x, i = static_cast<long>(blockIdx.y) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *chr = ch + c * cpitch;
+    double *ni = nco_i + c * npitch, *nq = nco_q + c * npitch, *mir = mi + c * mpitch, *mqr = mq + c * mpitch;
+    double s, cs;
+    sincos(arg[c * apitch + i] * ncoScale + phaseAdjust, &s, &cs);
+    ni[i + 1] = cs;
+    nq[i + 1] = s;
+    if (i + 1 < n) {
+        const double ap = chr[i + 1 - delay];
+        mir[i + 1] = cs * ap * 2;
+        mqr[i + 1] = s * ap * 2;
+    }
+    if (i == 0) {
+        const double ap = chr[-delay];
+        mir[0] = ni[0] * ap * 2;
+        mqr[0] = nq[0] * ap * 2;
+    }
+}
+
+// convolveBlockResampleFIR of the model (fmSupportLib.py:388-407) in stream form, gain U: rds_resample_kernel's phase walk, I and
+// Q together (same taps, same window).  mi, mq, ri, rq: the block's first sample of channel 0's row.
+__global__ __launch_bounds__(256) void rdsb_resample_kernel(const double *__restrict__ mi, const double *__restrict__ mq, long mpitch, long n_out,
+                                                            const double *__restrict__ h, int taps, int decim, int upsamp, double *__restrict__ ri,
+                                                            double *__restrict__ rq, long rpitch)
+{
+    const long c = blockIdx.x, k = static_cast<long>(blockIdx.y) * blockDim.x + threadIdx.x;
+    if (k >= n_out) return;
+    const long m = k * decim;
+    const int ph = static_cast<int>(m % upsamp);
+    const long b = m / upsamp;
+    const double *xi = mi + c * mpitch + b, *xq = mq + c * mpitch + b;
+    double acc_i = 0.0, acc_q = 0.0;
+    long j = 0;
+    for (int t = ph; t < taps; t += upsamp, j++) {
+        const double ht = h[t];
+        acc_i = acc_i + ht * xi[-j];
+        acc_q = acc_q + ht * xq[-j];
+    }
+    ri[c * rpitch + k] = acc_i * upsamp;
+    rq[c * rpitch + k] = acc_q * upsamp;
+}
+
+// Clock and data recovery of the model (fmSupportLib.py:103-249, the host cdr() in rds_common.cpp), ONE LANE PER CHANNEL, on the
+// in-phase matched-filter row, then differential decoding in place.  The host function materialises the sampled points and
+// re-scans them from the top after every restart; here one pass per attempt carries what the scan reads (the two previous
+// points for the three-in-a-row flip, the pair being formed) in registers and writes the Manchester bits as it goes -- an
+// attempt that fails is overwritten by the next one, which starts one symbol later behind one more head bit (block_count != 0).
+// state {pair0, pair1, start0, prev_size}: what fmrx_rds_process re-makes every block.  blk[c] != 0 after a channel's first call.
+__global__ __launch_bounds__(64) void rdsb_cdr_kernel(const double *__restrict__ y, long ypitch, long n, int n_ch, int sps, double pair0_in,
+                                                      double pair1_in, long start0, long prev_size, int *__restrict__ blk,
+                                                      uint8_t *__restrict__ bits, long max_bits, uint32_t *__restrict__ n_bits)
+{
+    const long ch = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (ch >= n_ch) return;
+    const double *x = y + ch * ypitch;
+    uint8_t *out = bits + ch * max_bits;
+    const bool counted = blk[ch] != 0;
+    double pair0 = pair0_in, pair1 = pair1_in;
+    long start = start0, nh = 0;
+    auto put = [&](long i, int v) {
+        if (i < max_bits) out[i] = static_cast<uint8_t>(v);
+    };
+    if (prev_size % 2 == 1 && start < n) {   // the point that completes the previous block's pair
+        pair1 = x[start];
+        put(nh++, pair0 > 0 ? 1 : 0);
+        pair0 = pair1;
+        start += sps;
+    }
+    long nm = nh;
+    for (;;) {
+        double a = 0.0, b = 0.0, s0 = 0.0;   // the two previous points (as flipped by the three-in-a-row rule); samples[0] as mended
+        bool failed = false;
+        long m = 0;
+        nm = nh;
+        for (long i = start; i < n; i += sps, m++) {
+            const double xi = x[i];
+            double p;
+            if (m >= 2 && a > 0 && b > 0 && xi > 0) p = -xi;           // the third of three high / low points is flipped
+            else if (m >= 2 && a < 0 && b < 0 && xi < 0) p = -xi;
+            else p = xi;
+            if (m == 0) s0 = p;
+            if (m & 1) {                                               // the pair (samples[m-1], samples[m])
+                double q0 = b, q1 = p;
+                if ((q0 < 0 && q1 < 0) || (q0 > 0 && q1 > 0)) {
+                    if (fabs(q0) < 0.3 || fabs(q1) < 0.3) {
+                        if (fabs(q0) < 0.3) q0 = -q0;
+                        else q1 = -q1;
+                    } else {                                           // cannot be mended: re-start one symbol later
+                        failed = true;
+                        break;
+                    }
+                }
+                if (m == 1) s0 = q0;
+                put(nm++, (q0 > 0 && q1 < 0) ? 1 : 0);                // manchestering
+            }
+            a = b;
+            b = p;
+        }
+        if (!failed) break;
+        start += sps;
+        if (counted) {
+            pair1 = s0;
+            put(nh++, pair0 > 0 ? 1 : 0);
+            pair0 = pair1;
+        }
+    }
+    if (nm > max_bits) nm = max_bits;                                  // (cannot happen: max_bits = n/sps + 4 > every count)
+    for (long i = nm - 1; i > 0; i--) out[i] = out[i] != out[i - 1];    // differential decoding (out[0] stays)
+    n_bits[ch] = static_cast<uint32_t>(nm);
+    blk[ch] = 1;
+}
+
+// carried state: per channel, every history <- the last samples of its row's block (blocks are at least as long as each
+// history, create() checks: source and destination never overlap)
+__global__ __launch_bounds__(256) void rdsb_tail_kernel(double *__restrict__ x, long xpitch, int hx, double *__restrict__ ch, long cpitch, int hc,
+                                                        double *__restrict__ mi, double *__restrict__ mq, long mpitch, int hm, double *__restrict__ ri,
+                                                        double *__restrict__ rq, long rpitch, int hr, long n, long n_out)
+{
+    const long c = blockIdx.x;
+    double *xr = x + c * xpitch, *cr = ch + c * cpitch, *mir = mi + c * mpitch, *mqr = mq + c * mpitch, *rir = ri + c * rpitch, *rqr = rq + c * rpitch;
+    for (int i = threadIdx.x; i < hx; i += blockDim.x) xr[i] = xr[n + i];
+    for (int i = threadIdx.x; i < hc; i += blockDim.x) cr[i] = cr[n + i];
+    for (int i = threadIdx.x; i < hm; i += blockDim.x) {
+        mir[i] = mir[n + i];
+        mqr[i] = mqr[n + i];
+    }
+    for (int i = threadIdx.x; i < hr; i += blockDim.x) {
+        rir[i] = rir[n_out + i];
+        rqr[i] = rqr[n_out + i];
+    }
+}
+
+long pitch_of(long n) { return (n + 8 + 3) / 4 * 4; }   // kR - 2 readable samples past the end, 32-byte rows
+
+const double kPllInit[8] = {0.0, 0.0, 1.0, 0.0, 1.0, 0.0, 1.0, 0.0};   // fmMonoBlock.py:186 (as fmrx_rds_reset)
+
+}  // namespace
+
+struct fmrx_rds_bank {
+    fmrx_rds_params p{};
+    int n_channels = 0, device = 0;
+    long block = 0, n_out = 0, max_bits = 0;
+    int Hx = 0, Hc = 0, Hm = 0, Hr = 0, delay = 0;
+    long xpitch = 0, cpitch = 0, apitch = 0, npitch = 0, mpitch = 0, rpitch = 0, ypitch = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+    DevBuf<float> in;
+    DevBuf<double> h_ch, h_car, h_rs, h_rrc, x, ch, car, arg, nco_i, nco_q, mi, mq, ri, rq, yi, yq, state;
+    DevBuf<int> blk;
+    DevBuf<uint8_t> bits;
+    DevBuf<uint32_t> n_bits;
+    std::vector<uint8_t> h_bits;
+    std::vector<uint32_t> h_n_bits;
+    std::vector<std::vector<uint8_t>> decoded;   // per channel: the bits frame synchronisation keeps (fmrx_rds::decoded)
+    bool pending = false;                          // a process_dev whose bits have not been collected
+    long calls = 0;
+};
+
+namespace {
+
+// back to the start-of-stream state, channels [lo, hi)
+int bank_reset(fmrx_rds_bank *b, int lo, int hi)
+{
+    FMRX_HIP(hipSetDevice(b->device));
+    FMRX_HIP(hipDeviceSynchronize());
+    const size_t cnt = static_cast<size_t>(hi - lo);
+    auto hist = [&](DevBuf<double> &d, long pitch, int h) -> int {
+        FMRX_HIP(hipMemset2D(d.p + lo * pitch, pitch * sizeof(double), 0, h * sizeof(double), cnt));
+        return FMRX_OK;
+    };
+    FMRX_TRY(hist(b->x, b->xpitch, b->Hx));
+    FMRX_TRY(hist(b->ch, b->cpitch, b->Hc));
+    FMRX_TRY(hist(b->mi, b->mpitch, b->Hm));
+    FMRX_TRY(hist(b->mq, b->mpitch, b->Hm));
+    FMRX_TRY(hist(b->ri, b->rpitch, b->Hr));
+    FMRX_TRY(hist(b->rq, b->rpitch, b->Hr));
+    std::vector<double> init(8 * cnt);
+    for (size_t c = 0; c < cnt; c++) std::copy(kPllInit, kPllInit + 8, init.begin() + 8 * c);
+    FMRX_HIP(hipMemcpy(b->state.p + 8 * lo, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+    FMRX_HIP(hipMemset(b->blk.p + lo, 0, cnt * sizeof(int)));
+    for (int c = lo; c < hi; c++) b->decoded[c].clear();
+    FMRX_HIP(hipDeviceSynchronize());
+    return FMRX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmrx_rds_bank_create(fmrx_rds_bank **out, const fmrx_rds_params *p, int n_channels, size_t block, int device)
+{
+    if (!out || !p) return fail(FMRX_EINVAL, "rds_bank_create: null argument");
+    if (p->taps < 3 || p->taps > 65535 || p->upsamp < 1 || p->decim < 1 || p->sps < 1 || p->rrc_taps < 2 || p->if_Fs <= 0)
+        return fail(FMRX_EINVAL, "rds_bank_create: bad parameters");
+    if (n_channels < 1) return fail(FMRX_EINVAL, "rds_bank_create: n_channels must be >= 1");
+    if (block == 0 || block > (1u << 30) || (block * p->upsamp) % p->decim)
+        return fail(FMRX_EINVAL, "rds_bank_create: block of %zu samples: block*upsamp must be a multiple of decim %d", block, p->decim);
+    const int delay = (p->taps - 1) / 2, Hx = p->taps - 1, Hm = (101 * p->upsamp - 1) / p->upsamp, Hc = std::max(p->taps - 1, delay + 1),
+              Hr = p->rrc_taps - 1;
+    const size_t n_out = block * p->upsamp / p->decim;
+    // every carried history is refreshed by a copy of its row's tail to its front: the block must be at least as long as each
+    if (block < static_cast<size_t>(std::max(std::max(Hx, Hc), Hm)) || n_out < static_cast<size_t>(Hr))
+        return fail(FMRX_EINVAL, "rds_bank_create: block of %zu samples is shorter than a filter history (%d / %d / %d input samples, %d resampled)",
+                    block, Hx, Hc, Hm, Hr);
+    FMRX_TRY(require_device());
+    FMRX_HIP(hipSetDevice(device));
+    fmrx_rds_bank *b = new fmrx_rds_bank;
+    b->p = *p;
+    b->n_channels = n_channels;
+    b->device = device;
+    b->block = static_cast<long>(block);
+    b->n_out = static_cast<long>(n_out);
+    b->max_bits = b->n_out / p->sps + 4;
+    b->delay = delay;
+    b->Hx = Hx;
+    b->Hc = Hc;
+    b->Hm = Hm;
+    b->Hr = Hr;
+    const long n = b->block, no = b->n_out;
+    b->xpitch = pitch_of(Hx + n);
+    b->cpitch = pitch_of(Hc + n);
+    b->apitch = pitch_of(n);
+    b->npitch = pitch_of(n + 1);
+    b->mpitch = pitch_of(Hm + n);
+    b->rpitch = pitch_of(Hr + no);
+    b->ypitch = pitch_of(no);
+    auto body = [&]() -> int {
+        const int rs_taps = 101 * p->upsamp;
+        std::vector<double> h(std::max(rs_taps, p->taps));
+        auto up = [&](DevBuf<double> &d, int cnt) -> int {
+            FMRX_TRY(d.alloc(cnt));
+            FMRX_HIP(hipMemcpy(d.p, h.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
+            return FMRX_OK;
+        };
+        // the single-stream handle's taps (fmrx_rds_create; fmMonoBlock.py:138-141)
+        design_bpf64(p->taps, p->if_Fs, 54e3, 60e3, h.data());
+        FMRX_TRY(up(b->h_ch, p->taps));
+        design_bpf64(p->taps, p->if_Fs, 113.5e3, 114.5e3, h.data());
+        FMRX_TRY(up(b->h_car, p->taps));
+        design_lpf64(rs_taps, static_cast<double>(p->if_Fs) * p->upsamp, 3e3, h.data());
+        FMRX_TRY(up(b->h_rs, rs_taps));
+        design_rrc64(2375.0 * p->sps, p->rrc_taps, h.data());
+        FMRX_TRY(up(b->h_rrc, p->rrc_taps));
+        const size_t N = static_cast<size_t>(n_channels);
+        auto rows = [&](DevBuf<double> &d, long pitch) -> int {
+            FMRX_TRY(d.alloc(static_cast<size_t>(pitch) * N));
+            FMRX_HIP(hipMemset(d.p, 0, d.bytes()));
+            return FMRX_OK;
+        };
+        FMRX_TRY(rows(b->x, b->xpitch));
+        FMRX_TRY(rows(b->ch, b->cpitch));
+        FMRX_TRY(rows(b->car, b->apitch));
+        FMRX_TRY(rows(b->arg, b->apitch));
+        FMRX_TRY(rows(b->nco_i, b->npitch));
+        FMRX_TRY(rows(b->nco_q, b->npitch));
+        FMRX_TRY(rows(b->mi, b->mpitch));
+        FMRX_TRY(rows(b->mq, b->mpitch));
+        FMRX_TRY(rows(b->ri, b->rpitch));
+        FMRX_TRY(rows(b->rq, b->rpitch));
+        FMRX_TRY(rows(b->yi, b->ypitch));
+        FMRX_TRY(rows(b->yq, b->ypitch));
+        FMRX_TRY(b->state.alloc(8 * N));
+        FMRX_TRY(b->blk.alloc(N));
+        FMRX_TRY(b->bits.alloc(static_cast<size_t>(b->max_bits) * N));
+        FMRX_TRY(b->n_bits.alloc(N));
+        b->h_bits.resize(static_cast<size_t>(b->max_bits) * N);
+        b->h_n_bits.resize(N);
+        b->decoded.resize(N);
+        FMRX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        FMRX_HIP(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
+        return bank_reset(b, 0, n_channels);
+    };
+    const int rc = body();
+    if (rc != FMRX_OK) {
+        fmrx_rds_bank_destroy(b);
+        return rc;
+    }
+    *out = b;
+    return FMRX_OK;
+}
+
+int fmrx_rds_bank_destroy(fmrx_rds_bank *b)
+{
+    if (!b) return FMRX_OK;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    if (b->done) (void)hipEventDestroy(b->done);
+    delete b;
+    return FMRX_OK;
+}
+
+int fmrx_rds_bank_reset(fmrx_rds_bank *b, int channel)
+{
+    if (!b) return fail(FMRX_EINVAL, "rds_bank_reset: null handle");
+    if (channel >= b->n_channels) return fail(FMRX_EINVAL, "rds_bank_reset: channel %d of %d", channel, b->n_channels);
+    if (b->pending) return fail(FMRX_EINVAL, "rds_bank_reset: the last process_dev has not been collected");
+    return channel < 0 ? bank_reset(b, 0, b->n_channels) : bank_reset(b, channel, channel + 1);
+}
+
+size_t fmrx_rds_bank_n_out(const fmrx_rds_bank *b) { return b ? static_cast<size_t>(b->n_out) : 0; }
+size_t fmrx_rds_bank_max_bits(const fmrx_rds_bank *b) { return b ? static_cast<size_t>(b->max_bits) : 0; }
+
+int fmrx_rds_bank_process_dev(fmrx_rds_bank *b, const float *d_demod, size_t pitch, void *stream)
+{
+    if (!b || !d_demod) return fail(FMRX_EINVAL, "rds_bank_process_dev: null argument");
+    if (pitch < static_cast<size_t>(b->block))
+        return fail(FMRX_EINVAL, "rds_bank_process_dev: pitch %zu floats is shorter than the block (%ld)", pitch, b->block);
+    // every frame-sync report depends on the bits of every earlier call: they are never dropped
+    if (b->pending) return fail(FMRX_EINVAL, "rds_bank_process_dev: the previous call has not been collected (fmrx_rds_bank_collect)");
+    FMRX_HIP(hipSetDevice(b->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const fmrx_rds_params &p = b->p;
+    const long n = b->block, no = b->n_out;
+    const unsigned N = static_cast<unsigned>(b->n_channels), lanes = (N + 63) / 64;
+    auto tiles = [](long cnt, long per) { return static_cast<unsigned>((cnt + per - 1) / per); };
+    double *x = b->x.p + b->Hx, *ch = b->ch.p + b->Hc, *mi = b->mi.p + b->Hm, *mq = b->mq.p + b->Hm, *ri = b->ri.p + b->Hr, *rq = b->rq.p + b->Hr;
+    const double phase_adjust = 3 * kPi / 8;
+    hipLaunchKernelGGL(rdsb_cvt_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, d_demod, static_cast<long>(pitch), n, x, b->xpitch);
+    hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, x, x, b->xpitch, n, b->h_ch.p, p.taps, ch, ch, b->cpitch);
+    hipLaunchKernelGGL(rdsb_fir_kernel<true>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, ch, ch, b->cpitch, n, b->h_car.p, p.taps, b->car.p,
+                       b->car.p, b->apitch);
+    hipLaunchKernelGGL(rdsb_pll_lanes_kernel, dim3(lanes), dim3(64), 0, s, b->car.p, b->apitch, n, b->n_channels, b->arg.p, b->state.p,
+                       b->nco_i.p, b->nco_q.p, b->npitch, 114e3, static_cast<double>(p.if_Fs), 0.002, 0.5, phase_adjust);
+    hipLaunchKernelGGL(rdsb_mix_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, b->arg.p, b->apitch, n, ch, b->cpitch, b->delay, 0.5, phase_adjust,
+                       b->nco_i.p, b->nco_q.p, b->npitch, mi, mq, b->mpitch);
+    hipLaunchKernelGGL(rdsb_resample_kernel, dim3(N, tiles(no, 256)), dim3(256), 0, s, mi, mq, b->mpitch, no, b->h_rs.p, 101 * p.upsamp, p.decim,
+                       p.upsamp, ri, rq, b->rpitch);
+    hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(no, 256 * kR), 2), dim3(256), 0, s, ri, rq, b->rpitch, no, b->h_rrc.p, p.rrc_taps,
+                       b->yi.p, b->yq.p, b->ypitch);
+    // fmMonoBlock.py:276-280 (fmrx_rds_process): the CDR state is re-made every block
+    hipLaunchKernelGGL(rdsb_cdr_kernel, dim3(lanes), dim3(64), 0, s, b->yi.p, b->ypitch, no, b->n_channels, p.sps, 0.0, 0.0, 158L, 0L, b->blk.p,
+                       b->bits.p, b->max_bits, b->n_bits.p);
+    hipLaunchKernelGGL(rdsb_tail_kernel, dim3(N), dim3(256), 0, s, b->x.p, b->xpitch, b->Hx, b->ch.p, b->cpitch, b->Hc, b->mi.p, b->mq.p, b->mpitch,
+                       b->Hm, b->ri.p, b->rq.p, b->rpitch, b->Hr, n, no);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FMRX_EHIP, "rds bank kernels: %s", hipGetErrorString(e));
+    FMRX_HIP(hipEventRecord(b->done, s));
+    b->pending = true;
+    b->calls++;
+    return FMRX_OK;
+}
+
+int fmrx_rds_bank_collect(fmrx_rds_bank *b, double *rrc_i, double *rrc_q, uint8_t *bits, size_t *n_bits, char *offset_type)
+{
+    if (!b) return fail(FMRX_EINVAL, "rds_bank_collect: null handle");
+    if (!b->pending) return fail(FMRX_EINVAL, "rds_bank_collect: no call to collect");
+    FMRX_HIP(hipSetDevice(b->device));
+    b->pending = false;
+    hipStream_t s = b->stream;
+    const size_t N = static_cast<size_t>(b->n_channels), no = static_cast<size_t>(b->n_out), mb = static_cast<size_t>(b->max_bits);
+    FMRX_HIP(hipStreamWaitEvent(s, b->done, 0));
+    FMRX_HIP(hipMemcpyAsync(b->h_bits.data(), b->bits.p, N * mb, hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipMemcpyAsync(b->h_n_bits.data(), b->n_bits.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    const size_t yp = static_cast<size_t>(b->ypitch) * sizeof(double);
+    if (rrc_i) FMRX_HIP(hipMemcpy2DAsync(rrc_i, no * sizeof(double), b->yi.p, yp, no * sizeof(double), N, hipMemcpyDeviceToHost, s));
+    if (rrc_q) FMRX_HIP(hipMemcpy2DAsync(rrc_q, no * sizeof(double), b->yq.p, yp, no * sizeof(double), N, hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipStreamSynchronize(s));
+    // fmMonoBlock.py:283-297, per channel: frame synchronisation over the bits kept so far
+    for (size_t c = 0; c < N; c++) {
+        const size_t nb = b->h_n_bits[c];
+        const uint8_t *d = b->h_bits.data() + c * mb;
+        if (bits) std::memcpy(bits + c * mb, d, nb);
+        if (n_bits) n_bits[c] = nb;
+        std::vector<uint8_t> &dec = b->decoded[c];
+        dec.insert(dec.end(), d, d + nb);
+        size_t next = 0;
+        const char *off = frame_sync(dec.data(), dec.size(), &next);
+        dec.erase(dec.begin(), dec.begin() + static_cast<long>(std::min(next, dec.size())));
+        if (offset_type) std::strcpy(offset_type + 8 * c, off);
+    }
+    return FMRX_OK;
+}
+
+int fmrx_rds_bank_process(fmrx_rds_bank *b, const float *demod, double *rrc_i, double *rrc_q, uint8_t *bits, size_t *n_bits, char *offset_type)
+{
+    if (!b || !demod) return fail(FMRX_EINVAL, "rds_bank_process: null argument");
+    if (b->pending) return fail(FMRX_EINVAL, "rds_bank_process: the previous call has not been collected (fmrx_rds_bank_collect)");
+    FMRX_HIP(hipSetDevice(b->device));
+    const size_t n = static_cast<size_t>(b->block), N = static_cast<size_t>(b->n_channels);
+    FMRX_TRY(b->in.ensure(n * N));
+    FMRX_HIP(hipMemcpyAsync(b->in.p, demod, n * N * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    FMRX_TRY(fmrx_rds_bank_process_dev(b, b->in.p, n, b->stream));
+    return fmrx_rds_bank_collect(b, rrc_i, rrc_q, bits, n_bits, offset_type);
+}
+
+int fmrx_rds_bank_read_tap(fmrx_rds_bank *b, int channel, int which, double *out, size_t *n)
+{
+    if (!b || !n) return fail(FMRX_EINVAL, "rds_bank_read_tap: null argument");
+    if (channel < 0 || channel >= b->n_channels) return fail(FMRX_EINVAL, "rds_bank_read_tap: channel %d of %d", channel, b->n_channels);
+    const long c = channel;
+    const size_t last_n = b->calls ? static_cast<size_t>(b->block) : 0, last_out = b->calls ? static_cast<size_t>(b->n_out) : 0;
+    const double *src = nullptr;
+    size_t cnt = 0;
+    switch (which) {
+    case FMRX_RDS_TAP_CHANNEL: src = b->ch.p + c * b->cpitch + b->Hc; cnt = last_n; break;   // after the tail copy the block region is intact
+    case FMRX_RDS_TAP_CARRIER: src = b->car.p + c * b->apitch; cnt = last_n; break;
+    case FMRX_RDS_TAP_PLL_I: src = b->nco_i.p + c * b->npitch; cnt = last_n ? last_n + 1 : 0; break;
+    case FMRX_RDS_TAP_PLL_Q: src = b->nco_q.p + c * b->npitch; cnt = last_n ? last_n + 1 : 0; break;
+    case FMRX_RDS_TAP_RESAMPLED_I: src = b->ri.p + c * b->rpitch + b->Hr; cnt = last_out; break;
+    case FMRX_RDS_TAP_RRC_I: src = b->yi.p + c * b->ypitch; cnt = last_out; break;
+    case FMRX_RDS_TAP_RRC_Q: src = b->yq.p + c * b->ypitch; cnt = last_out; break;
+    case FMRX_RDS_TAP_PLL_STATE: src = b->state.p + 8 * c; cnt = 7; break;
+    default: return fail(FMRX_EINVAL, "rds_bank_read_tap: unknown tap %d", which);
+    }
+    *n = cnt;
+    if (!out || cnt == 0) return FMRX_OK;
+    FMRX_HIP(hipSetDevice(b->device));
+    FMRX_HIP(hipDeviceSynchronize());
+    FMRX_HIP(hipMemcpy(out, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    return FMRX_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,151 @@
+"""RDS banks (fmrx_rds_bank_*): time per call against the number of channels, device-resident discriminator rows.
+
+    python3 tools/rds_bank_bench.py [--mode 0] [--block 9600] [--channels 64,1024,4096,16384,65536] [--calls 8] [--warmup 2]
+                                    [--json out.json]
+
+Per channel count, reported separately:
+  process_dev  device-event time of fmrx_rds_bank_process_dev (the whole signal chain + CDR lanes, on one stream)
+  collect      host time of fmrx_rds_bank_collect once the device is done (bits D2H + per-channel frame synchronisation; the
+               matched-filter rows are not copied); collect_rrc: the same with both matched-filter rows copied to the host
+  x real time  N * (block / if_Fs) / (process_dev + collect)
+and, once: float64 operations per IF sample counted from the shapes, and the single-stream handle (fmrx_rds) on one of the same
+streams: process_dev device time and fmrx_rds_process host time per block.  Channel counts that do not fit the device's free
+memory are reported as skipped."""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def f64_ops_per_if_sample(p) -> dict:
+    """Multiplies and adds of the chain per IF sample (libm calls counted apart)."""
+    r = p.upsamp / p.decim
+    per_phase = 101                                   # taps of one polyphase branch (101*U taps)
+    ops = {
+        "channel_bpf": 2 * p.taps,
+        "carrier_bpf": 2 * p.taps + 1,                # (+ the square)
+        "pll": 9,                                     # phase detector inputs, loop filter, w*off + phase
+        "nco_mix": 2 + 4,
+        "resampler": r * 2 * (2 * per_phase + 1),     # I and Q, gain U
+        "rrc": r * 2 * 2 * p.rrc_taps,
+    }
+    ops["total"] = sum(ops.values())
+    ops["libm_calls"] = {"atan2": 1, "sincos": 2}
+    return ops
+
+
+def row_bytes(p, block: int) -> int:
+    """Device bytes per channel (the bank's rows, fmrx_rds_bank_create) plus the input row."""
+    no = block * p.upsamp // p.decim
+    pitch = lambda n: (n + 11) // 4 * 4
+    rows = (pitch(p.taps - 1 + block) + pitch(max(p.taps - 1, (p.taps - 1) // 2 + 1) + block) + 2 * pitch(block) + 2 * pitch(block + 1)
+            + 2 * pitch((101 * p.upsamp - 1) // p.upsamp + block) + 2 * pitch(p.rrc_taps - 1 + no) + 2 * pitch(no))
+    return 8 * rows + 4 * block + no // p.sps + 64
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", type=int, default=0)
+    ap.add_argument("--block", type=int, default=9600)
+    ap.add_argument("--channels", default="64,1024,4096,16384,65536")
+    ap.add_argument("--calls", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+
+    import torch
+    fmrx = importlib.import_module("software-defined-radio_amd")
+    from rds_signal import rds_demod_signal
+    if fmrx.device_count() < 1 or not torch.cuda.is_available():
+        raise SystemExit("rds_bank_bench: no GPU (there is no CPU path to measure)")
+    p = fmrx.RdsParams()
+    fmrx._check(fmrx.lib.fmrx_rds_mode_params(a.mode, ctypes.byref(p)))
+    block, calls = a.block, a.warmup + a.calls
+    period_s = block / p.if_Fs
+    # 64 distinct stations (seeds, chip offsets, amplitudes, noise); channel c carries station c % 64
+    S = 64
+    src = np.stack([rds_demod_signal(calls * block, float(p.if_Fs), seed=300 + s, amplitude=0.03 + 0.01 * (s % 7),
+                                     chip_offset=float((37 * s) % 101), noise=0.002 * (s % 4))[0] for s in range(S)])
+    d_src = torch.from_numpy(src).cuda()
+    results = {"mode": a.mode, "block": block, "block_ms": 1e3 * period_s, "f64_ops_per_if_sample": f64_ops_per_if_sample(p), "sweep": []}
+
+    # the single-stream handle, for comparison
+    r = fmrx.Rds(a.mode, max_block=block)
+    stream = torch.cuda.Stream()
+    dev_ms, host_ms = [], []
+    for k in range(calls):
+        row = d_src[0, k * block:(k + 1) * block]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        r.process_dev(row.data_ptr(), block, stream=stream.cuda_stream)
+        e1.record(stream)
+        e1.synchronize()
+        if k >= a.warmup:
+            dev_ms.append(e0.elapsed_time(e1))
+    for k in range(calls):
+        x = src[0, k * block:(k + 1) * block]
+        t0 = time.perf_counter()
+        r.process(x)
+        if k >= a.warmup:
+            host_ms.append(1e3 * (time.perf_counter() - t0))
+    r.close()
+    results["single_stream"] = {"process_dev_ms": statistics.median(dev_ms), "process_ms": statistics.median(host_ms),
+                                "x_real_time": 1e3 * period_s / statistics.median(host_ms)}
+    print(json.dumps({"single_stream": results["single_stream"]}), flush=True)
+
+    for n in [int(v) for v in a.channels.split(",")]:
+        free, _ = torch.cuda.mem_get_info()
+        need = n * row_bytes(p, block)
+        if need > 0.8 * free:
+            rec = {"channels": n, "skipped": f"needs {need / 1e9:.1f} GB, {free / 1e9:.1f} GB free"}
+            results["sweep"].append(rec)
+            print(json.dumps(rec), flush=True)
+            continue
+        bank = fmrx.RdsBank(a.mode, n, block)
+        rows = torch.empty((n, block), dtype=torch.float32, device="cuda")
+        idx = torch.arange(n, device="cuda") % S
+        pd, co, co_rrc = [], [], []
+        for k in range(calls):
+            rows.copy_(d_src[idx, k * block:(k + 1) * block])
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            bank.process_dev(rows.data_ptr(), block, stream=stream.cuda_stream)
+            e1.record(stream)
+            e1.synchronize()
+            t0 = time.perf_counter()
+            out = bank.collect(want_rrc=(k % 2 == 1))
+            t1 = time.perf_counter()
+            if k >= a.warmup:
+                pd.append(e0.elapsed_time(e1))
+                (co_rrc if k % 2 == 1 else co).append(1e3 * (t1 - t0))
+        synced = sum(o != " " for o in out["offset_type"])
+        bank.close()
+        del rows
+        t_pd, t_co = statistics.median(pd), statistics.median(co)
+        rec = {"channels": n, "process_dev_ms": t_pd, "process_dev_ms_min": min(pd), "process_dev_ms_max": max(pd), "collect_ms": t_co,
+               "collect_rrc_ms": statistics.median(co_rrc) if co_rrc else None, "call_ms": t_pd + t_co,
+               "x_real_time": n * 1e3 * period_s / (t_pd + t_co), "us_per_channel_block": 1e3 * (t_pd + t_co) / n,
+               "f64_gflops": n * block * results["f64_ops_per_if_sample"]["total"] / (t_pd * 1e6),
+               "offsets_reported_last_call": int(synced)}
+        results["sweep"].append(rec)
+        print(json.dumps(rec), flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(results, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
