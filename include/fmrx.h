@@ -462,8 +462,11 @@ FMRX_API int fmrx_fe_fir_decim_u8(const uint8_t *iq, size_t n_samples, const flo
 typedef struct fmrx_fe_plan fmrx_fe_plan;
 FMRX_API int fmrx_fe_plan_create(fmrx_fe_plan **out, const float *h, size_t taps, unsigned decim);
 FMRX_API int fmrx_fe_plan_destroy(fmrx_fe_plan *plan);
-/* 1 when a specialised (register-window, packed-FMA) kernel exists for the
- * plan's (taps, decim); 0 when it will run the generic kernel */
+/* 1 when the vector-ALU kernel (register window, packed FMA; fe_variant "valu")
+ * exists for the plan's (taps, decim), which needs h[0] == 0.  It says nothing
+ * about the matrix-core kernel (the default variant): that one runs for any taps
+ * fe_mfma_scale accepts (finite, max|h| in [1e-30, 1e30]) at its nine shapes,
+ * whatever this returns.  Otherwise the generic kernel runs. */
 FMRX_API int fmrx_fe_plan_is_specialised(const fmrx_fe_plan *plan);
 /* bytes of history kept in front of a block: 2*(taps-1) rounded up to a multiple
  * of 16, plus 16*decim (so the fused kernel can recompute the previous block's

@@ -8,11 +8,15 @@
 // tap times a byte only has to be right to a fraction of a float32 ulp of the SUM.  So the taps
 // are quantised once, on the host, to 24-bit fixed point q[k] = round(h[k] * 2^s) (s chosen so
 // max|q| < 2^23) and split into three signed base-256 digits q = d2*65536 + d1*256 + d0.  Three
-// int8 MFMAs per K-step accumulate sum_k d_i[k]*(u8[k]-128) EXACTLY in int32; the epilogue forms
-// (acc2*65536 + acc1*256 + acc0) * 2^-(s+7) with two roundings.  The result is the correctly
-// rounded FIR with taps perturbed by <= 2^-(s+1) ~ 4e-9 each: closer to the real-number answer
-// than the reference's own 101-term float32 accumulation (tests: <= 2e-6 relative RMS of the
-// oracle, as for any reordering of that sum; silence stays exactly 0).
+// int8 MFMAs per K-step accumulate sum_k d_i[k]*(u8[k]-128) EXACTLY in int32; the epilogue is
+// fmaf(float(acc2), 2^16*sc, float(acc0 + 256*acc1)*sc), sc = 2^-(s+7).  Two roundings: float(lo)
+// rounds once |lo| > 2^24, so the result is NOT always the correctly rounded sum_k q[k]*x[k]*sc (near
+// cancellation between the two terms it can be many ulp from it), but it is within
+//   sum_k |x_k|/128 * 2^-(s+1) + 2^-24 |float(lo)*sc| + 2^-24 |y|
+// of the real-number FIR (taps perturbed by <= 2^-(s+1) ~ 4e-9 each): closer to it than the
+// reference's own 101-term float32 accumulation.  Every output is determined to the bit by that
+// integer arithmetic: tests/test_gpu_fe_exact.py compares it with an integer model
+// (tests/_fe_model.py); silence stays exactly 0.
 //
 // Shape.  One MFMA tile = v_mfma_i32_16x16x64_i8:
 //   rows    (M=16) = 8 consecutive IF outputs x {I, Q}
