@@ -647,8 +647,8 @@ __global__ void chs_resample_exact_kernel(const float *__restrict__ demod, long 
 // alone, so for 64 channels at once the taps are wave-uniform -- SGPR operands from a step-major table, as in the exact FIRs
 // above -- and only the samples are per lane.  A wave owns kRS = 7 consecutive outputs of 64 channels at a time (both modes' U are
 // multiples of 7: groups never straddle a period, the table has U / 7 groups) and visits their common window newest sample first:
-// output r meets its taps j ascending (the reference's order, src/filter.cpp:205-212) while one sample per lane and step feeds all
-// seven outputs; (mono, stereo) -- in mono banks two neighbouring outputs -- ride in the two halves of the packed instructions.
+// output r meets its taps j ascending (the reference's order, src/filter.cpp:205-212; the fast bank fuses each product and sum
+// into one fma, the exact bank rounds them separately) while one sample per lane and step feeds all seven outputs; (mono, stereo) -- in mono banks two neighbouring outputs -- ride in the two halves of the packed instructions.
 // Samples reach the lanes through LDS, 32 per channel and batch (below: why not lane = channel for the loads too); the taps of
 // four steps are two s_load_dwordx16, requested one iteration ahead.  Outside a group's window the table holds zeros: acc + 0*x
 // leaves acc as it is (acc is never -0: it starts at +0 and sums round to nearest), rows are finite, and the rows' histories

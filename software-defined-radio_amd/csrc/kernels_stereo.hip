@@ -10,8 +10,10 @@
 // wave's loads walk 2.4 KB of contiguous, L1-resident data) -- no LDS, no barrier.
 // ~101 packed FMAs per IF sample for both filters.
 //
-// Numerics: one FMA per tap, taps ascending in n as the reference does; differs
-// from its separate multiply/add by float32 rounding only (generic kernel = exact).
+// Numerics: one FMA per tap, starting from +0, taps DESCENDING in n (the window's oldest
+// sample, h[T-1], first; the reference sums them ascending), so it differs from the
+// reference's separate multiply/add by float32 rounding only (generic kernel = exact).
+// tests/test_gpu_fir_exact.py pins that order bit for bit.
 #include "device_math.hpp"
 #include "fmrx_internal.hpp"
 
