@@ -10,10 +10,15 @@ src/threadMonoOnly.cpp:185-191), synthetic 2.4 MS/s FM I/Q, blocks of 1,024,000 
 "step" = one pass of the whole chain over a device-resident batch of `--blocks` (default 1024)
 consecutive blocks of ONE stream (2.1 GB of u8 I/Q: 8 x the 256 MiB Infinity Cache), submitted as one block-parallel call: an offline,
 one-long-stream figure (a live 2.4 MS/s channel delivers 51,200-sample blocks; the per-block latency of
-that regime is reported separately as `small_block`).  The mono chain is a sliding-window map of its
+that regime is reported separately as `small_block`, with --full).  The mono chain is a sliding-window map of its
 input, so the block-parallel call equals block-by-block streaming
 (tests/test_gpu_parity.py::test_fused_mono_kernel, ::test_block_split_invariance_on_device).  Inputs are
 resident in HBM when the timed region starts; the s16 PCM is written to HBM.
+
+A plain run does what the headline needs: set up, settle, warm up, time the K steps, dump (--dump-outputs)
+and print.  --full (N=1) then measures everything else: the side legs (the other modes, stereo, receiver
+banks, the S1 / S2 kernels, small blocks, host buffers, the CLI, RDS, streaming reads), the CPU baseline,
+and with --fe-variant valu the front-end kernel's share of the step that the roofline reports.
 
 N>1: one process per GPU, one independent channel per GPU (seed + rank), no data-path collective: weak
 scaling.  `python bench.py --gpus N` starts the N ranks itself (child processes, control plane over
@@ -601,9 +606,12 @@ def main() -> int:
     ap.add_argument("--fe-variant", default="mfma", choices=["mfma", "valu"],
                     help="mfma (default): matrix-core kernels, whole mono chain fused; valu: the vector-ALU kernels "
                          "(front end + discriminator, then the audio kernel) -- the 'no MFMA' form of the north star")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-legs", action="store_true", help="skip the N=1 side measurements (other modes, S1/S2 kernels, copy probe)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else (N=1): the side legs, the CPU baseline, and with "
+                         "--fe-variant valu the front-end kernel's share of the step; a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full: skip the N=1 side measurements (other modes, S1/S2 kernels, copy probe)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: the CPU baseline's time budget")
     ap.add_argument("--dist-backend", default="gloo", choices=["gloo", "nccl"],
                     help="control-plane backend for N>1 (barrier + max of the elapsed time only; gloo: RCCL stays unused as the north star says)")
     ap.add_argument("--all-on-device0", action="store_true", help="rehearsal: every rank uses GPU 0")
@@ -686,7 +694,9 @@ def main() -> int:
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, d_pcm.cpu().numpy(), B)
     fused = args.fe_variant == "mfma"
-    if not fused:   # vector-ALU variant: the step is two kernels; the front end's share from the handle's event brackets
+    if not fused and not args.full:   # the front end's share below takes profiled steps of its own
+        fe_ms = None
+    elif not fused:   # vector-ALU variant: the step is two kernels; the front end's share from the handle's event brackets
         pl.set_profiling(4)
         for _ in range(16):
             step()
@@ -696,7 +706,7 @@ def main() -> int:
         fe_ms = max(fe_ms - t4["audio_ms"] / c4, 1e-6)
 
     legs = {}
-    if world == 1 and fused and not args.no_side_legs:
+    if args.full and world == 1 and fused and not args.no_side_legs:
         legs = side_legs(torch, fmrx, synth, args, pl, step, d_iq, n_bytes, stream)
 
     out = None
@@ -704,7 +714,7 @@ def main() -> int:
         value = job_throughput(world, n_samples, args.steps, elapsed)
         bytes_per_sample = S3_BYTES if fused else S2_BYTES
         fe_bytes = bytes_per_sample * n_samples
-        achieved = fe_bytes / (fe_ms * 1e-3) / 1e9
+        achieved = None if fe_ms is None else fe_bytes / (fe_ms * 1e-3) / 1e9
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "fe_traffic.json")   # PMC-derived bytes per launch of this command
         if fused and os.path.exists(tpath):
@@ -740,14 +750,16 @@ def main() -> int:
                 "algorithmic_bytes_per_sample": round(bytes_per_sample, 3),
                 "algorithmic_bytes_note": "SURVEY 8d S3 (whole mono chain, s16 out: 2 + 2/50)" if fused else "SURVEY 8d S2 (2 + 4/10)",
                 "fe_variant": args.fe_variant,
-                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "algorithmic_bytes_per_launch": int(fe_bytes), "avg_launch_ms": round(fe_ms, 4),
+                "bound": "hbm", "achieved": None if fe_ms is None else round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": None if fe_ms is None else round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                "algorithmic_bytes_per_launch": int(fe_bytes), "avg_launch_ms": None if fe_ms is None else round(fe_ms, 4),
                 "launches_timed": args.steps,
                 "timing": "HIP events on the launch stream around the K timed launches / K (dispatch gaps included, nothing subtracted)",
-                "useful_tflops": round(FE_FLOP_PER_SAMPLE * n_samples / (fe_ms * 1e-3) / 1e12, 2),
+                "useful_tflops": None if fe_ms is None else round(FE_FLOP_PER_SAMPLE * n_samples / (fe_ms * 1e-3) / 1e12, 2),
             },
         }
+        if fe_ms is None:
+            out["roofline"]["note"] = "the front-end kernel's share of the two-kernel step is measured with --full"
         if legs:
             out["north_star_form"] = legs.pop("north_star_form")
             reads = legs.pop("measured_streaming_GBs", None)
@@ -757,7 +769,7 @@ def main() -> int:
                 if best:
                     out["roofline"]["frac_of_best_measured_streaming"] = round(achieved / best, 4)
             out["legs"] = legs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     if dist is not None:
         dist.barrier()

@@ -1,6 +1,7 @@
 """bench.py's one-line JSON contract: on a box without a GPU it must say so and exit non-zero
-(libfmrx has no CPU fallback); on the GPU a tiny run must carry every field the driver reads plus
-the `roofline` and `cpu_baseline` objects."""
+(libfmrx has no CPU fallback); on the GPU a tiny plain run must carry every field the driver reads
+and the `roofline` object and nothing that --full measures, and a tiny --full run the side legs and
+the `cpu_baseline` object as well."""
 import json
 import os
 import subprocess
@@ -26,7 +27,7 @@ def test_bench_without_gpu_fails_loudly(fmrx):
 
 @pytest.mark.gpu
 def test_bench_json_contract(fmrx):
-    rc, out, err = _run("--steps", "8", "--warmup", "2", "--blocks", "64", "--settle-ms", "50", "--cpu-seconds", "0.5")
+    rc, out, err = _run("--steps", "8", "--warmup", "2", "--blocks", "64", "--settle-ms", "50", "--cpu-seconds", "0.5", "--full")
     assert rc == 0, err
     for k, typ in [("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                    ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
@@ -71,6 +72,27 @@ def test_bench_json_contract(fmrx):
     hb = out["legs"]["host_buffers"]
     assert "error" not in hb and hb["h2d_GBs"] > 5 and hb["value"] > 1000, hb
     assert out["legs"]["cli_stdin_stdout"]["rc"] == 0 and out["legs"]["cli_stdin_stdout"]["output_bytes"] * 50 == out["legs"]["cli_stdin_stdout"]["input_bytes"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_only(fmrx):
+    """Without --full the line carries the headline and the fused kernel's roofline (from the timed steps' own events) and
+    nothing that takes runs of its own: no side legs, no CPU baseline; with --fe-variant valu no front-end share either."""
+    rc, out, err = _run("--steps", "8", "--warmup", "2", "--blocks", "64", "--settle-ms", "50")
+    assert rc == 0, err
+    for k, typ in [("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool),
+                   ("dtype", str), ("config", dict), ("roofline", dict)]:
+        assert isinstance(out[k], typ), (k, out.get(k))
+    assert out["steps"] == 8 and out["warmup"] == 2 and out["dtype"] == "i8+f32" and out["higher_is_better"] is True
+    assert abs(out["value"] - out["config"]["samples_per_step_per_gpu"] / (out["ms_per_step"] * 1e-3) / 1e6) / out["value"] < 0.01
+    r = out["roofline"]
+    assert 0.05 < r["frac"] < 1.0 and 0 < r["avg_launch_ms"] <= out["ms_per_step"] * 1.02 and r["launches_timed"] == 8
+    assert not {"legs", "north_star_form", "cpu_baseline"} & set(out) and "measured_streaming_GBs" not in r
+    rc, out, err = _run("--steps", "4", "--warmup", "1", "--blocks", "16", "--settle-ms", "0", "--fe-variant", "valu")
+    assert rc == 0 and out["dtype"] == "f32" and out["value"] > 0, err
+    r = out["roofline"]
+    assert r["fe_variant"] == "valu" and r["avg_launch_ms"] is None and r["frac"] is None and "--full" in r["note"]
+    assert not {"legs", "north_star_form", "cpu_baseline"} & set(out)
 
 
 def test_dump_outputs_writes_every_block_or_a_fixed_sample(tmp_path):
