@@ -138,12 +138,9 @@ int fmrx_channels_create_ex(fmrx_channels **out, const fmrx_params *p, int n_cha
     c->block_bytes = block_bytes;
     c->opt = options_snapshot();
     auto body = [&]() -> int {
-        std::vector<float> h(p->rf_taps);
-        design_lpf(static_cast<float>(p->rf_Fs), 100000.0f, p->rf_taps, h.data());        // src/project.cpp:50
-        FMRX_TRY(fe_plan_init(c->fe, h.data(), p->rf_taps, p->rf_decim));
-        h.resize(p->audio_taps);
-        design_lpf(static_cast<float>(p->if_Fs), 16000.0f, p->audio_taps, h.data());      // src/project.cpp:321
-        FMRX_TRY(audio_plan_init(c->audio, h.data(), p->audio_taps, p->audio_decim));
+        const Filters f = design_filters(*p, false);
+        FMRX_TRY(fe_plan_init(c->fe, f.rf.data(), p->rf_taps, p->rf_decim));
+        FMRX_TRY(audio_plan_init(c->audio, f.audio.data(), p->audio_taps, p->audio_decim));
         // samples an audio output reaches back: rf_decim*audio_taps + rf_taps - 1, plus what the kernel's tiles read in
         // front of a run (one IF sample for the discriminator, 16-byte rounding): rounded up to whole audio samples
         // and 16-byte multiples

@@ -1141,28 +1141,24 @@ int stereo_bank_create(StereoBank **out, const fmrx_params &p, int n_channels, i
     b->opt = options_snapshot();
     b->block_bytes = block_bytes;
     auto body = [&]() -> int {
-        std::vector<float> h(p.rf_taps);
-        design_lpf(static_cast<float>(p.rf_Fs), 100000.0f, p.rf_taps, h.data());             // src/project.cpp:50
-#define X(T_, D_) if (p.rf_taps == T_ && p.rf_decim == D_) FMRX_TRY((fe_table_init<T_, D_>(*b, h.data())));
+        const Filters f = design_filters(p, audio_channels == 2);
+#define X(T_, D_) if (p.rf_taps == T_ && p.rf_decim == D_) FMRX_TRY((fe_table_init<T_, D_>(*b, f.rf.data())));
         CHS_FE_CASES(X)
 #undef X
         if (!b->exact) {   // the matrix-core front end (int8 MFMA on the raw bytes): its tap image, and the history its windows reach
-            FMRX_TRY(fe_plan_init(b->fe, h.data(), p.rf_taps, p.rf_decim));
+            FMRX_TRY(fe_plan_init(b->fe, f.rf.data(), p.rf_taps, p.rf_decim));
             const int lead = fe_mfma_bank_lead(b->fe);
             if (!b->fe.mfma || lead < 0) return fail(FMRX_EINVAL, "channels: no matrix-core front end for rf %d taps / decim %d", p.rf_taps, p.rf_decim);
             const size_t need = (static_cast<size_t>(lead) + 15) / 16 * 16;
             if (need > b->hist_bytes) b->hist_bytes = need;
         }
         b->resample = p.audio_upsamp > 0;
-        std::vector<float> ha(p.audio_taps);
-        // src/project.cpp:321-323: the resampling modes design the filter at the upsampled rate
-        design_lpf(static_cast<float>(b->resample ? p.if_Fs * p.audio_upsamp : p.if_Fs), 16000.0f, p.audio_taps, ha.data());
         if (b->resample) {
             FMRX_TRY(b->h_res.alloc(p.audio_taps));
-            FMRX_HIP(hipMemcpy(b->h_res.p, ha.data(), p.audio_taps * sizeof(float), hipMemcpyHostToDevice));
-            FMRX_TRY(resample_lanes_table_init(*b, ha.data()));
+            FMRX_HIP(hipMemcpy(b->h_res.p, f.audio.data(), p.audio_taps * sizeof(float), hipMemcpyHostToDevice));
+            FMRX_TRY(resample_lanes_table_init(*b, f.audio.data()));
         } else {
-#define X(T_, D_) if (p.audio_taps == T_ && p.audio_decim == D_) FMRX_TRY((out_table_init<T_, D_>(*b, ha.data())));
+#define X(T_, D_) if (p.audio_taps == T_ && p.audio_decim == D_) FMRX_TRY((out_table_init<T_, D_>(*b, f.audio.data())));
             CHS_OUT_CASES(X)
 #undef X
         }
@@ -1194,10 +1190,7 @@ int stereo_bank_create(StereoBank **out, const fmrx_params &p, int n_channels, i
         FMRX_TRY(b->demod.alloc(b->dpitch * N + 64));
         FMRX_HIP(hipMemset(b->demod.p, 0, b->demod.bytes()));
         if (audio_channels == 2) {
-            std::vector<float> hc(p.stereo_taps), hs(p.stereo_taps);
-            design_bpf(static_cast<float>(p.if_Fs), 18.5e3f, 19.5e3f, p.stereo_taps, hc.data());   // src/project.cpp:172
-            design_bpf(static_cast<float>(p.if_Fs), 22e3f, 54e3f, p.stereo_taps, hs.data());       // :173
-#define X(T_) if (p.stereo_taps == T_) FMRX_TRY(bpf_table_init<T_>(*b, hs.data(), hc.data()));
+#define X(T_) if (p.stereo_taps == T_) FMRX_TRY(bpf_table_init<T_>(*b, f.stereo.data(), f.pilot.data()));
             CHS_BPF_CASES(X)
 #undef X
             if (b->exact) {

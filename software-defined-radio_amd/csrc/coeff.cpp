@@ -46,6 +46,25 @@ void design_bpf(float Fs, float Fb, float Fe, int taps, float *h)
     }
 }
 
+// The reference designs these from its PARAMS (src/project.cpp:50, 172-173, 321-323); the same float arguments give the same taps
+Filters design_filters(const fmrx_params &p, bool stereo)
+{
+    Filters f;
+    f.rf.resize(p.rf_taps);
+    design_lpf(static_cast<float>(p.rf_Fs), 100000.0f, p.rf_taps, f.rf.data());   // src/project.cpp:50
+    f.audio.resize(p.audio_taps);
+    // src/project.cpp:321-323: the resampling modes design the filter at the upsampled rate
+    const int audio_fs = p.audio_upsamp > 0 ? p.if_Fs * p.audio_upsamp : p.if_Fs;
+    design_lpf(static_cast<float>(audio_fs), 16000.0f, p.audio_taps, f.audio.data());
+    if (stereo) {
+        f.pilot.resize(p.stereo_taps);
+        f.stereo.resize(p.stereo_taps);
+        design_bpf(static_cast<float>(p.if_Fs), 18.5e3f, 19.5e3f, p.stereo_taps, f.pilot.data());   // src/project.cpp:172
+        design_bpf(static_cast<float>(p.if_Fs), 22e3f, 54e3f, p.stereo_taps, f.stereo.data());      // :173
+    }
+    return f;
+}
+
 }  // namespace fmrx
 
 extern "C" {

@@ -309,5 +309,10 @@ int stereo_bank_read_tap(StereoBank *b, int channel, int which, float *out, size
 // ---- host-side coefficient design (coeff.cpp) --------------------------------
 void design_lpf(float Fs, float Fc, int taps, float *h);
 void design_bpf(float Fs, float Fb, float Fe, int taps, float *h);
+// the reference's filters of one receiver: rf and audio low-pass; with `stereo`, the pilot and stereo band-pass
+struct Filters {
+    std::vector<float> rf, audio, pilot, stereo;
+};
+Filters design_filters(const fmrx_params &p, bool stereo);
 
 }  // namespace fmrx

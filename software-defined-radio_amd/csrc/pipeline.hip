@@ -58,7 +58,7 @@ struct fmrx_pipeline {
     int fe_cur = 0;
     DevBuf<float> prev_iq[2];
     int prev_cur = 0;
-    DevBuf<float> ifb, mono, tmp_hist;
+    DevBuf<float> ifb, mono;
     // discriminator output, two buffers [Hd | n_if] used alternately: the history of a block is the
     // tail of the previous block's buffer, so nothing has to be copied between blocks unless a kernel
     // needs it contiguous in front of its input (materialise_history)
@@ -66,17 +66,21 @@ struct fmrx_pipeline {
     int demod_last = 0;          // buffer that holds the last processed block
     size_t demod_n_last = 0;     // its length; its history front is valid iff demod_front[demod_last]
     bool demod_front[2] = {true, true};
-    DevBuf<float> carrier, bpf, pll, pll_state, pll_scratch, mixer, st_final, left, right;
-    // option overlap_calls (stereo, modes 0/1, parallel PLL): the three stages of a call run on internal streams, a call apart
-    // each -- front (front end, band-pass pair, the PLL's chunk records), PLL (lanes + repair), output stage -- on the buffer
-    // set of the call's parity (set 0 = the buffers above); the caller's stream waits for the output stage's event
-    DevBuf<float> carrier1, bpf1, pll1, lti_rec[2];
+    DevBuf<float> pll_state, pll_scratch, mixer, st_final, left, right;
+    // the stereo intermediates a call writes: set[0] always, except under option overlap_calls (stereo, modes 0/1, parallel
+    // PLL), where the three stages of a call run on internal streams, a call apart each -- front (front end, band-pass pair,
+    // the PLL's chunk records), PLL (lanes + repair), output stage -- on the set of the call's parity; the caller's stream
+    // waits for the output stage's event
+    struct StereoSet {
+        DevBuf<float> carrier, bpf, pll;
+    } set[2];
+    int last_set = 0;                // set the last call used (read_tap)
+    DevBuf<float> lti_rec[2];
     hipStream_t ov_stream[3] = {};   // front, PLL, output
     hipEvent_t ov_done[3][2] = {};   // [stage][parity]: the stage of the last call of that parity has finished
     hipEvent_t ov_entry = nullptr;   // the caller's stream at the call: what it did with the previous output is over
     bool ov_ready = false;           // overlap_setup has completed
     int ov_active = 0;               // the regime (option value) of the last call
-    int last_set = 0;                // buffer set the last call used (read_tap)
     // state_stereofilt: the mixer output's last Hm samples (index Hm+g holds sample g < 0), written by one call
     // and read by the next: two buffers used alternately, mix_cur = the one the next call reads
     DevBuf<float> mix_tail[2];
@@ -102,6 +106,23 @@ struct fmrx_pipeline {
     static constexpr int kRing = 128;
     hipEvent_t ev[kRing][4] = {};
     unsigned long calls = 0;      // profiled calls since profiling was enabled
+
+    ~fmrx_pipeline()
+    {
+        for (hipStream_t st : {stream, stream2, ov_stream[0], ov_stream[1], ov_stream[2]})
+            if (st) {
+                (void)hipStreamSynchronize(st);
+                (void)hipStreamDestroy(st);
+            }
+        for (auto &q : ev)
+            for (auto &e : q)
+                if (e) (void)hipEventDestroy(e);
+        for (auto &q : ov_done)
+            for (auto &e : q)
+                if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_kern[0], ev_kern[1], ev_done[0], ev_done[1], ov_entry})
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
@@ -240,17 +261,12 @@ int fmrx_pipeline_create(fmrx_pipeline **out, const fmrx_params *p, int channels
         FMRX_HIP(hipStreamCreateWithFlags(&pl->stream, hipStreamNonBlocking));
         for (auto &q : pl->ev)
             for (auto &e : q) FMRX_HIP(hipEventCreate(&e));
-        // coefficients: project.cpp:50 (rf), :321-323 (audio), :172-173 (stereo)
-        std::vector<float> h(p->rf_taps);
-        design_lpf(static_cast<float>(p->rf_Fs), static_cast<float>(100000), p->rf_taps, h.data());
-        FMRX_TRY(fe_plan_init(pl->fe, h.data(), p->rf_taps, p->rf_decim));
-        h.resize(p->audio_taps);
-        const int design_fs = pl->resample ? p->if_Fs * p->audio_upsamp : p->if_Fs;
-        design_lpf(static_cast<float>(design_fs), static_cast<float>(16000), p->audio_taps, h.data());
+        const Filters f = design_filters(*p, channels == 2);
+        FMRX_TRY(fe_plan_init(pl->fe, f.rf.data(), p->rf_taps, p->rf_decim));
         if (pl->resample) {
-            FMRX_TRY(resample_plan_init(pl->rs, h.data(), p->audio_taps, p->audio_decim, p->audio_upsamp));
+            FMRX_TRY(resample_plan_init(pl->rs, f.audio.data(), p->audio_taps, p->audio_decim, p->audio_upsamp));
         } else {
-            FMRX_TRY(audio_plan_init(pl->audio, h.data(), p->audio_taps, p->audio_decim));
+            FMRX_TRY(audio_plan_init(pl->audio, f.audio.data(), p->audio_taps, p->audio_decim));
         }
         const size_t n_max = max_block_bytes / 2;
         const size_t n_if = n_max / p->rf_decim;
@@ -265,16 +281,12 @@ int fmrx_pipeline_create(fmrx_pipeline **out, const fmrx_params *p, int channels
             FMRX_TRY(pl->demod_buf[i].alloc(pl->Hd + n_if + 16 + kResampleBack));
             FMRX_HIP(hipMemset(pl->demod_buf[i].p, 0, (pl->Hd + n_if + 16 + kResampleBack) * sizeof(float)));
         }
-        FMRX_TRY(pl->tmp_hist.alloc(pl->Hd + pl->Hm + 16));
         FMRX_TRY(pl->mono.alloc(n_au));
         if (channels == 2) {
-            std::vector<float> hc(p->stereo_taps), hs(p->stereo_taps);
-            design_bpf(static_cast<float>(p->if_Fs), 18.5e3f, 19.5e3f, p->stereo_taps, hc.data());
-            design_bpf(static_cast<float>(p->if_Fs), 22e3f, 54e3f, p->stereo_taps, hs.data());
-            FMRX_TRY(bpf_pair_plan_init(pl->bpf_plan, hs.data(), hc.data(), p->stereo_taps));
-            FMRX_TRY(pl->carrier.alloc(n_if + 16));
-            FMRX_TRY(pl->bpf.alloc(n_if + 16));
-            FMRX_TRY(pl->pll.alloc(n_if + 17));
+            FMRX_TRY(bpf_pair_plan_init(pl->bpf_plan, f.stereo.data(), f.pilot.data(), p->stereo_taps));
+            FMRX_TRY(pl->set[0].carrier.alloc(n_if + 16));
+            FMRX_TRY(pl->set[0].bpf.alloc(n_if + 16));
+            FMRX_TRY(pl->set[0].pll.alloc(n_if + 17));
             FMRX_TRY(pl->pll_state.alloc(8));
             FMRX_TRY(pl->pll_scratch.alloc(pll_parallel_scratch_floats(n_if)));
             FMRX_HIP(hipMemset(pl->pll_scratch.p, 0, 8 * sizeof(float)));
@@ -301,30 +313,6 @@ int fmrx_pipeline_destroy(fmrx_pipeline *pl)
 {
     if (!pl) return FMRX_OK;
     (void)hipSetDevice(pl->device);
-    if (pl->stream) {
-        (void)hipStreamSynchronize(pl->stream);
-        (void)hipStreamDestroy(pl->stream);
-    }
-    for (auto &q : pl->ev)
-        for (auto &e : q)
-            if (e) (void)hipEventDestroy(e);
-    if (pl->stream2) {
-        (void)hipStreamSynchronize(pl->stream2);
-        (void)hipStreamDestroy(pl->stream2);
-    }
-    for (auto &e : pl->ev_kern)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : pl->ev_done)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &st : pl->ov_stream)
-        if (st) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-    for (auto &q : pl->ov_done)
-        for (auto &e : q)
-            if (e) (void)hipEventDestroy(e);
-    if (pl->ov_entry) (void)hipEventDestroy(pl->ov_entry);
     delete pl;
     return FMRX_OK;
 }
@@ -390,9 +378,9 @@ static int overlap_setup(fmrx_pipeline *pl)
     // every handle is created only where it is still missing: a call that failed half way (out of memory, say) is simply
     // continued by the next one, nothing is created twice and nothing leaks (destroy frees whatever exists)
     const size_t n_if = (pl->max_bytes / 2) / pl->p.rf_decim;
-    FMRX_TRY(pl->carrier1.ensure(pl->carrier.n));
-    FMRX_TRY(pl->bpf1.ensure(pl->bpf.n));
-    FMRX_TRY(pl->pll1.ensure(pl->pll.n));
+    FMRX_TRY(pl->set[1].carrier.ensure(pl->set[0].carrier.n));
+    FMRX_TRY(pl->set[1].bpf.ensure(pl->set[0].bpf.n));
+    FMRX_TRY(pl->set[1].pll.ensure(pl->set[0].pll.n));
     for (auto &b : pl->lti_rec) FMRX_TRY(b.ensure(pll_parallel_lti_floats(n_if) + 2));
     for (auto &q : pl->ov_done)
         for (auto &e : q)
@@ -404,272 +392,326 @@ static int overlap_setup(fmrx_pipeline *pl)
     return FMRX_OK;
 }
 
+// ---- one process call, in stages ----------------------------------------------------------
+// What the stages of one call share: the caller's arguments, then what call_setup derives from them
+struct Call {
+    const uint8_t *iq;
+    size_t n_bytes;
+    float *audio_f32;            // the caller's outputs (either may be null)
+    int16_t *pcm16;
+    int pcm_policy;
+    hipStream_t s;               // the caller's stream
+    hipStream_t sf, sp, so;      // front (front end, band-pass pair), PLL, stereo output stage: s but under overlap_calls
+    size_t n, n_if, n_au;
+    int cur;                     // this block's discriminator buffer (the other one holds the last block's); overlap parity
+    float *dbuf, *demod;         // that buffer [Hd | n_if], and its block region
+    const float *hist_end;       // one past the previous block's last discriminator sample
+    const uint8_t *hist;         // the front end's byte history and IF[-1]; *_next: where the next block's go
+    uint8_t *hist_next;
+    const float *prev;
+    float *prev_next;
+    bool keep_if;                // the IF stream is materialised
+    bool ovl;                    // option overlap_calls applies
+    bool fused;                  // the fused mono kernel does the whole call
+    bool prof;                   // the call records the event quadruple ev
+    hipEvent_t *ev;
+};
+
+// profiling: event k of the call's quadruple {start, after the front end, after the audio stage, end}, on the caller's stream
+static int mark(const Call &c, int k)
+{
+    if (c.prof) FMRX_HIP(hipEventRecord(c.ev[k], c.s));
+    return FMRX_OK;
+}
+
+// for kernels that index history at negative offsets of their input
+static int materialise_history(fmrx_pipeline *pl, const Call &c)
+{
+    FMRX_HIP(hipMemcpyAsync(c.dbuf, c.hist_end - pl->Hd, pl->Hd * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    pl->demod_front[c.cur] = true;
+    return FMRX_OK;
+}
+
+// after the front end: the next block's IF[-1], byte history (unless the front-end kernel wrote it: hist_done) and
+// discriminator history are this block's
+static void advance_state(fmrx_pipeline *pl, const Call &c, bool hist_done)
+{
+    pl->prev_cur ^= 1;
+    pl->prev_override = false;
+    pl->fe_cur ^= 1;
+    const int hb = pl->fe.hist_bytes;
+    if (!hist_done)
+        hipLaunchKernelGGL(hist_update_kernel, dim3((hb + 255) / 256), dim3(256), 0, c.sf, c.hist, c.iq,
+                           static_cast<long>(c.n_bytes), hb, c.hist_next);
+    pl->demod_last = c.cur;
+    pl->demod_n_last = c.n_if;
+}
+
+static int call_setup(fmrx_pipeline *pl, Call &c)
+{
+    const fmrx_params &p = pl->p;
+    c.sf = c.sp = c.so = c.s;
+    c.n = c.n_bytes / 2;
+    c.n_if = c.n / p.rf_decim;
+    c.n_au = n_audio_of(pl, c.n_bytes);
+    pl->last_n_if = c.n_if;
+    pl->last_n_audio = c.n_au;
+    // this block's discriminator output goes to the buffer the previous block did not use
+    c.cur = pl->demod_last ^ 1;
+    c.dbuf = pl->demod_buf[c.cur].p;
+    c.demod = c.dbuf + pl->Hd;
+    c.hist_end = pl->demod_buf[pl->demod_last].p + pl->Hd + pl->demod_n_last;
+    pl->demod_front[c.cur] = false;
+    c.hist = pl->fe_hist[pl->fe_cur].p;
+    c.hist_next = pl->fe_hist[pl->fe_cur ^ 1].p;
+    c.prev = pl->prev_iq[pl->prev_cur].p;
+    c.prev_next = pl->prev_iq[pl->prev_cur ^ 1].p;
+    // events around every prof_every-th call: a record costs ~5 us of stream time
+    c.prof = pl->profiling && (pl->seq++ % static_cast<unsigned long>(pl->prof_every) == 0);
+    c.ev = pl->ev[pl->calls % fmrx_pipeline::kRing];
+    FMRX_TRY(mark(c, 0));
+    const bool mfma = pl->opt.fe_variant == 0;
+    // option demod = 1: the model's arctangent demodulator on the IF stream (materialised for it), instead of the front-end kernels' own discriminator
+    c.keep_if = pl->keep_if || pl->opt.demod == 1;
+    // option overlap_calls: front | PLL | output stage of the stereo chain of consecutive calls on internal streams (see the struct)
+    c.ovl = pl->opt.overlap_calls != 0 && pl->channels == 2 && !pl->resample && !pl->force_generic && !c.keep_if &&
+            !pl->profiling && pl->opt.pll_mode == 0 && mfma && c.n_if >= static_cast<size_t>(pl->Hd) &&
+            fe_mfma_available(pl->fe, c.iq, c.n, c.hist) && stereo_out_available(p.audio_taps, p.audio_decim);
+    c.fused = pl->channels == 1 && !pl->resample && !pl->force_generic && !c.keep_if && mfma &&
+              c.n_if >= static_cast<size_t>(pl->Hd) && static_cast<long>(c.n_au) >= pl->opt.fused_min_audio &&
+              mono_fused_available(pl->fe, pl->audio, c.iq, c.n, c.hist);
+    return FMRX_OK;
+}
+
+static int overlap_begin(fmrx_pipeline *pl, Call &c)
+{
+    const int regime = c.ovl ? pl->opt.overlap_calls : 0;
+    if (regime != pl->ov_active) {   // change of regime between calls: everything in flight first
+        FMRX_HIP(hipDeviceSynchronize());
+        pl->ov_active = regime;
+    }
+    if (c.ovl) FMRX_TRY(overlap_setup(pl));
+    pl->last_set = c.ovl ? c.cur : 0;
+    if (!c.ovl) return FMRX_OK;
+    // overlap_calls 1: the front on an internal stream, PLL and output stage on the caller's (fewest event operations: at these
+    // step sizes the host's enqueue rate is the next limit); 2: all three on internal streams
+    c.sf = pl->ov_stream[0];
+    if (pl->opt.overlap_calls >= 2) {
+        c.sp = pl->ov_stream[1];
+        c.so = pl->ov_stream[2];
+    }
+    // the front writes this parity's buffers: the last call of the same parity must be through with them; the output
+    // stage writes the caller's buffers: whatever the caller's stream still does with them comes first (the input is the
+    // one thing the option vouches for)
+    FMRX_HIP(hipStreamWaitEvent(c.sf, pl->ov_done[2][c.cur], 0));
+    if (c.so != c.s) {
+        FMRX_HIP(hipEventRecord(pl->ov_entry, c.s));
+        FMRX_HIP(hipStreamWaitEvent(c.so, pl->ov_entry, 0));
+    }
+    return FMRX_OK;
+}
+
+// ---- RF_FrontEnd + RF_MONO of modes 0/1 in one kernel (kernels_fe_mfma.hip): the discriminator output stays on chip;
+//      only its tail (state_mono) is written for the next block ----
+static int fused_mono(fmrx_pipeline *pl, const Call &c)
+{
+    const bool hist_done = c.n_bytes >= static_cast<size_t>(pl->fe.hist_bytes);
+    // f32 audio is written only where somebody will read it: the caller's buffer, or the handle's own when
+    // no PCM was asked for either (read_tap); PCM-only callers get the reference's output format and nothing else
+    float *dst = c.audio_f32 ? c.audio_f32 : (c.pcm16 ? nullptr : pl->mono.p);
+    FMRX_TRY(mono_fused_launch(pl->fe, pl->audio, c.iq, c.n, c.hist, c.prev, c.hist_end, c.demod, pl->Hd, c.prev_next, dst,
+                               c.pcm16, c.pcm_policy, hist_done ? c.hist_next : nullptr, pl->opt, c.s));
+    pl->if_valid = false;
+    pl->demod_valid = false;
+    pl->last_mono = dst;
+    FMRX_TRY(mark(c, 1));
+    advance_state(pl, c, hist_done);
+    return mark(c, 2);
+}
+
+// ---- RF_FrontEnd: project.cpp:82-128 (u8 -> IF I/Q -> discriminator) ----
+static int front_end(fmrx_pipeline *pl, const Call &c)
+{
+    const int hb = pl->fe.hist_bytes;
+    bool hist_done = false;
+    pl->demod_valid = true;
+    if (!pl->force_generic && pl->opt.fe_variant == 0 && fe_mfma_available(pl->fe, c.iq, c.n, c.hist)) {
+        // matrix-core kernel: int8 MFMA FIR + discriminator, HBM-bound (kernels_fe_mfma.hip)
+        hist_done = c.n_bytes >= static_cast<size_t>(hb);
+        // everything but mono modes 0/1 reads the discriminator history at negative indices of this block's buffer:
+        // the kernel copies it there itself (it is the tail of the previous block's buffer)
+        const bool want_front = !(pl->channels == 1 && !pl->resample) && c.n_if >= static_cast<size_t>(pl->Hd);
+        FMRX_TRY(fe_mfma_launch(pl->fe, c.iq, c.n, c.hist, pl->prev_override ? c.prev : nullptr, c.demod,
+                                c.keep_if ? pl->ifb.p : nullptr, c.prev_next,
+                                hist_done ? c.hist_next : nullptr, pl->opt, c.sf, want_front ? c.hist_end - pl->Hd : nullptr,
+                                want_front ? c.dbuf : nullptr, pl->Hd));
+        if (want_front) pl->demod_front[c.cur] = true;
+        pl->if_valid = c.keep_if;
+    } else if (!pl->force_generic && fe_fused_available(pl->fe, c.iq, c.n)) {
+        // one kernel; the IF stream is written only when somebody asked to look at it, and the kernel
+        // also leaves the stream's last bytes (I_state/Q_state, filter.cpp:182-187) for the next block
+        hist_done = c.n_bytes >= static_cast<size_t>(hb);
+        FMRX_TRY(fe_demod_launch(pl->fe, c.iq, c.n, c.hist, pl->prev_override ? c.prev : nullptr, c.demod,
+                                 c.keep_if ? pl->ifb.p : nullptr, c.prev_next, hist_done ? c.hist_next : nullptr, pl->opt, c.s));
+        pl->if_valid = c.keep_if;
+    } else {
+        FMRX_TRY(fe_launch(pl->fe, c.iq, c.n, c.hist, pl->ifb.p, pl->opt, c.s, pl->force_generic));
+        FMRX_TRY(k_fm_demod_if(pl->ifb.p, c.n_if, c.prev, c.prev_next, c.demod, 0, c.s));
+        pl->if_valid = true;
+    }
+    // fmDemodArctan (model/fmSupportLib.py:502-531) over the IF stream, IF[-1] = the carried prev_i / prev_q (their phase is the
+    // model's state_phase modulo 2 pi; zeros at the start of a stream: atan2(0, 0) = 0 = the model's initial phase)
+    if (pl->opt.demod == 1) FMRX_TRY(k_fm_demod_arctan_if(pl->ifb.p, c.n_if, c.prev, c.demod, c.s));
+    FMRX_TRY(mark(c, 1));
+    advance_state(pl, c, hist_done);
+    // a block shorter than the history keeps its own front valid, so that "tail of the previous
+    // buffer" stays a contiguous Hd samples for whoever comes next
+    if (c.n_if < static_cast<size_t>(pl->Hd)) FMRX_TRY(materialise_history(pl, c));
+    return FMRX_OK;
+}
+
+// ---- outputs of the stages that write the handle's own buffers: f32 copies, PCM ----
+static int write_outputs(const Call &c, const float *out_l, const float *out_r)
+{
+    if (c.audio_f32) {
+        FMRX_HIP(hipMemcpyAsync(c.audio_f32, out_l, c.n_au * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+        if (out_r) FMRX_HIP(hipMemcpyAsync(c.audio_f32 + c.n_au, out_r, c.n_au * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    }
+    if (c.pcm16) {
+        if (out_r) FMRX_TRY(k_pcm16_stereo(out_l, out_r, c.n_au, c.pcm16, c.pcm_policy, c.s));
+        else FMRX_TRY(k_pcm16(out_l, c.n_au, c.pcm16, c.pcm_policy, c.s));
+    }
+    return FMRX_OK;
+}
+
+static int mono_back_end(fmrx_pipeline *pl, const Call &c)
+{
+    if (!pl->resample) {
+        // ---- RF_MONO, modes 0/1: audio FIR + decimate + PCM in one kernel (project.cpp:346;
+        //      threadMonoOnly.cpp:185-191), straight into the caller's buffers ----
+        float *dst = c.audio_f32 ? c.audio_f32 : pl->mono.p;
+        const bool fast = audio_fast_available(pl->audio, c.demod) && !pl->force_generic;
+        if (!fast && !pl->demod_front[c.cur]) FMRX_TRY(materialise_history(pl, c));
+        FMRX_TRY(audio_fir_launch(pl->audio, c.demod, fast ? c.hist_end : nullptr, c.n_if, 0, dst, c.pcm16, c.pcm_policy, c.s,
+                                  pl->force_generic));
+        pl->last_mono = dst;
+        return mark(c, 2);
+    }
+    // ---- RF_MONO, modes 2/3: rational resampler (project.cpp:353) ----
+    if (!pl->demod_front[c.cur]) FMRX_TRY(materialise_history(pl, c));
+    if (!pl->force_generic && resample_mfma_available(pl->rs, c.demod, c.n_if, 0, pl->opt)) {
+        // the matrix-core kernel writes the caller's buffers itself; PCM-only callers get the reference's output
+        // format and nothing else (as the fused mono kernel of modes 0/1)
+        float *dst = c.audio_f32 ? c.audio_f32 : (c.pcm16 ? nullptr : pl->mono.p);
+        FMRX_TRY(resample_launch(pl->rs, c.demod, c.n_if, 0, dst, pl->opt, c.s, false, false, c.pcm16, c.pcm_policy,
+                                 resample_margins(pl, c.demod, c.n_if, 0)));
+        pl->last_mono = dst;
+        return mark(c, 2);
+    }
+    FMRX_TRY(audio_stage(pl, c.demod, c.n_if, 0, pl->mono.p, c.s));
+    pl->last_mono = pl->mono.p;
+    FMRX_TRY(mark(c, 2));
+    return write_outputs(c, pl->mono.p, nullptr);
+}
+
+// fmPLL on the pilot band: the serial recurrence, or the parallel one (a stream's first block walks a serial head first);
+// under overlap_calls the chunk records belong to the front, and events order the front, PLL and output streams
+static int pll_stage(fmrx_pipeline *pl, const Call &c, fmrx_pipeline::StereoSet &b)
+{
+    const size_t n_if = c.n_if;
+    const float fs = static_cast<float>(pl->p.if_Fs);
+    if (pl->force_generic || pl->opt.pll_mode != 0) {
+        // the serial recurrence: glibc's functions in the bit-exact mode (and pll_mode 2), fast math for pll_mode 1
+        const int fast = !pl->force_generic && pl->opt.pll_mode == 1;
+        FMRX_TRY(k_fm_pll(b.carrier.p, n_if, b.pll.p, pl->pll_state.p, 19e3f, fs, 2.0f, 0.0f, 0.01f, fast, c.s));
+    } else {
+        // a stream's first block starts unlocked: walk its first samples serially so that the
+        // segment lanes extrapolate from a locked state; later blocks start locked already
+        size_t head = 0;
+        if (!pl->pll_warm) head = n_if < static_cast<size_t>(kPllHead) ? n_if : static_cast<size_t>(kPllHead);
+        // what depends on the input alone (the linear system's chunk records) belongs to the front
+        float *lti = c.ovl ? pl->lti_rec[c.cur].p : nullptr;
+        if (c.ovl && n_if > head)
+            FMRX_TRY(k_fm_pll_parallel(b.carrier.p + head, n_if - head, b.pll.p + head, pl->pll_state.p, 19e3f, fs, 2.0f, 0.0f,
+                                       0.01f, pl->pll_scratch.p, pl->opt, c.sf, pl->pll_off + static_cast<double>(head), 1, lti));
+        if (c.ovl) {   // read-after-write: the lanes read this call's carrier / chunk records, which the front wrote on its own stream
+            FMRX_HIP(hipEventRecord(pl->ov_done[0][c.cur], c.sf));
+            FMRX_HIP(hipStreamWaitEvent(c.sp, pl->ov_done[0][c.cur], 0));
+        }
+        if (head > 0)
+            FMRX_TRY(k_fm_pll(b.carrier.p, head, b.pll.p, pl->pll_state.p, 19e3f, fs, 2.0f, 0.0f, 0.01f, 1, c.sp));
+        if (n_if > head)
+            FMRX_TRY(k_fm_pll_parallel(b.carrier.p + head, n_if - head, b.pll.p + head, pl->pll_state.p, 19e3f, fs, 2.0f, 0.0f,
+                                       0.01f, pl->pll_scratch.p, pl->opt, c.sp, pl->pll_off + static_cast<double>(head),
+                                       c.ovl ? 2 : 3, lti));
+        pl->pll_warm = true;
+        if (c.so != c.sp) {   // read-after-write: the output stage reads the NCO values and the PLL state the lanes / repair left
+            FMRX_HIP(hipEventRecord(pl->ov_done[1][c.cur], c.sp));
+            FMRX_HIP(hipStreamWaitEvent(c.so, pl->ov_done[1][c.cur], 0));
+        }
+    }
+    pl->pll_off += static_cast<double>(n_if);
+    return FMRX_OK;
+}
+
+// ---- RF_STEREO: project.cpp:194-280 ----
+static int stereo_back_end(fmrx_pipeline *pl, const Call &c)
+{
+    const fmrx_params &p = pl->p;
+    if (!pl->demod_front[c.cur]) FMRX_TRY(materialise_history(pl, c));
+    pl->last_mono = pl->mono.p;
+    fmrx_pipeline::StereoSet &b = pl->set[pl->last_set];
+    const bool fused_out = !pl->resample && !pl->force_generic && stereo_out_available(p.audio_taps, p.audio_decim);
+    float *mixer = pl->mixer.p + pl->Hm;
+    if (!fused_out) FMRX_TRY(audio_stage(pl, c.demod, c.n_if, pl->delay, pl->mono.p, c.s));  // all-pass = index offset
+    FMRX_TRY(mark(c, 2));
+    FMRX_TRY(bpf_pair_launch(pl->bpf_plan, c.demod, c.n_if, b.bpf.p, b.carrier.p, c.sf, pl->force_generic));
+    FMRX_TRY(pll_stage(pl, c, b));
+    const float *tail_in = pl->mix_tail[pl->mix_cur].p;
+    float *tail_out = pl->mix_tail[pl->mix_cur ^ 1].p;
+    if (fused_out) {
+        // mixer, both audio FIRs, L/R combine and PCM in one kernel, straight into the caller's buffers
+        FMRX_TRY(stereo_out_launch(c.demod, b.bpf.p, b.pll.p, tail_in, tail_out, pl->Hm, c.n_if, pl->delay, pl->audio.h.p,
+                                   p.audio_taps, p.audio_decim, pl->mono.p, pl->st_final.p,
+                                   c.audio_f32 ? c.audio_f32 : (c.pcm16 ? nullptr : pl->left.p),
+                                   c.audio_f32 ? c.audio_f32 + c.n_au : (c.pcm16 ? nullptr : pl->right.p), c.pcm16,
+                                   c.pcm_policy, pl->keep_if ? mixer : nullptr, c.so));
+        if (c.ovl) {   // the caller's stream sees the call's output in its own order, as always
+            FMRX_HIP(hipEventRecord(pl->ov_done[2][c.cur], c.so));
+            if (c.so != c.s) FMRX_HIP(hipStreamWaitEvent(c.s, pl->ov_done[2][c.cur], 0));
+        }
+        pl->mixer_valid = pl->keep_if;
+        pl->mix_cur ^= 1;
+        return FMRX_OK;
+    }
+    FMRX_HIP(hipMemcpyAsync(pl->mixer.p, tail_in, pl->Hm * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    FMRX_TRY(k_mix(b.bpf.p, b.pll.p, c.n_if, mixer, c.s));
+    FMRX_TRY(audio_stage(pl, mixer, c.n_if, 0, pl->st_final.p, c.s));
+    FMRX_TRY(k_combine(pl->st_final.p, pl->mono.p, c.n_au, pl->left.p, pl->right.p, c.s));
+    // the mixer output's last Hm samples (of [history | block]) are the next block's state_stereofilt
+    FMRX_HIP(hipMemcpyAsync(tail_out, pl->mixer.p + c.n_if, pl->Hm * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    pl->mix_cur ^= 1;
+    pl->mixer_valid = true;
+    return write_outputs(c, pl->left.p, pl->right.p);
+}
+
 int fmrx_pipeline_process_dev(fmrx_pipeline *pl, const uint8_t *d_iq, size_t n_bytes, float *d_audio_f32,
                               int16_t *d_pcm16, int pcm_policy, void *stream)
 {
     if (!pl || !d_iq) return fail(FMRX_EINVAL, "process_dev: null argument");
     FMRX_TRY(check_block(pl, n_bytes));
     FMRX_HIP(hipSetDevice(pl->device));   // the handle's buffers live there, whatever the caller's current device
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const fmrx_params &p = pl->p;
-    const size_t n = n_bytes / 2;
-    const size_t n_if = n / p.rf_decim;
-    const size_t n_au = n_audio_of(pl, n_bytes);
-    pl->last_n_if = n_if;
-    pl->last_n_audio = n_au;
-    // this block's discriminator output goes to the buffer the previous block did not use
-    const int last = pl->demod_last, cur = last ^ 1;
-    float *dbuf = pl->demod_buf[cur].p;
-    float *demod = dbuf + pl->Hd;
-    const float *hist_end = pl->demod_buf[last].p + pl->Hd + pl->demod_n_last;   // one past the previous block's last sample
-    pl->demod_front[cur] = false;
-    auto materialise_history = [&]() -> int {   // for kernels that index history at negative offsets of their input
-        FMRX_HIP(hipMemcpyAsync(dbuf, hist_end - pl->Hd, pl->Hd * sizeof(float), hipMemcpyDeviceToDevice, s));
-        pl->demod_front[cur] = true;
-        return FMRX_OK;
-    };
-
-    // events around every prof_every-th call: a record costs ~5 us of stream time
-    const bool prof = pl->profiling && (pl->seq++ % static_cast<unsigned long>(pl->prof_every) == 0);
-    hipEvent_t *ev = pl->ev[pl->calls % fmrx_pipeline::kRing];
-    if (prof) FMRX_HIP(hipEventRecord(ev[0], s));
-
-    // ---- RF_FrontEnd: project.cpp:82-128 (u8 -> IF I/Q -> discriminator) ----
-    const uint8_t *hist = pl->fe_hist[pl->fe_cur].p;
-    uint8_t *hist_next = pl->fe_hist[pl->fe_cur ^ 1].p;
-    const int hb = pl->fe.hist_bytes;
-    const float *prev = pl->prev_iq[pl->prev_cur].p;
-    float *prev_next = pl->prev_iq[pl->prev_cur ^ 1].p;
-    bool hist_done = false;
-    pl->demod_valid = true;
-    const bool mfma = pl->opt.fe_variant == 0;
-    // option demod = 1: the model's arctangent demodulator on the IF stream (materialised for it), instead of the front-end kernels' own discriminator
-    const bool arctan = pl->opt.demod == 1;
-    const bool keep_if = pl->keep_if || arctan;
-    // option overlap_calls: front | PLL | output stage of the stereo chain of consecutive calls on internal streams (see the struct)
-    const bool ovl = pl->opt.overlap_calls != 0 && pl->channels == 2 && !pl->resample && !pl->force_generic && !keep_if &&
-                     !pl->profiling && pl->opt.pll_mode == 0 && mfma && n_if >= static_cast<size_t>(pl->Hd) &&
-                     fe_mfma_available(pl->fe, d_iq, n, hist) && stereo_out_available(p.audio_taps, p.audio_decim);
-    const int regime = ovl ? pl->opt.overlap_calls : 0;
-    if (regime != pl->ov_active) {   // change of regime between calls: everything in flight first
-        FMRX_HIP(hipDeviceSynchronize());
-        pl->ov_active = regime;
-    }
-    if (ovl) FMRX_TRY(overlap_setup(pl));
-    // overlap_calls 1: the front on an internal stream, PLL and output stage on the caller's (fewest event operations: at these
-    // step sizes the host's enqueue rate is the next limit); 2: all three on internal streams
-    const bool ovl3 = ovl && pl->opt.overlap_calls >= 2;
-    hipStream_t sf = ovl ? pl->ov_stream[0] : s, sp = ovl3 ? pl->ov_stream[1] : s, so = ovl3 ? pl->ov_stream[2] : s;
-    const int bs = ovl ? cur : 0;   // buffer set of the stereo intermediates
-    pl->last_set = bs;
-    float *carrier_b = bs ? pl->carrier1.p : pl->carrier.p, *bpf_b = bs ? pl->bpf1.p : pl->bpf.p, *pll_b = bs ? pl->pll1.p : pl->pll.p;
-    if (ovl) {
-        // the front writes this parity's buffers: the last call of the same parity must be through with them; the output
-        // stage writes the caller's buffers: whatever the caller's stream still does with them comes first (the input is the
-        // one thing the option vouches for)
-        FMRX_HIP(hipStreamWaitEvent(sf, pl->ov_done[2][cur], 0));
-        if (so != s) {
-            FMRX_HIP(hipEventRecord(pl->ov_entry, s));
-            FMRX_HIP(hipStreamWaitEvent(so, pl->ov_entry, 0));
-        }
-    }
-    if (pl->channels == 1 && !pl->resample && !pl->force_generic && !keep_if && mfma &&
-        n_if >= static_cast<size_t>(pl->Hd) && static_cast<long>(n_au) >= pl->opt.fused_min_audio &&
-        mono_fused_available(pl->fe, pl->audio, d_iq, n, hist)) {
-        // ---- RF_FrontEnd + RF_MONO of modes 0/1 in one kernel (kernels_fe_mfma.hip): the discriminator
-        //      output stays on chip; only its tail (state_mono) is written for the next block ----
-        hist_done = n_bytes >= static_cast<size_t>(hb);
-        // f32 audio is written only where somebody will read it: the caller's buffer, or the handle's own when
-        // no PCM was asked for either (read_tap); PCM-only callers get the reference's output format and nothing else
-        float *dst = d_audio_f32 ? d_audio_f32 : (d_pcm16 ? nullptr : pl->mono.p);
-        FMRX_TRY(mono_fused_launch(pl->fe, pl->audio, d_iq, n, hist, prev, hist_end, demod, pl->Hd, prev_next, dst, d_pcm16,
-                                   pcm_policy, hist_done ? hist_next : nullptr, pl->opt, s));
-        pl->if_valid = false;
-        pl->demod_valid = false;
-        pl->last_mono = dst;
-        pl->prev_cur ^= 1;
-        pl->prev_override = false;
-        pl->fe_cur ^= 1;
-        if (prof) FMRX_HIP(hipEventRecord(ev[1], s));
-        if (!hist_done)
-            hipLaunchKernelGGL(hist_update_kernel, dim3((hb + 255) / 256), dim3(256), 0, s, hist, d_iq,
-                               static_cast<long>(n_bytes), hb, hist_next);
-        pl->demod_last = cur;
-        pl->demod_n_last = n_if;
-        if (prof) {
-            FMRX_HIP(hipEventRecord(ev[2], s));
-            FMRX_HIP(hipEventRecord(ev[3], s));
-            pl->calls++;
-        }
-        return FMRX_OK;
-    }
-    if (!pl->force_generic && mfma && fe_mfma_available(pl->fe, d_iq, n, hist)) {
-        // matrix-core kernel: int8 MFMA FIR + discriminator, HBM-bound (kernels_fe_mfma.hip)
-        hist_done = n_bytes >= static_cast<size_t>(hb);
-        // everything but mono modes 0/1 reads the discriminator history at negative indices of this block's buffer:
-        // the kernel copies it there itself (it is the tail of the previous block's buffer)
-        const bool want_front = !(pl->channels == 1 && !pl->resample) && n_if >= static_cast<size_t>(pl->Hd);
-        FMRX_TRY(fe_mfma_launch(pl->fe, d_iq, n, hist, pl->prev_override ? prev : nullptr, demod,
-                                keep_if ? pl->ifb.p : nullptr, prev_next,
-                                hist_done ? hist_next : nullptr, pl->opt, sf, want_front ? hist_end - pl->Hd : nullptr,
-                                want_front ? dbuf : nullptr, pl->Hd));
-        if (want_front) pl->demod_front[cur] = true;
-        pl->if_valid = keep_if;
-    } else if (!pl->force_generic && fe_fused_available(pl->fe, d_iq, n)) {
-        // one kernel; the IF stream is written only when somebody asked to look at it, and the kernel
-        // also leaves the stream's last bytes (I_state/Q_state, filter.cpp:182-187) for the next block
-        hist_done = n_bytes >= static_cast<size_t>(hb);
-        FMRX_TRY(fe_demod_launch(pl->fe, d_iq, n, hist, pl->prev_override ? prev : nullptr, demod,
-                                 keep_if ? pl->ifb.p : nullptr, prev_next, hist_done ? hist_next : nullptr, pl->opt, s));
-        pl->if_valid = keep_if;
+    Call c{d_iq, n_bytes, d_audio_f32, d_pcm16, pcm_policy, static_cast<hipStream_t>(stream)};
+    FMRX_TRY(call_setup(pl, c));
+    FMRX_TRY(overlap_begin(pl, c));
+    if (c.fused) {
+        FMRX_TRY(fused_mono(pl, c));
     } else {
-        FMRX_TRY(fe_launch(pl->fe, d_iq, n, hist, pl->ifb.p, pl->opt, s, pl->force_generic));
-        FMRX_TRY(k_fm_demod_if(pl->ifb.p, n_if, prev, prev_next, demod, 0, s));
-        pl->if_valid = true;
+        FMRX_TRY(front_end(pl, c));
+        FMRX_TRY(pl->channels == 1 ? mono_back_end(pl, c) : stereo_back_end(pl, c));
     }
-    // fmDemodArctan (model/fmSupportLib.py:502-531) over the IF stream, IF[-1] = the carried prev_i / prev_q (their phase is the
-    // model's state_phase modulo 2 pi; zeros at the start of a stream: atan2(0, 0) = 0 = the model's initial phase)
-    if (arctan) FMRX_TRY(k_fm_demod_arctan_if(pl->ifb.p, n_if, prev, demod, s));
-    pl->prev_cur ^= 1;
-    pl->prev_override = false;
-    pl->fe_cur ^= 1;
-    if (prof) FMRX_HIP(hipEventRecord(ev[1], s));
-    if (!hist_done)
-        hipLaunchKernelGGL(hist_update_kernel, dim3((hb + 255) / 256), dim3(256), 0, sf, hist, d_iq,
-                           static_cast<long>(n_bytes), hb, hist_next);
-    // a block shorter than the history keeps its own front valid, so that "tail of the previous
-    // buffer" stays a contiguous Hd samples for whoever comes next
-    if (n_if < static_cast<size_t>(pl->Hd)) FMRX_TRY(materialise_history());
-    pl->demod_last = cur;
-    pl->demod_n_last = n_if;
-
-    if (pl->channels == 1 && !pl->resample) {
-        // ---- RF_MONO, modes 0/1: audio FIR + decimate + PCM in one kernel (project.cpp:346;
-        //      threadMonoOnly.cpp:185-191), straight into the caller's buffers ----
-        float *dst = d_audio_f32 ? d_audio_f32 : pl->mono.p;
-        const bool fast = audio_fast_available(pl->audio, demod) && !pl->force_generic;
-        if (!fast && !pl->demod_front[cur]) FMRX_TRY(materialise_history());
-        FMRX_TRY(audio_fir_launch(pl->audio, demod, fast ? hist_end : nullptr, n_if, 0, dst, d_pcm16, pcm_policy, s,
-                                  pl->force_generic));
-        pl->last_mono = dst;
-        if (prof) {
-            FMRX_HIP(hipEventRecord(ev[2], s));
-            FMRX_HIP(hipEventRecord(ev[3], s));
-            pl->calls++;
-        }
-        return FMRX_OK;
-    }
-
-    if (!pl->demod_front[cur]) FMRX_TRY(materialise_history());
-    float *out_l = pl->mono.p, *out_r = nullptr;
-    pl->last_mono = pl->mono.p;
-    if (pl->channels == 1) {
-        // ---- RF_MONO, modes 2/3: rational resampler (project.cpp:353) ----
-        if (!pl->force_generic && resample_mfma_available(pl->rs, demod, n_if, 0, pl->opt)) {
-            // the matrix-core kernel writes the caller's buffers itself; PCM-only callers get the reference's output
-            // format and nothing else (as the fused mono kernel of modes 0/1)
-            float *dst = d_audio_f32 ? d_audio_f32 : (d_pcm16 ? nullptr : pl->mono.p);
-            FMRX_TRY(resample_launch(pl->rs, demod, n_if, 0, dst, pl->opt, s, false, false, d_pcm16, pcm_policy,
-                                     resample_margins(pl, demod, n_if, 0)));
-            pl->last_mono = dst;
-            if (prof) {
-                FMRX_HIP(hipEventRecord(ev[2], s));
-                FMRX_HIP(hipEventRecord(ev[3], s));
-                pl->calls++;
-            }
-            return FMRX_OK;
-        }
-        FMRX_TRY(audio_stage(pl, demod, n_if, 0, pl->mono.p, s));
-        if (prof) FMRX_HIP(hipEventRecord(ev[2], s));
-    } else {
-        // ---- RF_STEREO: project.cpp:194-280 ----
-        const bool fused_out = !pl->resample && !pl->force_generic && stereo_out_available(p.audio_taps, p.audio_decim);
-        float *mixer = pl->mixer.p + pl->Hm;
-        if (!fused_out) {
-            FMRX_TRY(audio_stage(pl, demod, n_if, pl->delay, pl->mono.p, s));  // all-pass = index offset
-        }
-        if (prof) FMRX_HIP(hipEventRecord(ev[2], s));
-        FMRX_TRY(bpf_pair_launch(pl->bpf_plan, demod, n_if, bpf_b, carrier_b, sf, pl->force_generic));
-        if (pl->force_generic || pl->opt.pll_mode != 0) {
-            // the serial recurrence: glibc's functions in the bit-exact mode (and pll_mode 2), fast math for pll_mode 1
-            const int fast = !pl->force_generic && pl->opt.pll_mode == 1;
-            FMRX_TRY(k_fm_pll(carrier_b, n_if, pll_b, pl->pll_state.p, 19e3f, static_cast<float>(p.if_Fs), 2.0f,
-                              0.0f, 0.01f, fast, s));
-        } else {
-            // a stream's first block starts unlocked: walk its first samples serially so that the
-            // segment lanes extrapolate from a locked state; later blocks start locked already
-            size_t head = 0;
-            if (!pl->pll_warm) head = n_if < static_cast<size_t>(kPllHead) ? n_if : static_cast<size_t>(kPllHead);
-            // what depends on the input alone (the linear system's chunk records) belongs to the front
-            float *lti = ovl ? pl->lti_rec[cur].p : nullptr;
-            if (ovl && n_if > head)
-                FMRX_TRY(k_fm_pll_parallel(carrier_b + head, n_if - head, pll_b + head, pl->pll_state.p, 19e3f,
-                                           static_cast<float>(p.if_Fs), 2.0f, 0.0f, 0.01f, pl->pll_scratch.p, pl->opt, sf,
-                                           pl->pll_off + static_cast<double>(head), 1, lti));
-            if (ovl) {   // read-after-write: the lanes read this call's carrier / chunk records, which the front wrote on its own stream
-                FMRX_HIP(hipEventRecord(pl->ov_done[0][cur], sf));
-                FMRX_HIP(hipStreamWaitEvent(sp, pl->ov_done[0][cur], 0));
-            }
-            if (head > 0)
-                FMRX_TRY(k_fm_pll(carrier_b, head, pll_b, pl->pll_state.p, 19e3f, static_cast<float>(p.if_Fs),
-                                  2.0f, 0.0f, 0.01f, 1, sp));
-            if (n_if > head)
-                FMRX_TRY(k_fm_pll_parallel(carrier_b + head, n_if - head, pll_b + head, pl->pll_state.p, 19e3f,
-                                           static_cast<float>(p.if_Fs), 2.0f, 0.0f, 0.01f, pl->pll_scratch.p, pl->opt, sp,
-                                           pl->pll_off + static_cast<double>(head), ovl ? 2 : 3, lti));
-            pl->pll_warm = true;
-            if (so != sp) {   // read-after-write: the output stage reads the NCO values and the PLL state the lanes / repair left
-                FMRX_HIP(hipEventRecord(pl->ov_done[1][cur], sp));
-                FMRX_HIP(hipStreamWaitEvent(so, pl->ov_done[1][cur], 0));
-            }
-        }
-        pl->pll_off += static_cast<double>(n_if);
-        const float *tail_in = pl->mix_tail[pl->mix_cur].p;
-        float *tail_out = pl->mix_tail[pl->mix_cur ^ 1].p;
-        if (fused_out) {
-            // mixer, both audio FIRs, L/R combine and PCM in one kernel, straight into the caller's buffers
-            FMRX_TRY(stereo_out_launch(demod, bpf_b, pll_b, tail_in, tail_out, pl->Hm, n_if, pl->delay, pl->audio.h.p,
-                                       p.audio_taps, p.audio_decim, pl->mono.p, pl->st_final.p,
-                                       d_audio_f32 ? d_audio_f32 : (d_pcm16 ? nullptr : pl->left.p),
-                                       d_audio_f32 ? d_audio_f32 + n_au : (d_pcm16 ? nullptr : pl->right.p), d_pcm16,
-                                       pcm_policy, pl->keep_if ? mixer : nullptr, so));
-            if (ovl) {   // the caller's stream sees the call's output in its own order, as always
-                FMRX_HIP(hipEventRecord(pl->ov_done[2][cur], so));
-                if (so != s) FMRX_HIP(hipStreamWaitEvent(s, pl->ov_done[2][cur], 0));
-            }
-            pl->mixer_valid = pl->keep_if;
-            pl->mix_cur ^= 1;
-            if (prof) {
-                FMRX_HIP(hipEventRecord(ev[3], s));
-                pl->calls++;
-            }
-            return FMRX_OK;
-        }
-        FMRX_HIP(hipMemcpyAsync(pl->mixer.p, tail_in, pl->Hm * sizeof(float), hipMemcpyDeviceToDevice, s));
-        FMRX_TRY(k_mix(bpf_b, pll_b, n_if, mixer, s));
-        FMRX_TRY(audio_stage(pl, mixer, n_if, 0, pl->st_final.p, s));
-        FMRX_TRY(k_combine(pl->st_final.p, pl->mono.p, n_au, pl->left.p, pl->right.p, s));
-        // the mixer output's last Hm samples (of [history | block]) are the next block's state_stereofilt
-        FMRX_HIP(hipMemcpyAsync(tail_out, pl->mixer.p + n_if, pl->Hm * sizeof(float), hipMemcpyDeviceToDevice, s));
-        pl->mix_cur ^= 1;
-        pl->mixer_valid = true;
-        out_l = pl->left.p;
-        out_r = pl->right.p;
-    }
-
-    // ---- outputs ----
-    if (d_audio_f32) {
-        FMRX_HIP(hipMemcpyAsync(d_audio_f32, out_l, n_au * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (out_r) FMRX_HIP(hipMemcpyAsync(d_audio_f32 + n_au, out_r, n_au * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if (d_pcm16) {
-        if (out_r) FMRX_TRY(k_pcm16_stereo(out_l, out_r, n_au, d_pcm16, pcm_policy, s));
-        else FMRX_TRY(k_pcm16(out_l, n_au, d_pcm16, pcm_policy, s));
-    }
-    if (prof) {
-        FMRX_HIP(hipEventRecord(ev[3], s));
-        pl->calls++;
-    }
+    FMRX_TRY(mark(c, 3));
+    if (c.prof) pl->calls++;
     return FMRX_OK;
 }
 
@@ -754,19 +796,14 @@ int fmrx_pipeline_read_tap(fmrx_pipeline *pl, int which, float *out, size_t *n)
     switch (which) {
     case FMRX_TAP_IF_I:
     case FMRX_TAP_IF_Q: cnt = n_if; break;
-    case FMRX_TAP_DEMOD:
-        // the block was shifted into the history position by carry_history: it is the
-        // last n_if samples of [Hd | n_if] only until the next block; read it from the
-        // tail copy kept in front when the block is shorter than that -- simplest: the
-        // block region itself is still intact (carry copies, it does not move)
-        src = pl->demod_buf[pl->demod_last].p + pl->Hd; cnt = n_if; break;
+    case FMRX_TAP_DEMOD: src = pl->demod_buf[pl->demod_last].p + pl->Hd; cnt = n_if; break;   // the last block's region
     case FMRX_TAP_MONO:
         src = pl->last_mono; cnt = n_au;
         if (!src && out && cnt) return fail(FMRX_EINVAL, "read_tap: the last call wrote s16 PCM only (no f32 audio buffer was passed)");
         break;
-    case FMRX_TAP_CARRIER: if (st) { src = pl->last_set ? pl->carrier1.p : pl->carrier.p; cnt = n_if; } break;
-    case FMRX_TAP_STEREO_BPF: if (st) { src = pl->last_set ? pl->bpf1.p : pl->bpf.p; cnt = n_if; } break;
-    case FMRX_TAP_PLL: if (st) { src = pl->last_set ? pl->pll1.p : pl->pll.p; cnt = n_if + 1; } break;
+    case FMRX_TAP_CARRIER: if (st) { src = pl->set[pl->last_set].carrier.p; cnt = n_if; } break;
+    case FMRX_TAP_STEREO_BPF: if (st) { src = pl->set[pl->last_set].bpf.p; cnt = n_if; } break;
+    case FMRX_TAP_PLL: if (st) { src = pl->set[pl->last_set].pll.p; cnt = n_if + 1; } break;
     case FMRX_TAP_MIXER:
         if (st) { src = pl->mixer.p + pl->Hm; cnt = n_if; }
         if (st && out && cnt && !pl->mixer_valid)
@@ -786,7 +823,6 @@ int fmrx_pipeline_read_tap(fmrx_pipeline *pl, int which, float *out, size_t *n)
         return fail(FMRX_EINVAL, "read_tap: the IF stream is not materialised by the fused front end; call "
                                  "fmrx_pipeline_set_keep_intermediates(pl, 1) before processing");
     if (which == FMRX_TAP_IF_I || which == FMRX_TAP_IF_Q) {
-        // NOTE: demod of the block already shifted the history; IF is intact
         std::vector<float> z(2 * cnt);
         FMRX_HIP(hipMemcpy(z.data(), pl->ifb.p, 2 * cnt * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < cnt; k++) out[k] = z[2 * k + (which == FMRX_TAP_IF_Q)];

@@ -1317,3 +1317,33 @@ def test_submit_wait_is_process(fmrx, oracle, channels):
         bits_equal(a.process(more)["pcm16"], b.process(more)["pcm16"])
         for h in (h_in, h_f32, h_pcm):
             fmrx.hostFree(h)
+
+
+@pytest.mark.parametrize("mode,channels,fused_min_audio,demod_on_chip", [
+    (0, 1, 0, True),           # the fused mono kernel
+    (0, 1, 10**12, False),     # front end + audio FIR
+    (2, 1, None, False),       # front end + resampler
+    (0, 2, None, False),       # stereo
+], ids=["fused mono", "two-kernel mono", "mono mode 2", "stereo"])
+def test_profiling_events(fmrx, oracle, mode, channels, fused_min_audio, demod_on_chip):
+    """set_profiling: every call records its four events on every path; timing_sum counts the calls, and the three stage
+    times are finite, >= 0 and add up to the total within the events' resolution."""
+    pl = fmrx.Pipeline(mode, channels)
+    if fused_min_audio is not None:
+        pl.set_option("fused_min_audio", fused_min_audio)
+    bb, calls = pl.max_block_bytes, 3
+    iq = oracle.synth_fm_u8(bb // 2 * calls, seed=91)
+    pl.set_profiling(True)
+    for k in range(calls):
+        pl.process(iq[k * bb:(k + 1) * bb])
+    if demod_on_chip:   # the path under test is the fused kernel's
+        with pytest.raises(fmrx.FmrxError):
+            pl.read_tap("demod")
+    else:
+        assert len(pl.read_tap("demod")) == pl.n_if(bb)
+    t, n = pl.timing_sum()
+    assert n == calls
+    stages = [t["front_end_ms"], t["audio_ms"], t["rest_ms"]]
+    assert all(np.isfinite(x) and x >= 0 for x in stages + [t["total_ms"]]), t
+    assert t["total_ms"] > 0, t
+    assert abs(sum(stages) - t["total_ms"]) <= 3 * calls * 2e-3 + 1e-4 * t["total_ms"], t
