@@ -32,9 +32,11 @@
 // taps loaded once, the next block fetched under the current block's products).  Per output ~190 MACs are issued
 // instead of 101, but as 1/64 of a matrix instruction instead of a dependent chain with two LDS gathers per MAC.
 // The sum is an fma chain over the window (newest sample first, like the reference's j ascending) instead of
-// separately rounded products and sums: equal to float32 rounding (1e-7), not bit for bit.
+// separately rounded products and sums: within float32 rounding (1e-7) of the reference, not its bits; bit for bit the fmaf
+// chain of tests/_fir_model.py (resample_mfma: K-steps ascending, K index 0..3 inside each MFMA).
 #include "device_math.hpp"
 #include "fmrx_internal.hpp"
+#include "resample_mfma_host.hpp"
 
 #include <algorithm>
 
@@ -186,10 +188,7 @@ __global__ __launch_bounds__(kLT) void resample_lds_kernel(const float *__restri
 }
 
 
-// ---- matrix-core resampler -----------------------------------------------------------------------------------
-constexpr int kRsTiles = 4;                    // output tiles per workgroup: one per wave
-constexpr int kRsPieces = 160;                 // 16-byte pieces per staged row at most (16 rows x 161 x 16 B = 41 KB)
-
+// ---- matrix-core resampler (host-side geometry: resample_mfma_host.hpp) --------------------------------------
 // workgroup (chain, grp): output tiles [m0, m1) of group grp (wave w = tile m0 + w, its taps resident in registers) x the period
 // blocks pb = 8 chain + xcd, + 8 n_chain, ...: 16 periods each.  groups[4 grp ..] = m0, m1, lo, pieces: the 16 LDS rows hold
 // inputs [lo, lo + 4 pieces) of each period, row stride pieces | 1 (odd: rows then start on all 16 bank groups), and one more
@@ -330,65 +329,18 @@ __global__ __launch_bounds__(256, ELEM ? 2 : KS4 >= 14 ? 3 : 4) void resample_mf
 static int resample_mfma_plan(ResamplePlan &pl, const float *h)
 {
     pl.mfma = false;
-    const int U = pl.upsamp, D = pl.decim, J = pl.J;
-    if (D % 4 != 0 || U < 16) return FMRX_OK;
-    const int ntiles = (U + 15) / 16;
-    std::vector<int> top(ntiles), b0(ntiles);
-    int K = 0;
-    for (int m = 0; m < ntiles; m++) {
-        const int r_last = std::min(16 * m + 15, U - 1);
-        const int bmax = static_cast<int>(static_cast<long>(r_last) * D / U);
-        b0[m] = static_cast<int>(static_cast<long>(16 * m) * D / U);
-        top[m] = (bmax + 1 + 3) / 4 * 4 - 1;
-        K = std::max(K, top[m] - b0[m] + J);
-    }
-    const int KS4 = std::max(8, (K + 31) / 32 * 2);             // K-steps in sixteens: an even count from 8 to 16 (kernel instances)
-    if (KS4 > 16) return FMRX_OK;
-    // tile groups of kRsTiles consecutive tiles (one per wave): a period's staged window = what the group's tiles read
-    std::vector<int> grp;
-    int max_pieces = 0;
-    for (int m = 0; m < ntiles; m += kRsTiles) {
-        const int m1 = std::min(m + kRsTiles, ntiles);
-        const int lo = top[m] - 16 * KS4 + 1;                      // oldest input tile m reads; top % 4 == 3 -> a multiple of 4
-        const int pieces = (top[m1 - 1] - lo + 1) / 4;
-        if (pieces > kRsPieces) return FMRX_OK;
-        max_pieces = std::max(max_pieces, pieces);
-        grp.insert(grp.end(), {m, m1, lo, pieces});
-    }
-    // tap image [tile][lane][K-step]: lane (row i = lane & 15, kq = lane >> 4), K-step ks <-> K index w = 16 (ks/4) + 4 kq + ks%4
-    std::vector<float> img(static_cast<size_t>(ntiles) * 64 * 4 * KS4, 0.0f);
-    for (int m = 0; m < ntiles; m++)
-        for (int lane = 0; lane < 64; lane++) {
-            const int i = lane & 15, kq = lane >> 4, r = 16 * m + i;
-            if (r >= U) continue;
-            const long rd = static_cast<long>(r) * D;
-            const int ph = static_cast<int>(rd % U), bi = static_cast<int>(rd / U);
-            for (int ks = 0; ks < 4 * KS4; ks++) {
-                const int w = 16 * (ks / 4) + 4 * kq + ks % 4;
-                const int j = bi - (top[m] - w);
-                if (j >= 0 && j < J && ph + static_cast<long>(j) * U < pl.taps)
-                    img[(static_cast<size_t>(m) * 64 + lane) * 4 * KS4 + ks] = h[ph + j * U];
-            }
-        }
-    FMRX_TRY(pl.mfma_img.alloc(img.size()));
-    FMRX_HIP(hipMemcpy(pl.mfma_img.p, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-    FMRX_TRY(pl.mfma_top.alloc(top.size()));
-    FMRX_HIP(hipMemcpy(pl.mfma_top.p, top.data(), top.size() * sizeof(int), hipMemcpyHostToDevice));
-    FMRX_TRY(pl.mfma_groups.alloc(grp.size()));
-    FMRX_HIP(hipMemcpy(pl.mfma_groups.p, grp.data(), grp.size() * sizeof(int), hipMemcpyHostToDevice));
-    pl.mfma_ks4 = KS4;
-    pl.mfma_ngroups = static_cast<int>(grp.size() / 4);
-    pl.mfma_pieces = max_pieces;
-    // what piece staging reads: from the first period's lowest window start to the last period's highest one + 16 NL pieces
-    {
-        const int nl = std::max(4, (max_pieces + 15) / 16);
-        int lo_min = 0, lo_max = 0;
-        for (size_t g = 0; g < grp.size(); g += 4) {
-            lo_min = std::min(lo_min, grp[g + 2]);
-            lo_max = std::max(lo_max, grp[g + 2]);
-        }
-        pl.mfma_reach_ok = -lo_min <= kResampleFront && lo_max + 64 * nl - D <= kResampleBack;
-    }
+    RsMfmaGeometry g;
+    if (!resample_mfma_geometry(h, pl.taps, pl.upsamp, pl.decim, g)) return FMRX_OK;
+    FMRX_TRY(pl.mfma_img.alloc(g.img.size()));
+    FMRX_HIP(hipMemcpy(pl.mfma_img.p, g.img.data(), g.img.size() * sizeof(float), hipMemcpyHostToDevice));
+    FMRX_TRY(pl.mfma_top.alloc(g.top.size()));
+    FMRX_HIP(hipMemcpy(pl.mfma_top.p, g.top.data(), g.top.size() * sizeof(int), hipMemcpyHostToDevice));
+    FMRX_TRY(pl.mfma_groups.alloc(g.groups.size()));
+    FMRX_HIP(hipMemcpy(pl.mfma_groups.p, g.groups.data(), g.groups.size() * sizeof(int), hipMemcpyHostToDevice));
+    pl.mfma_ks4 = g.ks4;
+    pl.mfma_ngroups = static_cast<int>(g.groups.size() / 4);
+    pl.mfma_pieces = g.max_pieces;
+    pl.mfma_reach_ok = resample_mfma_reach_ok(g, pl.decim, kResampleFront, kResampleBack);
     pl.mfma = true;
     return FMRX_OK;
 }
@@ -424,15 +376,14 @@ template <int KS4>
 static int resample_mfma_launch_nl(const ResamplePlan &pl, const float *x, size_t n_in, float *d_y, int16_t *d_pcm, int wrap,
                                    hipStream_t stream, bool pieces16, int chains)
 {
-    const int nl = std::max(4, (pl.mfma_pieces + 15) / 16);
     if (!pieces16) {
-        switch ((nl + 1) / 2 * 2) {
+        switch (resample_mfma_nl_elem(pl.mfma_pieces)) {
 #define X(N_) case N_: return resample_mfma_launch_ks<KS4, N_, true>(pl, x, n_in, d_y, d_pcm, wrap, stream, chains);
             X(4) X(6) X(8) X(10)
 #undef X
         }
     } else {
-        switch (nl) {
+        switch (resample_mfma_nl(pl.mfma_pieces)) {
 #define X(N_) case N_: return resample_mfma_launch_ks<KS4, N_, false>(pl, x, n_in, d_y, d_pcm, wrap, stream, chains);
             X(4) X(5) X(6) X(7) X(8) X(9) X(10)
 #undef X

@@ -22,9 +22,10 @@ kernels), the shortest the pipeline accepts (below the mixer history Hm where th
 short-block tail), blocks spanning several workgroups, ~1 024 000-sample blocks, and one block of more tiles than
 audio_fir_kernel has persistent workgroups (each of those walks two tiles).
 
+The f32 matrix-core sums (the audio FIR inside mono_fused_kernel, resample_mfma_kernel) are pinned the same way, bit for
+bit against an fmaf-chain model, by tests/test_gpu_mfma_exact.py.
+
 Out of scope, on purpose:
-  * the f32 matrix-core sums (the audio FIR inside mono_fused_kernel, resample_mfma_kernel): the accumulation order inside
-    v_mfma_f32_* is not something a numpy model can claim.  They stay compared with the kernels pinned here;
   * the PLL and the discriminator's v_rcp_f32 (the PLL's output is an input tap here, as the discriminator's is);
   * the exact banks: already bit for bit against the oracle (tests/test_gpu_channels.py)."""
 import math
