@@ -405,6 +405,58 @@ FMRX_API int fmrx_rds_diff_decode(const uint8_t *in, size_t n, uint8_t *out);
 FMRX_API int fmrx_rds_frame_sync(const uint8_t *bits, size_t n, char *offset_type, size_t *next_index);
 
 /* ------------------------------------------------------------------ */
+/* RDS station decoder: PI, PTY, PS name, RadioText                     */
+/* ------------------------------------------------------------------ */
+/* Next to the model-faithful bit recovery above (which restarts every block and so never carries an RDS group across calls):
+ * a decoder whose chip timing, Manchester pairing, differential decoding and block sync carry across calls, on the in-phase
+ * matched-filter row that fmrx_rds_process returns (rrc_i), then groups (IEC 62106: 0A/0B PS name, TA, MS; 2A/2B RadioText;
+ * PI, PTY, TP from every group) into a station record.  Algorithm and constants: rds_station.hpp.  The host decoder below and
+ * the RDS bank's stations (fmrx_rds_bank_set_stations) compute the same records byte for byte.  The host decoder is host code
+ * (one station's ~2 400 samples per 40 ms call). */
+typedef struct fmrx_rds_station {
+    uint16_t pi;          /* programme identification (block A, or C' of version-B groups) */
+    uint8_t pty, tp;      /* programme type, traffic programme (block B) */
+    uint8_t ta, ms;       /* traffic announcement, music / speech (group 0) */
+    uint8_t synced;       /* block sync held at the end of the last call */
+    uint8_t seen;         /* bit 0: PI decoded, bit 1: PTY / TP decoded */
+    uint8_t ps_mask;      /* PS segments (2 characters each) received */
+    uint8_t rt_ab;        /* RadioText A/B flag of the text held; 2 = no group 2 yet */
+    uint16_t rt_mask;     /* RadioText segments received (2A: 4 characters each, 2B: 2) */
+    uint32_t blocks;      /* blocks checked while synced */
+    uint32_t good_blocks; /* of which passed their syndrome */
+    uint32_t groups;      /* groups assembled */
+    char ps[8];           /* programme service name, spaces where not yet received (not NUL-terminated) */
+    char rt[64];          /* RadioText, spaces where not yet received; cleared when the A/B flag changes */
+} fmrx_rds_station;
+typedef struct fmrx_rds_group {
+    uint16_t block[4];    /* information words of slots A, B, C/C', D (0 where the slot failed) */
+    uint8_t ok_mask;      /* bit s: slot s passed its syndrome; bit 4: slot 2 carried offset C' */
+    uint8_t reserved[3];  /* 0 */
+    uint32_t bit_index;   /* index of the group's first bit in the decoder's bit stream (mod 2^32) */
+} fmrx_rds_group;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_rds_station) == 96, "fmrx_rds_station layout");
+static_assert(sizeof(fmrx_rds_group) == 16, "fmrx_rds_group layout");
+#else
+_Static_assert(sizeof(fmrx_rds_station) == 96, "fmrx_rds_station layout");
+_Static_assert(sizeof(fmrx_rds_group) == 16, "fmrx_rds_group layout");
+#endif
+typedef struct fmrx_rds_station_decoder fmrx_rds_station_decoder;
+/* sps: matched-filter samples per chip, 2..64 (fmrx_rds_params.sps: 26 in mode 0, 43 in mode 2) */
+FMRX_API int fmrx_rds_station_create(fmrx_rds_station_decoder **out, int sps);
+FMRX_API int fmrx_rds_station_destroy(fmrx_rds_station_decoder *d);
+FMRX_API int fmrx_rds_station_reset(fmrx_rds_station_decoder *d);
+/* Upper bound of the groups one feed_rrc of n_samples can produce (feed_bits of n bits: 2*(n/26 + 1)). */
+FMRX_API size_t fmrx_rds_station_max_groups(const fmrx_rds_station_decoder *d, size_t n_samples);
+/* One call's rrc_i [n] -> the groups completed in it (g [max_g]; groups beyond max_g are counted in st->groups but not
+ * stored), *n_g, and the station record after it (st).  g / n_g may be NULL together. */
+FMRX_API int fmrx_rds_station_feed_rrc(fmrx_rds_station_decoder *d, const double *rrc_i, size_t n, fmrx_rds_group *g, size_t max_g,
+                                       size_t *n_g, fmrx_rds_station *st);
+/* The same from differentially decoded bits (0 / 1): block sync and groups alone. */
+FMRX_API int fmrx_rds_station_feed_bits(fmrx_rds_station_decoder *d, const uint8_t *bits, size_t n, fmrx_rds_group *g, size_t max_g,
+                                        size_t *n_g, fmrx_rds_station *st);
+
+/* ------------------------------------------------------------------ */
 /* RDS banks: the RDS chain of N channels per device call               */
 /* ------------------------------------------------------------------ */
 /* fmrx_rds for N independent stations at once, in a fixed number of kernel launches per call whatever N: the float64 chain
@@ -431,6 +483,18 @@ FMRX_API int fmrx_rds_bank_collect(fmrx_rds_bank *b, double *rrc_i, double *rrc_
 FMRX_API int fmrx_rds_bank_process(fmrx_rds_bank *b, const float *demod, double *rrc_i, double *rrc_q, uint8_t *bits,
                                    size_t *n_bits, char *offset_type);
 FMRX_API int fmrx_rds_bank_read_tap(fmrx_rds_bank *b, int channel, int which, double *out, size_t *n);  /* FMRX_RDS_TAP_* */
+/* Stations: one station decoder per channel (rds_station.hpp) as a kernel of process_dev, one lane per channel on the
+ * matched-filter row; records stay on the device until fmrx_rds_bank_stations.  Off by default (a bank then runs exactly the
+ * kernels it runs without this); on / off only before the first call or right after fmrx_rds_bank_reset(b, -1).  With stations
+ * on, either fmrx_rds_bank_stations or fmrx_rds_bank_collect takes the last call off the "not collected" rule, and collect's
+ * frame-sync report covers the bits of the calls it saw.  fmrx_rds_bank_reset(b, c) clears channel c's decoder too. */
+FMRX_API int fmrx_rds_bank_set_stations(fmrx_rds_bank *b, int on);
+/* groups per channel one call can produce: the row length of g below */
+FMRX_API size_t fmrx_rds_bank_max_groups(const fmrx_rds_bank *b);
+/* waits for the last process_dev; st [n_channels] (required), g [n_channels][max_groups] and n_g [n_channels] (both or neither):
+ * every channel's station record and the groups its last call completed, exactly what an fmrx_rds_station_decoder fed the
+ * channel's rrc_i rows produces */
+FMRX_API int fmrx_rds_bank_stations(fmrx_rds_bank *b, fmrx_rds_station *st, fmrx_rds_group *g, size_t *n_g);
 /* Receiver banks that keep discriminator rows (stereo banks, exact banks, the resampling modes' banks): where the last
  * call's rows are, for fmrx_rds_bank_process_dev on the same stream.  FMRX_EINVAL for the fused mono bank of modes 0/1.
  * A call leaves its rows intact (only the history in front of each row is rewritten) until the next fmrx_channels_process*;

@@ -156,6 +156,15 @@ _sig("fmrx_rds_bank_process_dev", [_vp, _vp, _sz, _vp])
 _sig("fmrx_rds_bank_collect", [_vp, _vp, _vp, _vp, _vp, _vp])
 _sig("fmrx_rds_bank_process", [_vp, _f32p, _vp, _vp, _vp, _vp, _vp])
 _sig("fmrx_rds_bank_read_tap", [_vp, _int, _int, _vp, C.POINTER(_sz)])
+_sig("fmrx_rds_bank_set_stations", [_vp, _int])
+_sig("fmrx_rds_bank_max_groups", [_vp], _sz)
+_sig("fmrx_rds_bank_stations", [_vp, _vp, _vp, _vp])
+_sig("fmrx_rds_station_create", [C.POINTER(_vp), _int])
+_sig("fmrx_rds_station_destroy", [_vp])
+_sig("fmrx_rds_station_reset", [_vp])
+_sig("fmrx_rds_station_max_groups", [_vp, _sz], _sz)
+_sig("fmrx_rds_station_feed_rrc", [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp])
+_sig("fmrx_rds_station_feed_bits", [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp])
 _sig("fmrx_channels_demod_layout", [_vp, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz)])
 _sig("fmrx_fe_fir_decim_u8", [_u8p, _sz, _f32p, _sz, _uint, _vp, _vp, _vp, _int])
 _sig("fmrx_fe_plan_create", [C.POINTER(_vp), _f32p, _sz, _uint])
@@ -738,12 +747,87 @@ class RdsBank:
                                          bits.ctypes.data, nb.ctypes.data, off))
         return self._result(*out)
 
+    def set_stations(self, on=True):
+        """A station decoder per channel on the device (off by default); only before the first call or right after reset()."""
+        _check(lib.fmrx_rds_bank_set_stations(self._h, 1 if on else 0))
+        self.max_groups = lib.fmrx_rds_bank_max_groups(self._h)
+
+    def stations(self, raw=False):
+        """Waits for the last process_dev -> (stations: list of dicts, groups: per channel the RDS_GROUP_DTYPE records of the last
+        call).  raw=True: the station records as an RDS_STATION_DTYPE array [n_channels] instead of dicts."""
+        n, mg = self.n_channels, lib.fmrx_rds_bank_max_groups(self._h)
+        st = np.zeros(n, RDS_STATION_DTYPE)
+        g = np.zeros((n, mg), RDS_GROUP_DTYPE)
+        ng = np.zeros(n, np.uint64)
+        _check(lib.fmrx_rds_bank_stations(self._h, st.ctypes.data, g.ctypes.data, ng.ctypes.data))
+        groups = [g[c, :int(ng[c])].copy() for c in range(n)]
+        return (st if raw else [rds_station_dict(r) for r in st]), groups
+
     def read_tap(self, channel, name) -> np.ndarray:
         n = _sz(0)
         _check(lib.fmrx_rds_bank_read_tap(self._h, channel, RDS_TAPS[name], None, C.byref(n)))
         out = np.zeros(n.value)
         _check(lib.fmrx_rds_bank_read_tap(self._h, channel, RDS_TAPS[name], out.ctypes.data, C.byref(n)))
         return out
+
+
+# fmrx_rds_station / fmrx_rds_group (include/fmrx.h): 96 and 16 bytes, no padding
+RDS_STATION_DTYPE = np.dtype([("pi", "<u2"), ("pty", "u1"), ("tp", "u1"), ("ta", "u1"), ("ms", "u1"), ("synced", "u1"), ("seen", "u1"),
+                              ("ps_mask", "u1"), ("rt_ab", "u1"), ("rt_mask", "<u2"), ("blocks", "<u4"), ("good_blocks", "<u4"),
+                              ("groups", "<u4"), ("ps", "u1", (8,)), ("rt", "u1", (64,))])
+RDS_GROUP_DTYPE = np.dtype([("block", "<u2", (4,)), ("ok_mask", "u1"), ("reserved", "u1", (3,)), ("bit_index", "<u4")])
+assert RDS_STATION_DTYPE.itemsize == 96 and RDS_GROUP_DTYPE.itemsize == 16
+
+
+def rds_station_dict(rec) -> dict:
+    """One fmrx_rds_station record (an element of an RDS_STATION_DTYPE array) -> dict; ps and rt as str (latin-1: the RDS
+    character table agrees with ASCII for the letters, digits and punctuation)."""
+    d = {k: int(rec[k]) for k in ("pi", "pty", "tp", "ta", "ms", "seen", "ps_mask", "rt_ab", "rt_mask", "blocks", "good_blocks", "groups")}
+    d["synced"] = bool(rec["synced"])
+    d["ps"] = bytes(rec["ps"]).decode("latin-1")
+    d["rt"] = bytes(rec["rt"]).decode("latin-1")
+    return d
+
+
+class RdsStationDecoder:
+    """The RDS station decoder on the host (fmrx_rds_station_*): PI, PTY, PS and RadioText from the in-phase matched-filter rows
+    an Rds handle returns (feed_rrc), or from differentially decoded bits (feed_bits).  State carries across feeds.  Each feed
+    returns (station dict, the groups it completed as an RDS_GROUP_DTYPE array); .record holds the raw station record."""
+
+    def __init__(self, mode=0, sps: int | None = None):
+        if sps is None:
+            p = RdsParams()
+            _check(lib.fmrx_rds_mode_params(mode, C.byref(p)))
+            sps = p.sps
+        self.sps = int(sps)
+        self._h = _vp()
+        _check(lib.fmrx_rds_station_create(C.byref(self._h), self.sps))
+        self.record = np.zeros(1, RDS_STATION_DTYPE)
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_rds_station_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        _check(lib.fmrx_rds_station_reset(self._h))
+
+    def _feed(self, fn, data, max_g):
+        g, n = np.zeros(max_g, RDS_GROUP_DTYPE), _sz(0)
+        rec = np.zeros(1, RDS_STATION_DTYPE)
+        _check(fn(self._h, data.ctypes.data, len(data), g.ctypes.data, max_g, C.byref(n), rec.ctypes.data))
+        self.record = rec
+        return rds_station_dict(rec[0]), g[:n.value].copy()
+
+    def feed_rrc(self, row):
+        x = np.ascontiguousarray(row, np.float64)
+        return self._feed(lib.fmrx_rds_station_feed_rrc, x, lib.fmrx_rds_station_max_groups(self._h, len(x)))
+
+    def feed_bits(self, bits):
+        b = np.ascontiguousarray(np.asarray(bits) != 0, np.uint8)
+        return self._feed(lib.fmrx_rds_station_feed_bits, b, 2 * (len(b) // 26 + 1))
 
 
 class FrontEndPlan:

@@ -6,6 +6,7 @@
 // become FMRX_EINVAL) -> H2D into per-thread scratch -> HIP kernel(s) -> D2H.
 // No stage has a CPU implementation: without a device they return FMRX_ENODEV.
 #include "fmrx_internal.hpp"
+#include "rds_station.hpp"
 #include "build_id.hpp"   // FMRX_SRC_HASH: written by the Makefile (SHA-256 over the library's sources)
 
 namespace fmrx {
@@ -596,6 +597,81 @@ int fmrx_fe_fir_decim_u8(const uint8_t *iq, size_t n_samples, const float *h, si
     FMRX_TRY(sync0());
     if (hist) std::memcpy(hist, iq + 2 * n_samples - live, live);  // carry: the last taps-1 samples, as bytes
     return FMRX_OK;
+}
+
+}  // extern "C"
+
+// ---- RDS station decoder on the host (rds_station.hpp; the bank's rdsb_station_kernel runs the same functions) ----------
+struct fmrx_rds_station_decoder {
+    fmrx::rdsst::Dec d;
+    double E[fmrx::rdsst::kMaxSps];
+    fmrx_rds_station rec;
+};
+
+namespace {
+void station_reset(fmrx_rds_station_decoder *d, int sps)
+{
+    fmrx::rdsst::init(d->d, sps);
+    for (double &e : d->E) e = 0.0;
+    fmrx::rdsst::clear_record(&d->rec);
+}
+
+template <typename F>
+int station_feed(fmrx_rds_station_decoder *d, size_t n, fmrx_rds_group *g, size_t max_g, size_t *n_g, fmrx_rds_station *st, F each)
+{
+    if (!d || !st) return fail(FMRX_EINVAL, "rds_station_feed: null argument");
+    if ((g == nullptr) != (n_g == nullptr)) return fail(FMRX_EINVAL, "rds_station_feed: g and n_g go together");
+    fmrx::rdsst::Out o{&d->rec, g, g ? static_cast<uint32_t>(std::min<size_t>(max_g, 0xFFFFFFFFu)) : 0u, 0u};
+    for (size_t i = 0; i < n; i++) each(i, o);
+    fmrx::rdsst::finish(d->d, &d->rec);
+    *st = d->rec;
+    if (n_g) *n_g = o.n_g;
+    return FMRX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fmrx_rds_station_create(fmrx_rds_station_decoder **out, int sps)
+{
+    if (!out) return fail(FMRX_EINVAL, "rds_station_create: null argument");
+    if (sps < 2 || sps > fmrx::rdsst::kMaxSps) return fail(FMRX_EINVAL, "rds_station_create: sps %d not in 2..%d", sps, fmrx::rdsst::kMaxSps);
+    fmrx_rds_station_decoder *d = new fmrx_rds_station_decoder;
+    station_reset(d, sps);
+    *out = d;
+    return FMRX_OK;
+}
+
+int fmrx_rds_station_destroy(fmrx_rds_station_decoder *d)
+{
+    delete d;
+    return FMRX_OK;
+}
+
+int fmrx_rds_station_reset(fmrx_rds_station_decoder *d)
+{
+    if (!d) return fail(FMRX_EINVAL, "rds_station_reset: null handle");
+    station_reset(d, d->d.sps);
+    return FMRX_OK;
+}
+
+size_t fmrx_rds_station_max_groups(const fmrx_rds_station_decoder *d, size_t n_samples)
+{
+    return d ? fmrx::rdsst::max_groups_for_samples(n_samples, d->d.sps) : 0;
+}
+
+int fmrx_rds_station_feed_rrc(fmrx_rds_station_decoder *d, const double *rrc_i, size_t n, fmrx_rds_group *g, size_t max_g, size_t *n_g,
+                              fmrx_rds_station *st)
+{
+    if (n && !rrc_i) return fail(FMRX_EINVAL, "rds_station_feed_rrc: null row");
+    return station_feed(d, n, g, max_g, n_g, st, [&](size_t i, fmrx::rdsst::Out &o) { fmrx::rdsst::feed_sample(d->d, d->E, 1, rrc_i[i], o); });
+}
+
+int fmrx_rds_station_feed_bits(fmrx_rds_station_decoder *d, const uint8_t *bits, size_t n, fmrx_rds_group *g, size_t max_g, size_t *n_g,
+                               fmrx_rds_station *st)
+{
+    if (n && !bits) return fail(FMRX_EINVAL, "rds_station_feed_bits: null bits");
+    return station_feed(d, n, g, max_g, n_g, st, [&](size_t i, fmrx::rdsst::Out &o) { fmrx::rdsst::feed_bit(d->d, bits[i] ? 1 : 0, o); });
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 //   rdsb_resample_kernel    rational resampler U/D, 101*U taps, gain U, I and Q                       (rds_resample_kernel x 2)
 //   rdsb_fir_kernel<0>      root-raised-cosine matched filter, I and Q (grid z)                      (rds_fir_kernel x 2)
 //   rdsb_cdr_kernel         clock and data recovery, Manchester and differential decoding, one lane per channel (host cdr())
+//   rdsb_station_kernel     with stations on only: the station decoder of rds_station.hpp, one lane per channel (fmrx_rds_station_*)
 //   rdsb_tail_kernel        carried state: every row's tail -> its history                            (rds_tail_kernel x 6)
 // Frame synchronisation stays on the host (fmrx_rds_bank_collect), ~190 new bits per channel and call.
 //
@@ -26,6 +27,7 @@
 //   bits   u8 [N][max_bits], n_bits u32 [N], blk i32 [N] (0 until a channel's first call: the CDR's block_count != 0 test)
 #include "fmrx_internal.hpp"
 #include "rds_common.hpp"
+#include "rds_station.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -39,6 +41,7 @@ namespace {
 
 constexpr int kR = 4;        // consecutive outputs per thread of the FIR kernels
 constexpr int kPllB = 32;    // samples per lane and batch of the PLL lanes (two 128-byte lines of a double row)
+constexpr int kStB = 32;     // samples per lane and batch of the station lanes
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -284,6 +287,53 @@ __global__ __launch_bounds__(64) void rdsb_cdr_kernel(const double *__restrict__
     blk[ch] = 1;
 }
 
+// The station decoder of rds_station.hpp (fmrx_rds_station_feed_rrc's arithmetic), ONE LANE PER CHANNEL, on the in-phase
+// matched-filter row.  The row arrives a batch ahead through registers into LDS, as in rdsb_pll_lanes_kernel; the per-phase
+// energies live in LDS for the call (they are indexed by the sample's phase); the decoder's scalars stay in registers.  Station
+// records (text as it arrives, the scalars at the end) and group records go out with ordinary vector stores.
+// Dynamic LDS: (kStB + sps) * 64 doubles, [sample][lane] then [phase][lane].  Rows are 16-byte aligned (even pitches).
+__global__ __launch_bounds__(64) void rdsb_station_kernel(const double *__restrict__ y, long ypitch, long n, int n_ch, rdsst::Dec *__restrict__ dec,
+                                                          double *__restrict__ energy, fmrx_rds_station *__restrict__ st,
+                                                          fmrx_rds_group *__restrict__ grp, int max_g, uint32_t *__restrict__ n_g)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const long ch = static_cast<long>(blockIdx.x) * 64 + lane;
+    if (ch >= n_ch) return;
+    double *lin = lds + lane, *E = lds + kStB * 64 + lane;
+    rdsst::Dec d = dec[ch];
+    const int sps = d.sps;
+    double *er = energy + ch * rdsst::kMaxSps;
+    for (int p = 0; p < sps; p++) E[p * 64] = er[p];
+    rdsst::Out o{st + ch, grp + ch * max_g, static_cast<uint32_t>(max_g), 0u};
+    const double *row = y + ch * ypitch;
+    const d2 *row2 = reinterpret_cast<const d2 *>(row);
+    const long nb = n / kStB;
+    d2 pre[kStB / 2];
+    if (nb > 0) {
+#pragma unroll
+        for (int g = 0; g < kStB / 2; g++) pre[g] = row2[g];
+    }
+    for (long b = 0; b < nb; b++) {
+#pragma unroll
+        for (int g = 0; g < kStB / 2; g++) {
+            lin[(2 * g) * 64] = pre[g].x;
+            lin[(2 * g + 1) * 64] = pre[g].y;
+        }
+        if (b + 1 < nb) {
+#pragma unroll
+            for (int g = 0; g < kStB / 2; g++) pre[g] = row2[(b + 1) * (kStB / 2) + g];
+        }
+#pragma unroll 1
+        for (int j = 0; j < kStB; j++) rdsst::feed_sample(d, E, 64, lin[j * 64], o);
+    }
+    for (long k = nb * kStB; k < n; k++) rdsst::feed_sample(d, E, 64, row[k], o);
+    rdsst::finish(d, st + ch);
+    dec[ch] = d;
+    for (int p = 0; p < sps; p++) er[p] = E[p * 64];
+    n_g[ch] = o.n_g;
+}
+
 // carried state: per channel, every history <- the last samples of its row's block (blocks are at least as long as each
 // history, create() checks: source and destination never overlap)
 __global__ __launch_bounds__(256) void rdsb_tail_kernel(double *__restrict__ x, long xpitch, int hx, double *__restrict__ ch, long cpitch, int hc,
@@ -328,6 +378,15 @@ struct fmrx_rds_bank {
     std::vector<std::vector<uint8_t>> decoded;   // per channel: the bits frame synchronisation keeps (fmrx_rds::decoded)
     bool pending = false;                          // a process_dev whose bits have not been collected
     long calls = 0;
+    bool fresh = true;                             // no call since create / reset(-1): stations may be switched
+    bool stations = false;                         // rdsb_station_kernel runs in process_dev
+    long max_g = 0;                                // group records per channel and call
+    DevBuf<rdsst::Dec> dec;                        // [N] station decoders' scalars
+    DevBuf<double> energy;                         // [N][kMaxSps] their per-phase energies
+    DevBuf<fmrx_rds_station> st;                   // [N] station records
+    DevBuf<fmrx_rds_group> grp;                    // [N][max_g] the last call's groups
+    DevBuf<uint32_t> n_g;                          // [N] how many
+    std::vector<uint32_t> h_n_g;
 };
 
 namespace {
@@ -353,6 +412,18 @@ int bank_reset(fmrx_rds_bank *b, int lo, int hi)
     FMRX_HIP(hipMemcpy(b->state.p + 8 * lo, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
     FMRX_HIP(hipMemset(b->blk.p + lo, 0, cnt * sizeof(int)));
     for (int c = lo; c < hi; c++) b->decoded[c].clear();
+    if (b->dec.p) {                                // the station decoders, as fmrx_rds_station_create leaves them
+        std::vector<rdsst::Dec> d(cnt);
+        std::vector<fmrx_rds_station> r(cnt);
+        for (size_t c = 0; c < cnt; c++) {
+            rdsst::init(d[c], b->p.sps);
+            rdsst::clear_record(&r[c]);
+        }
+        FMRX_HIP(hipMemcpy(b->dec.p + lo, d.data(), cnt * sizeof(rdsst::Dec), hipMemcpyHostToDevice));
+        FMRX_HIP(hipMemcpy(b->st.p + lo, r.data(), cnt * sizeof(fmrx_rds_station), hipMemcpyHostToDevice));
+        FMRX_HIP(hipMemset(b->energy.p + lo * rdsst::kMaxSps, 0, cnt * rdsst::kMaxSps * sizeof(double)));
+        FMRX_HIP(hipMemset(b->n_g.p + lo, 0, cnt * sizeof(uint32_t)));
+    }
     FMRX_HIP(hipDeviceSynchronize());
     return FMRX_OK;
 }
@@ -385,6 +456,7 @@ int fmrx_rds_bank_create(fmrx_rds_bank **out, const fmrx_rds_params *p, int n_ch
     b->block = static_cast<long>(block);
     b->n_out = static_cast<long>(n_out);
     b->max_bits = b->n_out / p->sps + 4;
+    b->max_g = p->sps >= 2 ? static_cast<long>(rdsst::max_groups_for_samples(static_cast<uint64_t>(b->n_out), p->sps)) : 0;
     b->delay = delay;
     b->Hx = Hx;
     b->Hc = Hc;
@@ -469,7 +541,63 @@ int fmrx_rds_bank_reset(fmrx_rds_bank *b, int channel)
     if (!b) return fail(FMRX_EINVAL, "rds_bank_reset: null handle");
     if (channel >= b->n_channels) return fail(FMRX_EINVAL, "rds_bank_reset: channel %d of %d", channel, b->n_channels);
     if (b->pending) return fail(FMRX_EINVAL, "rds_bank_reset: the last process_dev has not been collected");
-    return channel < 0 ? bank_reset(b, 0, b->n_channels) : bank_reset(b, channel, channel + 1);
+    if (channel < 0) {
+        FMRX_TRY(bank_reset(b, 0, b->n_channels));
+        b->fresh = true;
+        return FMRX_OK;
+    }
+    return bank_reset(b, channel, channel + 1);
+}
+
+int fmrx_rds_bank_set_stations(fmrx_rds_bank *b, int on)
+{
+    if (!b) return fail(FMRX_EINVAL, "rds_bank_set_stations: null handle");
+    if (!b->fresh) return fail(FMRX_EINVAL, "rds_bank_set_stations: only before the first call or right after fmrx_rds_bank_reset(b, -1)");
+    if (on && (b->p.sps < 2 || b->p.sps > rdsst::kMaxSps))
+        return fail(FMRX_EINVAL, "rds_bank_set_stations: the station decoder takes 2..%d samples per chip, not %d", rdsst::kMaxSps, b->p.sps);
+    if (on && !b->dec.p) {
+        FMRX_HIP(hipSetDevice(b->device));
+        const size_t N = static_cast<size_t>(b->n_channels);
+        FMRX_TRY(b->dec.alloc(N));
+        FMRX_TRY(b->energy.alloc(N * rdsst::kMaxSps));
+        FMRX_TRY(b->st.alloc(N));
+        FMRX_TRY(b->grp.alloc(N * static_cast<size_t>(b->max_g)));
+        FMRX_HIP(hipMemset(b->grp.p, 0, b->grp.bytes()));
+        FMRX_TRY(b->n_g.alloc(N));
+        b->h_n_g.resize(N);
+        b->stations = true;                         // (bank_reset initialises what is allocated)
+        const int rc = bank_reset(b, 0, b->n_channels);
+        if (rc != FMRX_OK) {
+            b->stations = false;
+            b->dec.release();
+            return rc;
+        }
+    }
+    b->stations = on != 0;
+    return FMRX_OK;
+}
+
+size_t fmrx_rds_bank_max_groups(const fmrx_rds_bank *b) { return b ? static_cast<size_t>(b->max_g) : 0; }
+
+int fmrx_rds_bank_stations(fmrx_rds_bank *b, fmrx_rds_station *st, fmrx_rds_group *g, size_t *n_g)
+{
+    if (!b || !st) return fail(FMRX_EINVAL, "rds_bank_stations: null argument");
+    if ((g == nullptr) != (n_g == nullptr)) return fail(FMRX_EINVAL, "rds_bank_stations: g and n_g go together");
+    if (!b->stations) return fail(FMRX_EINVAL, "rds_bank_stations: stations are off (fmrx_rds_bank_set_stations)");
+    FMRX_HIP(hipSetDevice(b->device));
+    b->pending = false;
+    hipStream_t s = b->stream;
+    const size_t N = static_cast<size_t>(b->n_channels);
+    FMRX_HIP(hipStreamWaitEvent(s, b->done, 0));
+    FMRX_HIP(hipMemcpyAsync(st, b->st.p, N * sizeof(fmrx_rds_station), hipMemcpyDeviceToHost, s));
+    if (g) {
+        FMRX_HIP(hipMemcpyAsync(g, b->grp.p, N * static_cast<size_t>(b->max_g) * sizeof(fmrx_rds_group), hipMemcpyDeviceToHost, s));
+        FMRX_HIP(hipMemcpyAsync(b->h_n_g.data(), b->n_g.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    FMRX_HIP(hipStreamSynchronize(s));
+    if (n_g)
+        for (size_t c = 0; c < N; c++) n_g[c] = b->h_n_g[c];
+    return FMRX_OK;
 }
 
 size_t fmrx_rds_bank_n_out(const fmrx_rds_bank *b) { return b ? static_cast<size_t>(b->n_out) : 0; }
@@ -505,6 +633,9 @@ int fmrx_rds_bank_process_dev(fmrx_rds_bank *b, const float *d_demod, size_t pit
     // fmMonoBlock.py:276-280 (fmrx_rds_process): the CDR state is re-made every block
     hipLaunchKernelGGL(rdsb_cdr_kernel, dim3(lanes), dim3(64), 0, s, b->yi.p, b->ypitch, no, b->n_channels, p.sps, 0.0, 0.0, 158L, 0L, b->blk.p,
                        b->bits.p, b->max_bits, b->n_bits.p);
+    if (b->stations)
+        hipLaunchKernelGGL(rdsb_station_kernel, dim3(lanes), dim3(64), (kStB + p.sps) * 64 * sizeof(double), s, b->yi.p, b->ypitch, no,
+                           b->n_channels, b->dec.p, b->energy.p, b->st.p, b->grp.p, static_cast<int>(b->max_g), b->n_g.p);
     hipLaunchKernelGGL(rdsb_tail_kernel, dim3(N), dim3(256), 0, s, b->x.p, b->xpitch, b->Hx, b->ch.p, b->cpitch, b->Hc, b->mi.p, b->mq.p, b->mpitch,
                        b->Hm, b->ri.p, b->rq.p, b->rpitch, b->Hr, n, no);
     hipError_t e = hipGetLastError();
@@ -512,6 +643,7 @@ int fmrx_rds_bank_process_dev(fmrx_rds_bank *b, const float *d_demod, size_t pit
     FMRX_HIP(hipEventRecord(b->done, s));
     b->pending = true;
     b->calls++;
+    b->fresh = false;
     return FMRX_OK;
 }
 

@@ -1,13 +1,19 @@
 """RDS banks (fmrx_rds_bank_*): time per call against the number of channels, device-resident discriminator rows.
 
     python3 tools/rds_bank_bench.py [--mode 0] [--block 9600] [--channels 64,1024,4096,16384,65536] [--calls 8] [--warmup 2]
-                                    [--json out.json]
+                                    [--stations] [--json out.json]
 
 Per channel count, reported separately:
   process_dev  device-event time of fmrx_rds_bank_process_dev (the whole signal chain + CDR lanes, on one stream)
   collect      host time of fmrx_rds_bank_collect once the device is done (bits D2H + per-channel frame synchronisation; the
                matched-filter rows are not copied); collect_rrc: the same with both matched-filter rows copied to the host
   x real time  N * (block / if_Fs) / (process_dev + collect)
+With --stations the streams are stations with PI / PS / RadioText (tests/rds_groups.py) and every channel count is measured
+twice, the second time with the bank's station decoders on (fmrx_rds_bank_set_stations):
+  process_dev_stations_ms  device-event time of process_dev with rdsb_station_kernel; station_kernel_share = its excess
+  stations_ms              host time of the fmrx_rds_bank_stations call (records + groups D2H), preallocated buffers
+  collect_c_ms             host time of the fmrx_rds_bank_collect call on the same bank, preallocated buffers, no rows
+  ps_right                 channels whose decoded PS name is the transmitted one after the last call
 and, once: float64 operations per IF sample counted from the shapes, and the single-stream handle (fmrx_rds) on one of the same
 streams: process_dev device time and fmrx_rds_process host time per block.  Channel counts that do not fit the device's free
 memory are reported as skipped."""
@@ -54,6 +60,48 @@ def row_bytes(p, block: int) -> int:
     return 8 * rows + 4 * block + no // p.sps + 64
 
 
+def stations_leg(fmrx, a, p, n, block, calls, d_src, S, stream, ps_of) -> dict:
+    """The same calls on a bank with stations on: process_dev device time, and the C calls stations / collect timed apart
+    (alternate calls; either takes a call off the not-collected rule)."""
+    import torch
+    bank = fmrx.RdsBank(a.mode, n, block)
+    bank.set_stations(True)
+    L, h = fmrx.lib, bank._h
+    mg = bank.max_groups
+    st = np.zeros(n, fmrx.RDS_STATION_DTYPE)
+    g = np.zeros((n, mg), fmrx.RDS_GROUP_DTYPE)
+    ng = np.zeros(n, np.uint64)
+    bits = np.zeros((n, bank.max_bits), np.uint8)
+    nb = np.zeros(n, np.uint64)
+    off = ctypes.create_string_buffer(8 * n)
+    rows = torch.empty((n, block), dtype=torch.float32, device="cuda")
+    idx = torch.arange(n, device="cuda") % S
+    pd, t_st, t_co = [], [], []
+    for k in range(calls):
+        rows.copy_(d_src[idx, k * block:(k + 1) * block])
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        bank.process_dev(rows.data_ptr(), block, stream=stream.cuda_stream)
+        e1.record(stream)
+        e1.synchronize()
+        t0 = time.perf_counter()
+        if k % 2 == 0 or k == calls - 1:
+            fmrx._check(L.fmrx_rds_bank_stations(h, st.ctypes.data, g.ctypes.data, ng.ctypes.data))
+            dt, lst = 1e3 * (time.perf_counter() - t0), t_st
+        else:
+            fmrx._check(L.fmrx_rds_bank_collect(h, None, None, bits.ctypes.data, nb.ctypes.data, off))
+            dt, lst = 1e3 * (time.perf_counter() - t0), t_co
+        if k >= a.warmup:
+            pd.append(e0.elapsed_time(e1))
+            lst.append(dt)
+    ps_right = sum(bytes(st[c]["ps"]).decode("latin-1") == ps_of[c % S] for c in range(n))
+    bank.close()
+    del rows
+    return {"process_dev_stations_ms": statistics.median(pd), "stations_ms": statistics.median(t_st),
+            "collect_c_ms": statistics.median(t_co) if t_co else None, "max_groups": int(mg), "ps_right": int(ps_right)}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", type=int, default=0)
@@ -61,6 +109,7 @@ def main() -> int:
     ap.add_argument("--channels", default="64,1024,4096,16384,65536")
     ap.add_argument("--calls", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--stations", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
 
@@ -75,8 +124,14 @@ def main() -> int:
     period_s = block / p.if_Fs
     # 64 distinct stations (seeds, chip offsets, amplitudes, noise); channel c carries station c % 64
     S = 64
-    src = np.stack([rds_demod_signal(calls * block, float(p.if_Fs), seed=300 + s, amplitude=0.03 + 0.01 * (s % 7),
-                                     chip_offset=float((37 * s) % 101), noise=0.002 * (s % 4))[0] for s in range(S)])
+    if a.stations:
+        from rds_groups import station_demod
+        ps_of = [f"BENCH{s:02d} "[:8] for s in range(S)]
+        src = np.stack([station_demod(calls * block, if_Fs=float(p.if_Fs), pi=0x2000 + s, ps=ps_of[s], rt=f"STATION {s}", seed=300 + s,
+                                      amplitude=0.03 + 0.01 * (s % 7), chip_offset=float((37 * s) % 101), noise=0.002 * (s % 4)) for s in range(S)])
+    else:
+        src = np.stack([rds_demod_signal(calls * block, float(p.if_Fs), seed=300 + s, amplitude=0.03 + 0.01 * (s % 7),
+                                         chip_offset=float((37 * s) % 101), noise=0.002 * (s % 4))[0] for s in range(S)])
     d_src = torch.from_numpy(src).cuda()
     results = {"mode": a.mode, "block": block, "block_ms": 1e3 * period_s, "f64_ops_per_if_sample": f64_ops_per_if_sample(p), "sweep": []}
 
@@ -139,6 +194,9 @@ def main() -> int:
                "x_real_time": n * 1e3 * period_s / (t_pd + t_co), "us_per_channel_block": 1e3 * (t_pd + t_co) / n,
                "f64_gflops": n * block * results["f64_ops_per_if_sample"]["total"] / (t_pd * 1e6),
                "offsets_reported_last_call": int(synced)}
+        if a.stations:
+            rec.update(stations_leg(fmrx, a, p, n, block, calls, d_src, S, stream, ps_of))
+            rec["station_kernel_share"] = rec["process_dev_stations_ms"] / t_pd - 1
         results["sweep"].append(rec)
         print(json.dumps(rec), flush=True)
     if a.json:
