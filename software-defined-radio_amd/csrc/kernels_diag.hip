@@ -4,6 +4,7 @@
 //   method 0: global_load_dwordx4, non-temporal, 4 loads in flight per wave, into registers
 //   method 1: LDS-DMA (global_load_lds_dwordx4) into a wave-private 4-slot ring, counted vmcnt, read back
 //   method m >= 2: as 1, chunks of m - 1 steps of 3 KiB dealt round-robin over the waves instead of one contiguous run per wave
+//   method | 0x10000: an LDS-DMA method (m >= 1) with the non-temporal cache policy (aux = 2), as the fused mono kernel streams its input
 // Persistent grid, every wave streams its own contiguous run; the data is XOR-reduced so nothing is dropped.
 #include "fmrx_internal.hpp"
 
@@ -35,6 +36,7 @@ __global__ __launch_bounds__(256) void read_regs_kernel(const u4 *__restrict__ x
 
 // SWEEP: steps are dealt round-robin over the waves (the chip reads one contiguous stretch at any moment) instead of every
 // wave owning one contiguous run
+template <int AUX>
 __global__ __launch_bounds__(256) void read_dma_kernel(const unsigned char *__restrict__ x, long n_bytes, unsigned *__restrict__ out, int SWEEP)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256) void read_dma_kernel(const unsigned char *__re
 #pragma unroll
         for (int k = 0; k < 3; k++)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(x + s * 3072 + k * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void *)(ring + slot * 3072 + k * 1024), 16, 0, 0);
+                                             (__attribute__((address_space(3))) void *)(ring + slot * 3072 + k * 1024), 16, 0, AUX);
     };
     u4 acc = {0, 0, 0, 0};
     for (int i = 0; i < 3 && s0 + i < s1; i++) issue(s0 + i, i);
@@ -77,14 +79,18 @@ int k_stream_read(const void *d_buf, size_t bytes, int method, unsigned *d_sink,
 {
     if (bytes < 3072 * 1024) return fail(FMRX_EINVAL, "stream_read: buffer too small to mean anything");
     if (reinterpret_cast<uintptr_t>(d_buf) % 16) return fail(FMRX_EINVAL, "stream_read: buffer must be 16-byte aligned");
-    if (method == 0)
+    const bool nt = (method & 0x10000) != 0;
+    const int m = method & 0xffff;
+    if (nt && m == 0) return fail(FMRX_EINVAL, "stream_read: the non-temporal variant is of the LDS-DMA methods");
+    const int sweep = m >= 2 ? m - 1 : 0;   // method m >= 2: chunks of m - 1 steps
+    if (m == 0)
         hipLaunchKernelGGL(read_regs_kernel, dim3(1024), dim3(256), 0, s, static_cast<const u4 *>(d_buf), static_cast<long>(bytes / 16), d_sink);
-    else if (method == 1)
-        hipLaunchKernelGGL(read_dma_kernel, dim3(512), dim3(256), 4 * 4 * 3072, s, static_cast<const unsigned char *>(d_buf),
-                           static_cast<long>(bytes - bytes % 3072), d_sink, 0);
-    else   // method m >= 2: chunks of m - 1 steps
-        hipLaunchKernelGGL(read_dma_kernel, dim3(512), dim3(256), 4 * 4 * 3072, s, static_cast<const unsigned char *>(d_buf),
-                           static_cast<long>(bytes - bytes % 3072), d_sink, method - 1);
+    else if (nt)
+        hipLaunchKernelGGL(read_dma_kernel<2>, dim3(512), dim3(256), 4 * 4 * 3072, s, static_cast<const unsigned char *>(d_buf),
+                           static_cast<long>(bytes - bytes % 3072), d_sink, sweep);
+    else
+        hipLaunchKernelGGL(read_dma_kernel<0>, dim3(512), dim3(256), 4 * 4 * 3072, s, static_cast<const unsigned char *>(d_buf),
+                           static_cast<long>(bytes - bytes % 3072), d_sink, sweep);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FMRX_EHIP, "launch stream_read: %s", hipGetErrorString(e));
     return FMRX_OK;

@@ -54,7 +54,11 @@ using i4 = int __attribute__((ext_vector_type(4)));
 using f2 = float __attribute__((ext_vector_type(2)));
 using f4 = float __attribute__((ext_vector_type(4)));
 
+// cache-policy operand of a load that no other wave reads again (it compiles to `nt`): the fused kernel's input stream
+constexpr int kNtPolicy = 2;
+
 constexpr int iclamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+constexpr int igcd(int a, int b) { return b == 0 ? a : igcd(b, a % b); }
 
 template <int T, int D, int PF = 0>
 struct MfCfg {
@@ -98,8 +102,8 @@ __device__ __forceinline__ void wait_vmcnt()
 // to dst (wave-uniform LDS address).  Bytes before the block come from the tail of the history; addresses past
 // the block are clamped to its last 16 bytes (what lands there only ever meets zero taps or outputs that are not
 // stored), so every instruction is issued with its full, compile-time set of lanes: the counted waits of the
-// kernels depend on that.
-template <int NPF, int REM_LANES>
+// kernels depend on that.  AUX is the cache policy of the loads (0 default, kNtPolicy non-temporal).
+template <int NPF, int REM_LANES, int AUX = 0>
 __device__ __forceinline__ void dma_window(const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist_end, long n_bytes,
                                            long s0, uint8_t *dst, int lane)
 {
@@ -110,7 +114,7 @@ __device__ __forceinline__ void dma_window(const uint8_t *__restrict__ x, const 
         for (int k = 0; k < NP; k++)
             if (k < NPF || lane < REM_LANES)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(base + (lane * 16 + k * 1024)),
-                                                 (__attribute__((address_space(3))) void *)(dst + k * 1024), 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void *)(dst + k * 1024), 16, 0, AUX);
     } else {
 #pragma unroll
         for (int k = 0; k < NP; k++)
@@ -119,7 +123,7 @@ __device__ __forceinline__ void dma_window(const uint8_t *__restrict__ x, const 
                 if (off > n_bytes - 16) off = n_bytes - 16;
                 const uint8_t *src = off < 0 ? hist_end + off : x + off;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                                 (__attribute__((address_space(3))) void *)(dst + k * 1024), 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void *)(dst + k * 1024), 16, 0, AUX);
             }
     }
 }
@@ -502,6 +506,10 @@ struct FuCfg {
     static constexpr int AB_OUT = 256;                             // audio outputs per batch
     static constexpr int TB = AB_OUT * DA / TILE_OUT;              // tiles per batch
     static_assert(TB * TILE_OUT == AB_OUT * DA, "batches end on tile boundaries");
+    // tile t sits in ring slot t mod NSLOT, so a batch (tiles TB*b ...) starts on a multiple of SLOT_STEP: NSTART instances
+    static constexpr int SLOT_STEP = igcd(TB, NSLOT);
+    static constexpr int NSTART = NSLOT / SLOT_STEP;
+    static constexpr int LANE_OFF_END = F::COL_BYTES * (F::COLS - 1) + 16 * 3 + 16;   // > every lane's B offset + 16
     static constexpr int AWIN = (TA - 1) + 15 * DA + 1;            // discriminator samples a column's 16 outputs touch
     static constexpr int AK = (AWIN + 15) / 16 * 4;                // K-steps of the 16x16x4 MFMA, in whole groups of 4
     // A finished batch is multiplied in NPH slices of KPT K-steps, one slice per following tile, so
@@ -529,8 +537,8 @@ template <class C, class F>
 __device__ __forceinline__ void fu_dma_slot(const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist_end, long n_bytes,
                                             int u, uint8_t *ring, int rs, int lane)
 {
-    dma_window<C::NPF, C::REM_LANES>(x, hist_end, n_bytes, static_cast<long>(u) * C::TILE_BYTES - F::FRONT,
-                                     ring + rs * C::TILE_BYTES, lane);
+    dma_window<C::NPF, C::REM_LANES, kNtPolicy>(x, hist_end, n_bytes, static_cast<long>(u) * C::TILE_BYTES - F::FRONT,
+                                                ring + rs * C::TILE_BYTES, lane);
 }
 
 template <int T, int D, int TA, int DA>
@@ -592,13 +600,9 @@ __global__ __launch_bounds__(256, 2) void mono_fused_kernel(
     for (int j = 0; j < C::AK; j++) asm volatile("" : "+v"(au[j]));
     asm volatile("" : "+v"(ci), "+v"(cq));
 
-    {
-        int rs = 0;
-        for (int u = tb; u <= tb + C::P && u <= t1; u++) {
-            fu_dma_slot<C, F>(x, hist_end, n_bytes, u, ring, rs, lane);
-            rs++;
-        }
-    }
+    // tile u lives in ring slot u mod NSLOT: every straight-line batch (tile TB*b + k) then knows its slots at compile
+    // time, up to the batch's start slot, one of NSLOT / gcd(TB, NSLOT)
+    for (int u = tb; u <= tb + C::P && u <= t1; u++) fu_dma_slot<C, F>(x, hist_end, n_bytes, u, ring, u % C::NSLOT, lane);
 
     const int col = lane & 15, g = lane >> 4;
     const int lane_off = F::COL_BYTES * col + 16 * g;
@@ -610,7 +614,7 @@ __global__ __launch_bounds__(256, 2) void mono_fused_kernel(
         const int adr = (C::NSLOT - 1) * C::TILE_BYTES + lane_off + 64 * j;
         wrap_adr[j] = adr >= C::RING ? adr - C::RING : adr;
     }
-    int slot = 0, fill = C::P + 1;                             // ring slot of tile t / of tile t+P+1
+    int slot = tb % C::NSLOT, fill = (tb + C::P + 1) % C::NSLOT;   // ring slot of tile t / of tile t+P+1
     int dpos = C::TILE_OUT;                                    // ring position of tile t's first sample (wave-uniform)
     // the batch being multiplied (at most one): its accumulators, next slice, window, outputs
     bool pend = false;
@@ -698,8 +702,20 @@ __global__ __launch_bounds__(256, 2) void mono_fused_kernel(
         t_fast1 = lim + 1 >= C::TB ? static_cast<int>((lim + 1) / C::TB) * C::TB : 0;
         fast_last = t1 % C::TB == 0 && t1 - C::TB >= t0 && t1 <= in_x && t1 - 1 <= no_tail;
     }
-    auto fast_tile = [&](auto kc, auto lastc, int t) {
+    // The straight-line tiles issue their DMA in the buffer form: one resource per wave, based at its dry tile (a call may be
+    // larger than the 32-bit offsets reach), 16*lane in one constant VGPR, the tile's offset in an SGPR; no 64-bit address
+    // arithmetic per piece.  The records end behind the run's reach (tile t1's window), inside the block.
+    int t_cur = tb;                                                // the next tile of this wave's run
+    const long rbase = static_cast<long>(tb) * C::TILE_BYTES;
+    const long reach = static_cast<long>(t1 - tb + 1) * C::TILE_BYTES + C::NP * 1024L;
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t *>(x + rbase), 0, static_cast<int>(reach < n_bytes - rbase ? reach : n_bytes - rbase), 0x00020000);
+    const int lane16 = 16 * lane;
+    const uint8_t *lring = ring + lane_off;                        // B fragments: this base + compile-time offsets
+    auto fast_tile = [&](auto kc, auto lastc, auto sc, int t) {
         constexpr int k = decltype(kc)::value;                     // tile k of its batch
+        constexpr int U = (decltype(sc)::value + k) % C::NSLOT;    // its ring slot ...
+        constexpr int FILL = (U + C::P + 1) % C::NSLOT;            // ... and that of tile t + P + 1
         // the run's last batch: the tiles behind it belong to the next wave, only tile t1's head is fetched
         constexpr bool STEADY = !decltype(lastc)::value || k + C::P + 1 <= C::TB;
         constexpr int WAIT = STEADY ? C::YOUNGER : (C::NP - 1) + C::NP * (C::TB - k - 1);
@@ -712,27 +728,33 @@ __global__ __launch_bounds__(256, 2) void mono_fused_kernel(
             }
         };
         if constexpr (STEADY) {
-            const uint8_t *src = x + (static_cast<long>(t + C::P + 1) * C::TILE_BYTES - F::FRONT);   // wave-uniform
-            uint8_t *dst = ring + fill * C::TILE_BYTES;
-#pragma unroll
-            for (int q = 0; q < C::NP; q++)
+            const int soff = (t + C::P + 1 - tb) * C::TILE_BYTES - F::FRONT;   // wave-uniform, > 0
+            for_each_index(std::make_integer_sequence<int, C::NP>{}, [&](auto qc) {
+                constexpr int q = decltype(qc)::value;
                 if (q < C::NPF || lane < C::REM_LANES)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + (lane * 16 + q * 1024)),
-                                                     (__attribute__((address_space(3))) void *)(dst + q * 1024), 16, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                        xr, (__attribute__((address_space(3))) void *)(ring + FILL * C::TILE_BYTES + q * 1024), 16, lane16,
+                        soff + q * 1024, 0, kNtPolicy);
+            });
         }
         wait_vmcnt<WAIT>();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         i4 b[F::KSTEPS];
-        if (slot != C::NSLOT - 1) {
-            const uint8_t *bsrc = ring + slot * C::TILE_BYTES + lane_off;
-#pragma unroll
-            for (int j = 0; j < F::KSTEPS; j++) b[j] = *reinterpret_cast<const i4 *>(bsrc + 64 * j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < F::KSTEPS; j++) b[j] = *reinterpret_cast<const i4 *>(ring + wrap_adr[j]);
-        }
+        for_each_index(std::make_integer_sequence<int, F::KSTEPS>{}, [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int OFF = U * C::TILE_BYTES + 64 * j;
+            // only the last slot's window can run past the ring's end, and then only for some lanes
+            if constexpr (OFF + C::LANE_OFF_END > C::RING) {
+                static_assert(U == C::NSLOT - 1, "only the last slot wraps");
+                b[j] = *reinterpret_cast<const i4 *>(ring + wrap_adr[j]);
+            } else {
+                b[j] = *reinterpret_cast<const i4 *>(lring + OFF);
+            }
+        });
         if constexpr (k < C::NPH) slice_load();
+        // all of the tile's LDS reads are in flight before the first is waited for: one round trip, not one per MFMA group
+        __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -763,13 +785,24 @@ __global__ __launch_bounds__(256, 2) void mono_fused_kernel(
         const int ol = F::COL_OUT * col + 2 * g;
         *reinterpret_cast<f2 *>(dring + dpos + ol) = (f2){d0, d1};
         if (dpos == 0 && ol < C::MIRROR) *reinterpret_cast<f2 *>(dring + C::DR + ol) = (f2){d0, d1};
-        slot = slot + 1 == C::NSLOT ? 0 : slot + 1;
-        fill = fill + 1 == C::NSLOT ? 0 : fill + 1;
         dpos = dpos + C::TILE_OUT == C::DR ? 0 : dpos + C::TILE_OUT;
         if constexpr (k < C::NPH) slice_k();
         if constexpr (k == C::NPH - 1) store_batch();
     };
-    for (int t = tb;;) {
+    // one straight-line batch [t, t + TB): one scalar branch picks the instance for its start slot
+    auto fast_batch = [&](auto lastc) {
+        const int s0 = t_cur % C::NSLOT;
+        for_each_index(std::make_integer_sequence<int, C::NSTART>{}, [&](auto ic) {
+            constexpr int S = decltype(ic)::value * C::SLOT_STEP;
+            if (s0 == S)
+                for_each_index(std::make_integer_sequence<int, C::TB>{}, [&](auto kc) {
+                    fast_tile(kc, lastc, std::integral_constant<int, S>{}, t_cur + decltype(kc)::value);
+                });
+        });
+        begin_batch(t_cur / C::TB);
+        t_cur += C::TB;
+    };
+    for (int &t = t_cur;;) {
         if (t >= t0 && (t < t_fast1 || (fast_last && t == t1 - C::TB)) && t % C::TB == 0 && (!pend || pend_ph == 0)) {
             if (!pend) {
                 // nothing is pending in front of the run's first batch: a batch whose outputs are all out of range takes
@@ -777,17 +810,10 @@ __global__ __launch_bounds__(256, 2) void mono_fused_kernel(
                 begin_batch(t / C::TB);
                 pend_a0 = n_audio;
             }
-            for (; t < t_fast1; t += C::TB) {
-                for_each_index(std::make_integer_sequence<int, C::TB>{},
-                               [&](auto kc) { fast_tile(kc, std::false_type{}, t + decltype(kc)::value); });
-                begin_batch(t / C::TB);
-            }
-            if (fast_last && t == t1 - C::TB) {
-                for_each_index(std::make_integer_sequence<int, C::TB>{},
-                               [&](auto kc) { fast_tile(kc, std::true_type{}, t + decltype(kc)::value); });
-                begin_batch(t / C::TB);
-                t += C::TB;
-            }
+            while (t < t_fast1) fast_batch(std::false_type{});
+            if (fast_last && t == t1 - C::TB) fast_batch(std::true_type{});
+            slot = t % C::NSLOT;
+            fill = (t + C::P + 1) % C::NSLOT;
         }
         const bool have_tile = t < t1;
         bool completed = false;
