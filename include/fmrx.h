@@ -262,6 +262,9 @@ FMRX_API int fmrx_pipeline_process_dev(fmrx_pipeline *pl, const uint8_t *d_iq, s
 #define FMRX_TAP_PLL 6
 #define FMRX_TAP_MIXER 7
 #define FMRX_TAP_STEREO_FINAL 8
+/* fast stereo banks, modes 0 and 1 only: the raw trigArg of every PLL step of the last call (n_if values; the output stage
+ * takes the NCO's cosine of it on chip).  Pipelines and every other bank refuse it (FMRX_EINVAL). */
+#define FMRX_TAP_TRIG_ARG 9
 FMRX_API int fmrx_pipeline_read_tap(fmrx_pipeline *pl, int which, float *out, size_t *n);
 /* carried state, serialised: floats in the order
  *   I_state[rf_taps-1], Q_state[rf_taps-1], prev_i, prev_q, state_mono[Ha]
@@ -344,7 +347,9 @@ FMRX_API int fmrx_channels_create(fmrx_channels **out, const fmrx_params *p, int
  * [n_channels][n_audio][audio_channels] (stereo: interleaved L,R as the writer at src/project.cpp:292-302). */
 FMRX_API int fmrx_channels_create_ex(fmrx_channels **out, const fmrx_params *p, int n_channels, int audio_channels, int exact,
                                      size_t block_bytes, int device);
-/* exact banks: one channel's intermediates of the last call (FMRX_TAP_DEMOD, _CARRIER, _STEREO_BPF, _PLL [n_if + 1]) */
+/* one channel's intermediates of the last call, kept by every bank but the fused mono bank of modes 0/1 (fmrx_channels_create's;
+ * FMRX_EINVAL): FMRX_TAP_DEMOD; stereo banks also FMRX_TAP_STEREO_BPF, _PLL [n_if + 1] and _CARRIER (exact banks: the pilot
+ * band-pass output; fast banks: its sign as the PLL reads it, -1 / 0 / +1), fast banks of modes 0/1 also _TRIG_ARG */
 FMRX_API int fmrx_channels_read_tap(fmrx_channels *c, int channel, int which, float *out, size_t *n);
 FMRX_API int fmrx_channels_destroy(fmrx_channels *c);
 FMRX_API size_t fmrx_channels_n_audio(const fmrx_channels *c);

@@ -28,7 +28,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fmrx.h")
 OK, EINVAL, ENODEV, EHIP, ENOMEM = 0, 1, 2, 3, 4
 PCM_WRAP, PCM_SATURATE = 1, 0
 TAPS = {"if_i": 0, "if_q": 1, "demod": 2, "mono_filt": 3, "carrier_filt": 4, "stereo_filt": 5, "pll": 6, "mixer": 7,
-        "stereo_final": 8}
+        "stereo_final": 8, "trig_arg": 9}
 
 
 class FmrxError(RuntimeError):
@@ -580,7 +580,8 @@ class Channels:
         return {"audio": f, "pcm16": s}
 
     def read_tap(self, channel, name) -> np.ndarray:
-        """Exact banks: one channel's intermediate of the last call ('demod', 'carrier_filt', 'stereo_filt', 'pll')."""
+        """One channel's intermediate of the last call ('demod'; stereo: 'carrier_filt' -- fast banks: its sign, -1 / 0 / +1 --,
+        'stereo_filt', 'pll'; fast stereo banks of modes 0/1: 'trig_arg'); the fused mono bank of modes 0/1 keeps none."""
         n = _sz(0)
         _check(lib.fmrx_channels_read_tap(self._h, channel, TAPS[name], None, C.byref(n)))
         out = np.zeros(n.value, np.float32)

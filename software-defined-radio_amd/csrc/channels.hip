@@ -288,7 +288,7 @@ int fmrx_channels_process(fmrx_channels *c, const uint8_t *iq, float *audio_f32,
 int fmrx_channels_read_tap(fmrx_channels *c, int channel, int which, float *out, size_t *n)
 {
     if (!c || !n) return fail(FMRX_EINVAL, "channels_read_tap: null argument");
-    if (!c->bank) return fail(FMRX_EINVAL, "channels_read_tap: only banks created with exact = 1 keep their intermediates in memory");
+    if (!c->bank) return fail(FMRX_EINVAL, "channels_read_tap: the fused mono bank of modes 0/1 keeps no intermediates in memory (stereo, exact and resampling-mode banks do)");
     FMRX_HIP(hipSetDevice(c->device));
     return stereo_bank_read_tap(c->bank, channel, which, out, n);
 }

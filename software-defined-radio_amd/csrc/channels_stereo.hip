@@ -30,7 +30,7 @@
 //   slots   u8  [n_channels][hist_bytes | block_bytes]   raw I/Q as on stdin; the history IS I_state/Q_state/prev_i/prev_q
 //   demod   f32 [n_channels][Hd | n_if | pad]            discriminator output; history = state_mono / _stereo / _carrier / _allpass
 //   carrier, bpf, trig f32 [n_channels][n_if + pad]      pilot band-pass, 22-54 kHz band-pass, raw trigArg of every PLL step -> NCO output
-//   pll     f32 [n_channels][8]                          state_PLL (6) ; nco0 [n_channels] = PLL[0] of this call
+//   pll     f32 [n_channels][8]                          state_PLL (6), fast banks: the PLL's fr (slot 6) ; nco0 [n_channels] = PLL[0] of this call
 //   mixtail f32 [2][n_channels][Hm]                      state_stereofilt, ping-pong
 #include "device_math.hpp"
 #include "fmrx_internal.hpp"
@@ -844,7 +844,7 @@ __global__ void chs_fill_state_kernel(float *__restrict__ pll, long n)
     const long i = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int u = static_cast<int>(i % 8);
-    pll[i] = (u == 2 || u == 4) ? 1.0f : 0.0f;                 // state_PLL = {0, 0, 1, 0, 1, 0}  (src/project.cpp:458)
+    pll[i] = (u == 2 || u == 4) ? 1.0f : 0.0f;                 // state_PLL = {0, 0, 1, 0, 1, 0}  (src/project.cpp:458); fast banks' fr = 0
 }
 
 }  // namespace
@@ -1396,21 +1396,35 @@ int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int w
     return FMRX_OK;
 }
 
-// diagnostics / tests: one channel's row of an intermediate of the last call.  which: FMRX_TAP_DEMOD, _CARRIER, _STEREO_BPF,
-// _PLL (n_if + 1 values: PLL[0] = the state's lastOut, then the finished NCO values)
+// diagnostics / tests: one channel's row of an intermediate of the last call.  which: FMRX_TAP_DEMOD, _CARRIER (fast banks: the
+// sign row the PLL reads, as -1 / 0 / +1), _STEREO_BPF, _PLL (n_if + 1 values: PLL[0] = the state's lastOut, then the finished
+// NCO values), _TRIG_ARG (fast banks of modes 0/1: the raw trigArg of every step -- their output stage takes the cosine on chip,
+// the row stays raw; the other banks' NCO pass overwrites it in place)
 int stereo_bank_read_tap(StereoBank *b, int channel, int which, float *out, size_t *n)
 {
     if (channel < 0 || channel >= b->n_channels) return fail(FMRX_EINVAL, "channels_read_tap: channel %d of %d", channel, b->n_channels);
     FMRX_HIP(hipDeviceSynchronize());
     const size_t n_if = static_cast<size_t>(b->n_if);
+    const bool stereo = b->audio_channels == 2;
     const float *src = nullptr;
     size_t cnt = n_if;
     switch (which) {
     // the finish kernel has copied the row's tail into its front already; the block itself is intact
     case FMRX_TAP_DEMOD: src = b->demod.p + channel * b->dpitch + b->Hd; break;
-    case FMRX_TAP_CARRIER: if (b->audio_channels == 2 && b->exact) src = b->carrier.p + channel * b->ypitch; break;
-    case FMRX_TAP_STEREO_BPF: if (b->audio_channels == 2) src = b->bpf.p + channel * b->ypitch; break;
-    case FMRX_TAP_PLL: if (b->audio_channels == 2) { src = b->trig.p + channel * b->ypitch; cnt = n_if + 1; } break;
+    case FMRX_TAP_CARRIER:
+        if (stereo && !b->exact) {
+            *n = cnt;
+            if (!out) return FMRX_OK;
+            std::vector<int8_t> sg(n_if);
+            FMRX_HIP(hipMemcpy(sg.data(), b->carrier8.p + channel * b->cpitch, n_if, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < n_if; k++) out[k] = static_cast<float>(sg[k]);
+            return FMRX_OK;
+        }
+        if (stereo) src = b->carrier.p + channel * b->ypitch;
+        break;
+    case FMRX_TAP_STEREO_BPF: if (stereo) src = b->bpf.p + channel * b->ypitch; break;
+    case FMRX_TAP_PLL: if (stereo) { src = b->trig.p + channel * b->ypitch; cnt = n_if + 1; } break;
+    case FMRX_TAP_TRIG_ARG: if (stereo && !b->exact && !b->resample) src = b->trig.p + channel * b->ypitch; break;
     default: break;
     }
     if (!src) return fail(FMRX_EINVAL, "channels_read_tap: tap %d is not kept by this bank", which);

@@ -698,7 +698,10 @@ __global__ __launch_bounds__(kRepairThreads) void pll_repair_kernel(
 // (one STATES set per receiver, src/project.cpp:455-468): a wave walks 64 channels' loops in lock step, the bank's
 // rows are [channel][sample].  in: the pilot band-pass output; trig: the raw trigArg of every step (the NCO output
 // cosf(trigArg*ncoScale + phaseAdjust) is off the chain: the bank's output kernel applies it); state: 8 floats per
-// channel, the reference's six first; nco0[channel] = PLL[0] of this call = the incoming state's lastOut.
+// channel, the reference's six first; nco0[channel] = PLL[0] of this call = the incoming state's lastOut.  FAST: slot 6
+// carries the angle s.fr itself from launch to launch (the reset state's 0 is the fr of (1, 0)), so that a call or chunk
+// seam leaves the trajectory alone -- rebuilding it from the carried (fbI, fbQ) = hardware cos / sin of it, as atan2f(fbQ,
+// fbI) / 2 pi, is not the identity.
 // Rows are 16-byte aligned with >= 16 readable floats behind their n samples (host contract): the input is fetched as
 // 16-byte groups three groups ahead of the chain.
 // IN8 (fast bank): the input is the SIGN of the pilot band-pass output, one signed byte per sample (+1 / -1; 0 = a sample that
@@ -725,8 +728,7 @@ __global__ __launch_bounds__(64, 1) void pll_channels_kernel(const float *__rest
     const long ch = static_cast<long>(blockIdx.x) * 64 + threadIdx.x;
     if (ch >= n_ch) return;
     float *st = state + 8 * ch;
-    PllState s{st[0], st[1], st[2], st[3], st[4], st[5], 0.0f};
-    if (MATH == kFast) s.fr = atan2f(st[3], st[2]) * 0.15915494309189533577f;
+    PllState s{st[0], st[1], st[2], st[3], st[4], st[5], MATH == kFast ? st[6] : 0.0f};
     if (nco0) nco0[ch] = s.last;
     const f4 *in4 = reinterpret_cast<const f4 *>(in + ch * pitch_in);
     const int8_t *in8 = reinterpret_cast<const int8_t *>(in) + ch * pitch_in;    // IN8: pitch in bytes
@@ -838,6 +840,7 @@ __global__ __launch_bounds__(64, 1) void pll_channels_kernel(const float *__rest
     }
     finish_state<MATH>(s, c);
     store_state(st, s);
+    if (MATH == kFast) st[6] = s.fr;
 }
 
 __global__ void libm_eval_kernel(int fn, const float *__restrict__ a, const float *__restrict__ b, size_t n,

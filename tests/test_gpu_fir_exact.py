@@ -26,7 +26,8 @@ The f32 matrix-core sums (the audio FIR inside mono_fused_kernel, resample_mfma_
 bit against an fmaf-chain model, by tests/test_gpu_mfma_exact.py.
 
 Out of scope, on purpose:
-  * the PLL and the discriminator's v_rcp_f32 (the PLL's output is an input tap here, as the discriminator's is);
+  * the PLL and the discriminator's v_rcp_f32 (the PLL's output is an input tap here, as the discriminator's is; the
+    fast PLL is pinned against its own model by tests/test_gpu_pll_exact.py);
   * the exact banks: already bit for bit against the oracle (tests/test_gpu_channels.py)."""
 import math
 
