@@ -81,6 +81,7 @@ FMRX_API int fmrx_set_device(int device);
  *                      complete when the call is made; the stages of consecutive calls then run on internal streams, a call
  *                      apart (1: the next call's front end under this call's PLL and output stage; 2: three lanes).  Outputs
  *                      stay complete in the order of the stream passed to the call; results are bit-identical.  Default 0
+ *   "tuner_variant"    wideband tuner: 0 = matrix-core kernel (default; FMRX_TUNER_VARIANT=mfma), 1 = generic kernel (=generic)
  *   "pll_warmup", "pll_segment"               lane shape of the parallel-in-time PLL (-1 = built-in)
  *   "pll_start"        where the parallel PLL's lanes start: 1 (default) = the locked loop solved as a linear system of the
  *                      input's signs + 64 true steps, 0 = the block's initial state plus drift + 512 true steps
@@ -547,6 +548,45 @@ FMRX_API size_t fmrx_fe_plan_history_bytes(const fmrx_fe_plan *plan);
  * I,Q, n_samples/decim pairs.  stream: hipStream_t (NULL = default stream). */
 FMRX_API int fmrx_fe_run_dev(const fmrx_fe_plan *plan, const uint8_t *d_iq, size_t n_samples, const uint8_t *d_hist,
                              float *d_if, int force_generic, void *stream);
+
+/* ------------------------------------------------------------------ */
+/* Wideband tuner: N channels of a receiver bank from one wide capture   */
+/* ------------------------------------------------------------------ */
+/* The stage in front of a bank: ONE wide capture (interleaved u8 I,Q at Fs_w = R * rf_Fs, R = 2 .. 32) in, N channels'
+ * u8 I,Q streams at rf_Fs out, each centred on its own offset f_c -- a frequency-translating decimating FIR per channel, one
+ * int8 matrix-core GEMM for all of them (csrc/kernels_tuner.hip), written straight into the bank's input slots.
+ *   y_c[m] = Q( g_c * sum_{k<T} h[k] * x[mR - k] * e^{-j 2 pi f_c (mR - k) / Fs_w} ),   x = (u8 - 128) as complex
+ * in exact integer arithmetic (defined by tests/_tuner_model.py):
+ *   w = round(f_c / Fs_w * 2^32) mod 2^32; taps g_c h[k] e^{+j 2 pi (w k mod 2^32) / 2^32} scaled by 2^s (s the largest
+ *   integer with both parts <= 127 * 256 in magnitude, -14 <= s <= 47) and rounded half away from zero to int16 pairs;
+ *   acc = sum_k taps[k] x[mR - k] in int32; rotation by (cos - j sin)(2 pi i / 4096) as round(32767 .), i = top 12 bits
+ *   of w * n mod 2^32, n = mR counted in wide samples since create / reset; out = clamp(128 + ((y + 2^(s+14)) >> (s+15)), 0, 255).
+ * Outputs do not depend on how the stream is cut into calls.
+ *
+ * fmrx_tuner_design / fmrx_tuner_table are host code (no device needed): the integers a channel uses.  design rejects
+ * (FMRX_EINVAL) non-finite or all-zero gain x taps, |f_c| >= Fs_w / 2, s outside its range, and tap sets whose worst case
+ * 128 * sum(|re| + |im|) does not fit int32.  table: cos_q15 / sin_q15 [4096] (either NULL: only *n is set). */
+typedef struct fmrx_tuner fmrx_tuner;
+FMRX_API int fmrx_tuner_design(const float *h, int taps, double Fs_w, double f_c, double gain, uint32_t *w, int *s, int16_t *re,
+                               int16_t *im);
+FMRX_API int fmrx_tuner_table(int16_t *cos_q15, int16_t *sin_q15, size_t *n);
+/* h [taps]: the prototype low-pass at Fs_w (2 .. 4096 taps; more than 256 run the generic kernel).  max_wide_samples: the
+ * largest call, a multiple of R.  Every channel starts at f_c = 0, gain 1.  The option "tuner_variant" is read here. */
+FMRX_API int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int device);
+FMRX_API int fmrx_tuner_destroy(fmrx_tuner *t);
+FMRX_API int fmrx_tuner_reset(fmrx_tuner *t);     /* start of stream: silence in front, sample counter 0; channels keep their settings */
+/* any time between calls; takes effect at the next call (which then waits once for its stream while it uploads) */
+FMRX_API int fmrx_tuner_set_channel(fmrx_tuner *t, int channel, double f_c_hz, double Fs_w, double gain);
+FMRX_API size_t fmrx_tuner_n_out_bytes(const fmrx_tuner *t, size_t n_wide);   /* 2 * n_wide / R; 0 unless n_wide % R == 0 */
+/* d_wide: DEVICE, 16-byte aligned, 2 * n_wide bytes, n_wide % R == 0.  Channel c's bytes go to d_out_first + c * pitch_bytes
+ * (both multiples of 16): exactly what fmrx_channels_input_layout returns, so tuner -> bank -> RDS bank chain on one stream;
+ * several tuners fill disjoint channel ranges of one bank by offsetting d_out_first.  Async on `stream`. */
+FMRX_API int fmrx_tuner_process_dev(fmrx_tuner *t, const uint8_t *d_wide, size_t n_wide, uint8_t *d_out_first, size_t pitch_bytes,
+                                    void *stream);
+/* host in, host out [n_channels][n_out_bytes] */
+FMRX_API int fmrx_tuner_process(fmrx_tuner *t, const uint8_t *wide, size_t n_wide, uint8_t *out);
+/* waits for the last call; per channel, over that call: output bytes that clamped, and sum (I-128)^2 + (Q-128)^2 */
+FMRX_API int fmrx_tuner_levels(fmrx_tuner *t, uint64_t *clipped, uint64_t *power);
 
 #ifdef __cplusplus
 }

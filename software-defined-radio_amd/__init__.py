@@ -172,6 +172,17 @@ _sig("fmrx_fe_plan_destroy", [_vp])
 _sig("fmrx_fe_plan_is_specialised", [_vp])
 _sig("fmrx_fe_plan_history_bytes", [_vp], _sz)
 _sig("fmrx_fe_run_dev", [_vp, _vp, _sz, _vp, _vp, _int, _vp])
+_dbl = C.c_double
+_sig("fmrx_tuner_design", [_f32p, _int, _dbl, _dbl, _dbl, C.POINTER(C.c_uint32), C.POINTER(_int), _i16p, _i16p])
+_sig("fmrx_tuner_table", [_vp, _vp, C.POINTER(_sz)])
+_sig("fmrx_tuner_create", [C.POINTER(_vp), _int, _f32p, _int, _int, _sz, _int])
+_sig("fmrx_tuner_destroy", [_vp])
+_sig("fmrx_tuner_reset", [_vp])
+_sig("fmrx_tuner_set_channel", [_vp, _int, _dbl, _dbl, _dbl])
+_sig("fmrx_tuner_n_out_bytes", [_vp, _sz], _sz)
+_sig("fmrx_tuner_process_dev", [_vp, _vp, _sz, _vp, _sz, _vp])
+_sig("fmrx_tuner_process", [_vp, _u8p, _sz, _u8p])
+_sig("fmrx_tuner_levels", [_vp, _vp, _vp])
 
 
 def _check(rc: int):
@@ -199,12 +210,12 @@ def set_device(dev: int) -> None:
     _check(lib.fmrx_set_device(dev))
 
 
-_FE_VARIANTS = {"mfma": 0, "valu": 1, "discriminator": 0, "arctan": 1}   # option values that have names
+_FE_VARIANTS = {"mfma": 0, "valu": 1, "generic": 1, "discriminator": 0, "arctan": 1}   # option values that have names
 
 
 def set_option(name: str, value) -> None:
     """Process-wide default of a run-time option (include/fmrx.h: fmrx_set_option); pipelines created
-    afterwards start from it.  fe_variant also takes "mfma" / "valu"."""
+    afterwards start from it.  fe_variant also takes "mfma" / "valu", tuner_variant "mfma" / "generic"."""
     _check(lib.fmrx_set_option(name.encode(), int(_FE_VARIANTS.get(value, value))))
 
 
@@ -829,6 +840,84 @@ class RdsStationDecoder:
     def feed_bits(self, bits):
         b = np.ascontiguousarray(np.asarray(bits) != 0, np.uint8)
         return self._feed(lib.fmrx_rds_station_feed_bits, b, 2 * (len(b) // 26 + 1))
+
+
+# --------------------------------------------------------------------------
+# Wideband tuner: one wide capture -> the input slots of a receiver bank
+# --------------------------------------------------------------------------
+def tunerLowPass(Fs_w, R, T) -> np.ndarray:
+    """The default prototype filter of a Tuner: impulseResponseLPF(Fs_w, Fc, T) with Fc half-way between what has to pass
+    and what has to stop.  Pass band: the +-128 kHz an FM channel occupies (75 kHz deviation + the 53 kHz multiplex).  Stop
+    band: from rf_Fs - 100 kHz (rf_Fs = Fs_w / R), the lowest offset whose alias after decimation lands inside the bank's own
+    100 kHz front-end low-pass.  Fc = (128 kHz + rf_Fs - 100 kHz) / 2: half-way, so the Hann-windowed design's transition
+    (about 2 Fs_w / T to either side) clears both edges from T = 8 R on: at T = 8 R the response is within 0.03 dB of its DC
+    gain at 128 kHz and below -54 dB from the stop-band edge to Fs_w / 2, for rf_Fs = 2.4 / 1.44 / 0.96 MS/s and R = 4 ... 20."""
+    rf_Fs = float(Fs_w) / int(R)
+    return impulseResponseLPF(float(Fs_w), 0.5 * (128e3 + rf_Fs - 100e3), int(T))
+
+
+class Tuner:
+    """N channels of one wide u8 I/Q capture (Fs_w = R * rf_Fs), each mixed to its own centre offset, low-pass filtered by
+    the prototype h and decimated by R, as u8 I/Q rows: the input of a receiver bank (fmrx_tuner_*; exact integer
+    arithmetic).  tuner.process_dev(d_wide, n_wide, *bank.input_layout(), stream) followed by
+    bank.process_dev(..., stream=stream) runs capture -> audio without the samples leaving the device."""
+
+    def __init__(self, R, h, n_channels, max_wide_samples, device=0):
+        self.R, self.n_channels, self.max_wide_samples = int(R), int(n_channels), int(max_wide_samples)
+        self.h = _f32(h)
+        self._h = _vp()
+        _check(lib.fmrx_tuner_create(C.byref(self._h), self.R, self.h, len(self.h), self.n_channels, self.max_wide_samples, device))
+
+    @staticmethod
+    def design(h, Fs_w, f_c, gain=1.0):
+        """Host only: (frequency word, scale exponent s, re int16[T], im int16[T]) of one channel."""
+        h = _f32(h)
+        w, s = C.c_uint32(0), _int(0)
+        re, im = np.zeros(len(h), np.int16), np.zeros(len(h), np.int16)
+        _check(lib.fmrx_tuner_design(h, len(h), Fs_w, f_c, gain, C.byref(w), C.byref(s), re, im))
+        return w.value, s.value, re, im
+
+    @staticmethod
+    def table():
+        """Host only: the rotation table (cos, sin) as int16[4096] each."""
+        n = _sz(0)
+        _check(lib.fmrx_tuner_table(None, None, C.byref(n)))
+        c, s = np.zeros(n.value, np.int16), np.zeros(n.value, np.int16)
+        _check(lib.fmrx_tuner_table(c.ctypes.data, s.ctypes.data, C.byref(n)))
+        return c, s
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_tuner_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        _check(lib.fmrx_tuner_reset(self._h))
+
+    def set_channel(self, channel, f_c_hz, Fs_w, gain=1.0):
+        _check(lib.fmrx_tuner_set_channel(self._h, channel, f_c_hz, Fs_w, gain))
+
+    def n_out_bytes(self, n_wide):
+        return lib.fmrx_tuner_n_out_bytes(self._h, n_wide)
+
+    def process(self, wide_u8):
+        """wide_u8: interleaved u8 I,Q (host), a multiple of R samples -> uint8 [n_channels, 2 * n_wide / R]."""
+        x = _u8(wide_u8).reshape(-1)
+        n_wide = len(x) // 2
+        out = np.zeros((self.n_channels, 2 * n_wide // self.R), np.uint8)
+        _check(lib.fmrx_tuner_process(self._h, x, n_wide, out.reshape(-1)))
+        return out
+
+    def process_dev(self, d_wide_ptr, n_wide, d_out_first, pitch_bytes, stream=None):
+        _check(lib.fmrx_tuner_process_dev(self._h, d_wide_ptr, n_wide, d_out_first, pitch_bytes, stream))
+
+    def levels(self):
+        """Of the last call, per channel: (output bytes that clamped, sum of (I-128)^2 + (Q-128)^2) as uint64 arrays."""
+        cl, pw = np.zeros(self.n_channels, np.uint64), np.zeros(self.n_channels, np.uint64)
+        _check(lib.fmrx_tuner_levels(self._h, cl.ctypes.data, pw.ctypes.data))
+        return cl, pw
 
 
 class FrontEndPlan:

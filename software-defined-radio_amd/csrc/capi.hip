@@ -58,6 +58,7 @@ bool option_ref(Options &o, const char *name, long **as_long, int **as_int)
     else if (n == "pll_start") *as_int = &o.pll_start;
     else if (n == "pll_mode") *as_int = &o.pll_mode;
     else if (n == "demod") *as_int = &o.demod;
+    else if (n == "tuner_variant") *as_int = &o.tuner_variant;
     else if (n == "resample_chains") *as_int = &o.resample_chains;
     else if (n == "overlap_calls") *as_int = &o.overlap_calls;
     else return false;
@@ -79,6 +80,7 @@ Options &default_options()
         if (const char *e = std::getenv("FMRX_PLL_SEGMENT")) d.pll_segment = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_START")) d.pll_start = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_MODE")) d.pll_mode = std::atoi(e);
+        if (const char *e = std::getenv("FMRX_TUNER_VARIANT")) d.tuner_variant = std::strcmp(e, "generic") == 0 ? 1 : 0;
         if (const char *e = std::getenv("FMRX_DEMOD")) d.demod = std::strcmp(e, "arctan") == 0 ? 1 : std::atoi(e);
         return d;
     }();
@@ -103,6 +105,7 @@ int set_option_in(Options &o, const char *name, long value)
     int *pi = nullptr;
     if (!option_ref(o, name, &pl, &pi)) return fail(FMRX_EINVAL, "unknown option '%s'", name ? name : "(null)");
     if (pi == &o.fe_variant && value != 0 && value != 1) return fail(FMRX_EINVAL, "option fe_variant: 0 (mfma) or 1 (valu)");
+    if (pi == &o.tuner_variant && value != 0 && value != 1) return fail(FMRX_EINVAL, "option tuner_variant: 0 (mfma) or 1 (generic)");
     if (pi == &o.pll_mode && (value < 0 || value > 2)) return fail(FMRX_EINVAL, "option pll_mode: 0, 1 or 2");
     if (pi == &o.demod && value != 0 && value != 1) return fail(FMRX_EINVAL, "option demod: 0 (the C++ reference's discriminator) or 1 (arctan)");
     if (pl) *pl = value;

@@ -59,6 +59,8 @@ struct Options {
                                    //   linear system of the input's signs, then 64 true warm-up steps; 0 = the block's initial state plus drift, 512 steps
     int pll_mode = 0;              // "pll_mode" / FMRX_PLL_MODE: stereo PLL of the specialised pipeline: 0 = parallel in time, fast math
                                    //   (default); 1 = serial, fast math; 2 = serial, glibc math (the cause-by-cause variants of DESIGN 2)
+    int tuner_variant = 0;         // "tuner_variant" / FMRX_TUNER_VARIANT: wideband tuner (tuner.hip): 0 = matrix-core kernel ("mfma"), 1 = generic kernel ("generic");
+                                   //   read when a tuner is created
     int demod = 0;                 // "demod" / FMRX_DEMOD: 0 = the C++ reference's discriminator (fmDemod, src/filter.cpp:248-266; default),
                                    //   1 = the Python model's arctangent demodulator (fmDemodArctan, model/fmSupportLib.py:502-531), float64
 };
@@ -314,5 +316,26 @@ struct Filters {
     std::vector<float> rf, audio, pilot, stereo;
 };
 Filters design_filters(const fmrx_params &p, bool stereo);
+
+// ---- wideband tuner (kernels_tuner.hip; handle and C ABI in tuner.hip) -----------------
+// One call's launch: the FIR + rotation kernel (matrix-core or generic) and the kernel that carries the history.
+struct TunerLaunch {
+    bool mfma = true;
+    const uint8_t *x = nullptr;          // this call's wide bytes (matrix kernel: 16-byte aligned)
+    long n_bytes = 0;                    // 2 * n_wide
+    const uint8_t *hist = nullptr;       // `front` bytes in front of the call, 16-byte aligned
+    uint8_t *hist_next = nullptr;        // receives the history the next call starts from
+    const int8_t *a_img = nullptr;       // matrix kernel: operand image [group][phase][ksp][64 lanes][16]
+    const int16_t *taps_re = nullptr, *taps_im = nullptr;   // generic kernel: [n_channels][T]
+    const uint2 *chan = nullptr;         // per channel {frequency word, output shift s + 15}
+    const unsigned *table = nullptr;     // rotation table, cos | sin << 16
+    uint8_t *out = nullptr;
+    long pitch = 0;
+    int n_channels = 0, R = 0, T = 0, front = 0, ks = 0, ksp = 0;
+    unsigned n0 = 0;                     // wide-sample index of the call's first sample, mod 2^32
+    unsigned long long *levels = nullptr;   // [n_channels][2] = {clipped, power}, zeroed by the caller
+};
+size_t tuner_mfma_lds_bytes(int R, int ks);
+int tuner_launch(const TunerLaunch &a, hipStream_t stream);
 
 }  // namespace fmrx

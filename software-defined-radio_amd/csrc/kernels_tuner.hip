@@ -1,0 +1,330 @@
+// kernels_tuner.hip -- the wideband tuner's kernels: N channels' frequency-translating decimating FIRs on ONE wide capture
+// (include/fmrx.h: fmrx_tuner_*; arithmetic defined by tests/_tuner_model.py).
+//
+//   y_c[m] = Q( e^{-j phi_c(mR)} * sum_k taps_c[k] * x[mR - k] ),   x = (u8 - 128) as complex, taps_c complex int16
+//
+// Everything is integer arithmetic: the complex-tap FIR on the raw bytes is exact in int32, the rotation by a 2^12-entry
+// table of round(32767 cos), round(32767 sin) is exact in int64, the rounding to u8 is one add and one arithmetic shift.
+//
+// The matrix kernel (tuner_mfma_kernel), on v_mfma_i32_16x16x64_i8:
+//   rows    (M=16) = 4 channels x {real, imaginary part of the accumulator} x 2 balanced base-256 digits of the taps
+//   columns (N=16) = 16 consecutive groups of 8 output times; a column's window starts 16 R bytes after its neighbour's, a
+//                    multiple of 16 for every R, so every B fragment is an aligned ds_read_b128 whatever 2 R is
+//   K              = the raw interleaved bytes of a column's window (XOR 0x80 when staged); the 8 output times of a column
+//                    ("phases") are 8 operand images of the same taps, shifted by 2 R bytes each, against the SAME B fragment.
+// A phase's taps cover 2 T of the window's 2 T + 14 R bytes: only the K-steps its image is non-zero in are stored and
+// multiplied.  Every lane holds 16 consecutive K bytes of its row / column in both operands, so the product does not depend
+// on how the hardware numbers k inside a lane.
+// The C layout gives lane (column, g) the four rows of channel g at one output time per phase: after the 8 phases it holds
+// 8 consecutive (I, Q) byte pairs of that channel = one 16-byte piece of its output row, stored with one global_store_dwordx4
+// (16 lanes: 256 contiguous bytes of a row).  No transpose, no second pass over the outputs.
+// A workgroup = 4 waves = 4 channel groups (16 channels) x 512 output times per step; the step's input window (1024 R bytes
+// plus the filter's reach) is staged once in LDS and shared by the four groups; the rotation table sits in LDS beside it.
+// The stage is padded by 16 bytes per 16 R (the column stride) so that the 16 columns of a B read spread over the banks.
+//
+// The generic kernel (tuner_generic_kernel): one thread per (channel, output), integer loops over the taps; any T, the
+// second device implementation the tests compare with the model (option tuner_variant = 1 / FMRX_TUNER_VARIANT=generic).
+#include "fmrx_internal.hpp"
+#include "tuner_host.hpp"
+
+namespace fmrx {
+namespace {
+
+using i4 = int __attribute__((ext_vector_type(4)));
+using u4 = unsigned __attribute__((ext_vector_type(4)));
+
+constexpr int kTT = 4;                        // tiles (of 16 columns x 8 outputs) per wave and step
+constexpr int kStepOut = 128 * kTT;           // outputs per channel and step
+
+// one output sample: accumulator (ar, ai) -> rotated, rounded, clamped (I, Q) bytes; counts clamps and power
+struct Rot {
+    int c, s;
+};
+__device__ __forceinline__ Rot rot_of(unsigned t) { return {static_cast<short>(t & 0xffffu), static_cast<short>(t >> 16)}; }
+
+__device__ __forceinline__ unsigned tuner_round_pair(int ar, int ai, Rot r, int sh, unsigned &clipped, unsigned long long &power)
+{
+    const long long yr = static_cast<long long>(ar) * r.c + static_cast<long long>(ai) * r.s;
+    const long long yi = static_cast<long long>(ai) * r.c - static_cast<long long>(ar) * r.s;
+    const long long half = 1LL << (sh - 1);
+    long long oi = 128 + ((yr + half) >> sh), oq = 128 + ((yi + half) >> sh);
+    const long long ci = oi < 0 ? 0 : (oi > 255 ? 255 : oi), cq = oq < 0 ? 0 : (oq > 255 ? 255 : oq);
+    clipped += (ci != oi) + (cq != oq);
+    const int di = static_cast<int>(ci) - 128, dq = static_cast<int>(cq) - 128;
+    power += static_cast<unsigned>(di * di + dq * dq);
+    return static_cast<unsigned>(ci) | (static_cast<unsigned>(cq) << 8);
+}
+
+// The same pair in 32-bit arithmetic, for 17 <= sh <= 47 (every gain a receiver would use): with a = ah 2^16 + al (al the
+// balanced low half) the products by the 16-bit table entries are 24-bit multiplies, y = ph 2^16 + pl with |ph|, |pl| < 2^31,
+// and since the rounding constant 2^(sh-1) is a multiple of 2^16,
+//   (y + 2^(sh-1)) >> sh  =  (u + 2^(k-1)) >> k  =  (u >> k) + (bit k-1 of u),   u = ph + (pl >> 16) = y >> 16,  k = sh - 16:
+// exactly the 64-bit form's result (nested floors of divisions by powers of two).
+__device__ __forceinline__ int tuner_round_k(int ph, int pl, int k)
+{
+    const int u = ph + (pl >> 16);
+    return 128 + (u >> k) + ((u >> (k - 1)) & 1);
+}
+__device__ __forceinline__ unsigned tuner_round_pair_fast(int ar, int ai, Rot r, int k, unsigned &clipped, unsigned &power)
+{
+    const int al = static_cast<short>(ar), bl = static_cast<short>(ai);
+    const int ah = (ar - al) >> 16, bh = (ai - bl) >> 16;
+    const int oi = tuner_round_k(__mul24(ah, r.c) + __mul24(bh, r.s), __mul24(al, r.c) + __mul24(bl, r.s), k);
+    const int oq = tuner_round_k(__mul24(bh, r.c) - __mul24(ah, r.s), __mul24(bl, r.c) - __mul24(al, r.s), k);
+    const int ci = min(max(oi, 0), 255), cq = min(max(oq, 0), 255);
+    clipped += (ci != oi) + (cq != oq);
+    const int di = ci - 128, dq = cq - 128;
+    power += static_cast<unsigned>(di * di + dq * dq);
+    return static_cast<unsigned>(ci) | (static_cast<unsigned>(cq) << 8);
+}
+
+__global__ __launch_bounds__(256, 2) void tuner_mfma_kernel(
+    const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
+    const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, long pitch, int n_channels,
+    long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    unsigned long long *__restrict__ levels)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    unsigned *tab = reinterpret_cast<unsigned *>(lds_raw);
+    uint8_t *stage = lds_raw + kTunerTableSize * 4;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = static_cast<int>(blockIdx.y) * 4 + wave;
+    const int n_groups = (n_channels + kTunerGroup - 1) / kTunerGroup;
+    const bool live = grp < n_groups;                               // wave-uniform
+    const int col = lane & 15, g = lane >> 4;
+    const int ch = grp * kTunerGroup + g;
+    const bool ch_ok = live && ch < n_channels;
+
+    for (int i = tid; i < kTunerTableSize; i += 256) tab[i] = table[i];
+
+    // K-step range of every phase (scalars)
+    int j0[kTunerPhases], j1[kTunerPhases];
+#pragma unroll
+    for (int p = 0; p < kTunerPhases; p++) {
+        j0[p] = (front + 2 * R * p - 2 * (T - 1)) / 64;
+        j1[p] = (front + 2 * R * p + 1) / 64 + 1;
+    }
+    unsigned w = 0;
+    int sh = 1;
+    if (ch_ok) {
+        const uint2 cp = chan[ch];
+        w = cp.x;
+        sh = static_cast<int>(cp.y);
+    }
+    const i4 *a_grp = a_img + static_cast<size_t>(live ? grp : 0) * kTunerPhases * ksp * 64 + lane;
+    const int n_pieces = 64 * R + 4 * ks;                           // 16-byte pieces of a step's window
+    unsigned clipped = 0;
+    unsigned long long power = 0;
+
+    const int step0 = static_cast<int>(blockIdx.x) * steps_per_wg;
+    for (int st = step0; st < step0 + steps_per_wg && st < n_steps; st++) {
+        const long m0 = static_cast<long>(st) * kStepOut;
+        const long q0 = 2L * R * m0 - front;                        // byte position of the window's start, relative to the call
+        __syncthreads();                                            // the previous step's reads are done (and the table is written)
+        for (int i = tid; i < n_pieces; i += 256) {
+            const long q = q0 + 16L * i;
+            u4 v;
+            if (q < 0) {
+                v = *reinterpret_cast<const u4 *>(hist + front + q);
+            } else if (q + 16 <= n_bytes) {
+                v = *reinterpret_cast<const u4 *>(x + q);
+            } else {
+                unsigned b[4];                                      // past the call: zero samples (0x80)
+#pragma unroll
+                for (int d = 0; d < 4; d++) {
+                    unsigned wd = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const long pos = q + 4 * d + k;
+                        wd |= (pos < n_bytes ? static_cast<unsigned>(x[pos]) : 0x80u) << (8 * k);
+                    }
+                    b[d] = wd;
+                }
+                v = u4{b[0], b[1], b[2], b[3]};
+            }
+            v ^= 0x80808080u;                                       // u8 -> u8 - 128 as int8
+            *reinterpret_cast<u4 *>(stage + 16 * (i + i / R)) = v;
+        }
+        __syncthreads();
+        if (!live) continue;
+
+        i4 acc[kTT][kTunerPhases];
+#pragma unroll
+        for (int tt = 0; tt < kTT; tt++)
+#pragma unroll
+            for (int p = 0; p < kTunerPhases; p++) acc[tt][p] = i4{0, 0, 0, 0};
+        // this lane's B fragment of K-step j, tile tt: piece R (16 tt + col) + 4 j + g, padded by one piece per R
+        int rem = g % R, blk = g / R;                               // (4 j + g) mod R and div R
+        for (int j = 0; j < ks; j++) {
+            i4 b[kTT];
+#pragma unroll
+            for (int tt = 0; tt < kTT; tt++)
+                b[tt] = *reinterpret_cast<const i4 *>(stage + 16 * ((R + 1) * (16 * tt + col) + 4 * j + g + blk));
+            // the 8 phases' A fragments of this K-step, issued together (a phase outside its range loads its nearest stored step)
+            i4 a[kTunerPhases];
+#pragma unroll
+            for (int p = 0; p < kTunerPhases; p++) {
+                int jr = j - j0[p];
+                jr = jr < 0 ? 0 : (jr >= ksp ? ksp - 1 : jr);
+                a[p] = a_grp[(p * ksp + jr) * 64];
+            }
+#pragma unroll
+            for (int p = 0; p < kTunerPhases; p++) {
+                if (j >= j0[p] && j < j1[p]) {
+#pragma unroll
+                    for (int tt = 0; tt < kTT; tt++) acc[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], b[tt], acc[tt][p], 0, 0, 0);
+                }
+            }
+            rem += 4;
+            while (rem >= R) {
+                rem -= R;
+                blk++;
+            }
+        }
+        if (!ch_ok) continue;
+#pragma unroll
+        for (int tt = 0; tt < kTT; tt++) {
+            const long mb = m0 + 128 * tt + 8 * col;                // this lane's first output time of the tile
+            if (mb >= n_out) continue;
+            unsigned pr[kTunerPhases];
+            unsigned ph = w * (n0 + static_cast<unsigned>(mb) * static_cast<unsigned>(R));
+            const unsigned dph = w * static_cast<unsigned>(R);
+            const bool whole = mb + kTunerPhases <= n_out;
+            if (sh >= 17 && sh <= 47) {
+                unsigned cl[kTunerPhases], pw[kTunerPhases];
+#pragma unroll
+                for (int p = 0; p < kTunerPhases; p++) {
+                    const int ar = acc[tt][p][0] + 256 * acc[tt][p][1], ai = acc[tt][p][2] + 256 * acc[tt][p][3];
+                    cl[p] = 0;
+                    pw[p] = 0;
+                    pr[p] = tuner_round_pair_fast(ar, ai, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh - 16, cl[p], pw[p]);
+                    ph += dph;
+                }
+                unsigned cs = 0, ps = 0;
+#pragma unroll
+                for (int p = 0; p < kTunerPhases; p++)
+                    if (whole || mb + p < n_out) {
+                        cs += cl[p];
+                        ps += pw[p];
+                    }
+                clipped += cs;
+                power += ps;
+            } else {
+#pragma unroll
+                for (int p = 0; p < kTunerPhases; p++) {
+                    const int ar = acc[tt][p][0] + 256 * acc[tt][p][1], ai = acc[tt][p][2] + 256 * acc[tt][p][3];
+                    unsigned cl = 0;
+                    unsigned long long pw = 0;
+                    pr[p] = tuner_round_pair(ar, ai, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh, cl, pw);
+                    if (mb + p < n_out) {
+                        clipped += cl;
+                        power += pw;
+                    }
+                    ph += dph;
+                }
+            }
+            uint8_t *dst = out + static_cast<long>(ch) * pitch + 2 * mb;
+            if (whole) {
+                *reinterpret_cast<u4 *>(dst) = u4{pr[0] | (pr[1] << 16), pr[2] | (pr[3] << 16), pr[4] | (pr[5] << 16), pr[6] | (pr[7] << 16)};
+            } else {
+#pragma unroll
+                for (int p = 0; p < kTunerPhases; p++)
+                    if (mb + p < n_out) *reinterpret_cast<unsigned short *>(dst + 2 * p) = static_cast<unsigned short>(pr[p]);
+            }
+        }
+    }
+    // levels: the 16 columns of a channel sit in the 16 lanes of one quarter
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        clipped += __shfl_xor(clipped, o);
+        power += __shfl_xor(power, o);
+    }
+    if (ch_ok && col == 0) {
+        if (clipped) atomicAdd(levels + 2 * ch, static_cast<unsigned long long>(clipped));
+        if (power) atomicAdd(levels + 2 * ch + 1, power);
+    }
+}
+
+__global__ __launch_bounds__(256) void tuner_generic_kernel(
+    const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, const int16_t *__restrict__ taps_re,
+    const int16_t *__restrict__ taps_im, const uint2 *__restrict__ chan, const unsigned *__restrict__ table,
+    uint8_t *__restrict__ out, long pitch, long n_out, int R, int T, int front, unsigned n0, unsigned long long *__restrict__ levels)
+{
+    const int ch = blockIdx.x;
+    const long m = static_cast<long>(blockIdx.y) * 256 + threadIdx.x;
+    unsigned clipped = 0;
+    unsigned long long power = 0;
+    if (m < n_out) {
+        const int16_t *re = taps_re + static_cast<long>(ch) * T, *im = taps_im + static_cast<long>(ch) * T;
+        int ar = 0, ai = 0;
+        for (int k = 0; k < T; k++) {
+            const long pos = 2 * (m * R - k);
+            const uint8_t *src = pos < 0 ? hist + front + pos : x + pos;
+            const int xr = static_cast<int>(src[0]) - 128, xq = static_cast<int>(src[1]) - 128;
+            const int gr = re[k], gi = im[k];
+            ar += gr * xr - gi * xq;
+            ai += gi * xr + gr * xq;
+        }
+        const uint2 cp = chan[ch];
+        const unsigned ph = cp.x * (n0 + static_cast<unsigned>(m) * static_cast<unsigned>(R));
+        const unsigned pr = tuner_round_pair(ar, ai, rot_of(table[ph >> (32 - kTunerTableBits)]), static_cast<int>(cp.y), clipped, power);
+        *reinterpret_cast<unsigned short *>(out + static_cast<long>(ch) * pitch + 2 * m) = static_cast<unsigned short>(pr);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        clipped += __shfl_xor(clipped, o);
+        power += __shfl_xor(power, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (clipped) atomicAdd(levels + 2 * ch, static_cast<unsigned long long>(clipped));
+        if (power) atomicAdd(levels + 2 * ch + 1, power);
+    }
+}
+
+// the carried history: the last `front` bytes of (old history | this call's input)
+__global__ __launch_bounds__(256) void tuner_hist_kernel(const uint8_t *__restrict__ x, long n_bytes, const uint8_t *__restrict__ old_hist,
+                                                         uint8_t *__restrict__ new_hist, int front)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= front) return;
+    const long pos = n_bytes - front + i;
+    new_hist[i] = pos < 0 ? old_hist[front + pos] : x[pos];
+}
+
+}  // namespace
+
+size_t tuner_mfma_lds_bytes(int R, int ks)
+{
+    const int n_pieces = 64 * R + 4 * ks;
+    return static_cast<size_t>(kTunerTableSize) * 4 + 16u * (n_pieces + n_pieces / R + 1);
+}
+
+int tuner_launch(const TunerLaunch &a, hipStream_t stream)
+{
+    const long n_out = a.n_bytes / (2L * a.R);
+    if (n_out > 0) {
+        if (a.mfma) {
+            const int n_steps = static_cast<int>((n_out + kStepOut - 1) / kStepOut);
+            const int gy = (a.n_channels + 4 * kTunerGroup - 1) / (4 * kTunerGroup);
+            // enough workgroups to fill the chip a few times over, as many steps each as that leaves (the table is loaded once
+            // per workgroup)
+            int per = static_cast<int>((static_cast<long>(n_steps) * gy + 2047) / 2048);
+            if (per < 1) per = 1;
+            const int gx = (n_steps + per - 1) / per;
+            const size_t lds = tuner_mfma_lds_bytes(a.R, a.ks);
+            hipLaunchKernelGGL(tuner_mfma_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x, a.hist, a.n_bytes,
+                               reinterpret_cast<const i4 *>(a.a_img), a.chan, a.table, a.out, a.pitch, a.n_channels, n_out, a.R, a.T,
+                               a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+        } else {
+            hipLaunchKernelGGL(tuner_generic_kernel, dim3(a.n_channels, static_cast<unsigned>((n_out + 255) / 256)), dim3(256), 0, stream,
+                               a.x, a.hist, a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.R, a.T, a.front, a.n0, a.levels);
+        }
+        FMRX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(tuner_hist_kernel, dim3((a.front + 255) / 256), dim3(256), 0, stream, a.x, a.n_bytes, a.hist, a.hist_next, a.front);
+    FMRX_HIP(hipGetLastError());
+    return FMRX_OK;
+}
+
+}  // namespace fmrx

@@ -1,0 +1,303 @@
+// tuner.hip -- the wideband tuner's handle and C ABI (include/fmrx.h: fmrx_tuner_*): one wide u8 I/Q capture at
+// Fs_w = R * rf_Fs in, N channels' u8 I/Q streams at rf_Fs out, written straight into a receiver bank's input slots
+// (fmrx_channels_input_layout).  Kernels: kernels_tuner.hip; arithmetic: tuner_host.hpp, defined by tests/_tuner_model.py
+// (DESIGN.md section 4.9).
+//
+// State carried by the handle: the last `front` raw bytes of the stream (front = 2 (T - 1) rounded up to 16; 0x80 = silence
+// at the start) in one of two device buffers that swap roles every call, and the wide-sample counter (uint64, used mod 2^32).
+// Channel parameters live on the host (taps as int16 pairs, frequency word, scale exponent, the matrix kernel's operand
+// image); fmrx_tuner_set_channel changes the host copy and marks the channel, the next call uploads what changed.
+#include "fmrx_internal.hpp"
+#include "tuner_host.hpp"
+
+#include <algorithm>
+
+using namespace fmrx;
+
+struct fmrx_tuner {
+    int device = 0, R = 0, T = 0, n_channels = 0;
+    long max_wide = 0;
+    bool mfma = true;
+    TunerShape sh;
+    size_t group_bytes = 0;
+    std::vector<float> h;
+    std::vector<int16_t> re, im;         // [n_channels][T]
+    std::vector<uint2> chan;             // {w, s + 15}
+    std::vector<int8_t> img;             // matrix kernel: [groups][group_bytes]
+    std::vector<uint8_t> dirty;
+    size_t n_dirty = 0;
+    DevBuf<int8_t> d_img;
+    DevBuf<int16_t> d_re, d_im;
+    DevBuf<uint2> d_chan;
+    DevBuf<unsigned> d_table;
+    DevBuf<uint8_t> d_hist[2];
+    int cur = 0;
+    DevBuf<unsigned long long> d_levels;
+    DevBuf<uint8_t> d_wide, d_out;       // fmrx_tuner_process only
+    size_t out_pitch = 0;
+    uint64_t counter = 0;
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+};
+
+namespace {
+
+int n_groups(const fmrx_tuner *t) { return (t->n_channels + kTunerGroup - 1) / kTunerGroup; }
+
+// one channel's integers into the host copies
+int design_channel(fmrx_tuner *t, int c, double f_c, double Fs_w, double gain)
+{
+    uint32_t w = 0;
+    int s = 0;
+    std::vector<int16_t> re(t->T), im(t->T);
+    if (const char *why = tuner_design(t->h.data(), t->T, Fs_w, f_c, gain, &w, &s, re.data(), im.data()))
+        return fail(FMRX_EINVAL, "tuner channel %d: %s", c, why);
+    std::copy(re.begin(), re.end(), t->re.begin() + static_cast<size_t>(c) * t->T);
+    std::copy(im.begin(), im.end(), t->im.begin() + static_cast<size_t>(c) * t->T);
+    t->chan[c] = make_uint2(w, static_cast<unsigned>(s + 15));
+    if (t->mfma)
+        tuner_fill_image(t->img.data() + static_cast<size_t>(c / kTunerGroup) * t->group_bytes, t->sh, t->T, t->R, c % kTunerGroup,
+                         re.data(), im.data());
+    if (!t->dirty[c]) {
+        t->dirty[c] = 1;
+        t->n_dirty++;
+    }
+    return FMRX_OK;
+}
+
+// what set_channel changed since the last call -> device (ordered on `stream`, complete when this returns)
+int upload_dirty(fmrx_tuner *t, hipStream_t stream)
+{
+    if (!t->n_dirty) return FMRX_OK;
+    const size_t N = t->n_channels, T = t->T;
+    if (t->n_dirty == N) {
+        FMRX_HIP(hipMemcpyAsync(t->d_chan.p, t->chan.data(), N * sizeof(uint2), hipMemcpyHostToDevice, stream));
+        if (t->mfma) {
+            FMRX_HIP(hipMemcpyAsync(t->d_img.p, t->img.data(), t->img.size(), hipMemcpyHostToDevice, stream));
+        } else {
+            FMRX_HIP(hipMemcpyAsync(t->d_re.p, t->re.data(), N * T * sizeof(int16_t), hipMemcpyHostToDevice, stream));
+            FMRX_HIP(hipMemcpyAsync(t->d_im.p, t->im.data(), N * T * sizeof(int16_t), hipMemcpyHostToDevice, stream));
+        }
+    } else {
+        for (size_t c = 0; c < N; c++) {
+            if (!t->dirty[c]) continue;
+            FMRX_HIP(hipMemcpyAsync(t->d_chan.p + c, t->chan.data() + c, sizeof(uint2), hipMemcpyHostToDevice, stream));
+            if (t->mfma) {
+                const size_t off = c / kTunerGroup * t->group_bytes;
+                FMRX_HIP(hipMemcpyAsync(t->d_img.p + off, t->img.data() + off, t->group_bytes, hipMemcpyHostToDevice, stream));
+            } else {
+                FMRX_HIP(hipMemcpyAsync(t->d_re.p + c * T, t->re.data() + c * T, T * sizeof(int16_t), hipMemcpyHostToDevice, stream));
+                FMRX_HIP(hipMemcpyAsync(t->d_im.p + c * T, t->im.data() + c * T, T * sizeof(int16_t), hipMemcpyHostToDevice, stream));
+            }
+        }
+    }
+    FMRX_HIP(hipStreamSynchronize(stream));   // the host copies are pageable and may change again right after the call
+    std::fill(t->dirty.begin(), t->dirty.end(), 0);
+    t->n_dirty = 0;
+    return FMRX_OK;
+}
+
+int clear_state(fmrx_tuner *t)
+{
+    if (t->ran) FMRX_HIP(hipStreamSynchronize(t->last_stream));
+    FMRX_HIP(hipMemset(t->d_hist[0].p, 0x80, t->d_hist[0].bytes()));
+    FMRX_HIP(hipMemset(t->d_hist[1].p, 0x80, t->d_hist[1].bytes()));
+    FMRX_HIP(hipMemset(t->d_levels.p, 0, t->d_levels.bytes()));
+    t->cur = 0;
+    t->counter = 0;
+    return FMRX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmrx_tuner_design(const float *h, int taps, double Fs_w, double f_c, double gain, uint32_t *w, int *s, int16_t *re, int16_t *im)
+{
+    if (!h || !w || !s || !re || !im) return fail(FMRX_EINVAL, "tuner_design: null argument");
+    if (const char *why = tuner_design(h, taps, Fs_w, f_c, gain, w, s, re, im)) return fail(FMRX_EINVAL, "tuner_design: %s", why);
+    return FMRX_OK;
+}
+
+int fmrx_tuner_table(int16_t *cos_q15, int16_t *sin_q15, size_t *n)
+{
+    if (!n) return fail(FMRX_EINVAL, "tuner_table: null argument");
+    *n = kTunerTableSize;
+    if (cos_q15 && sin_q15) tuner_table(cos_q15, sin_q15);
+    return FMRX_OK;
+}
+
+int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int device)
+{
+    if (!out || !h) return fail(FMRX_EINVAL, "tuner_create: null argument");
+    if (R < 2 || R > kTunerMaxR) return fail(FMRX_EINVAL, "tuner_create: decimation %d (2 .. %d)", R, kTunerMaxR);
+    if (taps < 2 || taps > kTunerMaxTaps) return fail(FMRX_EINVAL, "tuner_create: %d taps (2 .. %d)", taps, kTunerMaxTaps);
+    if (n_channels < 1 || n_channels > 65536) return fail(FMRX_EINVAL, "tuner_create: n_channels must be 1 .. 65536");
+    if (max_wide_samples < static_cast<size_t>(R) || max_wide_samples % R || max_wide_samples / R > (1u << 24))
+        return fail(FMRX_EINVAL, "tuner_create: max_wide_samples %zu must be a multiple of the decimation %d, at most 2^24 outputs per call",
+                    max_wide_samples, R);
+    FMRX_TRY(require_device());
+    FMRX_HIP(hipSetDevice(device));
+    fmrx_tuner *t = new fmrx_tuner;
+    t->device = device;
+    t->R = R;
+    t->T = taps;
+    t->n_channels = n_channels;
+    t->max_wide = static_cast<long>(max_wide_samples);
+    t->mfma = options_snapshot().tuner_variant == 0 && taps <= kTunerMfmaMaxTaps;
+    t->sh = tuner_shape(taps, R);
+    t->group_bytes = tuner_group_image_bytes(t->sh);
+    t->h.assign(h, h + taps);
+    auto body = [&]() -> int {
+        const size_t N = n_channels, T = taps;
+        t->re.assign(N * T, 0);
+        t->im.assign(N * T, 0);
+        t->chan.assign(N, make_uint2(0, 1));
+        t->dirty.assign(N, 0);
+        if (t->mfma) t->img.assign(static_cast<size_t>(n_groups(t)) * t->group_bytes, 0);
+        // every channel starts at the capture's centre with gain 1; designed once, copied to the rest
+        FMRX_TRY(design_channel(t, 0, 0.0, 1.0, 1.0));
+        for (size_t c = 1; c < N; c++) {
+            std::copy(t->re.begin(), t->re.begin() + T, t->re.begin() + c * T);
+            std::copy(t->im.begin(), t->im.begin() + T, t->im.begin() + c * T);
+            t->chan[c] = t->chan[0];
+            if (t->mfma && c < static_cast<size_t>(kTunerGroup))
+                tuner_fill_image(t->img.data(), t->sh, t->T, t->R, static_cast<int>(c), t->re.data(), t->im.data());
+        }
+        if (t->mfma)
+            for (int g = 1; g < n_groups(t); g++)
+                std::copy(t->img.begin(), t->img.begin() + t->group_bytes, t->img.begin() + static_cast<size_t>(g) * t->group_bytes);
+        std::fill(t->dirty.begin(), t->dirty.end(), 1);
+        t->n_dirty = N;
+        FMRX_TRY(t->d_chan.alloc(N));
+        if (t->mfma) {
+            FMRX_TRY(t->d_img.alloc(t->img.size()));
+        } else {
+            FMRX_TRY(t->d_re.alloc(N * T));
+            FMRX_TRY(t->d_im.alloc(N * T));
+        }
+        std::vector<int16_t> c(kTunerTableSize), s(kTunerTableSize);
+        std::vector<unsigned> tab(kTunerTableSize);
+        tuner_table(c.data(), s.data());
+        for (int i = 0; i < kTunerTableSize; i++)
+            tab[i] = static_cast<unsigned>(static_cast<uint16_t>(c[i])) | (static_cast<unsigned>(static_cast<uint16_t>(s[i])) << 16);
+        FMRX_TRY(t->d_table.alloc(kTunerTableSize));
+        FMRX_HIP(hipMemcpy(t->d_table.p, tab.data(), tab.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        FMRX_TRY(t->d_hist[0].alloc(t->sh.front));
+        FMRX_TRY(t->d_hist[1].alloc(t->sh.front));
+        FMRX_TRY(t->d_levels.alloc(2 * N));
+        if (t->mfma && tuner_mfma_lds_bytes(R, t->sh.ks) > 64 * 1024) return fail(FMRX_EINVAL, "tuner_create: window too large for the matrix kernel");
+        return clear_state(t);
+    };
+    const int rc = body();
+    if (rc != FMRX_OK) {
+        delete t;
+        return rc;
+    }
+    *out = t;
+    return FMRX_OK;
+}
+
+int fmrx_tuner_destroy(fmrx_tuner *t)
+{
+    if (!t) return FMRX_OK;
+    (void)hipSetDevice(t->device);
+    if (t->ran) (void)hipStreamSynchronize(t->last_stream);
+    delete t;
+    return FMRX_OK;
+}
+
+int fmrx_tuner_reset(fmrx_tuner *t)
+{
+    if (!t) return fail(FMRX_EINVAL, "tuner_reset: null handle");
+    FMRX_HIP(hipSetDevice(t->device));
+    return clear_state(t);
+}
+
+int fmrx_tuner_set_channel(fmrx_tuner *t, int channel, double f_c_hz, double Fs_w, double gain)
+{
+    if (!t) return fail(FMRX_EINVAL, "tuner_set_channel: null handle");
+    if (channel < 0 || channel >= t->n_channels) return fail(FMRX_EINVAL, "tuner_set_channel: channel %d of %d", channel, t->n_channels);
+    return design_channel(t, channel, f_c_hz, Fs_w, gain);
+}
+
+size_t fmrx_tuner_n_out_bytes(const fmrx_tuner *t, size_t n_wide) { return t && n_wide % t->R == 0 ? 2 * n_wide / t->R : 0; }
+
+int fmrx_tuner_process_dev(fmrx_tuner *t, const uint8_t *d_wide, size_t n_wide, uint8_t *d_out_first, size_t pitch_bytes, void *stream)
+{
+    if (!t || !d_wide || !d_out_first) return fail(FMRX_EINVAL, "tuner_process_dev: null argument");
+    if (n_wide == 0 || n_wide % t->R || n_wide > static_cast<size_t>(t->max_wide))
+        return fail(FMRX_EINVAL, "tuner_process_dev: %zu wide samples: a non-zero multiple of the decimation %d, at most %ld", n_wide, t->R,
+                    t->max_wide);
+    if (reinterpret_cast<uintptr_t>(d_wide) % 16) return fail(FMRX_EINVAL, "tuner_process_dev: d_wide must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_out_first) % 16 || pitch_bytes % 16)
+        return fail(FMRX_EINVAL, "tuner_process_dev: d_out_first and pitch_bytes must be multiples of 16 bytes");
+    if (t->n_channels > 1 && pitch_bytes < 2 * n_wide / t->R)
+        return fail(FMRX_EINVAL, "tuner_process_dev: pitch of %zu bytes is shorter than a channel's %zu output bytes", pitch_bytes, 2 * n_wide / t->R);
+    FMRX_HIP(hipSetDevice(t->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FMRX_TRY(upload_dirty(t, s));
+    FMRX_HIP(hipMemsetAsync(t->d_levels.p, 0, t->d_levels.bytes(), s));
+    TunerLaunch a;
+    a.mfma = t->mfma;
+    a.x = d_wide;
+    a.n_bytes = static_cast<long>(2 * n_wide);
+    a.hist = t->d_hist[t->cur].p;
+    a.hist_next = t->d_hist[t->cur ^ 1].p;
+    a.a_img = t->d_img.p;
+    a.taps_re = t->d_re.p;
+    a.taps_im = t->d_im.p;
+    a.chan = t->d_chan.p;
+    a.table = t->d_table.p;
+    a.out = d_out_first;
+    a.pitch = static_cast<long>(pitch_bytes);
+    a.n_channels = t->n_channels;
+    a.R = t->R;
+    a.T = t->T;
+    a.front = t->sh.front;
+    a.ks = t->sh.ks;
+    a.ksp = t->sh.ksp;
+    a.n0 = static_cast<unsigned>(t->counter & 0xffffffffu);
+    a.levels = t->d_levels.p;
+    FMRX_TRY(tuner_launch(a, s));
+    t->cur ^= 1;
+    t->counter += n_wide;
+    t->last_stream = s;
+    t->ran = true;
+    return FMRX_OK;
+}
+
+int fmrx_tuner_process(fmrx_tuner *t, const uint8_t *wide, size_t n_wide, uint8_t *out)
+{
+    if (!t || !wide || !out) return fail(FMRX_EINVAL, "tuner_process: null argument");
+    FMRX_HIP(hipSetDevice(t->device));
+    if (!t->d_wide.p) {
+        t->out_pitch = (2 * static_cast<size_t>(t->max_wide) / t->R + 15) / 16 * 16;
+        FMRX_TRY(t->d_wide.alloc(2 * static_cast<size_t>(t->max_wide)));
+        FMRX_TRY(t->d_out.alloc(t->out_pitch * t->n_channels));
+    }
+    if (n_wide == 0 || n_wide % t->R || n_wide > static_cast<size_t>(t->max_wide))
+        return fail(FMRX_EINVAL, "tuner_process: %zu wide samples: a non-zero multiple of the decimation %d, at most %ld", n_wide, t->R, t->max_wide);
+    FMRX_HIP(hipMemcpy(t->d_wide.p, wide, 2 * n_wide, hipMemcpyHostToDevice));
+    FMRX_TRY(fmrx_tuner_process_dev(t, t->d_wide.p, n_wide, t->d_out.p, t->out_pitch, nullptr));
+    FMRX_HIP(hipStreamSynchronize(nullptr));
+    const size_t row = 2 * n_wide / t->R;
+    FMRX_HIP(hipMemcpy2D(out, row, t->d_out.p, t->out_pitch, row, t->n_channels, hipMemcpyDeviceToHost));
+    return FMRX_OK;
+}
+
+int fmrx_tuner_levels(fmrx_tuner *t, uint64_t *clipped, uint64_t *power)
+{
+    if (!t || !clipped || !power) return fail(FMRX_EINVAL, "tuner_levels: null argument");
+    FMRX_HIP(hipSetDevice(t->device));
+    if (t->ran) FMRX_HIP(hipStreamSynchronize(t->last_stream));
+    std::vector<unsigned long long> lv(2 * static_cast<size_t>(t->n_channels));
+    FMRX_HIP(hipMemcpy(lv.data(), t->d_levels.p, lv.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int c = 0; c < t->n_channels; c++) {
+        clipped[c] = lv[2 * c];
+        power[c] = lv[2 * c + 1];
+    }
+    return FMRX_OK;
+}
+
+}  // extern "C"

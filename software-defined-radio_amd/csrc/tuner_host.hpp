@@ -1,0 +1,145 @@
+// tuner_host.hpp -- host-side (plain C++, no HIP) arithmetic of the wideband tuner (tuner.hip, kernels_tuner.hip):
+// frequency word, complex integer taps, the rotation table, and the matrix-core operand image of a channel group.
+// Header-only, like fe_mfma_host.hpp.  The arithmetic is DEFINED by tests/_tuner_model.py; this
+// file is the product's statement of it.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace fmrx {
+
+constexpr int kTunerTableBits = 12;                  // rotation table: 2^12 entries of round(32767 cos), round(32767 sin)
+constexpr int kTunerTableSize = 1 << kTunerTableBits;
+constexpr int kTunerDigits = 2;                      // balanced base-256 digits of a tap part
+constexpr double kTunerTapLimit = 127.0 * 256.0;     // max |re|, |im| of a scaled tap: both balanced digits of +q and -q fit int8
+constexpr int kTunerMinShift = -14, kTunerMaxShift = 47;   // range of s: the output shift s + 15 stays in 1 .. 62
+constexpr int kTunerMaxR = 32, kTunerMaxTaps = 4096;
+constexpr int kTunerMfmaMaxTaps = 256;               // the matrix kernel's operand image grows with T; longer filters run the generic kernel
+constexpr int kTunerPhases = 8;                      // consecutive outputs per MFMA column (16 bytes of a channel's row)
+constexpr int kTunerGroup = 4;                       // channels per MFMA tile: 4 rows each (re / im x 2 digits)
+constexpr double kTunerTwoPi = 6.283185307179586476925286766559;
+
+// w = round(f_c / Fs_w * 2^32) mod 2^32 (half away from zero); |f_c| < Fs_w / 2 is the caller's to check
+inline uint32_t tuner_freq_word(double f_c, double Fs_w)
+{
+    const double v = f_c / Fs_w * 4294967296.0;
+    const long long r = std::llround(v);
+    return static_cast<uint32_t>(static_cast<unsigned long long>(r) & 0xffffffffULL);
+}
+
+// error texts of tuner_design (nullptr = accepted)
+inline const char *tuner_design(const float *h, int T, double Fs_w, double f_c, double gain, uint32_t *w_out, int *s_out, int16_t *re,
+                                int16_t *im)
+{
+    if (!h || T < 2 || T > kTunerMaxTaps) return "taps: 2 .. 4096";
+    if (!(Fs_w > 0.0) || !std::isfinite(Fs_w)) return "Fs_w must be positive and finite";
+    if (!std::isfinite(f_c) || !(std::fabs(f_c) < Fs_w / 2)) return "|f_c| must be below Fs_w / 2";
+    if (!std::isfinite(gain)) return "gain must be finite";
+    const uint32_t w = tuner_freq_word(f_c, Fs_w);
+    std::vector<double> gr(T), gi(T);
+    double m = 0.0;
+    for (int k = 0; k < T; k++) {
+        if (!std::isfinite(h[k])) return "non-finite tap";
+        const uint32_t ph = w * static_cast<uint32_t>(k);                       // w k mod 2^32
+        const double a = kTunerTwoPi * (static_cast<double>(ph) / 4294967296.0);
+        const double g = gain * static_cast<double>(h[k]);
+        gr[k] = g * std::cos(a);
+        gi[k] = g * std::sin(a);
+        m = std::fmax(m, std::fmax(std::fabs(gr[k]), std::fabs(gi[k])));
+    }
+    if (!std::isfinite(m) || m == 0.0) return "gain x taps are all zero or not finite";
+    int s = static_cast<int>(std::floor(std::log2(kTunerTapLimit / m)));
+    while (std::ldexp(m, s) > kTunerTapLimit) s--;
+    while (std::ldexp(m, s + 1) <= kTunerTapLimit) s++;
+    if (s < kTunerMinShift || s > kTunerMaxShift) return "gain x taps out of range (scale exponent outside -14 .. 47)";
+    long long worst = 0;
+    for (int k = 0; k < T; k++) {
+        const long long qr = std::llround(std::ldexp(gr[k], s)), qi = std::llround(std::ldexp(gi[k], s));
+        re[k] = static_cast<int16_t>(qr);
+        im[k] = static_cast<int16_t>(qi);
+        worst += std::llabs(qr) + std::llabs(qi);
+    }
+    if (128 * worst > 2147483647LL) return "worst-case accumulator 128 * sum(|re| + |im|) does not fit int32";
+    *w_out = w;
+    *s_out = s;
+    return nullptr;
+}
+
+inline void tuner_table(int16_t *c, int16_t *s)
+{
+    for (int i = 0; i < kTunerTableSize; i++) {
+        const double a = kTunerTwoPi * (static_cast<double>(i) / kTunerTableSize);
+        c[i] = static_cast<int16_t>(std::llround(32767.0 * std::cos(a)));
+        s[i] = static_cast<int16_t>(std::llround(32767.0 * std::sin(a)));
+    }
+}
+
+// q = d0 + 256 d1, both digits in [-128, 127] (|q| <= 32512)
+inline void tuner_digits(int q, int8_t *dig)
+{
+    const int d0 = ((q + 128) & 255) - 128;
+    dig[0] = static_cast<int8_t>(d0);
+    dig[1] = static_cast<int8_t>((q - d0) / 256);
+}
+
+// Shape of the matrix kernel's tile for (T, R).  A column of the tile is 8 consecutive outputs (phases p = 0..7) of every
+// channel of the group; its window starts `front` bytes in front of the newest sample of its first output, so byte u of the
+// window meets, for phase p, tap k and part c (0 = I, 1 = Q):  u = front + 2 R p - 2 k + c.  Phase p's taps lie in the K-steps
+// j0[p] .. j1[p]-1 (64 bytes each); only those are stored (ksp = the largest count) and multiplied.
+struct TunerShape {
+    int front = 0;       // multiple of 16, >= 2 (T - 1)
+    int ks = 0;          // K-steps the whole window spans
+    int ksp = 0;         // K-steps stored per phase
+    int j0[kTunerPhases] = {}, j1[kTunerPhases] = {};
+};
+inline TunerShape tuner_shape(int T, int R)
+{
+    TunerShape s;
+    s.front = (2 * (T - 1) + 15) / 16 * 16;
+    for (int p = 0; p < kTunerPhases; p++) {
+        s.j0[p] = (s.front + 2 * R * p - 2 * (T - 1)) / 64;
+        s.j1[p] = (s.front + 2 * R * p + 1) / 64 + 1;
+        s.ksp = std::max(s.ksp, s.j1[p] - s.j0[p]);
+    }
+    s.ks = s.j1[kTunerPhases - 1];
+    return s;
+}
+inline size_t tuner_group_image_bytes(const TunerShape &s) { return static_cast<size_t>(kTunerPhases) * s.ksp * 64 * 16; }
+
+// One channel's rows of its group's A-operand image of v_mfma_i32_16x16x64_i8: [phase][K-step - j0[phase]][lane][16 bytes],
+// lane (row = lane & 15, quarter g = lane >> 4) holding what row `row` applies to window bytes 64 j + 16 g + 0..15.
+// Row = 4 * (channel in group) + 2 * part + digit, part 0 = real, 1 = imaginary part of the accumulator:
+//   real:  I bytes meet re[k], Q bytes meet -im[k];   imaginary:  I bytes meet im[k], Q bytes meet re[k].
+// The C layout (row = 4 (lane >> 4) + register) then hands lane (column, g) channel g's four rows of one output time.
+inline void tuner_fill_image(int8_t *img, const TunerShape &sh, int T, int R, int ch_in_group, const int16_t *re, const int16_t *im)
+{
+    for (int p = 0; p < kTunerPhases; p++)
+        for (int jr = 0; jr < sh.ksp; jr++)
+            for (int part = 0; part < 2; part++)
+                for (int d = 0; d < kTunerDigits; d++) {
+                    const int row = 4 * ch_in_group + 2 * part + d;
+                    for (int g = 0; g < 4; g++) {
+                        int8_t *dst = img + ((static_cast<size_t>(p) * sh.ksp + jr) * 64 + (16 * g + row)) * 16;
+                        for (int b = 0; b < 16; b++) {
+                            const int u = 64 * (sh.j0[p] + jr) + 16 * g + b;
+                            const int c = u & 1;
+                            const int e = sh.front + 2 * R * p + c - u;      // = 2 k
+                            int8_t v = 0;
+                            if (e >= 0 && e / 2 <= T - 1 && sh.j0[p] + jr < sh.j1[p]) {
+                                const int k = e / 2;
+                                const int q = part == 0 ? (c == 0 ? re[k] : -im[k]) : (c == 0 ? im[k] : re[k]);
+                                int8_t dig[2];
+                                tuner_digits(q, dig);
+                                v = dig[d];
+                            }
+                            dst[b] = v;
+                        }
+                    }
+                }
+}
+
+}  // namespace fmrx
