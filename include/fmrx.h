@@ -552,7 +552,8 @@ FMRX_API int fmrx_fe_run_dev(const fmrx_fe_plan *plan, const uint8_t *d_iq, size
 /* ------------------------------------------------------------------ */
 /* Wideband tuner: N channels of a receiver bank from one wide capture   */
 /* ------------------------------------------------------------------ */
-/* The stage in front of a bank: ONE wide capture (interleaved u8 I,Q at Fs_w = R * rf_Fs, R = 2 .. 32) in, N channels'
+/* The stage in front of a bank: ONE wide capture (interleaved I,Q at Fs_w = R * rf_Fs, R = 2 .. 32; u8, or s8 / s16 through
+ * fmrx_tuner_create_ex) in, N channels'
  * u8 I,Q streams at rf_Fs out, each centred on its own offset f_c -- a frequency-translating decimating FIR per channel, one
  * int8 matrix-core GEMM for all of them (csrc/kernels_tuner.hip), written straight into the bank's input slots.
  *   y_c[m] = Q( g_c * sum_{k<T} h[k] * x[mR - k] * e^{-j 2 pi f_c (mR - k) / Fs_w} ),   x = (u8 - 128) as complex
@@ -562,6 +563,16 @@ FMRX_API int fmrx_fe_run_dev(const fmrx_fe_plan *plan, const uint8_t *d_iq, size
  *   acc = sum_k taps[k] x[mR - k] in int32; rotation by (cos - j sin)(2 pi i / 4096) as round(32767 .), i = top 12 bits
  *   of w * n mod 2^32, n = mR counted in wide samples since create / reset; out = clamp(128 + ((y + 2^(s+14)) >> (s+15)), 0, 255).
  * Outputs do not depend on how the stream is cut into calls.
+ *
+ * Input formats (fmrx_tuner_create_ex; defined by tests/_tuner_formats_model.py).  The arithmetic above with
+ *   FMRX_TUNER_U8   x = u8 - 128                      B = 0   what an RTL dongle delivers
+ *   FMRX_TUNER_S8   x = the int8                      B = 0   HackRF, USRP sc8, bladeRF's 8-bit mode
+ *   FMRX_TUNER_S16  x = the little-endian int16       B = 8   Airspy, SDRplay, USRP sc16, bladeRF SC16_Q11, LimeSDR
+ * acc exact in 64 bits, and out = clamp(128 + ((y + 2^(s+14+B)) >> (s+15+B)), 0, 255): at gain 1 full scale in maps to full
+ * scale out.  A device that puts 12 or 14 bits into the low end of the short (SC16_Q11: +-2048; SDRplay: 14 bits) is
+ * brought to full scale by a `gain` of 16 or 4.  The shift stays in 1 .. 62, so an S16 tuner accepts -14 <= s <= 39:
+ * fmrx_tuner_set_channel returns FMRX_EINVAL beyond that (gain x taps below 1e-7).  The output, the u8 I,Q slots of a bank,
+ * is the same for every format; samples in front of a stream and past a call are zero samples (x = 0).
  *
  * fmrx_tuner_design / fmrx_tuner_table are host code (no device needed): the integers a channel uses.  design rejects
  * (FMRX_EINVAL) non-finite or all-zero gain x taps, |f_c| >= Fs_w / 2, s outside its range, and tap sets whose worst case
@@ -573,17 +584,26 @@ FMRX_API int fmrx_tuner_table(int16_t *cos_q15, int16_t *sin_q15, size_t *n);
 /* h [taps]: the prototype low-pass at Fs_w (2 .. 4096 taps; more than 256 run the generic kernel).  max_wide_samples: the
  * largest call, a multiple of R.  Every channel starts at f_c = 0, gain 1.  The option "tuner_variant" is read here. */
 FMRX_API int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int device);
+/* the same for a capture of the given format; fmrx_tuner_create is the FMRX_TUNER_U8 case.  An unknown format: FMRX_EINVAL. */
+#define FMRX_TUNER_U8 0
+#define FMRX_TUNER_S8 1
+#define FMRX_TUNER_S16 2
+FMRX_API int fmrx_tuner_create_ex(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int format,
+                                  int device);
+FMRX_API int fmrx_tuner_format(const fmrx_tuner *t);            /* FMRX_TUNER_*; -1 for a null handle */
+FMRX_API size_t fmrx_tuner_sample_bytes(const fmrx_tuner *t);   /* bytes per complex wide sample: 2, 2 or 4 */
 FMRX_API int fmrx_tuner_destroy(fmrx_tuner *t);
 FMRX_API int fmrx_tuner_reset(fmrx_tuner *t);     /* start of stream: silence in front, sample counter 0; channels keep their settings */
 /* any time between calls; takes effect at the next call (which then waits once for its stream while it uploads) */
 FMRX_API int fmrx_tuner_set_channel(fmrx_tuner *t, int channel, double f_c_hz, double Fs_w, double gain);
 FMRX_API size_t fmrx_tuner_n_out_bytes(const fmrx_tuner *t, size_t n_wide);   /* 2 * n_wide / R; 0 unless n_wide % R == 0 */
-/* d_wide: DEVICE, 16-byte aligned, 2 * n_wide bytes, n_wide % R == 0.  Channel c's bytes go to d_out_first + c * pitch_bytes
+/* d_wide: DEVICE, 16-byte aligned, n_wide complex samples in the tuner's format (fmrx_tuner_sample_bytes * n_wide bytes),
+ * n_wide % R == 0.  Channel c's bytes go to d_out_first + c * pitch_bytes
  * (both multiples of 16): exactly what fmrx_channels_input_layout returns, so tuner -> bank -> RDS bank chain on one stream;
  * several tuners fill disjoint channel ranges of one bank by offsetting d_out_first.  Async on `stream`. */
 FMRX_API int fmrx_tuner_process_dev(fmrx_tuner *t, const uint8_t *d_wide, size_t n_wide, uint8_t *d_out_first, size_t pitch_bytes,
                                     void *stream);
-/* host in, host out [n_channels][n_out_bytes] */
+/* host in (n_wide complex samples in the tuner's format), host out [n_channels][n_out_bytes] */
 FMRX_API int fmrx_tuner_process(fmrx_tuner *t, const uint8_t *wide, size_t n_wide, uint8_t *out);
 /* waits for the last call; per channel, over that call: output bytes that clamped, and sum (I-128)^2 + (Q-128)^2 */
 FMRX_API int fmrx_tuner_levels(fmrx_tuner *t, uint64_t *clipped, uint64_t *power);

@@ -176,12 +176,15 @@ _dbl = C.c_double
 _sig("fmrx_tuner_design", [_f32p, _int, _dbl, _dbl, _dbl, C.POINTER(C.c_uint32), C.POINTER(_int), _i16p, _i16p])
 _sig("fmrx_tuner_table", [_vp, _vp, C.POINTER(_sz)])
 _sig("fmrx_tuner_create", [C.POINTER(_vp), _int, _f32p, _int, _int, _sz, _int])
+_sig("fmrx_tuner_create_ex", [C.POINTER(_vp), _int, _f32p, _int, _int, _sz, _int, _int])
+_sig("fmrx_tuner_format", [_vp])
+_sig("fmrx_tuner_sample_bytes", [_vp], _sz)
 _sig("fmrx_tuner_destroy", [_vp])
 _sig("fmrx_tuner_reset", [_vp])
 _sig("fmrx_tuner_set_channel", [_vp, _int, _dbl, _dbl, _dbl])
 _sig("fmrx_tuner_n_out_bytes", [_vp, _sz], _sz)
 _sig("fmrx_tuner_process_dev", [_vp, _vp, _sz, _vp, _sz, _vp])
-_sig("fmrx_tuner_process", [_vp, _u8p, _sz, _u8p])
+_sig("fmrx_tuner_process", [_vp, _vp, _sz, _u8p])
 _sig("fmrx_tuner_levels", [_vp, _vp, _vp])
 
 
@@ -856,17 +859,27 @@ def tunerLowPass(Fs_w, R, T) -> np.ndarray:
     return impulseResponseLPF(float(Fs_w), 0.5 * (128e3 + rf_Fs - 100e3), int(T))
 
 
+TUNER_FORMATS = {"u8": 0, "s8": 1, "s16": 2}                       # FMRX_TUNER_U8 / _S8 / _S16
+_TUNER_DTYPES = {"u8": np.uint8, "s8": np.int8, "s16": np.int16}
+
+
 class Tuner:
-    """N channels of one wide u8 I/Q capture (Fs_w = R * rf_Fs), each mixed to its own centre offset, low-pass filtered by
+    """N channels of one wide I/Q capture (Fs_w = R * rf_Fs), each mixed to its own centre offset, low-pass filtered by
     the prototype h and decimated by R, as u8 I/Q rows: the input of a receiver bank (fmrx_tuner_*; exact integer
     arithmetic).  tuner.process_dev(d_wide, n_wide, *bank.input_layout(), stream) followed by
-    bank.process_dev(..., stream=stream) runs capture -> audio without the samples leaving the device."""
+    bank.process_dev(..., stream=stream) runs capture -> audio without the samples leaving the device.
+    fmt: the capture's format, "u8" (interleaved unsigned bytes), "s8" (int8) or "s16" (int16, 4 bytes per complex sample;
+    a device with 12 or 14 bits in the low end of the short takes a gain of 16 or 4)."""
 
-    def __init__(self, R, h, n_channels, max_wide_samples, device=0):
-        self.R, self.n_channels, self.max_wide_samples = int(R), int(n_channels), int(max_wide_samples)
+    def __init__(self, R, h, n_channels, max_wide_samples, device=0, fmt="u8"):
+        if fmt not in TUNER_FORMATS:
+            raise ValueError(f"Tuner: fmt {fmt!r}: one of {', '.join(TUNER_FORMATS)}")
+        self.R, self.n_channels, self.max_wide_samples, self.fmt = int(R), int(n_channels), int(max_wide_samples), fmt
         self.h = _f32(h)
         self._h = _vp()
-        _check(lib.fmrx_tuner_create(C.byref(self._h), self.R, self.h, len(self.h), self.n_channels, self.max_wide_samples, device))
+        _check(lib.fmrx_tuner_create_ex(C.byref(self._h), self.R, self.h, len(self.h), self.n_channels, self.max_wide_samples,
+                                        TUNER_FORMATS[fmt], device))
+        self.sample_bytes = int(lib.fmrx_tuner_sample_bytes(self._h))       # per complex wide sample: 2, 2 or 4
 
     @staticmethod
     def design(h, Fs_w, f_c, gain=1.0):
@@ -902,12 +915,17 @@ class Tuner:
     def n_out_bytes(self, n_wide):
         return lib.fmrx_tuner_n_out_bytes(self._h, n_wide)
 
-    def process(self, wide_u8):
-        """wide_u8: interleaved u8 I,Q (host), a multiple of R samples -> uint8 [n_channels, 2 * n_wide / R]."""
-        x = _u8(wide_u8).reshape(-1)
+    def process(self, wide):
+        """wide: interleaved I,Q (host) as uint8 / int8 / int16 for fmt u8 / s8 / s16 (another dtype is a TypeError, never a
+        conversion), a multiple of R samples -> uint8 [n_channels, 2 * n_wide / R]."""
+        if self.fmt == "u8" and not isinstance(wide, np.ndarray):
+            wide = _u8(wide)
+        if not isinstance(wide, np.ndarray) or wide.dtype != _TUNER_DTYPES[self.fmt]:
+            raise TypeError(f"Tuner.process: a {self.fmt} tuner takes a {np.dtype(_TUNER_DTYPES[self.fmt]).name} array, not {getattr(wide, 'dtype', type(wide).__name__)}")
+        x = np.ascontiguousarray(wide).reshape(-1)
         n_wide = len(x) // 2
         out = np.zeros((self.n_channels, 2 * n_wide // self.R), np.uint8)
-        _check(lib.fmrx_tuner_process(self._h, x, n_wide, out.reshape(-1)))
+        _check(lib.fmrx_tuner_process(self._h, x.ctypes.data, n_wide, out.reshape(-1)))
         return out
 
     def process_dev(self, d_wide_ptr, n_wide, d_out_first, pitch_bytes, stream=None):

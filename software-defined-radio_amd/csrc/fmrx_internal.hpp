@@ -321,13 +321,16 @@ Filters design_filters(const fmrx_params &p, bool stereo);
 // One call's launch: the FIR + rotation kernel (matrix-core or generic) and the kernel that carries the history.
 struct TunerLaunch {
     bool mfma = true;
-    const uint8_t *x = nullptr;          // this call's wide bytes (matrix kernel: 16-byte aligned)
-    long n_bytes = 0;                    // 2 * n_wide
-    const uint8_t *hist = nullptr;       // `front` bytes in front of the call, 16-byte aligned
+    int format = 0;                      // kTunerU8 / kTunerS8 / kTunerS16 (tuner_host.hpp): a value is 1, 1 or 2 raw bytes
+    const uint8_t *x = nullptr;          // this call's wide samples, raw (matrix kernel: 16-byte aligned)
+    long n_bytes = 0;                    // 2 * n_wide: the call's I and Q values (the raw bytes of the 8-bit formats)
+    const uint8_t *hist = nullptr;       // `front` values in front of the call, raw, 16-byte aligned
     uint8_t *hist_next = nullptr;        // receives the history the next call starts from
     const int8_t *a_img = nullptr;       // matrix kernel: operand image [group][phase][ksp][64 lanes][16]
     const int16_t *taps_re = nullptr, *taps_im = nullptr;   // generic kernel: [n_channels][T]
-    const uint2 *chan = nullptr;         // per channel {frequency word, output shift s + 15}
+    const uint2 *chan = nullptr;         // per channel {frequency word, output shift s + 15 + B}
+    const int2 *kconst = nullptr;        // 16-bit matrix kernel: per channel 128 * {sum(re - im), sum(im + re)}, what the low plane's
+                                         //   offset of 128 adds to acc
     const unsigned *table = nullptr;     // rotation table, cos | sin << 16
     uint8_t *out = nullptr;
     long pitch = 0;
@@ -335,7 +338,7 @@ struct TunerLaunch {
     unsigned n0 = 0;                     // wide-sample index of the call's first sample, mod 2^32
     unsigned long long *levels = nullptr;   // [n_channels][2] = {clipped, power}, zeroed by the caller
 };
-size_t tuner_mfma_lds_bytes(int R, int ks);
+size_t tuner_mfma_lds_bytes(int R, int ks, int format);
 int tuner_launch(const TunerLaunch &a, hipStream_t stream);
 
 }  // namespace fmrx

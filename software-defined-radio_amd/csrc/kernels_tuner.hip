@@ -24,8 +24,19 @@
 //
 // The generic kernel (tuner_generic_kernel): one thread per (channel, output), integer loops over the taps; any T, the
 // second device implementation the tests compare with the model (option tuner_variant = 1 / FMRX_TUNER_VARIANT=generic).
+//
+// Input formats (tuner_host.hpp; tests/_tuner_formats_model.py).  Signed 8-bit: the same two kernels without the XOR and
+// with 0x00 as the zero sample (tuner_mfma_s8_kernel, tuner_generic_s8_kernel).  Signed 16-bit (tuner_mfma_s16_kernel): the
+// window is staged as TWO byte planes, the low bytes (XOR 0x80: L = low byte - 128) and the high bytes (H, the int8 as it
+// is), split with byte permutes while staging; each plane has exactly the layout of the 8-bit stage and meets the SAME
+// operand image, into its own int32 accumulators (each within the 8-bit bound 128 sum(|re| + |im|)).  x = 256 H + L + 128,
+// so acc = 256 accH + accL + 128 (row sum of the taps): the last term is a per-channel constant (TunerLaunch::kconst), the
+// sum is formed in 64 bits in the epilogue, rotated and rounded as the model does with the shift s + 15 + 8.  Two tiles per
+// wave and step instead of four keep the accumulators at 128 registers; every A fragment still feeds four MFMAs.
 #include "fmrx_internal.hpp"
 #include "tuner_host.hpp"
+
+#include <type_traits>
 
 namespace fmrx {
 namespace {
@@ -42,10 +53,9 @@ struct Rot {
 };
 __device__ __forceinline__ Rot rot_of(unsigned t) { return {static_cast<short>(t & 0xffffu), static_cast<short>(t >> 16)}; }
 
-__device__ __forceinline__ unsigned tuner_round_pair(int ar, int ai, Rot r, int sh, unsigned &clipped, unsigned long long &power)
+// a rotated sample (yr, yi) -> rounded, clamped (I, Q) bytes
+__device__ __forceinline__ unsigned tuner_round_y(long long yr, long long yi, int sh, unsigned &clipped, unsigned long long &power)
 {
-    const long long yr = static_cast<long long>(ar) * r.c + static_cast<long long>(ai) * r.s;
-    const long long yi = static_cast<long long>(ai) * r.c - static_cast<long long>(ar) * r.s;
     const long long half = 1LL << (sh - 1);
     long long oi = 128 + ((yr + half) >> sh), oq = 128 + ((yi + half) >> sh);
     const long long ci = oi < 0 ? 0 : (oi > 255 ? 255 : oi), cq = oq < 0 ? 0 : (oq > 255 ? 255 : oq);
@@ -53,6 +63,25 @@ __device__ __forceinline__ unsigned tuner_round_pair(int ar, int ai, Rot r, int 
     const int di = static_cast<int>(ci) - 128, dq = static_cast<int>(cq) - 128;
     power += static_cast<unsigned>(di * di + dq * dq);
     return static_cast<unsigned>(ci) | (static_cast<unsigned>(cq) << 8);
+}
+
+__device__ __forceinline__ unsigned tuner_round_pair(int ar, int ai, Rot r, int sh, unsigned &clipped, unsigned long long &power)
+{
+    const long long yr = static_cast<long long>(ar) * r.c + static_cast<long long>(ai) * r.s;
+    const long long yi = static_cast<long long>(ai) * r.c - static_cast<long long>(ar) * r.s;
+    return tuner_round_y(yr, yi, sh, clipped, power);
+}
+
+// The 16-bit format's pair: acc = k + l + 256 h per part (k the channel's constant, l and h the low and the high plane's
+// sums, each an int32), |acc| < 2^40.  The rotation is taken term by term, every product int32 x int16 -> int64, so that
+// nothing wider than a 32 x 32 -> 64 multiply-add is needed: |y| < 2^56.
+__device__ __forceinline__ unsigned tuner_round_pair_planes(int lr, int li, int hr, int hi, int kr, int ki, Rot r, int sh, unsigned &clipped,
+                                                            unsigned long long &power)
+{
+    const long long c = r.c, s = r.s;
+    const long long yr = (lr * c + li * s) + (kr * c + ki * s) + 256 * (hr * c + hi * s);
+    const long long yi = (li * c - lr * s) + (ki * c - kr * s) + 256 * (hi * c - hr * s);
+    return tuner_round_y(yr, yi, sh, clipped, power);
 }
 
 // The same pair in 32-bit arithmetic, for 17 <= sh <= 47 (every gain a receiver would use): with a = ah 2^16 + al (al the
@@ -78,7 +107,35 @@ __device__ __forceinline__ unsigned tuner_round_pair_fast(int ar, int ai, Rot r,
     return static_cast<unsigned>(ci) | (static_cast<unsigned>(cq) << 8);
 }
 
-__global__ __launch_bounds__(256, 2) void tuner_mfma_kernel(
+// a lane's 8 consecutive (I, Q) pairs -> its 16-byte piece of the channel's row (n_left: outputs from this one to the call's end)
+__device__ __forceinline__ void tuner_store_piece(uint8_t *dst, const unsigned (&pr)[kTunerPhases], bool whole, long n_left)
+{
+    if (whole) {
+        *reinterpret_cast<u4 *>(dst) = u4{pr[0] | (pr[1] << 16), pr[2] | (pr[3] << 16), pr[4] | (pr[5] << 16), pr[6] | (pr[7] << 16)};
+    } else {
+#pragma unroll
+        for (int p = 0; p < kTunerPhases; p++)
+            if (p < n_left) *reinterpret_cast<unsigned short *>(dst + 2 * p) = static_cast<unsigned short>(pr[p]);
+    }
+}
+
+// levels of the matrix kernels: the 16 columns of a channel sit in the 16 lanes of one quarter
+__device__ __forceinline__ void tuner_add_levels(unsigned clipped, unsigned long long power, bool first_lane, unsigned long long *lv)
+{
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        clipped += __shfl_xor(clipped, o);
+        power += __shfl_xor(power, o);
+    }
+    if (first_lane) {
+        if (clipped) atomicAdd(lv, static_cast<unsigned long long>(clipped));
+        if (power) atomicAdd(lv + 1, power);
+    }
+}
+
+// kFlip: what turns a raw byte into the int8 x (0x80 for unsigned bytes, 0 for signed ones) = the raw byte of a zero sample
+template <unsigned kFlip>
+__device__ __forceinline__ void tuner_mfma_body(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
     const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, long pitch, int n_channels,
     long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
@@ -130,20 +187,20 @@ __global__ __launch_bounds__(256, 2) void tuner_mfma_kernel(
             } else if (q + 16 <= n_bytes) {
                 v = *reinterpret_cast<const u4 *>(x + q);
             } else {
-                unsigned b[4];                                      // past the call: zero samples (0x80)
+                unsigned b[4];                                      // past the call: zero samples
 #pragma unroll
                 for (int d = 0; d < 4; d++) {
                     unsigned wd = 0;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
                         const long pos = q + 4 * d + k;
-                        wd |= (pos < n_bytes ? static_cast<unsigned>(x[pos]) : 0x80u) << (8 * k);
+                        wd |= (pos < n_bytes ? static_cast<unsigned>(x[pos]) : kFlip) << (8 * k);
                     }
                     b[d] = wd;
                 }
                 v = u4{b[0], b[1], b[2], b[3]};
             }
-            v ^= 0x80808080u;                                       // u8 -> u8 - 128 as int8
+            if (kFlip) v ^= kFlip * 0x01010101u;                    // u8 -> u8 - 128 as int8
             *reinterpret_cast<u4 *>(stage + 16 * (i + i / R)) = v;
         }
         __syncthreads();
@@ -224,51 +281,219 @@ __global__ __launch_bounds__(256, 2) void tuner_mfma_kernel(
                     ph += dph;
                 }
             }
-            uint8_t *dst = out + static_cast<long>(ch) * pitch + 2 * mb;
-            if (whole) {
-                *reinterpret_cast<u4 *>(dst) = u4{pr[0] | (pr[1] << 16), pr[2] | (pr[3] << 16), pr[4] | (pr[5] << 16), pr[6] | (pr[7] << 16)};
-            } else {
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++)
-                    if (mb + p < n_out) *reinterpret_cast<unsigned short *>(dst + 2 * p) = static_cast<unsigned short>(pr[p]);
-            }
+            tuner_store_piece(out + static_cast<long>(ch) * pitch + 2 * mb, pr, whole, n_out - mb);
         }
     }
-    // levels: the 16 columns of a channel sit in the 16 lanes of one quarter
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-        clipped += __shfl_xor(clipped, o);
-        power += __shfl_xor(power, o);
-    }
-    if (ch_ok && col == 0) {
-        if (clipped) atomicAdd(levels + 2 * ch, static_cast<unsigned long long>(clipped));
-        if (power) atomicAdd(levels + 2 * ch + 1, power);
-    }
+    tuner_add_levels(clipped, power, ch_ok && col == 0, levels + 2 * ch);
 }
 
-__global__ __launch_bounds__(256) void tuner_generic_kernel(
+__global__ __launch_bounds__(256, 2) void tuner_mfma_kernel(
+    const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
+    const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, long pitch, int n_channels,
+    long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    unsigned long long *__restrict__ levels)
+{
+    tuner_mfma_body<0x80u>(x, hist, n_bytes, a_img, chan, table, out, pitch, n_channels, n_out, R, T, front, ks, ksp, n0, n_steps, steps_per_wg, levels);
+}
+
+__global__ __launch_bounds__(256, 2) void tuner_mfma_s8_kernel(
+    const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
+    const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, long pitch, int n_channels,
+    long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    unsigned long long *__restrict__ levels)
+{
+    tuner_mfma_body<0u>(x, hist, n_bytes, a_img, chan, table, out, pitch, n_channels, n_out, R, T, front, ks, ksp, n0, n_steps, steps_per_wg, levels);
+}
+
+// ---- signed 16-bit input: two byte planes against the same operand image ------------------------------------------
+constexpr int kTT16 = 2;                      // tiles per wave and step: two planes of accumulators each
+constexpr int kStepOut16 = 128 * kTT16;
+
+// x, hist: raw little-endian int16 I,Q values (n_values of them in the call, `front` in the history); a plane's byte u is
+// value u's low or high byte, so plane positions are the 8-bit kernel's byte positions and the raw position is twice that.
+__global__ __launch_bounds__(256, 2) void tuner_mfma_s16_kernel(
+    const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_values, const i4 *__restrict__ a_img,
+    const uint2 *__restrict__ chan, const int2 *__restrict__ kconst, const unsigned *__restrict__ table, uint8_t *__restrict__ out,
+    long pitch, int n_channels, long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    unsigned long long *__restrict__ levels)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    unsigned *tab = reinterpret_cast<unsigned *>(lds_raw);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = static_cast<int>(blockIdx.y) * 4 + wave;
+    const int n_groups = (n_channels + kTunerGroup - 1) / kTunerGroup;
+    const bool live = grp < n_groups;                               // wave-uniform
+    const int col = lane & 15, g = lane >> 4;
+    const int ch = grp * kTunerGroup + g;
+    const bool ch_ok = live && ch < n_channels;
+    const int n_pieces = 16 * kTT16 * R + 4 * ks;                   // 16-byte pieces of a step's window, per plane
+    uint8_t *stage_l = lds_raw + kTunerTableSize * 4;
+    uint8_t *stage_h = stage_l + 16 * (n_pieces + n_pieces / R + 1);
+
+    for (int i = tid; i < kTunerTableSize; i += 256) tab[i] = table[i];
+
+    int j0[kTunerPhases], j1[kTunerPhases];
+#pragma unroll
+    for (int p = 0; p < kTunerPhases; p++) {
+        j0[p] = (front + 2 * R * p - 2 * (T - 1)) / 64;
+        j1[p] = (front + 2 * R * p + 1) / 64 + 1;
+    }
+    unsigned w = 0;
+    int sh = 1, kr = 0, ki = 0;
+    if (ch_ok) {
+        const uint2 cp = chan[ch];
+        w = cp.x;
+        sh = static_cast<int>(cp.y);
+        const int2 kc = kconst[ch];
+        kr = kc.x;
+        ki = kc.y;
+    }
+    const i4 *a_grp = a_img + static_cast<size_t>(live ? grp : 0) * kTunerPhases * ksp * 64 + lane;
+    unsigned clipped = 0;
+    unsigned long long power = 0;
+
+    const int step0 = static_cast<int>(blockIdx.x) * steps_per_wg;
+    for (int st = step0; st < step0 + steps_per_wg && st < n_steps; st++) {
+        const long m0 = static_cast<long>(st) * kStepOut16;
+        const long q0 = 2L * R * m0 - front;                        // plane position of the window's start, relative to the call
+        __syncthreads();
+        for (int i = tid; i < n_pieces; i += 256) {
+            const long q = q0 + 16L * i;
+            u4 v0, v1;                                              // 16 values = 32 raw bytes -> one piece per plane
+            if (q < 0) {
+                const u4 *src = reinterpret_cast<const u4 *>(hist + 2 * (front + q));
+                v0 = src[0];
+                v1 = src[1];
+            } else if (q + 16 <= n_values) {
+                const u4 *src = reinterpret_cast<const u4 *>(x + 2 * q);
+                v0 = src[0];
+                v1 = src[1];
+            } else {
+                unsigned b[8];                                      // past the call: zero samples
+#pragma unroll
+                for (int d = 0; d < 8; d++) {
+                    unsigned wd = 0;
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        const long pos = q + 2 * d + k;
+                        wd |= (pos < n_values ? static_cast<unsigned>(reinterpret_cast<const unsigned short *>(x)[pos]) : 0u) << (16 * k);
+                    }
+                    b[d] = wd;
+                }
+                v0 = u4{b[0], b[1], b[2], b[3]};
+                v1 = u4{b[4], b[5], b[6], b[7]};
+            }
+            // a raw word is (low, high) of value 2 d, (low, high) of value 2 d + 1: even bytes -> low plane, odd -> high plane
+            const u4 lo = u4{__builtin_amdgcn_perm(v0[1], v0[0], 0x06040200u), __builtin_amdgcn_perm(v0[3], v0[2], 0x06040200u),
+                             __builtin_amdgcn_perm(v1[1], v1[0], 0x06040200u), __builtin_amdgcn_perm(v1[3], v1[2], 0x06040200u)};
+            const u4 hi = u4{__builtin_amdgcn_perm(v0[1], v0[0], 0x07050301u), __builtin_amdgcn_perm(v0[3], v0[2], 0x07050301u),
+                             __builtin_amdgcn_perm(v1[1], v1[0], 0x07050301u), __builtin_amdgcn_perm(v1[3], v1[2], 0x07050301u)};
+            const int off = 16 * (i + i / R);
+            *reinterpret_cast<u4 *>(stage_l + off) = lo ^ 0x80808080u;   // low byte - 128 as int8
+            *reinterpret_cast<u4 *>(stage_h + off) = hi;
+        }
+        __syncthreads();
+        if (!live) continue;
+
+        i4 accl[kTT16][kTunerPhases], acch[kTT16][kTunerPhases];
+#pragma unroll
+        for (int tt = 0; tt < kTT16; tt++)
+#pragma unroll
+            for (int p = 0; p < kTunerPhases; p++) accl[tt][p] = acch[tt][p] = i4{0, 0, 0, 0};
+        int rem = g % R, blk = g / R;                               // (4 j + g) mod R and div R
+        for (int j = 0; j < ks; j++) {
+            i4 bl[kTT16], bh[kTT16];
+#pragma unroll
+            for (int tt = 0; tt < kTT16; tt++) {
+                const int off = 16 * ((R + 1) * (16 * tt + col) + 4 * j + g + blk);
+                bl[tt] = *reinterpret_cast<const i4 *>(stage_l + off);
+                bh[tt] = *reinterpret_cast<const i4 *>(stage_h + off);
+            }
+            i4 a[kTunerPhases];
+#pragma unroll
+            for (int p = 0; p < kTunerPhases; p++) {
+                int jr = j - j0[p];
+                jr = jr < 0 ? 0 : (jr >= ksp ? ksp - 1 : jr);
+                a[p] = a_grp[(p * ksp + jr) * 64];
+            }
+#pragma unroll
+            for (int p = 0; p < kTunerPhases; p++) {
+                if (j >= j0[p] && j < j1[p]) {
+#pragma unroll
+                    for (int tt = 0; tt < kTT16; tt++) {
+                        accl[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], bl[tt], accl[tt][p], 0, 0, 0);
+                        acch[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], bh[tt], acch[tt][p], 0, 0, 0);
+                    }
+                }
+            }
+            rem += 4;
+            while (rem >= R) {
+                rem -= R;
+                blk++;
+            }
+        }
+        if (!ch_ok) continue;
+#pragma unroll
+        for (int tt = 0; tt < kTT16; tt++) {
+            const long mb = m0 + 128 * tt + 8 * col;                // this lane's first output time of the tile
+            if (mb >= n_out) continue;
+            unsigned pr[kTunerPhases];
+            unsigned ph = w * (n0 + static_cast<unsigned>(mb) * static_cast<unsigned>(R));
+            const unsigned dph = w * static_cast<unsigned>(R);
+            const bool whole = mb + kTunerPhases <= n_out;
+#pragma unroll
+            for (int p = 0; p < kTunerPhases; p++) {
+                const int lr = accl[tt][p][0] + 256 * accl[tt][p][1], li = accl[tt][p][2] + 256 * accl[tt][p][3];
+                const int hr = acch[tt][p][0] + 256 * acch[tt][p][1], hi = acch[tt][p][2] + 256 * acch[tt][p][3];
+                unsigned cl = 0;
+                unsigned long long pw = 0;
+                pr[p] = tuner_round_pair_planes(lr, li, hr, hi, kr, ki, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh, cl, pw);
+                if (whole || mb + p < n_out) {
+                    clipped += cl;
+                    power += pw;
+                }
+                ph += dph;
+            }
+            tuner_store_piece(out + static_cast<long>(ch) * pitch + 2 * mb, pr, whole, n_out - mb);
+        }
+    }
+    tuner_add_levels(clipped, power, ch_ok && col == 0, levels + 2 * ch);
+}
+
+// FMT: kTunerU8 / kTunerS8 / kTunerS16.  x, hist: raw values (bytes, or little-endian int16 for S16); the 16-bit format's sums
+// need 64 bits (|acc| < 2^40), the 8-bit formats' fit int32 as before.
+template <int FMT>
+__device__ __forceinline__ void tuner_generic_body(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, const int16_t *__restrict__ taps_re,
     const int16_t *__restrict__ taps_im, const uint2 *__restrict__ chan, const unsigned *__restrict__ table,
     uint8_t *__restrict__ out, long pitch, long n_out, int R, int T, int front, unsigned n0, unsigned long long *__restrict__ levels)
 {
+    using value_t = std::conditional_t<FMT == kTunerS16, int16_t, std::conditional_t<FMT == kTunerS8, int8_t, uint8_t>>;
+    using acc_t = std::conditional_t<FMT == kTunerS16, long long, int>;
+    constexpr int kBias = FMT == kTunerU8 ? 128 : 0;
+    const value_t *xv = reinterpret_cast<const value_t *>(x), *hv = reinterpret_cast<const value_t *>(hist);
     const int ch = blockIdx.x;
     const long m = static_cast<long>(blockIdx.y) * 256 + threadIdx.x;
     unsigned clipped = 0;
     unsigned long long power = 0;
     if (m < n_out) {
         const int16_t *re = taps_re + static_cast<long>(ch) * T, *im = taps_im + static_cast<long>(ch) * T;
-        int ar = 0, ai = 0;
+        acc_t ar = 0, ai = 0;
         for (int k = 0; k < T; k++) {
             const long pos = 2 * (m * R - k);
-            const uint8_t *src = pos < 0 ? hist + front + pos : x + pos;
-            const int xr = static_cast<int>(src[0]) - 128, xq = static_cast<int>(src[1]) - 128;
+            const value_t *src = pos < 0 ? hv + front + pos : xv + pos;
+            const int xr = static_cast<int>(src[0]) - kBias, xq = static_cast<int>(src[1]) - kBias;
             const int gr = re[k], gi = im[k];
-            ar += gr * xr - gi * xq;
-            ai += gi * xr + gr * xq;
+            ar += static_cast<acc_t>(gr * xr) - gi * xq;            // a product is below 2^30, a difference of two is not
+            ai += static_cast<acc_t>(gi * xr) + gr * xq;
         }
         const uint2 cp = chan[ch];
         const unsigned ph = cp.x * (n0 + static_cast<unsigned>(m) * static_cast<unsigned>(R));
-        const unsigned pr = tuner_round_pair(ar, ai, rot_of(table[ph >> (32 - kTunerTableBits)]), static_cast<int>(cp.y), clipped, power);
+        const Rot r = rot_of(table[ph >> (32 - kTunerTableBits)]);
+        const long long yr = static_cast<long long>(ar) * r.c + static_cast<long long>(ai) * r.s;
+        const long long yi = static_cast<long long>(ai) * r.c - static_cast<long long>(ar) * r.s;
+        const unsigned pr = tuner_round_y(yr, yi, static_cast<int>(cp.y), clipped, power);
         *reinterpret_cast<unsigned short *>(out + static_cast<long>(ch) * pitch + 2 * m) = static_cast<unsigned short>(pr);
     }
 #pragma unroll
@@ -282,7 +507,20 @@ __global__ __launch_bounds__(256) void tuner_generic_kernel(
     }
 }
 
-// the carried history: the last `front` bytes of (old history | this call's input)
+#define FMRX_TUNER_GENERIC(NAME, FMT)                                                                                                        \
+    __global__ __launch_bounds__(256) void NAME(                                                                                             \
+        const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, const int16_t *__restrict__ taps_re,                                \
+        const int16_t *__restrict__ taps_im, const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, \
+        long pitch, long n_out, int R, int T, int front, unsigned n0, unsigned long long *__restrict__ levels)                               \
+    {                                                                                                                                        \
+        tuner_generic_body<FMT>(x, hist, taps_re, taps_im, chan, table, out, pitch, n_out, R, T, front, n0, levels);                         \
+    }
+FMRX_TUNER_GENERIC(tuner_generic_kernel, kTunerU8)
+FMRX_TUNER_GENERIC(tuner_generic_s8_kernel, kTunerS8)
+FMRX_TUNER_GENERIC(tuner_generic_s16_kernel, kTunerS16)
+#undef FMRX_TUNER_GENERIC
+
+// the carried history: the last `front` raw bytes of (old history | this call's input)
 __global__ __launch_bounds__(256) void tuner_hist_kernel(const uint8_t *__restrict__ x, long n_bytes, const uint8_t *__restrict__ old_hist,
                                                          uint8_t *__restrict__ new_hist, int front)
 {
@@ -294,35 +532,46 @@ __global__ __launch_bounds__(256) void tuner_hist_kernel(const uint8_t *__restri
 
 }  // namespace
 
-size_t tuner_mfma_lds_bytes(int R, int ks)
+size_t tuner_mfma_lds_bytes(int R, int ks, int format)
 {
-    const int n_pieces = 64 * R + 4 * ks;
-    return static_cast<size_t>(kTunerTableSize) * 4 + 16u * (n_pieces + n_pieces / R + 1);
+    const int tiles = format == kTunerS16 ? kTT16 : kTT, planes = format == kTunerS16 ? 2 : 1;
+    const int n_pieces = 16 * tiles * R + 4 * ks;
+    return static_cast<size_t>(kTunerTableSize) * 4 + 16u * planes * (n_pieces + n_pieces / R + 1);
 }
 
 int tuner_launch(const TunerLaunch &a, hipStream_t stream)
 {
     const long n_out = a.n_bytes / (2L * a.R);
+    const int vb = tuner_value_bytes(a.format);
     if (n_out > 0) {
         if (a.mfma) {
-            const int n_steps = static_cast<int>((n_out + kStepOut - 1) / kStepOut);
+            const int step_out = a.format == kTunerS16 ? kStepOut16 : kStepOut;
+            const int n_steps = static_cast<int>((n_out + step_out - 1) / step_out);
             const int gy = (a.n_channels + 4 * kTunerGroup - 1) / (4 * kTunerGroup);
             // enough workgroups to fill the chip a few times over, as many steps each as that leaves (the table is loaded once
             // per workgroup)
             int per = static_cast<int>((static_cast<long>(n_steps) * gy + 2047) / 2048);
             if (per < 1) per = 1;
             const int gx = (n_steps + per - 1) / per;
-            const size_t lds = tuner_mfma_lds_bytes(a.R, a.ks);
-            hipLaunchKernelGGL(tuner_mfma_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x, a.hist, a.n_bytes,
-                               reinterpret_cast<const i4 *>(a.a_img), a.chan, a.table, a.out, a.pitch, a.n_channels, n_out, a.R, a.T,
-                               a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+            const size_t lds = tuner_mfma_lds_bytes(a.R, a.ks, a.format);
+            if (a.format == kTunerS16) {
+                hipLaunchKernelGGL(tuner_mfma_s16_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x, a.hist, a.n_bytes,
+                                   reinterpret_cast<const i4 *>(a.a_img), a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels, n_out, a.R,
+                                   a.T, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+            } else {
+                hipLaunchKernelGGL(a.format == kTunerS8 ? tuner_mfma_s8_kernel : tuner_mfma_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x,
+                                   a.hist, a.n_bytes, reinterpret_cast<const i4 *>(a.a_img), a.chan, a.table, a.out, a.pitch, a.n_channels,
+                                   n_out, a.R, a.T, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+            }
         } else {
-            hipLaunchKernelGGL(tuner_generic_kernel, dim3(a.n_channels, static_cast<unsigned>((n_out + 255) / 256)), dim3(256), 0, stream,
-                               a.x, a.hist, a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.R, a.T, a.front, a.n0, a.levels);
+            const auto kernel = a.format == kTunerS16 ? tuner_generic_s16_kernel : a.format == kTunerS8 ? tuner_generic_s8_kernel : tuner_generic_kernel;
+            hipLaunchKernelGGL(kernel, dim3(a.n_channels, static_cast<unsigned>((n_out + 255) / 256)), dim3(256), 0, stream, a.x, a.hist,
+                               a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.R, a.T, a.front, a.n0, a.levels);
         }
         FMRX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(tuner_hist_kernel, dim3((a.front + 255) / 256), dim3(256), 0, stream, a.x, a.n_bytes, a.hist, a.hist_next, a.front);
+    hipLaunchKernelGGL(tuner_hist_kernel, dim3((a.front * vb + 255) / 256), dim3(256), 0, stream, a.x, a.n_bytes * vb, a.hist, a.hist_next,
+                       a.front * vb);
     FMRX_HIP(hipGetLastError());
     return FMRX_OK;
 }

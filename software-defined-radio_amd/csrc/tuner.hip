@@ -1,10 +1,11 @@
-// tuner.hip -- the wideband tuner's handle and C ABI (include/fmrx.h: fmrx_tuner_*): one wide u8 I/Q capture at
-// Fs_w = R * rf_Fs in, N channels' u8 I/Q streams at rf_Fs out, written straight into a receiver bank's input slots
-// (fmrx_channels_input_layout).  Kernels: kernels_tuner.hip; arithmetic: tuner_host.hpp, defined by tests/_tuner_model.py
-// (DESIGN.md section 4.9).
+// tuner.hip -- the wideband tuner's handle and C ABI (include/fmrx.h: fmrx_tuner_*): one wide I/Q capture (u8, s8 or
+// little-endian s16) at Fs_w = R * rf_Fs in, N channels' u8 I/Q streams at rf_Fs out, written straight into a receiver
+// bank's input slots (fmrx_channels_input_layout).  Kernels: kernels_tuner.hip; arithmetic: tuner_host.hpp, defined by
+// tests/_tuner_model.py and, for the input formats, tests/_tuner_formats_model.py.
 //
-// State carried by the handle: the last `front` raw bytes of the stream (front = 2 (T - 1) rounded up to 16; 0x80 = silence
-// at the start) in one of two device buffers that swap roles every call, and the wide-sample counter (uint64, used mod 2^32).
+// State carried by the handle: the last `front` raw values of the stream (front = 2 (T - 1) rounded up to 16; zero samples
+// at the start: bytes 0x80 for u8, 0x00 for the signed formats) in one of two device buffers that swap roles every call,
+// and the wide-sample counter (uint64, used mod 2^32).
 // Channel parameters live on the host (taps as int16 pairs, frequency word, scale exponent, the matrix kernel's operand
 // image); fmrx_tuner_set_channel changes the host copy and marks the channel, the next call uploads what changed.
 #include "fmrx_internal.hpp"
@@ -15,20 +16,22 @@
 using namespace fmrx;
 
 struct fmrx_tuner {
-    int device = 0, R = 0, T = 0, n_channels = 0;
+    int device = 0, R = 0, T = 0, n_channels = 0, format = kTunerU8;
     long max_wide = 0;
     bool mfma = true;
     TunerShape sh;
     size_t group_bytes = 0;
     std::vector<float> h;
     std::vector<int16_t> re, im;         // [n_channels][T]
-    std::vector<uint2> chan;             // {w, s + 15}
+    std::vector<uint2> chan;             // {w, s + 15 + B}
+    std::vector<int2> kconst;            // 16-bit matrix kernel: 128 * {sum(re - im), sum(im + re)}
     std::vector<int8_t> img;             // matrix kernel: [groups][group_bytes]
     std::vector<uint8_t> dirty;
     size_t n_dirty = 0;
     DevBuf<int8_t> d_img;
     DevBuf<int16_t> d_re, d_im;
     DevBuf<uint2> d_chan;
+    DevBuf<int2> d_kconst;
     DevBuf<unsigned> d_table;
     DevBuf<uint8_t> d_hist[2];
     int cur = 0;
@@ -38,7 +41,10 @@ struct fmrx_tuner {
     uint64_t counter = 0;
     hipStream_t last_stream = nullptr;
     bool ran = false;
+    bool wide_planes() const { return mfma && format == kTunerS16; }
 };
+
+static_assert(FMRX_TUNER_U8 == kTunerU8 && FMRX_TUNER_S8 == kTunerS8 && FMRX_TUNER_S16 == kTunerS16, "fmrx.h and tuner_host.hpp");
 
 namespace {
 
@@ -52,9 +58,20 @@ int design_channel(fmrx_tuner *t, int c, double f_c, double Fs_w, double gain)
     std::vector<int16_t> re(t->T), im(t->T);
     if (const char *why = tuner_design(t->h.data(), t->T, Fs_w, f_c, gain, &w, &s, re.data(), im.data()))
         return fail(FMRX_EINVAL, "tuner channel %d: %s", c, why);
+    if (s > tuner_max_shift(t->format))
+        return fail(FMRX_EINVAL, "tuner channel %d: gain x taps too small for 16-bit input (scale exponent %d outside -14 .. %d)", c, s,
+                    tuner_max_shift(t->format));
     std::copy(re.begin(), re.end(), t->re.begin() + static_cast<size_t>(c) * t->T);
     std::copy(im.begin(), im.end(), t->im.begin() + static_cast<size_t>(c) * t->T);
-    t->chan[c] = make_uint2(w, static_cast<unsigned>(s + 15));
+    t->chan[c] = make_uint2(w, static_cast<unsigned>(s + 15 + tuner_extra_bits(t->format)));
+    if (t->wide_planes()) {
+        long long sr = 0, si = 0;
+        for (int k = 0; k < t->T; k++) {
+            sr += re[k] - im[k];
+            si += im[k] + re[k];
+        }
+        t->kconst[c] = make_int2(static_cast<int>(128 * sr), static_cast<int>(128 * si));   // |.| <= 128 sum(|re| + |im|) < 2^31
+    }
     if (t->mfma)
         tuner_fill_image(t->img.data() + static_cast<size_t>(c / kTunerGroup) * t->group_bytes, t->sh, t->T, t->R, c % kTunerGroup,
                          re.data(), im.data());
@@ -72,6 +89,7 @@ int upload_dirty(fmrx_tuner *t, hipStream_t stream)
     const size_t N = t->n_channels, T = t->T;
     if (t->n_dirty == N) {
         FMRX_HIP(hipMemcpyAsync(t->d_chan.p, t->chan.data(), N * sizeof(uint2), hipMemcpyHostToDevice, stream));
+        if (t->wide_planes()) FMRX_HIP(hipMemcpyAsync(t->d_kconst.p, t->kconst.data(), N * sizeof(int2), hipMemcpyHostToDevice, stream));
         if (t->mfma) {
             FMRX_HIP(hipMemcpyAsync(t->d_img.p, t->img.data(), t->img.size(), hipMemcpyHostToDevice, stream));
         } else {
@@ -82,6 +100,7 @@ int upload_dirty(fmrx_tuner *t, hipStream_t stream)
         for (size_t c = 0; c < N; c++) {
             if (!t->dirty[c]) continue;
             FMRX_HIP(hipMemcpyAsync(t->d_chan.p + c, t->chan.data() + c, sizeof(uint2), hipMemcpyHostToDevice, stream));
+            if (t->wide_planes()) FMRX_HIP(hipMemcpyAsync(t->d_kconst.p + c, t->kconst.data() + c, sizeof(int2), hipMemcpyHostToDevice, stream));
             if (t->mfma) {
                 const size_t off = c / kTunerGroup * t->group_bytes;
                 FMRX_HIP(hipMemcpyAsync(t->d_img.p + off, t->img.data() + off, t->group_bytes, hipMemcpyHostToDevice, stream));
@@ -100,8 +119,8 @@ int upload_dirty(fmrx_tuner *t, hipStream_t stream)
 int clear_state(fmrx_tuner *t)
 {
     if (t->ran) FMRX_HIP(hipStreamSynchronize(t->last_stream));
-    FMRX_HIP(hipMemset(t->d_hist[0].p, 0x80, t->d_hist[0].bytes()));
-    FMRX_HIP(hipMemset(t->d_hist[1].p, 0x80, t->d_hist[1].bytes()));
+    FMRX_HIP(hipMemset(t->d_hist[0].p, tuner_zero_byte(t->format), t->d_hist[0].bytes()));
+    FMRX_HIP(hipMemset(t->d_hist[1].p, tuner_zero_byte(t->format), t->d_hist[1].bytes()));
     FMRX_HIP(hipMemset(t->d_levels.p, 0, t->d_levels.bytes()));
     t->cur = 0;
     t->counter = 0;
@@ -129,7 +148,13 @@ int fmrx_tuner_table(int16_t *cos_q15, int16_t *sin_q15, size_t *n)
 
 int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int device)
 {
+    return fmrx_tuner_create_ex(out, R, h, taps, n_channels, max_wide_samples, FMRX_TUNER_U8, device);
+}
+
+int fmrx_tuner_create_ex(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int format, int device)
+{
     if (!out || !h) return fail(FMRX_EINVAL, "tuner_create: null argument");
+    if (!tuner_format_ok(format)) return fail(FMRX_EINVAL, "tuner_create: format %d (FMRX_TUNER_U8, _S8 or _S16)", format);
     if (R < 2 || R > kTunerMaxR) return fail(FMRX_EINVAL, "tuner_create: decimation %d (2 .. %d)", R, kTunerMaxR);
     if (taps < 2 || taps > kTunerMaxTaps) return fail(FMRX_EINVAL, "tuner_create: %d taps (2 .. %d)", taps, kTunerMaxTaps);
     if (n_channels < 1 || n_channels > 65536) return fail(FMRX_EINVAL, "tuner_create: n_channels must be 1 .. 65536");
@@ -143,6 +168,7 @@ int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_c
     t->R = R;
     t->T = taps;
     t->n_channels = n_channels;
+    t->format = format;
     t->max_wide = static_cast<long>(max_wide_samples);
     t->mfma = options_snapshot().tuner_variant == 0 && taps <= kTunerMfmaMaxTaps;
     t->sh = tuner_shape(taps, R);
@@ -153,6 +179,7 @@ int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_c
         t->re.assign(N * T, 0);
         t->im.assign(N * T, 0);
         t->chan.assign(N, make_uint2(0, 1));
+        if (t->wide_planes()) t->kconst.assign(N, make_int2(0, 0));
         t->dirty.assign(N, 0);
         if (t->mfma) t->img.assign(static_cast<size_t>(n_groups(t)) * t->group_bytes, 0);
         // every channel starts at the capture's centre with gain 1; designed once, copied to the rest
@@ -161,6 +188,7 @@ int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_c
             std::copy(t->re.begin(), t->re.begin() + T, t->re.begin() + c * T);
             std::copy(t->im.begin(), t->im.begin() + T, t->im.begin() + c * T);
             t->chan[c] = t->chan[0];
+            if (t->wide_planes()) t->kconst[c] = t->kconst[0];
             if (t->mfma && c < static_cast<size_t>(kTunerGroup))
                 tuner_fill_image(t->img.data(), t->sh, t->T, t->R, static_cast<int>(c), t->re.data(), t->im.data());
         }
@@ -170,6 +198,7 @@ int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_c
         std::fill(t->dirty.begin(), t->dirty.end(), 1);
         t->n_dirty = N;
         FMRX_TRY(t->d_chan.alloc(N));
+        if (t->wide_planes()) FMRX_TRY(t->d_kconst.alloc(N));
         if (t->mfma) {
             FMRX_TRY(t->d_img.alloc(t->img.size()));
         } else {
@@ -183,10 +212,10 @@ int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_c
             tab[i] = static_cast<unsigned>(static_cast<uint16_t>(c[i])) | (static_cast<unsigned>(static_cast<uint16_t>(s[i])) << 16);
         FMRX_TRY(t->d_table.alloc(kTunerTableSize));
         FMRX_HIP(hipMemcpy(t->d_table.p, tab.data(), tab.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        FMRX_TRY(t->d_hist[0].alloc(t->sh.front));
-        FMRX_TRY(t->d_hist[1].alloc(t->sh.front));
+        FMRX_TRY(t->d_hist[0].alloc(static_cast<size_t>(t->sh.front) * tuner_value_bytes(format)));
+        FMRX_TRY(t->d_hist[1].alloc(static_cast<size_t>(t->sh.front) * tuner_value_bytes(format)));
         FMRX_TRY(t->d_levels.alloc(2 * N));
-        if (t->mfma && tuner_mfma_lds_bytes(R, t->sh.ks) > 64 * 1024) return fail(FMRX_EINVAL, "tuner_create: window too large for the matrix kernel");
+        if (t->mfma && tuner_mfma_lds_bytes(R, t->sh.ks, format) > 64 * 1024) return fail(FMRX_EINVAL, "tuner_create: window too large for the matrix kernel");
         return clear_state(t);
     };
     const int rc = body();
@@ -221,6 +250,10 @@ int fmrx_tuner_set_channel(fmrx_tuner *t, int channel, double f_c_hz, double Fs_
     return design_channel(t, channel, f_c_hz, Fs_w, gain);
 }
 
+int fmrx_tuner_format(const fmrx_tuner *t) { return t ? t->format : -1; }
+
+size_t fmrx_tuner_sample_bytes(const fmrx_tuner *t) { return t ? 2 * static_cast<size_t>(tuner_value_bytes(t->format)) : 0; }
+
 size_t fmrx_tuner_n_out_bytes(const fmrx_tuner *t, size_t n_wide) { return t && n_wide % t->R == 0 ? 2 * n_wide / t->R : 0; }
 
 int fmrx_tuner_process_dev(fmrx_tuner *t, const uint8_t *d_wide, size_t n_wide, uint8_t *d_out_first, size_t pitch_bytes, void *stream)
@@ -240,6 +273,8 @@ int fmrx_tuner_process_dev(fmrx_tuner *t, const uint8_t *d_wide, size_t n_wide, 
     FMRX_HIP(hipMemsetAsync(t->d_levels.p, 0, t->d_levels.bytes(), s));
     TunerLaunch a;
     a.mfma = t->mfma;
+    a.format = t->format;
+    a.kconst = t->d_kconst.p;
     a.x = d_wide;
     a.n_bytes = static_cast<long>(2 * n_wide);
     a.hist = t->d_hist[t->cur].p;
@@ -273,12 +308,12 @@ int fmrx_tuner_process(fmrx_tuner *t, const uint8_t *wide, size_t n_wide, uint8_
     FMRX_HIP(hipSetDevice(t->device));
     if (!t->d_wide.p) {
         t->out_pitch = (2 * static_cast<size_t>(t->max_wide) / t->R + 15) / 16 * 16;
-        FMRX_TRY(t->d_wide.alloc(2 * static_cast<size_t>(t->max_wide)));
+        FMRX_TRY(t->d_wide.alloc(fmrx_tuner_sample_bytes(t) * static_cast<size_t>(t->max_wide)));
         FMRX_TRY(t->d_out.alloc(t->out_pitch * t->n_channels));
     }
     if (n_wide == 0 || n_wide % t->R || n_wide > static_cast<size_t>(t->max_wide))
         return fail(FMRX_EINVAL, "tuner_process: %zu wide samples: a non-zero multiple of the decimation %d, at most %ld", n_wide, t->R, t->max_wide);
-    FMRX_HIP(hipMemcpy(t->d_wide.p, wide, 2 * n_wide, hipMemcpyHostToDevice));
+    FMRX_HIP(hipMemcpy(t->d_wide.p, wide, fmrx_tuner_sample_bytes(t) * n_wide, hipMemcpyHostToDevice));
     FMRX_TRY(fmrx_tuner_process_dev(t, t->d_wide.p, n_wide, t->d_out.p, t->out_pitch, nullptr));
     FMRX_HIP(hipStreamSynchronize(nullptr));
     const size_t row = 2 * n_wide / t->R;

@@ -23,6 +23,17 @@ constexpr int kTunerPhases = 8;                      // consecutive outputs per 
 constexpr int kTunerGroup = 4;                       // channels per MFMA tile: 4 rows each (re / im x 2 digits)
 constexpr double kTunerTwoPi = 6.283185307179586476925286766559;
 
+// Input formats (include/fmrx.h: FMRX_TUNER_U8 / S8 / S16; arithmetic defined by tests/_tuner_formats_model.py).  A wide
+// sample is an (I, Q) pair of values: x = u8 - 128, the int8, or the little-endian int16.  A format carries B extra bits of
+// input scale (the output shift is s + 15 + B, so unity gain maps full scale in to full scale out); the "zero sample" in
+// front of a stream and past a call is the value whose x is 0.
+constexpr int kTunerU8 = 0, kTunerS8 = 1, kTunerS16 = 2;
+inline bool tuner_format_ok(int f) { return f == kTunerU8 || f == kTunerS8 || f == kTunerS16; }
+inline int tuner_value_bytes(int f) { return f == kTunerS16 ? 2 : 1; }          // bytes per I or Q value
+inline int tuner_extra_bits(int f) { return f == kTunerS16 ? 8 : 0; }           // B
+inline int tuner_zero_byte(int f) { return f == kTunerU8 ? 0x80 : 0x00; }       // every byte of a zero sample
+inline int tuner_max_shift(int f) { return kTunerMaxShift - tuner_extra_bits(f); }   // largest s: s + 15 + B <= 62
+
 // w = round(f_c / Fs_w * 2^32) mod 2^32 (half away from zero); |f_c| < Fs_w / 2 is the caller's to check
 inline uint32_t tuner_freq_word(double f_c, double Fs_w)
 {

@@ -2,7 +2,8 @@
 share of the chain capture -> tuner -> exact stereo bank -> RDS bank.
 
     python3 tools/tuner_bench.py [--channels 16,192,1024,4096] [--R 8] [--also-R 4,10,20] [--outputs 51200] [--calls 20]
-                                 [--warmup 3] [--variant mfma|generic] [--chain 192] [--once N] [--json out.json]
+                                 [--warmup 3] [--variant mfma|generic] [--format u8|s8|s16] [--chain 192] [--once N]
+                                 [--json out.json]
 
 Per configuration (rf_Fs = 2.4 MS/s, Fs_w = R * rf_Fs, T = 8 R taps of tunerLowPass, channels on the 100 kHz raster; one call =
 `outputs` output samples per channel), from device events around every call after the warm-up, the median of `calls` calls:
@@ -14,7 +15,9 @@ Per configuration (rf_Fs = 2.4 MS/s, Fs_w = R * rf_Fs, T = 8 R taps of tunerLowP
   bound         which roof is nearer: the larger of output bytes / HBM peak and useful operations / int8 peak
 --chain N: the three stages of one 192 000-byte bank block (96 000 outputs per channel, 40 ms of signal), each between its
 own pair of events on one stream, N channels.  --once N: a single configuration, `calls` calls and nothing else (for a
-counters-only profiler run around this script)."""
+counters-only profiler run around this script).  --format: the capture's format, for the tables, --chain and --once alike
+(s16: 4 bytes per wide sample in, two byte planes against the same operand image, so twice the matrix operations issued per
+output; the output bytes and the useful-operation count of the 8-bit formats are kept as the yardstick)."""
 from __future__ import annotations
 
 import argparse
@@ -40,23 +43,33 @@ def shape_ksteps(T, R):
     return sum((front + 2 * R * p + 1) // 64 + 1 - (front + 2 * R * p - 2 * (T - 1)) // 64 for p in range(8))
 
 
-def make_tuner(fmrx, R, N, n_wide, T=None):
+TORCH_DTYPE = {"u8": "uint8", "s8": "int8", "s16": "int16"}
+
+
+def random_wide(torch, fmt, n_wide, lo, hi, g):
+    """2 n_wide random I,Q values of the format on the device; lo / hi as fractions of full scale around zero"""
+    full = 32768 if fmt == "s16" else 128
+    off = 128 if fmt == "u8" else 0
+    return torch.randint(off + int(lo * full), off + int(hi * full), (2 * n_wide,), dtype=getattr(torch, TORCH_DTYPE[fmt]), device="cuda", generator=g)
+
+
+def make_tuner(fmrx, R, N, n_wide, T=None, fmt="u8"):
     Fs_w = RF_FS * R
     T = T or 8 * R
     h = fmrx.tunerLowPass(Fs_w, R, T)
-    t = fmrx.Tuner(R, h, N, n_wide)
+    t = fmrx.Tuner(R, h, N, n_wide, fmt=fmt)
     slots = int(Fs_w // 100e3) - 1
     for c in range(N):
         t.set_channel(c, ((c % slots) - slots // 2) * 100e3, Fs_w, 2.0)
     return t, T
 
 
-def time_config(fmrx, torch, R, N, outputs, calls, warmup):
+def time_config(fmrx, torch, R, N, outputs, calls, warmup, fmt="u8"):
     n_wide = outputs * R
-    t, T = make_tuner(fmrx, R, N, n_wide)
+    t, T = make_tuner(fmrx, R, N, n_wide, fmt=fmt)
     pitch = (2 * outputs + 15) // 16 * 16
     g = torch.Generator(device="cuda").manual_seed(R * 100003 + N)
-    d_wide = torch.randint(0, 256, (2 * n_wide,), dtype=torch.uint8, device="cuda", generator=g)
+    d_wide = random_wide(torch, fmt, n_wide, -1.0, 1.0, g)
     d_out = torch.zeros(N * pitch, dtype=torch.uint8, device="cuda")
     stream = torch.cuda.Stream()
     torch.cuda.synchronize()
@@ -73,9 +86,9 @@ def time_config(fmrx, torch, R, N, outputs, calls, warmup):
     med = statistics.median(ms) * 1e-3
     out_bytes = 2.0 * N * outputs
     ops = 16.0 * T * N * outputs
-    issued = shape_ksteps(T, R) * (16 * 16 * 64 * 2) * ((N + 3) // 4) * ((outputs + 127) // 128)
+    issued = shape_ksteps(T, R) * (16 * 16 * 64 * 2) * ((N + 3) // 4) * ((outputs + 127) // 128) * (2 if fmt == "s16" else 1)
     t_hbm, t_mm = out_bytes / HBM_PEAK, ops / INT8_PEAK
-    res = dict(R=R, T=T, channels=N, outputs=outputs, calls=calls, ms_median=med * 1e3, ms_min=ms[0], ms_max=ms[-1],
+    res = dict(format=fmt, R=R, T=T, channels=N, outputs=outputs, calls=calls, ms_median=med * 1e3, ms_min=ms[0], ms_max=ms[-1],
                wide_MS_s=n_wide / med / 1e6, x_real_time=(outputs / RF_FS) / med, out_GB_s=out_bytes / med / 1e9,
                hbm_share=out_bytes / med / HBM_PEAK, int8_Top_s=ops / med / 1e12, int8_share=ops / med / INT8_PEAK,
                issued_Top_s=issued / med / 1e12, bound="HBM writes" if t_hbm >= t_mm else "int8 matrix",
@@ -85,16 +98,16 @@ def time_config(fmrx, torch, R, N, outputs, calls, warmup):
     return res
 
 
-def time_chain(fmrx, torch, N, calls, warmup):
+def time_chain(fmrx, torch, N, calls, warmup, fmt="u8"):
     R, bb = 8, 192000
     outputs = bb // 2
     n_wide = outputs * R
-    t, T = make_tuner(fmrx, R, N, n_wide)
+    t, T = make_tuner(fmrx, R, N, n_wide, fmt=fmt)
     bank = fmrx.Channels(0, N, audio_channels=2, exact=True, block_bytes=bb)
     rds = fmrx.RdsBank(0, N, bb // 20)
     rds.set_stations(True)
     g = torch.Generator(device="cuda").manual_seed(7)
-    d_wide = torch.randint(96, 160, (2 * n_wide,), dtype=torch.uint8, device="cuda", generator=g)
+    d_wide = random_wide(torch, fmt, n_wide, -0.25, 0.25, g)
     d_audio = torch.zeros(N * 2 * bank.n_audio, dtype=torch.float32, device="cuda")
     d_pcm = torch.zeros(N * 2 * bank.n_audio, dtype=torch.int16, device="cuda")
     stream = torch.cuda.Stream()
@@ -121,7 +134,7 @@ def time_chain(fmrx, torch, N, calls, warmup):
     total = sum(med.values())
     for x in (t, bank, rds):
         x.close()
-    return dict(channels=N, R=R, T=T, block_bytes=bb, signal_ms=outputs / RF_FS * 1e3, ms=med, total_ms=total,
+    return dict(format=fmt, channels=N, R=R, T=T, block_bytes=bb, signal_ms=outputs / RF_FS * 1e3, ms=med, total_ms=total,
                 tuner_share=med["tuner"] / total)
 
 
@@ -134,6 +147,7 @@ def main() -> int:
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--variant", default="mfma")
+    ap.add_argument("--format", default="u8", choices=sorted(TORCH_DTYPE))
     ap.add_argument("--chain", type=int, default=192)
     ap.add_argument("--once", type=int, default=0)
     ap.add_argument("--json", default=None)
@@ -144,22 +158,22 @@ def main() -> int:
         print("tuner_bench: no GPU; nothing is measured without one", file=sys.stderr)
         return 1
     fmrx.set_option("tuner_variant", a.variant)
-    out = {"version": fmrx.version(), "variant": a.variant, "configs": []}
+    out = {"version": fmrx.version(), "variant": a.variant, "format": a.format, "configs": []}
     if a.once:
         configs = [(a.R, a.once)]
     else:
         configs = [(a.R, int(n)) for n in a.channels.split(",") if n] + [(int(r), 192) for r in a.also_R.split(",") if r]
     for R, N in configs:
-        r = time_config(fmrx, torch, R, N, a.outputs, a.calls, a.warmup)
+        r = time_config(fmrx, torch, R, N, a.outputs, a.calls, a.warmup, a.format)
         out["configs"].append(r)
-        print(f"R={R:2d} T={r['T']:3d} N={N:5d}: {r['ms_median']:8.4f} ms/call (min {r['ms_min']:.4f}, max {r['ms_max']:.4f}), "
+        print(f"{a.format:>3s} R={R:2d} T={r['T']:3d} N={N:5d}: {r['ms_median']:8.4f} ms/call (min {r['ms_min']:.4f}, max {r['ms_max']:.4f}), "
               f"{r['wide_MS_s']:9.0f} wide MS/s, {r['x_real_time']:8.1f} x real time, out {r['out_GB_s']:7.1f} GB/s "
               f"({100 * r['hbm_share']:.1f} % of HBM peak), int8 {r['int8_Top_s']:7.1f} Top/s useful ({100 * r['int8_share']:.1f} % of peak; "
               f"issued {r['issued_Top_s']:.1f}), nearer roof: {r['bound']} ({100 * r['roof_share']:.1f} %)", flush=True)
     if a.chain and not a.once:
-        c = time_chain(fmrx, torch, a.chain, max(a.calls // 2, 5), a.warmup)
+        c = time_chain(fmrx, torch, a.chain, max(a.calls // 2, 5), a.warmup, a.format)
         out["chain"] = c
-        print(f"chain, N={c['channels']}, one {c['block_bytes']}-byte block ({c['signal_ms']:.1f} ms of signal): tuner {c['ms']['tuner']:.3f} ms, "
+        print(f"chain, {a.format}, N={c['channels']}, one {c['block_bytes']}-byte block ({c['signal_ms']:.1f} ms of signal): tuner {c['ms']['tuner']:.3f} ms, "
               f"exact stereo bank {c['ms']['bank']:.3f} ms, RDS bank {c['ms']['rds_bank']:.3f} ms; tuner share {100 * c['tuner_share']:.1f} %", flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)

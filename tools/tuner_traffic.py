@@ -4,8 +4,8 @@
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d DIR/fetch -- python3 tools/tuner_bench.py --once 192 --calls 3 --warmup 1
     python3 tools/tuner_traffic.py DIR [--channels 192] [--R 8] [--outputs 51200] [--json out.json]
 
-Per dispatch of tuner_mfma_kernel: WRITE_SIZE (KiB; exact on gfx950, profiles/fe_traffic.json) over the output bytes
-2 N n_wide / R, and FETCH_SIZE over the 2 n_wide input bytes (as counted, and times the 2 that file describes for wide
+Per dispatch of tuner_mfma_kernel (--kernel tuner_mfma_s16_kernel --sample-bytes 4 for a run with --format s16): WRITE_SIZE (KiB; exact on gfx950, profiles/fe_traffic.json) over the output bytes
+2 N n_wide / R, and FETCH_SIZE over the sample-bytes * n_wide input bytes (as counted, and times the 2 that file describes for wide
 coalesced reads)."""
 import argparse
 import csv
@@ -28,9 +28,10 @@ def main() -> int:
     ap.add_argument("--R", type=int, default=8)
     ap.add_argument("--outputs", type=int, default=51200)
     ap.add_argument("--kernel", default="tuner_mfma_kernel")
+    ap.add_argument("--sample-bytes", type=int, default=2)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
-    out_bytes, in_bytes = 2 * a.channels * a.outputs, 2 * a.outputs * a.R
+    out_bytes, in_bytes = 2 * a.channels * a.outputs, a.sample_bytes * a.outputs * a.R
     w, f = counter(f"{a.dir}/write", "WRITE_SIZE", a.kernel), counter(f"{a.dir}/fetch", "FETCH_SIZE", a.kernel)
     if not w or not f:
         print(f"tuner_traffic: no {a.kernel} dispatches under {a.dir}", file=sys.stderr)
