@@ -37,9 +37,9 @@ struct fmrx_channels {
     DevBuf<float> zeros, audio_all;
     DevBuf<int16_t> pcm_all, pcm_out;
     DevBuf<float> f32_out;
-    // banks in the reference's evaluation order, and every stereo bank: channels_stereo.hip
+    // banks in the reference's evaluation order, and every stereo bank: bank.hip
     int audio_channels = 1, exact = 0;
-    StereoBank *bank = nullptr;
+    Bank *bank = nullptr;
 };
 
 namespace {
@@ -80,6 +80,69 @@ __global__ void channels_finish_kernel(uint8_t *__restrict__ slots, long slot_by
         for (long i = threadIdx.x; i < hist_bytes / 16; i += blockDim.x) dst[i] = src[i];
 }
 
+// the block region of the first slot, and the slots' pitch: where a call's input goes
+void slots_layout(const fmrx_channels *c, uint8_t **first, size_t *pitch)
+{
+    if (c->bank) return bank_input_layout(c->bank, first, pitch);
+    *first = c->slots.p + c->hist_bytes;
+    *pitch = c->slot_bytes;
+}
+
+// channel-major array [n_channels][block_bytes] -> the block region of every slot: one strided copy
+int load_slots(fmrx_channels *c, const uint8_t *iq, hipMemcpyKind kind, hipStream_t s)
+{
+    uint8_t *first;
+    size_t pitch;
+    slots_layout(c, &first, &pitch);
+    FMRX_HIP(hipMemcpy2DAsync(first, pitch, iq, c->block_bytes, c->block_bytes, c->n_channels, kind, s));
+    return FMRX_OK;
+}
+
+// mono, fast, modes 0/1: the slots of all channels as one pseudo-stream through the fused mono kernel
+int create_fused(fmrx_channels *c, size_t unit)
+{
+    const fmrx_params *p = &c->p;
+    const Filters f = design_filters(*p, false);
+    FMRX_TRY(fe_plan_init(c->fe, f.rf.data(), p->rf_taps, p->rf_decim));
+    FMRX_TRY(audio_plan_init(c->audio, f.audio.data(), p->audio_taps, p->audio_decim));
+    // samples an audio output reaches back: rf_decim*audio_taps + rf_taps - 1, plus what the kernel's tiles read in
+    // front of a run (one IF sample for the discriminator, 16-byte rounding): rounded up to whole audio samples
+    // and 16-byte multiples
+    const size_t reach = static_cast<size_t>(p->rf_decim) * (p->audio_taps + 1) + p->rf_taps + 8 * p->rf_decim;
+    size_t hs = (reach * 2 + unit - 1) / unit * unit;
+    while (hs % 16) hs += unit;
+    c->hist_bytes = hs;
+    if (c->block_bytes < hs) return fail(FMRX_EINVAL, "channels_create: block_bytes %zu < the %zu bytes of history a channel carries", c->block_bytes, hs);
+    c->slot_bytes = hs + c->block_bytes;
+    c->n_audio = c->block_bytes / unit;
+    c->junk_audio = hs / unit;
+    const size_t total = c->slot_bytes * c->n_channels;
+    if (!mono_fused_available(c->fe, c->audio, reinterpret_cast<const uint8_t *>(16), total / 2, reinterpret_cast<const uint8_t *>(16)))
+        return fail(FMRX_EINVAL, "channels_create: no fused mono kernel for rf_taps %d / decim %d / audio_taps %d / decim %d",
+                    p->rf_taps, p->rf_decim, p->audio_taps, p->audio_decim);
+    FMRX_TRY(c->slots.alloc(total + 64));
+    FMRX_TRY(k_fill_u8(c->slots.p, total + 64, 128, nullptr));                        // silence: the state of a stream that starts here
+    FMRX_TRY(c->zeros.alloc(p->audio_taps + 64));
+    FMRX_HIP(hipMemset(c->zeros.p, 0, (p->audio_taps + 64) * sizeof(float)));
+    const size_t all = total / unit;
+    FMRX_TRY(c->audio_all.alloc(all + 16));
+    FMRX_TRY(c->pcm_all.alloc(all + 16));
+    FMRX_HIP(hipDeviceSynchronize());
+    return FMRX_OK;
+}
+
+// either kind of bank, then what both have: the stream and the device-side outputs of the host-array entry point
+int create_body(fmrx_channels *c, bool fused, size_t unit)
+{
+    if (fused) FMRX_TRY(create_fused(c, unit));
+    else FMRX_TRY(bank_create(&c->bank, c->p, c->n_channels, c->audio_channels, c->exact, c->block_bytes));
+    if (c->bank) c->n_audio = bank_n_audio(c->bank);
+    FMRX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    FMRX_TRY(c->pcm_out.alloc(c->n_audio * c->n_channels * c->audio_channels));
+    FMRX_TRY(c->f32_out.alloc(c->n_audio * c->n_channels * c->audio_channels));
+    return FMRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -95,40 +158,11 @@ int fmrx_channels_create_ex(fmrx_channels **out, const fmrx_params *p, int n_cha
     if (!out || !p) return fail(FMRX_EINVAL, "channels_create: null argument");
     if (n_channels < 1) return fail(FMRX_EINVAL, "channels_create: n_channels must be >= 1");
     if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "channels_create: audio_channels must be 1 (mono) or 2 (stereo)");
-    if (audio_channels == 2 || exact || p->audio_upsamp != 0) {   // (mono, fast, modes 0/1: the fused-kernel bank below)
-        // integer-decimation modes: whole audio samples; resampling modes: the finer rule (n_if * U % D == 0) is checked by the bank
-        const size_t unit4 = static_cast<size_t>(2) * p->rf_decim * (p->audio_upsamp ? 1 : p->audio_decim);
-        if (block_bytes == 0 || block_bytes % unit4 || block_bytes % 16)
-            return fail(FMRX_EINVAL, "channels_create: block_bytes must be a multiple of 16 and of %zu", unit4);
-        FMRX_TRY(require_device());
-        FMRX_HIP(hipSetDevice(device));
-        fmrx_channels *c = new fmrx_channels;
-        c->p = *p;
-        c->n_channels = n_channels;
-        c->device = device;
-        c->block_bytes = block_bytes;
-        c->audio_channels = audio_channels;
-        c->exact = exact ? 1 : 0;
-        c->opt = options_snapshot();
-        auto body = [&]() -> int {
-            FMRX_TRY(stereo_bank_create(&c->bank, *p, n_channels, audio_channels, c->exact, block_bytes));
-            c->n_audio = stereo_bank_n_audio(c->bank);
-            FMRX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-            FMRX_TRY(c->pcm_out.alloc(c->n_audio * n_channels * audio_channels));
-            FMRX_TRY(c->f32_out.alloc(c->n_audio * n_channels * audio_channels));
-            return FMRX_OK;
-        };
-        const int rc = body();
-        if (rc != FMRX_OK) {
-            fmrx_channels_destroy(c);
-            return rc;
-        }
-        *out = c;
-        return FMRX_OK;
-    }
-    const size_t unit = static_cast<size_t>(2) * p->rf_decim * p->audio_decim;
+    const bool fused = audio_channels == 1 && !exact && p->audio_upsamp == 0;   // mono, fast, modes 0/1; every other bank: bank.hip
+    // integer-decimation modes: whole audio samples; resampling modes: the finer rule (n_if * U % D == 0) is checked by the bank
+    const size_t unit = static_cast<size_t>(2) * p->rf_decim * (p->audio_upsamp ? 1 : p->audio_decim);
     if (block_bytes == 0 || block_bytes % unit || block_bytes % 16)
-        return fail(FMRX_EINVAL, "channels_create: block_bytes must be a multiple of 16 and of 2*rf_decim*audio_decim = %zu", unit);
+        return fail(FMRX_EINVAL, "channels_create: block_bytes must be a multiple of 16 and of %zu", unit);
     FMRX_TRY(require_device());
     FMRX_HIP(hipSetDevice(device));
     fmrx_channels *c = new fmrx_channels;
@@ -136,40 +170,10 @@ int fmrx_channels_create_ex(fmrx_channels **out, const fmrx_params *p, int n_cha
     c->n_channels = n_channels;
     c->device = device;
     c->block_bytes = block_bytes;
+    c->audio_channels = audio_channels;
+    c->exact = exact ? 1 : 0;
     c->opt = options_snapshot();
-    auto body = [&]() -> int {
-        const Filters f = design_filters(*p, false);
-        FMRX_TRY(fe_plan_init(c->fe, f.rf.data(), p->rf_taps, p->rf_decim));
-        FMRX_TRY(audio_plan_init(c->audio, f.audio.data(), p->audio_taps, p->audio_decim));
-        // samples an audio output reaches back: rf_decim*audio_taps + rf_taps - 1, plus what the kernel's tiles read in
-        // front of a run (one IF sample for the discriminator, 16-byte rounding): rounded up to whole audio samples
-        // and 16-byte multiples
-        const size_t reach = static_cast<size_t>(p->rf_decim) * (p->audio_taps + 1) + p->rf_taps + 8 * p->rf_decim;
-        size_t hs = (reach * 2 + unit - 1) / unit * unit;
-        while (hs % 16) hs += unit;
-        c->hist_bytes = hs;
-        if (block_bytes < hs) return fail(FMRX_EINVAL, "channels_create: block_bytes %zu < the %zu bytes of history a channel carries", block_bytes, hs);
-        c->slot_bytes = hs + block_bytes;
-        c->n_audio = block_bytes / unit;
-        c->junk_audio = hs / unit;
-        const size_t total = c->slot_bytes * n_channels;
-        if (!mono_fused_available(c->fe, c->audio, reinterpret_cast<const uint8_t *>(16), total / 2, reinterpret_cast<const uint8_t *>(16)))
-            return fail(FMRX_EINVAL, "channels_create: no fused mono kernel for rf_taps %d / decim %d / audio_taps %d / decim %d",
-                        p->rf_taps, p->rf_decim, p->audio_taps, p->audio_decim);
-        FMRX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        FMRX_TRY(c->slots.alloc(total + 64));
-        FMRX_TRY(k_fill_u8(c->slots.p, total + 64, 128, nullptr));                        // silence: the state of a stream that starts here
-        FMRX_TRY(c->zeros.alloc(p->audio_taps + 64));
-        FMRX_HIP(hipMemset(c->zeros.p, 0, (p->audio_taps + 64) * sizeof(float)));
-        const size_t all = total / unit;
-        FMRX_TRY(c->audio_all.alloc(all + 16));
-        FMRX_TRY(c->pcm_all.alloc(all + 16));
-        FMRX_TRY(c->pcm_out.alloc(c->n_audio * n_channels));
-        FMRX_TRY(c->f32_out.alloc(c->n_audio * n_channels));
-        FMRX_HIP(hipDeviceSynchronize());
-        return FMRX_OK;
-    };
-    const int rc = body();
+    const int rc = create_body(c, fused, unit);
     if (rc != FMRX_OK) {
         fmrx_channels_destroy(c);
         return rc;
@@ -188,7 +192,7 @@ int fmrx_channels_destroy(fmrx_channels *c)
     }
     if (c->bank) {
         (void)hipDeviceSynchronize();
-        stereo_bank_destroy(c->bank);
+        bank_destroy(c->bank);
     }
     delete c;
     return FMRX_OK;
@@ -199,13 +203,7 @@ size_t fmrx_channels_n_audio(const fmrx_channels *c) { return c ? c->n_audio : 0
 int fmrx_channels_input_layout(const fmrx_channels *c, uint8_t **d_first_block, size_t *pitch_bytes)
 {
     if (!c || !d_first_block || !pitch_bytes) return fail(FMRX_EINVAL, "channels_input_layout: null argument");
-    if (c->bank) {
-        *d_first_block = stereo_bank_first_block(c->bank);
-        *pitch_bytes = stereo_bank_pitch(c->bank);
-        return FMRX_OK;
-    }
-    *d_first_block = c->slots.p + c->hist_bytes;
-    *pitch_bytes = c->slot_bytes;
+    slots_layout(c, d_first_block, pitch_bytes);
     return FMRX_OK;
 }
 
@@ -213,7 +211,7 @@ int fmrx_channels_demod_layout(const fmrx_channels *c, const float **d_row0, siz
 {
     if (!c || !d_row0 || !pitch || !n_if) return fail(FMRX_EINVAL, "channels_demod_layout: null argument");
     if (!c->bank) return fail(FMRX_EINVAL, "channels_demod_layout: the fused mono bank of modes 0/1 keeps no discriminator rows");
-    stereo_bank_demod_layout(c->bank, d_row0, pitch, n_if);
+    bank_demod_layout(c->bank, d_row0, pitch, n_if);
     return FMRX_OK;
 }
 
@@ -222,7 +220,7 @@ int fmrx_channels_reset(fmrx_channels *c, int channel)
     if (!c) return fail(FMRX_EINVAL, "channels_reset: null handle");
     if (channel >= c->n_channels) return fail(FMRX_EINVAL, "channels_reset: channel %d of %d", channel, c->n_channels);
     FMRX_HIP(hipSetDevice(c->device));
-    if (c->bank) return stereo_bank_reset(c->bank, channel);
+    if (c->bank) return bank_reset(c->bank, channel);
     FMRX_HIP(hipDeviceSynchronize());
     if (channel < 0) return k_fill_u8(c->slots.p, c->slot_bytes * c->n_channels, 128, nullptr);
     return k_fill_u8(c->slots.p + static_cast<size_t>(channel) * c->slot_bytes, c->hist_bytes, 128, nullptr);
@@ -233,7 +231,7 @@ int fmrx_channels_process_dev(fmrx_channels *c, float *d_audio_f32, int16_t *d_p
     if (!c) return fail(FMRX_EINVAL, "channels_process_dev: null handle");
     FMRX_HIP(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->bank) return stereo_bank_process_dev(c->bank, d_audio_f32, d_pcm16, pcm_policy, s);
+    if (c->bank) return bank_process_dev(c->bank, d_audio_f32, d_pcm16, pcm_policy, s);
     const size_t total = c->slot_bytes * c->n_channels;
     const float *zend = c->zeros.p + c->p.audio_taps + 32;     // "one past the previous block's last discriminator sample": zeros
     FMRX_TRY(mono_fused_launch(c->fe, c->audio, c->slots.p, total / 2, c->fe.silence.p, c->zeros.p, zend, nullptr, 0, nullptr,
@@ -253,15 +251,7 @@ int fmrx_channels_load_dev(fmrx_channels *c, const uint8_t *d_iq, void *stream)
 {
     if (!c || !d_iq) return fail(FMRX_EINVAL, "channels_load_dev: null argument");
     FMRX_HIP(hipSetDevice(c->device));
-    uint8_t *first = c->slots.p + c->hist_bytes;
-    size_t pitch = c->slot_bytes;
-    if (c->bank) {
-        first = stereo_bank_first_block(c->bank);
-        pitch = stereo_bank_pitch(c->bank);
-    }
-    FMRX_HIP(hipMemcpy2DAsync(first, pitch, d_iq, c->block_bytes, c->block_bytes, c->n_channels, hipMemcpyDeviceToDevice,
-                              static_cast<hipStream_t>(stream)));
-    return FMRX_OK;
+    return load_slots(c, d_iq, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
 }
 
 int fmrx_channels_process(fmrx_channels *c, const uint8_t *iq, float *audio_f32, int16_t *pcm16, int pcm_policy)
@@ -269,14 +259,7 @@ int fmrx_channels_process(fmrx_channels *c, const uint8_t *iq, float *audio_f32,
     if (!c || !iq) return fail(FMRX_EINVAL, "channels_process: null argument");
     FMRX_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    // channel-major host array [n_channels][block_bytes] -> the block region of every slot: one strided copy
-    uint8_t *first = c->slots.p + c->hist_bytes;
-    size_t pitch = c->slot_bytes;
-    if (c->bank) {
-        first = stereo_bank_first_block(c->bank);
-        pitch = stereo_bank_pitch(c->bank);
-    }
-    FMRX_HIP(hipMemcpy2DAsync(first, pitch, iq, c->block_bytes, c->block_bytes, c->n_channels, hipMemcpyHostToDevice, s));
+    FMRX_TRY(load_slots(c, iq, hipMemcpyHostToDevice, s));
     FMRX_TRY(fmrx_channels_process_dev(c, audio_f32 ? c->f32_out.p : nullptr, pcm16 ? c->pcm_out.p : nullptr, pcm_policy, s));
     const size_t n = c->n_audio * c->n_channels * c->audio_channels;
     if (audio_f32) FMRX_HIP(hipMemcpyAsync(audio_f32, c->f32_out.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -290,7 +273,7 @@ int fmrx_channels_read_tap(fmrx_channels *c, int channel, int which, float *out,
     if (!c || !n) return fail(FMRX_EINVAL, "channels_read_tap: null argument");
     if (!c->bank) return fail(FMRX_EINVAL, "channels_read_tap: the fused mono bank of modes 0/1 keeps no intermediates in memory (stereo, exact and resampling-mode banks do)");
     FMRX_HIP(hipSetDevice(c->device));
-    return stereo_bank_read_tap(c->bank, channel, which, out, n);
+    return bank_read_tap(c->bank, channel, which, out, n);
 }
 
 }  // extern "C"

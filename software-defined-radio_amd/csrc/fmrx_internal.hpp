@@ -125,7 +125,7 @@ int fe_mfma_launch(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, cons
                    float *d_demod, float *d_if, float *d_prev_out, uint8_t *d_hist_next, const Options &o, hipStream_t stream,
                    const float *d_dhist_src = nullptr, float *d_dhist_dst = nullptr, int dhist_n = 0);
 // (d_dhist_src -> d_dhist_dst, dhist_n floats: the discriminator history copied in front of this block's output by the kernel itself)
-// the same kernel over a bank of receivers' slots (channels_stereo.hip): see kernels_fe_mfma.hip
+// the same kernel over a bank of receivers' slots (bank.hip): see kernels_fe_mfma.hip
 int fe_mfma_bank_lead(const FePlan &pl);   // bytes of the stream a row needs in front of its block
 int fe_mfma_bank_launch(const FePlan &pl, const uint8_t *d_slots, long total_bytes, long in_pitch, long block_off, int n_channels,
                         long k_lo, long k_hi, float *d_demod, long out_pitch, long out_off, hipStream_t stream);
@@ -295,18 +295,16 @@ int k_stream_read(const void *d_buf, size_t bytes, int method, unsigned *d_sink,
 // d_seg_db: (n/nfft)*(nfft/2) floats of scratch; d_freq, d_psd: nfft/2 floats
 int k_estimate_psd(const float *d_x, size_t n, float Fs, int nfft, float *d_seg_db, float *d_freq, float *d_psd, hipStream_t s);
 
-// ---- banks of receivers in the reference's evaluation order (channels_stereo.hip) ----
-struct StereoBank;
-bool stereo_bank_supported(const fmrx_params &p, int audio_channels);
-int stereo_bank_create(StereoBank **out, const fmrx_params &p, int n_channels, int audio_channels, int exact, size_t block_bytes);
-void stereo_bank_destroy(StereoBank *b);
-size_t stereo_bank_n_audio(const StereoBank *b);
-uint8_t *stereo_bank_first_block(const StereoBank *b);
-size_t stereo_bank_pitch(const StereoBank *b);
-void stereo_bank_demod_layout(const StereoBank *b, const float **d_row0, size_t *pitch, size_t *n_if);
-int stereo_bank_reset(StereoBank *b, int channel);
-int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStream_t s);
-int stereo_bank_read_tap(StereoBank *b, int channel, int which, float *out, size_t *n);
+// ---- banks of receivers: every stereo bank, the exact mono banks, the fast mono banks of modes 2 / 3 (bank.hip, kernels_bank.hip) ----
+struct Bank;
+int bank_create(Bank **out, const fmrx_params &p, int n_channels, int audio_channels, int exact, size_t block_bytes);
+void bank_destroy(Bank *b);
+size_t bank_n_audio(const Bank *b);
+void bank_input_layout(const Bank *b, uint8_t **d_first_block, size_t *pitch_bytes);
+void bank_demod_layout(const Bank *b, const float **d_row0, size_t *pitch, size_t *n_if);
+int bank_reset(Bank *b, int channel);
+int bank_process_dev(Bank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStream_t s);
+int bank_read_tap(Bank *b, int channel, int which, float *out, size_t *n);
 
 // ---- host-side coefficient design (coeff.cpp) --------------------------------
 void design_lpf(float Fs, float Fc, int taps, float *h);

@@ -1,5 +1,5 @@
-// channels_stereo.hip -- N independent STEREO receivers per device call (include/fmrx.h: fmrx_channels_create_ex,
-// audio_channels = 2), and the bit-exact form of the mono bank.
+// kernels_bank.hip -- the kernels of a receiver bank (bank.hip: every stereo bank, the bit-exact mono banks and the fast mono banks of
+// modes 2 and 3), the host-side builders of their tap tables, their launchers, and the resolver from a bank's shapes to those.
 //
 // The reference runs one receiver per process (one PARAMS / STATES set, src/project.cpp:455-468); its stereo
 // thread body RF_STEREO (src/project.cpp:154-309) is, per block of fm_demod:
@@ -32,8 +32,10 @@
 //   carrier, bpf, trig f32 [n_channels][n_if + pad]      pilot band-pass, 22-54 kHz band-pass, raw trigArg of every PLL step -> NCO output
 //   pll     f32 [n_channels][8]                          state_PLL (6), fast banks: the PLL's fr (slot 6) ; nco0 [n_channels] = PLL[0] of this call
 //   mixtail f32 [2][n_channels][Hm]                      state_stereofilt, ping-pong
+#include <type_traits>
+
+#include "bank_kernels.hpp"
 #include "device_math.hpp"
-#include "fmrx_internal.hpp"
 #include "glibc_libm.hpp"
 
 #pragma clang fp contract(off)
@@ -56,8 +58,6 @@ typedef uint32_t u4 __attribute__((ext_vector_type(4)));
         hipError_t e_ = hipGetLastError();                                                        \
         if (e_ != hipSuccess) return fail(FMRX_EHIP, "launch %s: %s", name, hipGetErrorString(e_)); \
     } while (0)
-
-constexpr int kR = 8;   // consecutive outputs per thread of the exact FIR kernels (= table entries per step)
 
 // ---- front end, reference order ------------------------------------------------------------------------------
 // Thread: outputs k0 .. k0+R-1 (I and Q in the two halves of v_pk_mul_f32 / v_pk_add_f32).  Window sample j
@@ -470,7 +470,7 @@ __global__ __launch_bounds__(64) void chs_out_kernel(const float *__restrict__ d
     const int t = threadIdx.x;
     const long c = blockIdx.x / wgs_per_channel;
     // this launch: audio outputs [a_lo, a_hi) of the block's n_out, from the IF samples [.., g_hi) that exist by now (a block is
-    // walked in chunks so that the PLL's lanes of one chunk run next to the wide kernels of the next: stereo_bank_process_dev)
+    // walked in chunks so that the PLL's lanes of one chunk run next to the wide kernels of the next: bank.hip, process_stereo)
     const long a0 = a_lo + (blockIdx.x % wgs_per_channel) * C::NOUT;
     const long g0 = D * a0 - (T - 1);                      // IF index of window sample 0
     const float *dm = demod + c * dpitch + Hd;
@@ -652,7 +652,7 @@ __global__ void chs_resample_exact_kernel(const float *__restrict__ demod, long 
 // Samples reach the lanes through LDS, 32 per channel and batch (below: why not lane = channel for the loads too); the taps of
 // four steps are two s_load_dwordx16, requested one iteration ahead.  Outside a group's window the table holds zeros: acc + 0*x
 // leaves acc as it is (acc is never -0: it starts at +0 and sums round to nearest), rows are finite, and the rows' histories
-// are long enough for the window's rounding up to whole batches (StereoBank::res_hist).  Against one thread per (channel,
+// are long enough for the window's rounding up to whole batches (Bank::res_hist).  Against one thread per (channel,
 // output) -- 101 gathered taps and 101-202 gathered samples per output, bound by the texture addressers -- 16 384 receivers x 4
 // blocks of mode 2: stereo 12 -> 3.2 ms per call, mono 9 -> 1.7 ms (bit-identical outputs).  What bounds it now is the traffic of
 // re-reading the windows: neighbouring groups' windows overlap (160 samples per 38 of advance), and 64 channels' windows of 2-3
@@ -849,82 +849,44 @@ __global__ void chs_fill_state_kernel(float *__restrict__ pll, long n)
 
 }  // namespace
 
-// ---- host side ---------------------------------------------------------------------------------------------------
-struct StereoBank {
-    fmrx_params p{};
-    int n_channels = 0, audio_channels = 2, exact = 1;
-    size_t block_bytes = 0, hist_bytes = 0, slot_bytes = 0;
-    long n = 0, n_if = 0, n_audio = 0;
-    int Ha = 0, delay = 0, Hd = 0, Hm = 0, St = 0;
-    long dpitch = 0, ypitch = 0;
-    DevBuf<uint8_t> slots;
-    DevBuf<float> fe_table, bpf_table, out_table;
-    FePlan fe;                      // fast banks: the matrix-core front end's tap image
-    Options opt;
-    DevBuf<float> demod, carrier, bpf, trig, pll, nco0, mixtail[2];
-    DevBuf<int8_t> carrier8;        // fast banks: the sign of the pilot band-pass output, one byte per IF sample
-    long cpitch = 0;
-    // resampling modes (2, 3): the plain audio taps and, stereo, the mixer rows [Hm | n_if]
-    bool resample = false;
-    DevBuf<float> h_res, mixer;
-    long mpitch = 0;
-    // ... and, when U is a multiple of 7 (both of the reference's), the step-major tap table of chs_resample_lanes_kernel
-    DevBuf<float> res_table;
-    DevBuf<int> res_top;
-    int res_groups = 0, res_iters = 0, res_hist = 0;   // res_hist: samples of history its windows reach (>= Ha, by the rounding to whole iterations)
-    int mix_cur = 0;
-    // A stereo call walks the block in chunks on two internal streams: `wide` carries the front end, the band-pass pair and the
-    // output stage of every chunk, `lanes` the PLL -- the PLL's few waves (one per 64 channels, a dependent chain each) leave
-    // the chip almost idle, and chunk c+1's wide kernels fill it meanwhile.  Events: chunk c's band-pass output is ready
-    // (wide -> lanes), its PLL is through (lanes -> wide); fork / join with the caller's stream around the call.
-    static constexpr int kMaxChunks = 8;
-    int max_chunks = kMaxChunks;
-    hipStream_t wide = nullptr, lanes = nullptr;
-    hipStream_t front = nullptr;    // fast banks: the HBM-bound front end runs on its own stream, next to the vector-ALU-bound kernels
-    hipEvent_t ev_bpf[kMaxChunks] = {}, ev_pll[kMaxChunks] = {}, ev_fe[kMaxChunks] = {}, ev_fork = nullptr, ev_join = nullptr;
-    ~StereoBank()
-    {
-        for (hipStream_t st : {wide, lanes, front})
-            if (st) {
-                (void)hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-        for (auto &e : ev_bpf)
-            if (e) (void)hipEventDestroy(e);
-        for (auto &e : ev_pll)
-            if (e) (void)hipEventDestroy(e);
-        for (auto &e : ev_fe)
-            if (e) (void)hipEventDestroy(e);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-    }
-};
-
+// ---- host side: tap tables, launchers, and the resolver from a bank's shapes to both ---------------------------------
 namespace {
 
-template <int T, int D>
-int fe_table_init(StereoBank &b, const float *h)
+int upload(DevBuf<float> &d, const std::vector<float> &tab)
 {
-    using C = FeX<T, D>;
+    FMRX_TRY(d.alloc(tab.size()));
+    FMRX_HIP(hipMemcpy(d.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    return FMRX_OK;
+}
+
+// The step-major table of fex_step / outx_step (C = FeX / OutX): step u visits window sample W-1-u, where output r meets
+// tap n = r D + (T-1) - (W-1-u); entry [u][r] = h[n] * scale, 0 where n is out of range; whole scalar loads of 16 entries.
+template <template <int, int> class C, int T, int D>
+std::vector<float> step_major_table(const float *h, float scale)
+{
+    using S = C<T, D>;
+    std::vector<float> tab(static_cast<size_t>(S::NG) * 16, 0.0f);
+    for (int u = 0; u < S::W; u++)
+        for (int r = 0; r < S::R; r++) {
+            const int n = r * D + (T - 1) - (S::W - 1 - u);
+            if (n >= 0 && n < T) tab[static_cast<size_t>(u) * S::R + r] = h[n] * scale;
+        }
+    return tab;
+}
+
+template <int T, int D>
+int fe_table_init(Bank &b, const float *h)
+{
     for (int n = 0; n < T; n++) {
         const float a = std::fabs(h[n]);
         if (a != 0.0f && !(a >= 7.8886091e-31f && a <= 1.2676506e30f))   // 2^-100 .. 2^100
             return fail(FMRX_EINVAL, "channels (exact): rf tap %d = %g is outside the range in which h/128 * (u-128) is the reference's product", n, h[n]);
     }
-    std::vector<float> tab(static_cast<size_t>(C::NG) * 16, 0.0f);
-    for (int u = 0; u < C::W; u++)
-        for (int r = 0; r < kR; r++) {
-            const int n = r * D + (T - 1) - (C::W - 1 - u);
-            if (n >= 0 && n < T) tab[static_cast<size_t>(u) * 8 + r] = h[n] * 0.0078125f;
-        }
-    FMRX_TRY(b.fe_table.alloc(tab.size()));
-    FMRX_HIP(hipMemcpy(b.fe_table.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    b.hist_bytes = C::HIST;
-    return FMRX_OK;
+    return upload(b.fe_table, step_major_table<FeX, T, D>(h, 0.0078125f));
 }
 
 template <int T>
-int bpf_table_init(StereoBank &b, const float *h_st, const float *h_car)
+int bpf_table_init(Bank &b, const float *h_st, const float *h_car)
 {
     using C = BpX<T>;
     // P[m] = (h_st, h_car)[m - (R-1)], zero outside the filter, in groups of eight pairs; two groups of padding behind the last block
@@ -937,82 +899,17 @@ int bpf_table_init(StereoBank &b, const float *h_st, const float *h_car)
             tab[2 * static_cast<size_t>(m) + 1] = h_car[n];
         }
     }
-    FMRX_TRY(b.bpf_table.alloc(tab.size()));
-    FMRX_HIP(hipMemcpy(b.bpf_table.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    return FMRX_OK;
+    return upload(b.bpf_table, tab);
 }
 
-#define CHS_FE_CASES(X) X(101, 10) X(101, 5) X(101, 3) X(151, 10) X(151, 5) X(151, 3) X(13, 10) X(13, 5) X(13, 3)
-#define CHS_BPF_CASES(X) X(101) X(151) X(13)
-#define CHS_OUT_CASES(X) X(101, 5) X(101, 6) X(13, 5) X(13, 6)
-
-// IF outputs [k_lo, k_hi) of every channel's block
-template <int T, int D>
-int launch_fe(const StereoBank &b, long k_lo, long k_hi, hipStream_t s)
-{
-    using C = FeX<T, D>;
-    const long ntiles = (k_hi - k_lo + C::TILE - 1) / C::TILE;
-    const long wgs = ntiles;
-    hipLaunchKernelGGL((chs_fe_exact_kernel<T, D>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.slots.p,
-                       static_cast<long>(b.slot_bytes), static_cast<int>(b.hist_bytes), k_lo, k_hi, ntiles, wgs, b.fe_table.p, b.demod.p,
-                       b.dpitch, b.Hd);
-    CHS_LAUNCH_CHECK("chs_fe_exact_kernel");
-    return FMRX_OK;
-}
-
-template <int T>
-int launch_bpf(const StereoBank &b, long k_lo, long k_hi, hipStream_t s)
-{
-    const long wgs = (k_hi - k_lo + 64 * kR - 1) / (64 * kR);
-    if (b.exact)
-        hipLaunchKernelGGL((chs_bpf_kernel<T, true>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p, b.dpitch,
-                           b.Hd, k_lo, k_hi, wgs, b.bpf_table.p, b.bpf.p, b.carrier.p, b.ypitch, nullptr, 0L);
-    else
-        hipLaunchKernelGGL((chs_bpf_kernel<T, false>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p, b.dpitch,
-                           b.Hd, k_lo, k_hi, wgs, b.bpf_table.p, b.bpf.p, nullptr, b.ypitch, b.carrier8.p, b.cpitch);
-    CHS_LAUNCH_CHECK("chs_bpf_kernel");
-    return FMRX_OK;
-}
-
-// audio outputs [a_lo, a_hi) of every channel's block, from the IF samples [.., g_hi)
-template <int T, int D, bool STEREO>
-int launch_out(StereoBank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo, long a_hi, long g_hi, hipStream_t s)
-{
-    using C = OutX<T, D>;
-    if ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (reinterpret_cast<uintptr_t>(d_pcm) % 16) || (STEREO && b.n_audio % 4))
-        return fail(FMRX_EINVAL, "channels: output buffers must be 16-byte aligned");
-    const long wgs = (a_hi - a_lo + C::NOUT - 1) / C::NOUT;
-    if (b.exact)
-        hipLaunchKernelGGL((chs_out_kernel<T, D, STEREO, true>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p,
-                           b.dpitch, b.Hd, b.bpf.p, b.trig.p, b.ypitch, b.nco0.p, b.mixtail[b.mix_cur].p, b.mixtail[b.mix_cur ^ 1].p, b.Hm,
-                           b.n_if, g_hi, b.delay, 2.0f, 0.0f, b.out_table.p, wgs, d_audio, d_pcm, wrap, a_lo, a_hi, b.n_audio);
-    else if constexpr (STEREO)
-        hipLaunchKernelGGL((chs_out_kernel<T, D, true, false>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p,
-                           b.dpitch, b.Hd, b.bpf.p, b.trig.p, b.ypitch, b.nco0.p, b.mixtail[b.mix_cur].p, b.mixtail[b.mix_cur ^ 1].p, b.Hm,
-                           b.n_if, g_hi, b.delay, 2.0f, 0.0f, b.out_table.p, wgs, d_audio, d_pcm, wrap, a_lo, a_hi, b.n_audio);
-    CHS_LAUNCH_CHECK("chs_out_kernel");
-    return FMRX_OK;
-}
-
-int launch_nco(const StereoBank &b, long k_lo, long k_hi, hipStream_t s)
-{
-    const long wgs = (k_hi - k_lo + 1023) / 1024;
-    if (b.exact)
-        hipLaunchKernelGGL(chs_nco_kernel<true>, dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(256), 0, s, b.trig.p, b.ypitch, k_lo, k_hi,
-                           wgs, 2.0f, 0.0f, b.bpf.p, b.nco0.p, b.resample ? b.mixer.p : nullptr, b.mpitch, b.Hm);
-    else
-        hipLaunchKernelGGL(chs_nco_kernel<false>, dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(256), 0, s, b.trig.p, b.ypitch, k_lo, k_hi,
-                           wgs, 2.0f, 0.0f, b.bpf.p, b.nco0.p, b.resample ? b.mixer.p : nullptr, b.mpitch, b.Hm);
-    CHS_LAUNCH_CHECK("chs_nco_kernel");
-    return FMRX_OK;
-}
-
+// The resampling modes' tables: the plain audio taps, and where the ratio allows it the
 // step-major taps of chs_resample_lanes_kernel: [group of the period][step][8] (7 outputs + pad), steps newest sample first,
 // rounded up to whole iterations of 4 (+ one iteration of zeros that the kernel's look-ahead reads); top_of[group] = the window's
 // newest sample relative to the period's first
-int resample_lanes_table_init(StereoBank &b, const float *h)
+int resample_table_init(Bank &b, const float *h)
 {
     const int U = b.p.audio_upsamp, D = b.p.audio_decim, T = b.p.audio_taps;
+    FMRX_TRY(upload(b.h_res, std::vector<float>(h, h + T)));
     if (U <= 0 || U % kRS) return FMRX_OK;                         // other ratios: the one-thread-per-output kernel
     const int G = U / kRS;
     std::vector<int> top(G), n_of(U), ph_of(U);
@@ -1042,8 +939,7 @@ int resample_lanes_table_init(StereoBank &b, const float *h)
                 const long n = static_cast<long>(ph_of[k]) + static_cast<long>(j) * U;
                 if (j >= 0 && n < T) tab[(static_cast<size_t>(g) * iters * 4 + st) * 8 + r] = h[n];
             }
-    FMRX_TRY(b.res_table.alloc(tab.size()));
-    FMRX_HIP(hipMemcpy(b.res_table.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    FMRX_TRY(upload(b.res_table, tab));
     FMRX_TRY(b.res_top.alloc(G));
     FMRX_HIP(hipMemcpy(b.res_top.p, top.data(), G * sizeof(int), hipMemcpyHostToDevice));
     b.res_groups = G;
@@ -1051,25 +947,61 @@ int resample_lanes_table_init(StereoBank &b, const float *h)
     return FMRX_OK;
 }
 
+#define CHS_FE_CASES(X) X(101, 10) X(101, 5) X(101, 3) X(151, 10) X(151, 5) X(151, 3) X(13, 10) X(13, 5) X(13, 3)
+#define CHS_BPF_CASES(X) X(101) X(151) X(13)
+#define CHS_OUT_CASES(X) X(101, 5) X(101, 6) X(13, 5) X(13, 6)
+
+// IF outputs [k_lo, k_hi) of every channel's block
 template <int T, int D>
-int out_table_init(StereoBank &b, const float *h)
+int launch_fe(const Bank &b, long k_lo, long k_hi, hipStream_t s)
+{
+    using C = FeX<T, D>;
+    const long ntiles = (k_hi - k_lo + C::TILE - 1) / C::TILE;   // one workgroup each
+    hipLaunchKernelGGL((chs_fe_exact_kernel<T, D>), dim3(static_cast<unsigned>(ntiles * b.n_channels)), dim3(64), 0, s, b.slots.p,
+                       static_cast<long>(b.slot_bytes), static_cast<int>(b.hist_bytes), k_lo, k_hi, ntiles, ntiles, b.fe_table.p, b.demod.p,
+                       b.dpitch, b.Hd);
+    CHS_LAUNCH_CHECK("chs_fe_exact_kernel");
+    return FMRX_OK;
+}
+
+// fast banks: the matrix-core front end (kernels_fe_mfma.hip) over the same slots and rows
+int launch_fe_mfma(const Bank &b, long k_lo, long k_hi, hipStream_t s)
+{
+    return fe_mfma_bank_launch(b.fe, b.slots.p, static_cast<long>(b.slots.n), static_cast<long>(b.slot_bytes),
+                               static_cast<long>(b.hist_bytes), b.n_channels, k_lo, k_hi, b.demod.p, b.dpitch, b.Hd, s);
+}
+
+// (the pilot band-pass output: exact banks keep the float row `carrier`, fast banks the sign row `carrier8`; the other is null)
+template <int T, bool EXACT>
+int launch_bpf(const Bank &b, long k_lo, long k_hi, hipStream_t s)
+{
+    const long wgs = (k_hi - k_lo + 64 * kR - 1) / (64 * kR);
+    hipLaunchKernelGGL((chs_bpf_kernel<T, EXACT>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p, b.dpitch,
+                       b.Hd, k_lo, k_hi, wgs, b.bpf_table.p, b.bpf.p, b.carrier.p, b.ypitch, b.carrier8.p, b.cpitch);
+    CHS_LAUNCH_CHECK("chs_bpf_kernel");
+    return FMRX_OK;
+}
+
+// audio outputs [a_lo, a_hi) of every channel's block, from the IF samples [.., g_hi)
+template <int T, int D, bool STEREO, bool EXACT>
+int launch_out(Bank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo, long a_hi, long g_hi, hipStream_t s)
 {
     using C = OutX<T, D>;
-    std::vector<float> tab(static_cast<size_t>(C::NG) * 16, 0.0f);
-    for (int u = 0; u < C::W; u++)
-        for (int r = 0; r < kRO; r++) {
-            const int n = r * D + (T - 1) - (C::W - 1 - u);
-            if (n >= 0 && n < T) tab[static_cast<size_t>(u) * kRO + r] = h[n];
-        }
-    FMRX_TRY(b.out_table.alloc(tab.size()));
-    FMRX_HIP(hipMemcpy(b.out_table.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    if ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (reinterpret_cast<uintptr_t>(d_pcm) % 16) || (STEREO && b.n_audio % 4))
+        return fail(FMRX_EINVAL, "channels: output buffers must be 16-byte aligned");
+    const long wgs = (a_hi - a_lo + C::NOUT - 1) / C::NOUT;
+    hipLaunchKernelGGL((chs_out_kernel<T, D, STEREO, EXACT>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p,
+                       b.dpitch, b.Hd, b.bpf.p, b.trig.p, b.ypitch, b.nco0.p, b.mixtail[b.mix_cur].p, b.mixtail[b.mix_cur ^ 1].p, b.Hm,
+                       b.n_if, g_hi, b.delay, kNcoScale, kPhaseAdjust, b.out_table.p, wgs, d_audio, d_pcm, wrap, a_lo, a_hi, b.n_audio);
+    CHS_LAUNCH_CHECK("chs_out_kernel");
     return FMRX_OK;
 }
 
 // convolveBlockResampleFIR for the audio outputs [a_lo, a_hi) of every channel (a_lo: a multiple of U): whole periods by the
-// lane-per-channel kernel when its table exists, what is left (and every other ratio) by one thread per (channel, output)
-template <bool STEREO>
-int launch_resample(StereoBank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo, long a_hi, hipStream_t s)
+// lane-per-channel kernel when its table exists, what is left (and every other ratio) by one thread per (channel, output).
+// (g_hi: the launchers' common signature; the mixer rows of this chunk were written by its NCO pass, bank_launch_nco)
+template <bool STEREO, bool EXACT>
+int launch_resample(Bank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo, long a_hi, long /*g_hi*/, hipStream_t s)
 {
     const fmrx_params &p = b.p;
     long done = a_lo;
@@ -1084,14 +1016,10 @@ int launch_resample(StereoBank &b, float *d_audio, int16_t *d_pcm, int wrap, lon
             while (gpw > NW && cgs * periods * ((b.res_groups + gpw - 1) / gpw) * NW < 8192) gpw = (gpw + 1) / 2;
             gpw = (gpw + NW - 1) / NW * NW;                        // every wave of a workgroup gets a group
             const long parts = (b.res_groups + gpw - 1) / gpw;
-            auto go = [&](auto exactc) {
-                hipLaunchKernelGGL((chs_resample_lanes_kernel<STEREO, decltype(exactc)::value>), dim3(static_cast<unsigned>(cgs * periods * parts)),
-                                   dim3(64 * kRW<STEREO>), 0, s, b.demod.p, b.dpitch, b.Hd, STEREO ? b.mixer.p : nullptr, b.mpitch, b.Hm, b.delay, b.res_table.p,
-                                   b.res_top.p, b.res_groups, gpw, b.res_iters, p.audio_decim, p.audio_upsamp, periods, b.n_channels, d_audio, d_pcm,
-                                   wrap, a_lo, b.n_audio);
-            };
-            if (b.exact) go(std::true_type{});
-            else go(std::false_type{});
+            hipLaunchKernelGGL((chs_resample_lanes_kernel<STEREO, EXACT>), dim3(static_cast<unsigned>(cgs * periods * parts)),
+                               dim3(64 * kRW<STEREO>), 0, s, b.demod.p, b.dpitch, b.Hd, STEREO ? b.mixer.p : nullptr, b.mpitch, b.Hm, b.delay, b.res_table.p,
+                               b.res_top.p, b.res_groups, gpw, b.res_iters, p.audio_decim, p.audio_upsamp, periods, b.n_channels, d_audio, d_pcm,
+                               wrap, a_lo, b.n_audio);
             CHS_LAUNCH_CHECK("chs_resample_lanes_kernel");
             done = a_lo + periods * p.audio_upsamp;
         }
@@ -1108,348 +1036,61 @@ int launch_resample(StereoBank &b, float *d_audio, int16_t *d_pcm, int wrap, lon
 
 }  // namespace
 
-bool stereo_bank_supported(const fmrx_params &p, int audio_channels)
+// The one place the shape lists are expanded.  Fast banks keep the exact front end's table and history (its tap-range check
+// and slot layout hold for them too) and launch the matrix-core front end; the fast mono bank of modes 0/1 has no output
+// stage here (it is the fused-kernel bank of channels.hip).
+bool bank_resolve(const fmrx_params &p, int audio_channels, int exact, BankKernels &k)
 {
-    bool fe = false, au = false, st = audio_channels == 1;
-#define X(T_, D_) if (p.rf_taps == T_ && p.rf_decim == D_) fe = true;
+    const bool stereo = audio_channels == 2;
+    k = BankKernels{};
+#define X(T_, D_) \
+    if (p.rf_taps == T_ && p.rf_decim == D_) { k.hist_bytes = FeX<T_, D_>::HIST; k.fe_table = fe_table_init<T_, D_>; k.fe = exact ? launch_fe<T_, D_> : launch_fe_mfma; }
     CHS_FE_CASES(X)
 #undef X
-#define X(T_, D_) if (p.audio_taps == T_ && p.audio_decim == D_) au = true;
-    CHS_OUT_CASES(X)
-#undef X
-#define X(T_) if (p.stereo_taps == T_) st = true;
+#define X(T_) if (stereo && p.stereo_taps == T_) { k.bpf_table = bpf_table_init<T_>; k.bpf = exact ? launch_bpf<T_, true> : launch_bpf<T_, false>; }
     CHS_BPF_CASES(X)
 #undef X
-    if (p.audio_upsamp > 0) au = p.audio_taps >= 2 && p.audio_taps <= 65535;   // resampling modes: the batched reference-order resampler takes any taps
-    return fe && au && st;
+#define X(T_, D_)                                                                                                        \
+    if (p.audio_upsamp == 0 && p.audio_taps == T_ && p.audio_decim == D_) {                                              \
+        k.out_table = [](Bank &b, const float *h) { return upload(b.out_table, step_major_table<OutX, T_, D_>(h, 1.0f)); };  \
+        k.out = stereo ? (exact ? launch_out<T_, D_, true, true> : launch_out<T_, D_, true, false>) : (exact ? launch_out<T_, D_, false, true> : nullptr); \
+    }
+    CHS_OUT_CASES(X)
+#undef X
+    if (p.audio_upsamp > 0 && p.audio_taps >= 2 && p.audio_taps <= 65535) {   // resampling modes: the batched reference-order resampler takes any taps
+        k.out_table = resample_table_init;
+        k.out = stereo ? (exact ? launch_resample<true, true> : launch_resample<true, false>) : (exact ? launch_resample<false, true> : launch_resample<false, false>);
+    }
+    return k.fe && k.out && (!stereo || k.bpf);
 }
 
-void stereo_bank_destroy(StereoBank *b) { delete b; }
-
-int stereo_bank_create(StereoBank **out, const fmrx_params &p, int n_channels, int audio_channels, int exact, size_t block_bytes)
+int bank_launch_nco(bool exact, float *trig, long ypitch, int n_rows, long k_lo, long k_hi, const float *bpf, const float *nco0,
+                    float *mixer, long mpitch, int hm, hipStream_t s)
 {
-    if (!exact && audio_channels != 2 && p.audio_upsamp == 0)
-        return fail(FMRX_EINVAL, "channels: the fast mono bank of the integer-decimation modes is fmrx_channels_create's");
-    if (!stereo_bank_supported(p, audio_channels))
-        return fail(FMRX_EINVAL, "channels (exact): no reference-order kernels for rf %d/%d, audio %d/%d, stereo %d taps (modes 0 and 1 of the "
-                    "reference's tap sets are covered)", p.rf_taps, p.rf_decim, p.audio_taps, p.audio_decim, p.stereo_taps);
-    StereoBank *b = new StereoBank;
-    b->p = p;
-    b->n_channels = n_channels;
-    b->audio_channels = audio_channels;
-    b->exact = exact ? 1 : 0;
-    b->opt = options_snapshot();
-    b->block_bytes = block_bytes;
-    auto body = [&]() -> int {
-        const Filters f = design_filters(p, audio_channels == 2);
-#define X(T_, D_) if (p.rf_taps == T_ && p.rf_decim == D_) FMRX_TRY((fe_table_init<T_, D_>(*b, f.rf.data())));
-        CHS_FE_CASES(X)
-#undef X
-        if (!b->exact) {   // the matrix-core front end (int8 MFMA on the raw bytes): its tap image, and the history its windows reach
-            FMRX_TRY(fe_plan_init(b->fe, f.rf.data(), p.rf_taps, p.rf_decim));
-            const int lead = fe_mfma_bank_lead(b->fe);
-            if (!b->fe.mfma || lead < 0) return fail(FMRX_EINVAL, "channels: no matrix-core front end for rf %d taps / decim %d", p.rf_taps, p.rf_decim);
-            const size_t need = (static_cast<size_t>(lead) + 15) / 16 * 16;
-            if (need > b->hist_bytes) b->hist_bytes = need;
-        }
-        b->resample = p.audio_upsamp > 0;
-        if (b->resample) {
-            FMRX_TRY(b->h_res.alloc(p.audio_taps));
-            FMRX_HIP(hipMemcpy(b->h_res.p, f.audio.data(), p.audio_taps * sizeof(float), hipMemcpyHostToDevice));
-            FMRX_TRY(resample_lanes_table_init(*b, f.audio.data()));
-        } else {
-#define X(T_, D_) if (p.audio_taps == T_ && p.audio_decim == D_) FMRX_TRY((out_table_init<T_, D_>(*b, f.audio.data())));
-            CHS_OUT_CASES(X)
-#undef X
-        }
-        b->n = static_cast<long>(block_bytes / 2);
-        b->n_if = b->n / p.rf_decim;
-        b->n_audio = b->resample ? b->n_if * p.audio_upsamp / p.audio_decim : b->n_if / p.audio_decim;
-        if (b->resample && (b->n_if * p.audio_upsamp) % p.audio_decim)
-            return fail(FMRX_EINVAL, "channels: n_if * upsamp = %ld is not a multiple of audio_decim %d (a block must end on an output boundary)",
-                        b->n_if * p.audio_upsamp, p.audio_decim);
-        b->Ha = b->resample ? (p.audio_taps - 1) / p.audio_upsamp : p.audio_taps - 1;
-        b->St = audio_channels == 2 ? p.stereo_taps : 0;
-        b->delay = audio_channels == 2 ? (p.stereo_taps - 1) / 2 : 0;                        // allPass, src/filter.cpp:14-29
-        b->Hd = b->Ha + b->delay;
-        if (audio_channels == 2 && b->St - 1 + 3 > b->Hd) b->Hd = b->St - 1 + 3;
-        const int more = b->res_hist > b->Ha ? b->res_hist - b->Ha : 0;   // (the lane-per-channel resampler rounds its windows up to whole iterations)
-        if (b->Ha + b->delay + more > b->Hd) b->Hd = b->Ha + b->delay + more;
-        b->Hd = (b->Hd + 3) / 4 * 4 + 4;
-        b->Hm = (b->Ha + more + 3) / 4 * 4 + 4;
-        if (block_bytes < b->hist_bytes || b->n_if < b->Hd)
-            return fail(FMRX_EINVAL, "channels (exact): block of %zu bytes is shorter than the history a channel carries (%zu bytes, %d IF samples)",
-                        block_bytes, b->hist_bytes, b->Hd);
-        b->slot_bytes = b->hist_bytes + block_bytes;
-        b->dpitch = (b->Hd + b->n_if + 16 + 3) / 4 * 4;
-        b->ypitch = (b->n_if + 16 + 3) / 4 * 4;
-        const size_t N = static_cast<size_t>(n_channels);
-        // the last tile's lanes past the block read on (results discarded): 63*R outputs' worth of bytes behind the last slot
-        FMRX_TRY(b->slots.alloc(b->slot_bytes * N + 2 * 64 * kR * p.rf_decim + 64));
-        FMRX_TRY(k_fill_u8(b->slots.p, b->slots.n, 128, nullptr));                            // silence: a stream that starts here
-        FMRX_TRY(b->demod.alloc(b->dpitch * N + 64));
-        FMRX_HIP(hipMemset(b->demod.p, 0, b->demod.bytes()));
-        if (audio_channels == 2) {
-#define X(T_) if (p.stereo_taps == T_) FMRX_TRY(bpf_table_init<T_>(*b, f.stereo.data(), f.pilot.data()));
-            CHS_BPF_CASES(X)
-#undef X
-            if (b->exact) {
-                FMRX_TRY(b->carrier.alloc(b->ypitch * N + 64));
-                FMRX_HIP(hipMemset(b->carrier.p, 0, b->carrier.bytes()));
-            } else {
-                b->cpitch = (b->n_if + 64 + 15) / 16 * 16;
-                FMRX_TRY(b->carrier8.alloc(b->cpitch * N + 64));
-                FMRX_HIP(hipMemset(b->carrier8.p, 0, b->carrier8.bytes()));
-            }
-            FMRX_TRY(b->bpf.alloc(b->ypitch * N + 64));
-            FMRX_TRY(b->trig.alloc(b->ypitch * N + 64));
-            FMRX_TRY(b->pll.alloc(8 * N));
-            FMRX_TRY(b->nco0.alloc(N));
-            for (auto &m : b->mixtail) {
-                FMRX_TRY(m.alloc(static_cast<size_t>(b->Hm) * N));
-                FMRX_HIP(hipMemset(m.p, 0, m.bytes()));
-            }
-            if (b->resample) {
-                b->mpitch = (b->Hm + b->n_if + 16 + 3) / 4 * 4;
-                FMRX_TRY(b->mixer.alloc(b->mpitch * N + 64));
-                FMRX_HIP(hipMemset(b->mixer.p, 0, b->mixer.bytes()));
-            }
-            hipLaunchKernelGGL(chs_fill_state_kernel, dim3(static_cast<unsigned>((8 * N + 255) / 256)), dim3(256), 0, nullptr, b->pll.p,
-                               static_cast<long>(8 * N));
-            CHS_LAUNCH_CHECK("chs_fill_state_kernel");
-            FMRX_HIP(hipStreamCreateWithFlags(&b->wide, hipStreamNonBlocking));
-            FMRX_HIP(hipStreamCreateWithFlags(&b->lanes, hipStreamNonBlocking));
-            FMRX_HIP(hipStreamCreateWithFlags(&b->front, hipStreamNonBlocking));
-            for (auto &e : b->ev_fe) FMRX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            for (auto &e : b->ev_bpf) FMRX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            for (auto &e : b->ev_pll) FMRX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            FMRX_HIP(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-            FMRX_HIP(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
-        }
-        FMRX_HIP(hipDeviceSynchronize());
-        return FMRX_OK;
+    const long wgs = (k_hi - k_lo + 1023) / 1024;
+    auto go = [&](auto exactc) {
+        hipLaunchKernelGGL(chs_nco_kernel<decltype(exactc)::value>, dim3(static_cast<unsigned>(wgs * n_rows)), dim3(256), 0, s, trig, ypitch,
+                           k_lo, k_hi, wgs, kNcoScale, kPhaseAdjust, bpf, nco0, mixer, mpitch, hm);
     };
-    const int rc = body();
-    if (rc != FMRX_OK) {
-        delete b;
-        return rc;
-    }
-    *out = b;
+    if (exact) go(std::true_type{});
+    else go(std::false_type{});
+    CHS_LAUNCH_CHECK("chs_nco_kernel");
     return FMRX_OK;
 }
 
-size_t stereo_bank_n_audio(const StereoBank *b) { return static_cast<size_t>(b->n_audio); }
-uint8_t *stereo_bank_first_block(const StereoBank *b) { return b->slots.p + b->hist_bytes; }
-size_t stereo_bank_pitch(const StereoBank *b) { return b->slot_bytes; }
-void stereo_bank_demod_layout(const StereoBank *b, const float **d_row0, size_t *pitch, size_t *n_if)
+int bank_launch_finish(const Bank &b, hipStream_t s)
 {
-    *d_row0 = b->demod.p + b->Hd;   // the finish kernel rewrites only the history in front of each row
-    *pitch = static_cast<size_t>(b->dpitch);
-    *n_if = static_cast<size_t>(b->n_if);
-}
-
-// back to the start-of-stream state (src/project.cpp:61-65, 446-458): one channel, or all of them (channel < 0)
-int stereo_bank_reset(StereoBank *b, int channel)
-{
-    FMRX_HIP(hipDeviceSynchronize());
-    const long lo = channel < 0 ? 0 : channel, hi = channel < 0 ? b->n_channels : channel + 1;
-    for (long c = lo; c < hi && channel >= 0; c++) {
-        FMRX_TRY(k_fill_u8(b->slots.p + c * b->slot_bytes, b->hist_bytes, 128, nullptr));
-        FMRX_HIP(hipMemsetAsync(b->demod.p + c * b->dpitch, 0, b->Hd * sizeof(float), nullptr));
-        if (b->audio_channels == 2) {
-            for (auto &m : b->mixtail) FMRX_HIP(hipMemsetAsync(m.p + c * b->Hm, 0, b->Hm * sizeof(float), nullptr));
-            if (b->resample) FMRX_HIP(hipMemsetAsync(b->mixer.p + c * b->mpitch, 0, b->Hm * sizeof(float), nullptr));
-            hipLaunchKernelGGL(chs_fill_state_kernel, dim3(1), dim3(8), 0, nullptr, b->pll.p + 8 * c, 8L);
-        }
-    }
-    if (channel < 0) {
-        FMRX_TRY(k_fill_u8(b->slots.p, b->slot_bytes * b->n_channels, 128, nullptr));
-        FMRX_HIP(hipMemsetAsync(b->demod.p, 0, b->demod.bytes(), nullptr));
-        if (b->audio_channels == 2) {
-            for (auto &m : b->mixtail) FMRX_HIP(hipMemsetAsync(m.p, 0, m.bytes(), nullptr));
-            if (b->resample) FMRX_HIP(hipMemsetAsync(b->mixer.p, 0, b->mixer.bytes(), nullptr));
-            const long n8 = 8L * b->n_channels;
-            hipLaunchKernelGGL(chs_fill_state_kernel, dim3(static_cast<unsigned>((n8 + 255) / 256)), dim3(256), 0, nullptr, b->pll.p, n8);
-        }
-    }
-    CHS_LAUNCH_CHECK("chs_fill_state_kernel");
-    FMRX_HIP(hipDeviceSynchronize());
-    return FMRX_OK;
-}
-
-// d_audio: [n_channels][audio_channels][n_audio] (stereo: left, then right); d_pcm: [n_channels][n_audio][audio_channels]
-int stereo_bank_process_dev(StereoBank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStream_t s)
-{
-    const fmrx_params &p = b->p;
-    auto fe = [&](long k_lo, long k_hi, hipStream_t st) -> int {
-        if (!b->exact)
-            return fe_mfma_bank_launch(b->fe, b->slots.p, static_cast<long>(b->slots.n), static_cast<long>(b->slot_bytes),
-                                       static_cast<long>(b->hist_bytes), b->n_channels, k_lo, k_hi, b->demod.p, b->dpitch, b->Hd, st);
-#define X(T_, D_) if (p.rf_taps == T_ && p.rf_decim == D_) return launch_fe<T_, D_>(*b, k_lo, k_hi, st);
-        CHS_FE_CASES(X)
-#undef X
-        return FMRX_EINVAL;
-    };
-    if (b->audio_channels == 2) {
-        auto bpf = [&](long k_lo, long k_hi, hipStream_t st) -> int {
-#define X(T_) if (p.stereo_taps == T_) return launch_bpf<T_>(*b, k_lo, k_hi, st);
-            CHS_BPF_CASES(X)
-#undef X
-            return FMRX_EINVAL;
-        };
-        // IF samples [.., if_of(a)) are what the audio outputs [.., a) read: a * D in the integer-decimation modes, whole periods
-        // (U outputs <-> D samples) in the resampling modes
-        auto if_of = [&](long a) -> long { return b->resample ? a / p.audio_upsamp * p.audio_decim : a * p.audio_decim; };
-        auto out = [&](long a_lo, long a_hi, long g_hi, hipStream_t st) -> int {
-            if (b->resample) {
-                (void)g_hi;   // the mixer rows of this chunk were written by its NCO pass (launch_nco)
-                return launch_resample<true>(*b, d_audio, d_pcm, wrap, a_lo, a_hi, st);
-            }
-#define X(T_, D_) if (p.audio_taps == T_ && p.audio_decim == D_) return launch_out<T_, D_, true>(*b, d_audio, d_pcm, wrap, a_lo, a_hi, g_hi, st);
-            CHS_OUT_CASES(X)
-#undef X
-            return FMRX_EINVAL;
-        };
-        // chunks of whole output workgroups (512 audio samples; whole periods of U outputs in the resampling modes);
-        // chunk c = audio [a_c, a_c+1) = IF [if_of(a_c), if_of(a_c+1))
-        const long unit = b->resample ? p.audio_upsamp : 512;
-        long per = (b->n_audio + b->max_chunks - 1) / b->max_chunks;
-        per = (per + unit - 1) / unit * unit;
-        const int K = static_cast<int>((b->n_audio + per - 1) / per);
-        hipStream_t sw = K > 1 ? b->wide : s, sl = K > 1 ? b->lanes : s;
-        // fast banks: the front end is HBM-bound on the matrix cores, the band-pass pair and the output stage are bound by the
-        // vector ALUs: on two streams they run side by side
-        const bool split = K > 1 && !b->exact;
-        hipStream_t sf = split ? b->front : sw;
-        if (K > 1) {   // whatever the caller's stream did before the call (loading the slots, reading the last output) comes first
-            FMRX_HIP(hipEventRecord(b->ev_fork, s));
-            FMRX_HIP(hipStreamWaitEvent(sw, b->ev_fork, 0));
-            FMRX_HIP(hipStreamWaitEvent(sl, b->ev_fork, 0));
-            if (split) FMRX_HIP(hipStreamWaitEvent(sf, b->ev_fork, 0));
-        }
-        // The output stage of chunk c follows the band-pass pair of chunk c + lag on the wide stream.  Exact banks: lag 1 (the PLL is
-        // the longest stage; nothing on the wide stream is waited for).  Fast banks: lag 2 -- the PLL of chunk c starts when its
-        // band-pass pair ends and takes longer than the next chunk's band-pass pair: with lag 1 the wide stream idled a third
-        // of the time waiting for it.
-        const int lag = (b->exact || K < 3) ? 1 : 2;
-        // the front end works in whole tiles of its own (63 x 8 outputs per wave; 120 per matrix-core tile): its share of a chunk
-        // ends on the first tile boundary at or behind the chunk's end, so that no chunk pays for a partly filled last tile
-        // (2560-sample chunks are 5.08 tiles of 504: 15 % of the exact front end's work was computed and thrown away)
-        const long fe_tile = b->exact ? 63 * kR : 120;
-        long fe_done = 0;
-        for (int c = 0; c < K + lag; c++) {
-            if (c < K) {
-                const long a_lo = c * per, a_hi = a_lo + per < b->n_audio ? a_lo + per : b->n_audio;
-                const long k_lo = if_of(a_lo), k_hi = if_of(a_hi);
-                long fe_hi = (k_hi + fe_tile - 1) / fe_tile * fe_tile;
-                if (fe_hi > b->n_if || c == K - 1) fe_hi = b->n_if;
-                if (fe_hi > fe_done) FMRX_TRY(fe(fe_done, fe_hi, sf));
-                fe_done = fe_hi;
-                if (split) {   // read-after-write: the band-pass pair reads the discriminator rows the front end wrote on its own stream
-                    FMRX_HIP(hipEventRecord(b->ev_fe[c], sf));
-                    FMRX_HIP(hipStreamWaitEvent(sw, b->ev_fe[c], 0));
-                }
-                FMRX_TRY(bpf(k_lo, k_hi, sw));
-                if (K > 1) {
-                    FMRX_HIP(hipEventRecord(b->ev_bpf[c], sw));
-                    FMRX_HIP(hipStreamWaitEvent(sl, b->ev_bpf[c], 0));
-                }
-                // fmPLL(carrier_filt, 19 kHz, if_Fs, ncoScale 2, phaseAdjust 0, normBandwidth 0.01): src/project.cpp:237
-                if (b->exact)
-                    FMRX_TRY(k_fm_pll_channels(b->carrier.p + k_lo, b->ypitch, static_cast<size_t>(k_hi - k_lo), b->n_channels,
-                                               b->trig.p + k_lo, b->ypitch, b->pll.p, c == 0 ? b->nco0.p : nullptr, 19e3f,
-                                               static_cast<float>(p.if_Fs), 2.0f, 0.0f, 0.01f, sl, true, true));
-                else
-                    FMRX_TRY(k_fm_pll_channels(reinterpret_cast<const float *>(b->carrier8.p + k_lo), b->cpitch,
-                                               static_cast<size_t>(k_hi - k_lo), b->n_channels, b->trig.p + k_lo, b->ypitch, b->pll.p,
-                                               c == 0 ? b->nco0.p : nullptr, 19e3f, static_cast<float>(p.if_Fs), 2.0f, 0.0f, 0.01f, sl, true,
-                                               false, true));
-                if (K > 1) FMRX_HIP(hipEventRecord(b->ev_pll[c], sl));
-            }
-            if (c >= lag) {   // the output stage of an earlier chunk, behind this chunk's band-pass pair on the wide stream
-                const long a_lo = (c - lag) * per, a_hi = a_lo + per < b->n_audio ? a_lo + per : b->n_audio;
-                if (K > 1) FMRX_HIP(hipStreamWaitEvent(sw, b->ev_pll[c - lag], 0));   // (the PLL followed this chunk's band-pass pair: both are done)
-                // fast banks, modes 0/1: inside the output stage; the resampling modes materialise the mixer rows from finished NCO values
-                if (b->exact || b->resample) FMRX_TRY(launch_nco(*b, if_of(a_lo), if_of(a_hi), sw));
-                FMRX_TRY(out(a_lo, a_hi, if_of(a_hi), sw));
-            }
-        }
-        if (K > 1) {
-            FMRX_HIP(hipEventRecord(b->ev_join, sw));               // the last output stage follows everything else of the call
-            FMRX_HIP(hipStreamWaitEvent(s, b->ev_join, 0));
-        }
-        b->mix_cur ^= 1;
-    } else {
-        FMRX_TRY(fe(0, b->n_if, s));
-        if (b->resample) {
-            FMRX_TRY(launch_resample<false>(*b, d_audio, d_pcm, wrap, 0, b->n_audio, s));
-        } else {
-#define X(T_, D_) if (p.audio_taps == T_ && p.audio_decim == D_) FMRX_TRY((launch_out<T_, D_, false>(*b, d_audio, d_pcm, wrap, 0, b->n_audio, b->n_if, s)));
-            CHS_OUT_CASES(X)
-#undef X
-        }
-    }
-    hipLaunchKernelGGL(chs_finish_kernel, dim3(static_cast<unsigned>(b->n_channels)), dim3(64), 0, s, b->slots.p,
-                       static_cast<long>(b->slot_bytes), static_cast<long>(b->hist_bytes), b->demod.p, b->dpitch, b->Hd, b->n_if,
-                       b->resample && b->audio_channels == 2 ? b->mixer.p : nullptr, b->mpitch, b->Hm);
+    hipLaunchKernelGGL(chs_finish_kernel, dim3(static_cast<unsigned>(b.n_channels)), dim3(64), 0, s, b.slots.p,
+                       static_cast<long>(b.slot_bytes), static_cast<long>(b.hist_bytes), b.demod.p, b.dpitch, b.Hd, b.n_if,
+                       b.resample && b.audio_channels == 2 ? b.mixer.p : nullptr, b.mpitch, b.Hm);
     CHS_LAUNCH_CHECK("chs_finish_kernel");
     return FMRX_OK;
 }
 
-// diagnostics / tests: one channel's row of an intermediate of the last call.  which: FMRX_TAP_DEMOD, _CARRIER (fast banks: the
-// sign row the PLL reads, as -1 / 0 / +1), _STEREO_BPF, _PLL (n_if + 1 values: PLL[0] = the state's lastOut, then the finished
-// NCO values), _TRIG_ARG (fast banks of modes 0/1: the raw trigArg of every step -- their output stage takes the cosine on chip,
-// the row stays raw; the other banks' NCO pass overwrites it in place)
-int stereo_bank_read_tap(StereoBank *b, int channel, int which, float *out, size_t *n)
+int bank_launch_fill_state(float *pll, long n, hipStream_t s)
 {
-    if (channel < 0 || channel >= b->n_channels) return fail(FMRX_EINVAL, "channels_read_tap: channel %d of %d", channel, b->n_channels);
-    FMRX_HIP(hipDeviceSynchronize());
-    const size_t n_if = static_cast<size_t>(b->n_if);
-    const bool stereo = b->audio_channels == 2;
-    const float *src = nullptr;
-    size_t cnt = n_if;
-    switch (which) {
-    // the finish kernel has copied the row's tail into its front already; the block itself is intact
-    case FMRX_TAP_DEMOD: src = b->demod.p + channel * b->dpitch + b->Hd; break;
-    case FMRX_TAP_CARRIER:
-        if (stereo && !b->exact) {
-            *n = cnt;
-            if (!out) return FMRX_OK;
-            std::vector<int8_t> sg(n_if);
-            FMRX_HIP(hipMemcpy(sg.data(), b->carrier8.p + channel * b->cpitch, n_if, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < n_if; k++) out[k] = static_cast<float>(sg[k]);
-            return FMRX_OK;
-        }
-        if (stereo) src = b->carrier.p + channel * b->ypitch;
-        break;
-    case FMRX_TAP_STEREO_BPF: if (stereo) src = b->bpf.p + channel * b->ypitch; break;
-    case FMRX_TAP_PLL: if (stereo) { src = b->trig.p + channel * b->ypitch; cnt = n_if + 1; } break;
-    case FMRX_TAP_TRIG_ARG: if (stereo && !b->exact && !b->resample) src = b->trig.p + channel * b->ypitch; break;
-    default: break;
-    }
-    if (!src) return fail(FMRX_EINVAL, "channels_read_tap: tap %d is not kept by this bank", which);
-    *n = cnt;
-    if (!out) return FMRX_OK;
-    if (which == FMRX_TAP_PLL) {
-        FMRX_HIP(hipMemcpy(out, b->nco0.p + channel, sizeof(float), hipMemcpyDeviceToHost));
-        if (!b->exact && !b->resample) {
-            // the fast bank of modes 0/1 keeps the raw trigArg of every step (the cosine is taken inside the output stage): the same
-            // NCO pass the other banks run, here on a copy of the one row
-            DevBuf<float> tmp;
-            const long pitch = (static_cast<long>(n_if) + 16 + 3) / 4 * 4;
-            FMRX_TRY(tmp.alloc(static_cast<size_t>(pitch)));
-            FMRX_HIP(hipMemcpy(tmp.p, src, n_if * sizeof(float), hipMemcpyDeviceToDevice));
-            const long wgs = (static_cast<long>(n_if) + 1023) / 1024;
-            hipLaunchKernelGGL(chs_nco_kernel<false>, dim3(static_cast<unsigned>(wgs)), dim3(256), 0, nullptr, tmp.p, pitch, 0L, static_cast<long>(n_if),
-                               wgs, 2.0f, 0.0f, nullptr, nullptr, nullptr, 0L, 0);
-            CHS_LAUNCH_CHECK("chs_nco_kernel");
-            FMRX_HIP(hipMemcpy(out + 1, tmp.p, n_if * sizeof(float), hipMemcpyDeviceToHost));
-            return FMRX_OK;
-        }
-        FMRX_HIP(hipMemcpy(out + 1, src, n_if * sizeof(float), hipMemcpyDeviceToHost));
-        return FMRX_OK;
-    }
-    FMRX_HIP(hipMemcpy(out, src, cnt * sizeof(float), hipMemcpyDeviceToHost));
+    hipLaunchKernelGGL(chs_fill_state_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, pll, n);
+    CHS_LAUNCH_CHECK("chs_fill_state_kernel");
     return FMRX_OK;
 }
 

@@ -376,7 +376,7 @@ int launch_mfma(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, const u
     return FMRX_OK;
 }
 
-// ---- the same front end over a BANK of receivers (channels_stereo.hip) -------------------------------------------
+// ---- the same front end over a BANK of receivers (bank.hip, kernels_bank.hip) ----------------------------------
 // One launch covers the IF outputs [out_off, out_off + n_row) of EVERY channel's block: tile tau = (channel tau / tiles_per_row,
 // tile tau % tiles_per_row of that channel's range).  Input rows are the bank's slots [history | block] (pitch in_pitch
 // bytes; the history in front of a block holds the stream's last bytes, so every window is read from one contiguous

@@ -1,7 +1,7 @@
 // rds_bank.hip -- the RDS chain of N channels per device call (include/fmrx.h: fmrx_rds_bank_*).
 //
 // The single-stream handle (rds.hip) runs one station's chain in 17 launches per block, its float64 PLL in one lane of one wave
-// and its bit recovery on the host.  A receiver bank (channels.hip, channels_stereo.hip) demodulates 10^4 - 10^5 stations per
+// and its bit recovery on the host.  A receiver bank (channels.hip, bank.hip) demodulates 10^4 - 10^5 stations per
 // call; this file gives each of them its RDS chain in a FIXED number of launches, whatever the number of channels, with the
 // arithmetic of rds.hip unchanged -- every channel's results equal, bit for bit, what an fmrx_rds handle produces from the same
 // discriminator stream:

@@ -4,7 +4,7 @@ The kernels it models (the order of each read from its loop, checked on the GPU 
   bpf_pair_kernel (kernels_stereo.hip)       both band-pass filters, D = 1, taps DESCENDING (oldest window sample first)
   stereo_out_kernel (kernels_stereo.hip)     both audio FIRs, taps ascending, the mono one `delay` samples back
   audio_fir_kernel (kernels_audio.hip)       polyphase: branch p = 0 .. D-1, inside it m = p, p + D, ...; tap n = T-1-m
-  chs_bpf_kernel, chs_out_kernel (channels_stereo.hip, fast bank)   taps ascending (newest window sample first)
+  chs_bpf_kernel, chs_out_kernel (kernels_bank.hip, fast bank)      taps ascending (newest window sample first)
   chs_resample_lanes_kernel (fast bank, modes 2/3)   the reference's resampler order (j ascending), one fma per tap
 
 Every model takes the STREAM the kernel read -- the concatenation of a tap over the calls, zeros before the stream's

@@ -214,7 +214,7 @@ def stereo_out_shapes():
 def test_gpu_tests_cover_every_shape():
     """The GPU file's shape lists are the kernels' dispatch lists: a new shape cannot ship without its exact test."""
     import test_gpu_fir_exact as g
-    ks, cs = os.path.join(CSRC, "kernels_stereo.hip"), os.path.join(CSRC, "channels_stereo.hip")
+    ks, cs = os.path.join(CSRC, "kernels_stereo.hip"), os.path.join(CSRC, "kernels_bank.hip")
     assert sorted(define_list(ks, "FMRX_BPF_CASES")) == sorted(g.BPF_TAPS)
     assert sorted(parse_cases(os.path.join(CSRC, "kernels_audio.hip"), "FMRX_AUDIO_CASES")) == sorted(g.AUDIO_SHAPES)
     assert sorted(stereo_out_shapes()) == sorted(g.STEREO_OUT_SHAPES)

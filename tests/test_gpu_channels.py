@@ -67,6 +67,23 @@ def test_stereo_bank_exact(fmrx, oracle, mode, taps):
         check(b, range(N))
 
 
+def test_stereo_bank_exact_reset_all(fmrx, oracle):
+    """reset() of the whole bank puts every channel back at the start of its stream: an exact stereo bank processes two
+    blocks, all channels are reset, and the same two blocks give the same left, right and PCM bit for bit."""
+    p = oracle.mode_params(0, 101, 101, 101)
+    N, nblk, bb = 5, 2, p.block_bytes
+    streams = [channel_stream(oracle, c, bb // 2 * nblk, p.rf_Fs) for c in range(N)]
+    ch = fmrx.Channels(0, N, audio_channels=2, exact=True)
+    blocks = [np.stack([st[b * bb:(b + 1) * bb] for st in streams]) for b in range(nblk)]
+    first = [ch.process(iq) for iq in blocks]
+    assert any(np.any(first[1][k] != first[0][k]) for k in ("audio_l", "audio_r"))   # (the stream moves: the blocks differ)
+    ch.reset()
+    for b, iq in enumerate(blocks):
+        again = ch.process(iq)
+        for k in ("audio_l", "audio_r", "pcm16"):
+            bits_equal(again[k], first[b][k], f"{k} block {b} after reset()")
+
+
 def test_mono_bank_exact(fmrx, oracle):
     """The mono bank in the reference's evaluation order: audio bit for bit (the specialised mono bank promises 2e-6)."""
     for mode in (0, 1, 2, 3):

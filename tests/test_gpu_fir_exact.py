@@ -5,7 +5,7 @@ taps the kernels read:
   stereo_out_kernel (kernels_stereo.hip)        mixer = (stereo_filt * PLL) * 2; mono_filt, stereo_final = the ascending
                                                 chain (mono `delay` samples back); L = st + mono, R = mono - st; PCM
   audio_fir_kernel (kernels_audio.hip)          mono audio of modes 0/1 (two-kernel path) = the polyphase chain
-  chs_bpf_kernel, chs_out_kernel (channels_stereo.hip, fast bank)   stereo_filt, L/R = the ascending chain; the bank's
+  chs_bpf_kernel, chs_out_kernel (kernels_bank.hip, fast bank)      stereo_filt, L/R = the ascending chain; the bank's
                                                 IF equals the single-stream pipeline's bit for bit
   chs_resample_lanes_kernel (fast bank, 2/3)    L/R = the reference's resampler order with one fma per tap, on the delayed
                                                 demod and the mixer
