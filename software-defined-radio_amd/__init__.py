@@ -667,7 +667,8 @@ def framesync(diff_data):
 
 
 class Rds:
-    """The RDS chain of model/fmMonoBlock.py:238-296 on fm_demod blocks (fmrx_rds_*)."""
+    """The RDS chain of model/fmMonoBlock.py:238-296 on fm_demod blocks (fmrx_rds_*): the device chain of RdsBank with one channel,
+    any block of up to max_block samples per call, bits recovered on the host."""
 
     def __init__(self, mode=0, max_block=9600, device=0, params: RdsParams | None = None):
         self.params = params if params is not None else RdsParams()
@@ -706,8 +707,9 @@ class Rds:
 
 
 class RdsBank:
-    """The RDS chain of N channels per device call (fmrx_rds_bank_*): per channel, bit for bit what an Rds handle reports for
-    the same discriminator stream.  block: IF samples per channel and call (9600 = the receiver banks' block_bytes 192000)."""
+    """The RDS chain of N channels per device call (fmrx_rds_bank_*), bits recovered on the device.  An Rds handle runs the same
+    chain with one channel, so per channel this is, bit for bit, what an Rds handle reports for the same discriminator stream.
+    block: IF samples per channel and call (9600 = the receiver banks' block_bytes 192000)."""
 
     def __init__(self, mode=0, n_channels=1, block=9600, device=0, params: RdsParams | None = None):
         self.params = params if params is not None else RdsParams()

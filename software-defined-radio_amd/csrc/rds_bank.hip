@@ -1,31 +1,33 @@
-// rds_bank.hip -- the RDS chain of N channels per device call (include/fmrx.h: fmrx_rds_bank_*).
+// rds_bank.hip -- the RDS chain of N channels per device call: the chain itself (rds_chain.hpp), which the single-stream handle
+// (rds.hip: include/fmrx.h fmrx_rds_*) runs with one channel, and the bank around it (fmrx_rds_bank_*).
 //
-// The single-stream handle (rds.hip) runs one station's chain in 17 launches per block, its float64 PLL in one lane of one wave
-// and its bit recovery on the host.  A receiver bank (channels.hip, bank.hip) demodulates 10^4 - 10^5 stations per
-// call; this file gives each of them its RDS chain in a FIXED number of launches, whatever the number of channels, with the
-// arithmetic of rds.hip unchanged -- every channel's results equal, bit for bit, what an fmrx_rds handle produces from the same
-// discriminator stream:
-//   rdsb_cvt_kernel         f32 demod rows (caller's pitch) -> f64 rows behind their histories       (rds_cvt_kernel)
-//   rdsb_fir_kernel<0>      54-60 kHz channel band-pass, 151 taps                                     (rds_fir_kernel)
-//   rdsb_fir_kernel<1>      113.5-114.5 kHz band-pass of the squared channel row                      (rds_fir_kernel, square)
-//   rdsb_pll_lanes_kernel   the 114 kHz PLL, ONE LANE PER CHANNEL (64 channels per wave)              (rds_pll_kernel, rds_nco_state_kernel)
-//   rdsb_mix_kernel         NCO pair, I / Q mixers                                                    (rds_nco_kernel, rds_mix_kernel)
-//   rdsb_resample_kernel    rational resampler U/D, 101*U taps, gain U, I and Q                       (rds_resample_kernel x 2)
-//   rdsb_fir_kernel<0>      root-raised-cosine matched filter, I and Q (grid z)                      (rds_fir_kernel x 2)
-//   rdsb_cdr_kernel         clock and data recovery, Manchester and differential decoding, one lane per channel (host cdr())
-//   rdsb_station_kernel     with stations on only: the station decoder of rds_station.hpp, one lane per channel (fmrx_rds_station_*)
-//   rdsb_tail_kernel        carried state: every row's tail -> its history                            (rds_tail_kernel x 6)
+// A receiver bank (channels.hip, bank.hip) demodulates 10^4 - 10^5 stations per call; the chain gives each of them the float64
+// arithmetic of the reference's model (rds.hip lists the stages) in a FIXED number of launches, whatever the number of channels
+// (tests/_rds_stage_model.py is the model of every stage's order of operations):
+//   rdsb_cvt_kernel         f32 demod rows (caller's pitch) -> f64 rows behind their histories
+//   rdsb_fir_kernel<0>      54-60 kHz channel band-pass, 151 taps
+//   rdsb_fir_kernel<1>      113.5-114.5 kHz band-pass of the squared channel row
+//   rdsb_pll_lanes_kernel   the 114 kHz PLL, ONE LANE PER CHANNEL (64 channels per wave)
+//   rdsb_mix_kernel         NCO pair, I / Q mixers
+//   rdsb_resample_kernel    rational resampler U/D, 101*U taps, gain U, I and Q
+//   rdsb_fir_kernel<0>      root-raised-cosine matched filter, I and Q (grid z)
+//   rdsb_cdr_kernel         the bank only: clock and data recovery, Manchester and differential decoding, one lane per channel
+//                           (the host cdr(), which the single-stream handle calls)
+//   rdsb_tail_kernel        carried state: every row's tail -> its history
+//   rdsb_station_kernel     the bank with stations on only: the station decoder of rds_station.hpp, one lane per channel
+//                           (fmrx_rds_station_*)
 // Frame synchronisation stays on the host (fmrx_rds_bank_collect), ~190 new bits per channel and call.
 //
-// Data layout: channel-major float64 rows, the carried history (raw samples, as rds.hip keeps them) in front of the block and
+// Data layout: channel-major float64 rows, the carried history (raw samples) in front of the block and
 // a few samples of padding behind it (the register-window FIRs read up to kR - 2 samples past the block; results discarded):
 //   x      [N][Hx | n | pad]     converted discriminator output          ch     [N][Hc | n | pad]    channel band-pass
 //   car    [N][n | pad]          carrier band-pass (squared input)       arg    [N][n | pad]         raw trigArg of every PLL step
 //   nco_i, nco_q [N][n+1 | pad]  NCO pair, [0] = previous call's last    mi, mq [N][Hm | n | pad]    mixer rows
 //   ri, rq [N][Hr | n_out | pad] resampler output                        yi, yq [N][n_out | pad]     matched-filter output
-//   state  [N][8]                rds_pll_kernel's layout {integ, phase, fI, fQ, nco_i[n], off, nco_q[n], trigArg}
+//   state  [N][8]                {integ, phase, fI, fQ, nco_i[n], off, nco_q[n], trigArg}
 //   bits   u8 [N][max_bits], n_bits u32 [N], blk i32 [N] (0 until a channel's first call: the CDR's block_count != 0 test)
 #include "fmrx_internal.hpp"
+#include "rds_chain.hpp"
 #include "rds_common.hpp"
 #include "rds_station.hpp"
 
@@ -51,10 +53,11 @@ __global__ __launch_bounds__(256) void rdsb_cvt_kernel(const float *__restrict__
     if (i < n) x[c * xpitch + i] = static_cast<double>(in[c * in_pitch + i]);
 }
 
-// y[k] = sum_j h[j] * f(x[k-j]), f = identity or square, in rds_fir_kernel's order (acc = h[j]*v + acc, j from taps-1 down to 0).
+// y[k] = sum_j h[j] * f(x[k-j]), f = identity or square, in the order lfilter's transposed form adds them up
+// (acc = h[j]*v + acc, j from taps-1 down to 0).
 // A thread owns kR consecutive outputs and slides one register window over x: the window of step j is x[k0-j .. k0-j+kR-1],
 // one new sample per step, so every sample is loaded (and squared) once for all kR outputs while each output still meets its
-// taps in the single-stream order.  x, y: the block's first sample of channel 0's row (blockIdx.x = channel); blockIdx.z
+// taps in that order.  x, y: the block's first sample of channel 0's row (blockIdx.x = channel); blockIdx.z
 // selects the second (x, y) pair (the matched filter runs I and Q in one launch).  Reads x[-(taps-1) .. n+kR-2].
 template <bool SQUARE>
 __global__ __launch_bounds__(256) void rdsb_fir_kernel(const double *__restrict__ x0, const double *__restrict__ x1, long xpitch, long n,
@@ -88,10 +91,10 @@ __global__ __launch_bounds__(256) void rdsb_fir_kernel(const double *__restrict_
         if (k0 + r < n) y[r] = acc[r];
 }
 
-// The recurrence of fmPll (fmSupportLib.py:297-353) in float64, rds_pll_kernel's step, ONE LANE PER CHANNEL.  The carrier row
+// The recurrence of fmPll (fmSupportLib.py:297-353) in float64, ONE LANE PER CHANNEL.  The carrier row
 // arrives a batch ahead through registers into LDS and the chain touches LDS only; the state stays in
 // registers (the step is written out in the loop: no call, nothing in scratch).  Also: nco[0] <- the incoming state's last NCO
-// pair, and the outgoing one computed from the last trigArg (what rds_nco_kernel / rds_nco_state_kernel do for one stream).
+// pair, and the outgoing one computed from the last trigArg.
 // Rows are 16-byte aligned (even pitches).
 __global__ __launch_bounds__(64) void rdsb_pll_lanes_kernel(const double *__restrict__ car, long apitch, long n, int n_ch, double *__restrict__ arg,
                                                             double *__restrict__ state, double *__restrict__ nco_i, double *__restrict__ nco_q,
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(256) void rdsb_mix_kernel(const double *__restrict_
     }
 }
 
-// convolveBlockResampleFIR of the model (fmSupportLib.py:388-407) in stream form, gain U: rds_resample_kernel's phase walk, I and
+// convolveBlockResampleFIR of the model (fmSupportLib.py:388-407) in stream form, gain U: one phase walk per output, I and
 // Q together (same taps, same window).  mi, mq, ri, rq: the block's first sample of channel 0's row.
 __global__ __launch_bounds__(256) void rdsb_resample_kernel(const double *__restrict__ mi, const double *__restrict__ mq, long mpitch, long n_out,
                                                             const double *__restrict__ h, int taps, int decim, int upsamp, double *__restrict__ ri,
@@ -356,20 +359,167 @@ __global__ __launch_bounds__(256) void rdsb_tail_kernel(double *__restrict__ x, 
 
 long pitch_of(long n) { return (n + 8 + 3) / 4 * 4; }   // kR - 2 readable samples past the end, 32-byte rows
 
-const double kPllInit[8] = {0.0, 0.0, 1.0, 0.0, 1.0, 0.0, 1.0, 0.0};   // fmMonoBlock.py:186 (as fmrx_rds_reset)
-
 }  // namespace
 
+// ---- the chain (rds_chain.hpp) ---------------------------------------------------------------------------------------------
+
+int Chain::plan(const char *who, const fmrx_rds_params *pp, int n_ch, size_t max_block)
+{
+    if (pp->taps < 3 || pp->taps > 65535 || pp->upsamp < 1 || pp->decim < 1 || pp->sps < 1 || pp->rrc_taps < 2 || pp->if_Fs <= 0)
+        return fail(FMRX_EINVAL, "%s: bad parameters", who);
+    p = *pp;
+    n_channels = n_ch;
+    block = static_cast<long>(max_block);
+    delay = (p.taps - 1) / 2;
+    Hx = p.taps - 1;
+    Hm = (101 * p.upsamp - 1) / p.upsamp;
+    Hc = std::max(p.taps - 1, delay + 1);
+    Hr = p.rrc_taps - 1;
+    const long n = block, no = static_cast<long>(n_out(max_block));
+    xpitch = pitch_of(Hx + n);
+    cpitch = pitch_of(Hc + n);
+    apitch = pitch_of(n);
+    npitch = pitch_of(n + 1);
+    mpitch = pitch_of(Hm + n);
+    rpitch = pitch_of(Hr + no);
+    ypitch = pitch_of(no);
+    return FMRX_OK;
+}
+
+int Chain::check_block(const char *who, size_t n) const
+{
+    if (n < static_cast<size_t>(std::max(std::max(Hx, Hc), Hm)) || n_out(n) < static_cast<size_t>(Hr))
+        return fail(FMRX_EINVAL, "%s: block of %zu samples is shorter than a filter history (%d / %d / %d input samples, %d resampled)", who, n,
+                    Hx, Hc, Hm, Hr);
+    return FMRX_OK;
+}
+
+int Chain::create(int dev)
+{
+    device = dev;
+    const int rs_taps = 101 * p.upsamp;
+    std::vector<double> h(std::max(rs_taps, p.taps));
+    auto up = [&](DevBuf<double> &d, int cnt) -> int {
+        FMRX_TRY(d.alloc(cnt));
+        FMRX_HIP(hipMemcpy(d.p, h.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
+        return FMRX_OK;
+    };
+    design_bpf64(p.taps, p.if_Fs, 54e3, 60e3, h.data());                                // fmMonoBlock.py:138
+    FMRX_TRY(up(h_ch, p.taps));
+    design_bpf64(p.taps, p.if_Fs, 113.5e3, 114.5e3, h.data());                          // :139
+    FMRX_TRY(up(h_car, p.taps));
+    design_lpf64(rs_taps, static_cast<double>(p.if_Fs) * p.upsamp, 3e3, h.data());      // :140
+    FMRX_TRY(up(h_rs, rs_taps));
+    design_rrc64(2375.0 * p.sps, p.rrc_taps, h.data());                                 // :141
+    FMRX_TRY(up(h_rrc, p.rrc_taps));
+    const size_t N = static_cast<size_t>(n_channels);
+    auto rows = [&](DevBuf<double> &d, long pitch) -> int {
+        FMRX_TRY(d.alloc(static_cast<size_t>(pitch) * N));
+        FMRX_HIP(hipMemset(d.p, 0, d.bytes()));
+        return FMRX_OK;
+    };
+    FMRX_TRY(rows(x, xpitch));
+    FMRX_TRY(rows(ch, cpitch));
+    FMRX_TRY(rows(car, apitch));
+    FMRX_TRY(rows(arg, apitch));
+    FMRX_TRY(rows(nco_i, npitch));
+    FMRX_TRY(rows(nco_q, npitch));
+    FMRX_TRY(rows(mi, mpitch));
+    FMRX_TRY(rows(mq, mpitch));
+    FMRX_TRY(rows(ri, rpitch));
+    FMRX_TRY(rows(rq, rpitch));
+    FMRX_TRY(rows(yi, ypitch));
+    FMRX_TRY(rows(yq, ypitch));
+    return state.alloc(8 * N);
+}
+
+int Chain::reset(int lo, int hi)
+{
+    FMRX_HIP(hipSetDevice(device));
+    FMRX_HIP(hipDeviceSynchronize());
+    const size_t cnt = static_cast<size_t>(hi - lo);
+    auto hist = [&](DevBuf<double> &d, long pitch, int h) -> int {
+        FMRX_HIP(hipMemset2D(d.p + lo * pitch, pitch * sizeof(double), 0, h * sizeof(double), cnt));
+        return FMRX_OK;
+    };
+    FMRX_TRY(hist(x, xpitch, Hx));
+    FMRX_TRY(hist(ch, cpitch, Hc));
+    FMRX_TRY(hist(mi, mpitch, Hm));
+    FMRX_TRY(hist(mq, mpitch, Hm));
+    FMRX_TRY(hist(ri, rpitch, Hr));
+    FMRX_TRY(hist(rq, rpitch, Hr));
+    const double start[8] = {0.0, 0.0, 1.0, 0.0, 1.0, 0.0, 1.0, 0.0};   // fmMonoBlock.py:186
+    std::vector<double> init(8 * cnt);
+    for (size_t c = 0; c < cnt; c++) std::copy(start, start + 8, init.begin() + 8 * c);
+    FMRX_HIP(hipMemcpy(state.p + 8 * lo, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+    FMRX_HIP(hipDeviceSynchronize());
+    return FMRX_OK;
+}
+
+int Chain::run(const float *d_demod, size_t pitch, size_t n_in, hipStream_t s, const CdrRows *cdr)
+{
+    const long n = static_cast<long>(n_in), no = static_cast<long>(n_out(n_in));
+    const unsigned N = static_cast<unsigned>(n_channels), lanes = (N + 63) / 64;
+    auto tiles = [](long cnt, long per) { return static_cast<unsigned>((cnt + per - 1) / per); };
+    double *xb = x.p + Hx, *chb = ch.p + Hc, *mib = mi.p + Hm, *mqb = mq.p + Hm, *rib = ri.p + Hr, *rqb = rq.p + Hr;
+    const double phase_adjust = 3 * kPi / 8;
+    hipLaunchKernelGGL(rdsb_cvt_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, d_demod, static_cast<long>(pitch), n, xb, xpitch);
+    hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, xb, xb, xpitch, n, h_ch.p, p.taps, chb, chb, cpitch);
+    hipLaunchKernelGGL(rdsb_fir_kernel<true>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, chb, chb, cpitch, n, h_car.p, p.taps, car.p, car.p,
+                       apitch);
+    hipLaunchKernelGGL(rdsb_pll_lanes_kernel, dim3(lanes), dim3(64), 0, s, car.p, apitch, n, n_channels, arg.p, state.p, nco_i.p, nco_q.p, npitch,
+                       114e3, static_cast<double>(p.if_Fs), 0.002, 0.5, phase_adjust);
+    hipLaunchKernelGGL(rdsb_mix_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, arg.p, apitch, n, chb, cpitch, delay, 0.5, phase_adjust, nco_i.p,
+                       nco_q.p, npitch, mib, mqb, mpitch);
+    hipLaunchKernelGGL(rdsb_resample_kernel, dim3(N, tiles(no, 256)), dim3(256), 0, s, mib, mqb, mpitch, no, h_rs.p, 101 * p.upsamp, p.decim,
+                       p.upsamp, rib, rqb, rpitch);
+    hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(no, 256 * kR), 2), dim3(256), 0, s, rib, rqb, rpitch, no, h_rrc.p, p.rrc_taps, yi.p,
+                       yq.p, ypitch);
+    // fmMonoBlock.py:276-280 (fmrx_rds_process): the CDR state is re-made every block
+    if (cdr)
+        hipLaunchKernelGGL(rdsb_cdr_kernel, dim3(lanes), dim3(64), 0, s, yi.p, ypitch, no, n_channels, p.sps, 0.0, 0.0, 158L, 0L, cdr->blk,
+                           cdr->bits, cdr->max_bits, cdr->n_bits);
+    hipLaunchKernelGGL(rdsb_tail_kernel, dim3(N), dim3(256), 0, s, x.p, xpitch, Hx, ch.p, cpitch, Hc, mi.p, mq.p, mpitch, Hm, ri.p, rq.p, rpitch, Hr,
+                       n, no);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FMRX_EHIP, "rds kernels: %s", hipGetErrorString(e));
+    last_n = n_in;
+    last_out = static_cast<size_t>(no);
+    return FMRX_OK;
+}
+
+int Chain::tap(const char *who, int channel, int which, double *out, size_t *n)
+{
+    const long c = channel;
+    const double *src = nullptr;
+    size_t cnt = 0;
+    switch (which) {
+    case FMRX_RDS_TAP_CHANNEL: src = ch.p + c * cpitch + Hc; cnt = last_n; break;   // after the tail copy the block region is intact
+    case FMRX_RDS_TAP_CARRIER: src = car.p + c * apitch; cnt = last_n; break;
+    case FMRX_RDS_TAP_PLL_I: src = nco_i.p + c * npitch; cnt = last_n ? last_n + 1 : 0; break;
+    case FMRX_RDS_TAP_PLL_Q: src = nco_q.p + c * npitch; cnt = last_n ? last_n + 1 : 0; break;
+    case FMRX_RDS_TAP_RESAMPLED_I: src = ri.p + c * rpitch + Hr; cnt = last_out; break;
+    case FMRX_RDS_TAP_RRC_I: src = yi.p + c * ypitch; cnt = last_out; break;
+    case FMRX_RDS_TAP_RRC_Q: src = yq.p + c * ypitch; cnt = last_out; break;
+    case FMRX_RDS_TAP_PLL_STATE: src = state.p + 8 * c; cnt = 7; break;
+    default: return fail(FMRX_EINVAL, "%s: unknown tap %d", who, which);
+    }
+    *n = cnt;
+    if (!out || cnt == 0) return FMRX_OK;
+    FMRX_HIP(hipSetDevice(device));
+    FMRX_HIP(hipDeviceSynchronize());
+    FMRX_HIP(hipMemcpy(out, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    return FMRX_OK;
+}
+
+// ---- the bank: the chain of N channels with a fixed block, bits recovered on the device, stations ---------------------------
+
 struct fmrx_rds_bank {
-    fmrx_rds_params p{};
-    int n_channels = 0, device = 0;
-    long block = 0, n_out = 0, max_bits = 0;
-    int Hx = 0, Hc = 0, Hm = 0, Hr = 0, delay = 0;
-    long xpitch = 0, cpitch = 0, apitch = 0, npitch = 0, mpitch = 0, rpitch = 0, ypitch = 0;
+    Chain c;
+    long n_out = 0, max_bits = 0;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     DevBuf<float> in;
-    DevBuf<double> h_ch, h_car, h_rs, h_rrc, x, ch, car, arg, nco_i, nco_q, mi, mq, ri, rq, yi, yq, state;
     DevBuf<int> blk;
     DevBuf<uint8_t> bits;
     DevBuf<uint32_t> n_bits;
@@ -377,7 +527,6 @@ struct fmrx_rds_bank {
     std::vector<uint32_t> h_n_bits;
     std::vector<std::vector<uint8_t>> decoded;   // per channel: the bits frame synchronisation keeps (fmrx_rds::decoded)
     bool pending = false;                          // a process_dev whose bits have not been collected
-    long calls = 0;
     bool fresh = true;                             // no call since create / reset(-1): stations may be switched
     bool stations = false;                         // rdsb_station_kernel runs in process_dev
     long max_g = 0;                                // group records per channel and call
@@ -394,29 +543,15 @@ namespace {
 // back to the start-of-stream state, channels [lo, hi)
 int bank_reset(fmrx_rds_bank *b, int lo, int hi)
 {
-    FMRX_HIP(hipSetDevice(b->device));
-    FMRX_HIP(hipDeviceSynchronize());
+    FMRX_TRY(b->c.reset(lo, hi));
     const size_t cnt = static_cast<size_t>(hi - lo);
-    auto hist = [&](DevBuf<double> &d, long pitch, int h) -> int {
-        FMRX_HIP(hipMemset2D(d.p + lo * pitch, pitch * sizeof(double), 0, h * sizeof(double), cnt));
-        return FMRX_OK;
-    };
-    FMRX_TRY(hist(b->x, b->xpitch, b->Hx));
-    FMRX_TRY(hist(b->ch, b->cpitch, b->Hc));
-    FMRX_TRY(hist(b->mi, b->mpitch, b->Hm));
-    FMRX_TRY(hist(b->mq, b->mpitch, b->Hm));
-    FMRX_TRY(hist(b->ri, b->rpitch, b->Hr));
-    FMRX_TRY(hist(b->rq, b->rpitch, b->Hr));
-    std::vector<double> init(8 * cnt);
-    for (size_t c = 0; c < cnt; c++) std::copy(kPllInit, kPllInit + 8, init.begin() + 8 * c);
-    FMRX_HIP(hipMemcpy(b->state.p + 8 * lo, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
     FMRX_HIP(hipMemset(b->blk.p + lo, 0, cnt * sizeof(int)));
     for (int c = lo; c < hi; c++) b->decoded[c].clear();
     if (b->dec.p) {                                // the station decoders, as fmrx_rds_station_create leaves them
         std::vector<rdsst::Dec> d(cnt);
         std::vector<fmrx_rds_station> r(cnt);
         for (size_t c = 0; c < cnt; c++) {
-            rdsst::init(d[c], b->p.sps);
+            rdsst::init(d[c], b->c.p.sps);
             rdsst::clear_record(&r[c]);
         }
         FMRX_HIP(hipMemcpy(b->dec.p + lo, d.data(), cnt * sizeof(rdsst::Dec), hipMemcpyHostToDevice));
@@ -435,77 +570,27 @@ extern "C" {
 int fmrx_rds_bank_create(fmrx_rds_bank **out, const fmrx_rds_params *p, int n_channels, size_t block, int device)
 {
     if (!out || !p) return fail(FMRX_EINVAL, "rds_bank_create: null argument");
-    if (p->taps < 3 || p->taps > 65535 || p->upsamp < 1 || p->decim < 1 || p->sps < 1 || p->rrc_taps < 2 || p->if_Fs <= 0)
-        return fail(FMRX_EINVAL, "rds_bank_create: bad parameters");
-    if (n_channels < 1) return fail(FMRX_EINVAL, "rds_bank_create: n_channels must be >= 1");
-    if (block == 0 || block > (1u << 30) || (block * p->upsamp) % p->decim)
-        return fail(FMRX_EINVAL, "rds_bank_create: block of %zu samples: block*upsamp must be a multiple of decim %d", block, p->decim);
-    const int delay = (p->taps - 1) / 2, Hx = p->taps - 1, Hm = (101 * p->upsamp - 1) / p->upsamp, Hc = std::max(p->taps - 1, delay + 1),
-              Hr = p->rrc_taps - 1;
-    const size_t n_out = block * p->upsamp / p->decim;
-    // every carried history is refreshed by a copy of its row's tail to its front: the block must be at least as long as each
-    if (block < static_cast<size_t>(std::max(std::max(Hx, Hc), Hm)) || n_out < static_cast<size_t>(Hr))
-        return fail(FMRX_EINVAL, "rds_bank_create: block of %zu samples is shorter than a filter history (%d / %d / %d input samples, %d resampled)",
-                    block, Hx, Hc, Hm, Hr);
-    FMRX_TRY(require_device());
-    FMRX_HIP(hipSetDevice(device));
     fmrx_rds_bank *b = new fmrx_rds_bank;
-    b->p = *p;
-    b->n_channels = n_channels;
-    b->device = device;
-    b->block = static_cast<long>(block);
-    b->n_out = static_cast<long>(n_out);
-    b->max_bits = b->n_out / p->sps + 4;
-    b->max_g = p->sps >= 2 ? static_cast<long>(rdsst::max_groups_for_samples(static_cast<uint64_t>(b->n_out), p->sps)) : 0;
-    b->delay = delay;
-    b->Hx = Hx;
-    b->Hc = Hc;
-    b->Hm = Hm;
-    b->Hr = Hr;
-    const long n = b->block, no = b->n_out;
-    b->xpitch = pitch_of(Hx + n);
-    b->cpitch = pitch_of(Hc + n);
-    b->apitch = pitch_of(n);
-    b->npitch = pitch_of(n + 1);
-    b->mpitch = pitch_of(Hm + n);
-    b->rpitch = pitch_of(Hr + no);
-    b->ypitch = pitch_of(no);
+    auto checks = [&]() -> int {                    // before any device call
+        FMRX_TRY(b->c.plan("rds_bank_create", p, n_channels, block));
+        if (n_channels < 1) return fail(FMRX_EINVAL, "rds_bank_create: n_channels must be >= 1");
+        if (block == 0 || block > (1u << 30) || (block * p->upsamp) % p->decim)
+            return fail(FMRX_EINVAL, "rds_bank_create: block of %zu samples: block*upsamp must be a multiple of decim %d", block, p->decim);
+        FMRX_TRY(b->c.check_block("rds_bank_create", block));
+        return require_device();
+    };
+    int rc = checks();
+    if (rc != FMRX_OK) {
+        delete b;
+        return rc;
+    }
     auto body = [&]() -> int {
-        const int rs_taps = 101 * p->upsamp;
-        std::vector<double> h(std::max(rs_taps, p->taps));
-        auto up = [&](DevBuf<double> &d, int cnt) -> int {
-            FMRX_TRY(d.alloc(cnt));
-            FMRX_HIP(hipMemcpy(d.p, h.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
-            return FMRX_OK;
-        };
-        // the single-stream handle's taps (fmrx_rds_create; fmMonoBlock.py:138-141)
-        design_bpf64(p->taps, p->if_Fs, 54e3, 60e3, h.data());
-        FMRX_TRY(up(b->h_ch, p->taps));
-        design_bpf64(p->taps, p->if_Fs, 113.5e3, 114.5e3, h.data());
-        FMRX_TRY(up(b->h_car, p->taps));
-        design_lpf64(rs_taps, static_cast<double>(p->if_Fs) * p->upsamp, 3e3, h.data());
-        FMRX_TRY(up(b->h_rs, rs_taps));
-        design_rrc64(2375.0 * p->sps, p->rrc_taps, h.data());
-        FMRX_TRY(up(b->h_rrc, p->rrc_taps));
+        FMRX_HIP(hipSetDevice(device));
+        b->n_out = static_cast<long>(b->c.n_out(block));
+        b->max_bits = b->n_out / p->sps + 4;
+        b->max_g = p->sps >= 2 ? static_cast<long>(rdsst::max_groups_for_samples(static_cast<uint64_t>(b->n_out), p->sps)) : 0;
+        FMRX_TRY(b->c.create(device));
         const size_t N = static_cast<size_t>(n_channels);
-        auto rows = [&](DevBuf<double> &d, long pitch) -> int {
-            FMRX_TRY(d.alloc(static_cast<size_t>(pitch) * N));
-            FMRX_HIP(hipMemset(d.p, 0, d.bytes()));
-            return FMRX_OK;
-        };
-        FMRX_TRY(rows(b->x, b->xpitch));
-        FMRX_TRY(rows(b->ch, b->cpitch));
-        FMRX_TRY(rows(b->car, b->apitch));
-        FMRX_TRY(rows(b->arg, b->apitch));
-        FMRX_TRY(rows(b->nco_i, b->npitch));
-        FMRX_TRY(rows(b->nco_q, b->npitch));
-        FMRX_TRY(rows(b->mi, b->mpitch));
-        FMRX_TRY(rows(b->mq, b->mpitch));
-        FMRX_TRY(rows(b->ri, b->rpitch));
-        FMRX_TRY(rows(b->rq, b->rpitch));
-        FMRX_TRY(rows(b->yi, b->ypitch));
-        FMRX_TRY(rows(b->yq, b->ypitch));
-        FMRX_TRY(b->state.alloc(8 * N));
         FMRX_TRY(b->blk.alloc(N));
         FMRX_TRY(b->bits.alloc(static_cast<size_t>(b->max_bits) * N));
         FMRX_TRY(b->n_bits.alloc(N));
@@ -516,7 +601,7 @@ int fmrx_rds_bank_create(fmrx_rds_bank **out, const fmrx_rds_params *p, int n_ch
         FMRX_HIP(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
         return bank_reset(b, 0, n_channels);
     };
-    const int rc = body();
+    rc = body();
     if (rc != FMRX_OK) {
         fmrx_rds_bank_destroy(b);
         return rc;
@@ -528,7 +613,7 @@ int fmrx_rds_bank_create(fmrx_rds_bank **out, const fmrx_rds_params *p, int n_ch
 int fmrx_rds_bank_destroy(fmrx_rds_bank *b)
 {
     if (!b) return FMRX_OK;
-    (void)hipSetDevice(b->device);
+    (void)hipSetDevice(b->c.device);
     (void)hipDeviceSynchronize();
     if (b->stream) (void)hipStreamDestroy(b->stream);
     if (b->done) (void)hipEventDestroy(b->done);
@@ -539,10 +624,10 @@ int fmrx_rds_bank_destroy(fmrx_rds_bank *b)
 int fmrx_rds_bank_reset(fmrx_rds_bank *b, int channel)
 {
     if (!b) return fail(FMRX_EINVAL, "rds_bank_reset: null handle");
-    if (channel >= b->n_channels) return fail(FMRX_EINVAL, "rds_bank_reset: channel %d of %d", channel, b->n_channels);
+    if (channel >= b->c.n_channels) return fail(FMRX_EINVAL, "rds_bank_reset: channel %d of %d", channel, b->c.n_channels);
     if (b->pending) return fail(FMRX_EINVAL, "rds_bank_reset: the last process_dev has not been collected");
     if (channel < 0) {
-        FMRX_TRY(bank_reset(b, 0, b->n_channels));
+        FMRX_TRY(bank_reset(b, 0, b->c.n_channels));
         b->fresh = true;
         return FMRX_OK;
     }
@@ -553,11 +638,11 @@ int fmrx_rds_bank_set_stations(fmrx_rds_bank *b, int on)
 {
     if (!b) return fail(FMRX_EINVAL, "rds_bank_set_stations: null handle");
     if (!b->fresh) return fail(FMRX_EINVAL, "rds_bank_set_stations: only before the first call or right after fmrx_rds_bank_reset(b, -1)");
-    if (on && (b->p.sps < 2 || b->p.sps > rdsst::kMaxSps))
-        return fail(FMRX_EINVAL, "rds_bank_set_stations: the station decoder takes 2..%d samples per chip, not %d", rdsst::kMaxSps, b->p.sps);
+    if (on && (b->c.p.sps < 2 || b->c.p.sps > rdsst::kMaxSps))
+        return fail(FMRX_EINVAL, "rds_bank_set_stations: the station decoder takes 2..%d samples per chip, not %d", rdsst::kMaxSps, b->c.p.sps);
     if (on && !b->dec.p) {
-        FMRX_HIP(hipSetDevice(b->device));
-        const size_t N = static_cast<size_t>(b->n_channels);
+        FMRX_HIP(hipSetDevice(b->c.device));
+        const size_t N = static_cast<size_t>(b->c.n_channels);
         FMRX_TRY(b->dec.alloc(N));
         FMRX_TRY(b->energy.alloc(N * rdsst::kMaxSps));
         FMRX_TRY(b->st.alloc(N));
@@ -566,7 +651,7 @@ int fmrx_rds_bank_set_stations(fmrx_rds_bank *b, int on)
         FMRX_TRY(b->n_g.alloc(N));
         b->h_n_g.resize(N);
         b->stations = true;                         // (bank_reset initialises what is allocated)
-        const int rc = bank_reset(b, 0, b->n_channels);
+        const int rc = bank_reset(b, 0, b->c.n_channels);
         if (rc != FMRX_OK) {
             b->stations = false;
             b->dec.release();
@@ -584,10 +669,10 @@ int fmrx_rds_bank_stations(fmrx_rds_bank *b, fmrx_rds_station *st, fmrx_rds_grou
     if (!b || !st) return fail(FMRX_EINVAL, "rds_bank_stations: null argument");
     if ((g == nullptr) != (n_g == nullptr)) return fail(FMRX_EINVAL, "rds_bank_stations: g and n_g go together");
     if (!b->stations) return fail(FMRX_EINVAL, "rds_bank_stations: stations are off (fmrx_rds_bank_set_stations)");
-    FMRX_HIP(hipSetDevice(b->device));
+    FMRX_HIP(hipSetDevice(b->c.device));
     b->pending = false;
     hipStream_t s = b->stream;
-    const size_t N = static_cast<size_t>(b->n_channels);
+    const size_t N = static_cast<size_t>(b->c.n_channels);
     FMRX_HIP(hipStreamWaitEvent(s, b->done, 0));
     FMRX_HIP(hipMemcpyAsync(st, b->st.p, N * sizeof(fmrx_rds_station), hipMemcpyDeviceToHost, s));
     if (g) {
@@ -606,43 +691,23 @@ size_t fmrx_rds_bank_max_bits(const fmrx_rds_bank *b) { return b ? static_cast<s
 int fmrx_rds_bank_process_dev(fmrx_rds_bank *b, const float *d_demod, size_t pitch, void *stream)
 {
     if (!b || !d_demod) return fail(FMRX_EINVAL, "rds_bank_process_dev: null argument");
-    if (pitch < static_cast<size_t>(b->block))
-        return fail(FMRX_EINVAL, "rds_bank_process_dev: pitch %zu floats is shorter than the block (%ld)", pitch, b->block);
+    if (pitch < static_cast<size_t>(b->c.block))
+        return fail(FMRX_EINVAL, "rds_bank_process_dev: pitch %zu floats is shorter than the block (%ld)", pitch, b->c.block);
     // every frame-sync report depends on the bits of every earlier call: they are never dropped
     if (b->pending) return fail(FMRX_EINVAL, "rds_bank_process_dev: the previous call has not been collected (fmrx_rds_bank_collect)");
-    FMRX_HIP(hipSetDevice(b->device));
+    FMRX_HIP(hipSetDevice(b->c.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const fmrx_rds_params &p = b->p;
-    const long n = b->block, no = b->n_out;
-    const unsigned N = static_cast<unsigned>(b->n_channels), lanes = (N + 63) / 64;
-    auto tiles = [](long cnt, long per) { return static_cast<unsigned>((cnt + per - 1) / per); };
-    double *x = b->x.p + b->Hx, *ch = b->ch.p + b->Hc, *mi = b->mi.p + b->Hm, *mq = b->mq.p + b->Hm, *ri = b->ri.p + b->Hr, *rq = b->rq.p + b->Hr;
-    const double phase_adjust = 3 * kPi / 8;
-    hipLaunchKernelGGL(rdsb_cvt_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, d_demod, static_cast<long>(pitch), n, x, b->xpitch);
-    hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, x, x, b->xpitch, n, b->h_ch.p, p.taps, ch, ch, b->cpitch);
-    hipLaunchKernelGGL(rdsb_fir_kernel<true>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, ch, ch, b->cpitch, n, b->h_car.p, p.taps, b->car.p,
-                       b->car.p, b->apitch);
-    hipLaunchKernelGGL(rdsb_pll_lanes_kernel, dim3(lanes), dim3(64), 0, s, b->car.p, b->apitch, n, b->n_channels, b->arg.p, b->state.p,
-                       b->nco_i.p, b->nco_q.p, b->npitch, 114e3, static_cast<double>(p.if_Fs), 0.002, 0.5, phase_adjust);
-    hipLaunchKernelGGL(rdsb_mix_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, b->arg.p, b->apitch, n, ch, b->cpitch, b->delay, 0.5, phase_adjust,
-                       b->nco_i.p, b->nco_q.p, b->npitch, mi, mq, b->mpitch);
-    hipLaunchKernelGGL(rdsb_resample_kernel, dim3(N, tiles(no, 256)), dim3(256), 0, s, mi, mq, b->mpitch, no, b->h_rs.p, 101 * p.upsamp, p.decim,
-                       p.upsamp, ri, rq, b->rpitch);
-    hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(no, 256 * kR), 2), dim3(256), 0, s, ri, rq, b->rpitch, no, b->h_rrc.p, p.rrc_taps,
-                       b->yi.p, b->yq.p, b->ypitch);
-    // fmMonoBlock.py:276-280 (fmrx_rds_process): the CDR state is re-made every block
-    hipLaunchKernelGGL(rdsb_cdr_kernel, dim3(lanes), dim3(64), 0, s, b->yi.p, b->ypitch, no, b->n_channels, p.sps, 0.0, 0.0, 158L, 0L, b->blk.p,
-                       b->bits.p, b->max_bits, b->n_bits.p);
-    if (b->stations)
-        hipLaunchKernelGGL(rdsb_station_kernel, dim3(lanes), dim3(64), (kStB + p.sps) * 64 * sizeof(double), s, b->yi.p, b->ypitch, no,
-                           b->n_channels, b->dec.p, b->energy.p, b->st.p, b->grp.p, static_cast<int>(b->max_g), b->n_g.p);
-    hipLaunchKernelGGL(rdsb_tail_kernel, dim3(N), dim3(256), 0, s, b->x.p, b->xpitch, b->Hx, b->ch.p, b->cpitch, b->Hc, b->mi.p, b->mq.p, b->mpitch,
-                       b->Hm, b->ri.p, b->rq.p, b->rpitch, b->Hr, n, no);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "rds bank kernels: %s", hipGetErrorString(e));
+    const CdrRows cdr{b->blk.p, b->bits.p, b->max_bits, b->n_bits.p};
+    FMRX_TRY(b->c.run(d_demod, pitch, static_cast<size_t>(b->c.block), s, &cdr));
+    if (b->stations) {
+        const unsigned lanes = (static_cast<unsigned>(b->c.n_channels) + 63) / 64;
+        hipLaunchKernelGGL(rdsb_station_kernel, dim3(lanes), dim3(64), (kStB + b->c.p.sps) * 64 * sizeof(double), s, b->c.yi.p, b->c.ypitch, b->n_out,
+                           b->c.n_channels, b->dec.p, b->energy.p, b->st.p, b->grp.p, static_cast<int>(b->max_g), b->n_g.p);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(FMRX_EHIP, "rds bank kernels: %s", hipGetErrorString(e));
+    }
     FMRX_HIP(hipEventRecord(b->done, s));
     b->pending = true;
-    b->calls++;
     b->fresh = false;
     return FMRX_OK;
 }
@@ -651,16 +716,16 @@ int fmrx_rds_bank_collect(fmrx_rds_bank *b, double *rrc_i, double *rrc_q, uint8_
 {
     if (!b) return fail(FMRX_EINVAL, "rds_bank_collect: null handle");
     if (!b->pending) return fail(FMRX_EINVAL, "rds_bank_collect: no call to collect");
-    FMRX_HIP(hipSetDevice(b->device));
+    FMRX_HIP(hipSetDevice(b->c.device));
     b->pending = false;
     hipStream_t s = b->stream;
-    const size_t N = static_cast<size_t>(b->n_channels), no = static_cast<size_t>(b->n_out), mb = static_cast<size_t>(b->max_bits);
+    const size_t N = static_cast<size_t>(b->c.n_channels), no = static_cast<size_t>(b->n_out), mb = static_cast<size_t>(b->max_bits);
     FMRX_HIP(hipStreamWaitEvent(s, b->done, 0));
     FMRX_HIP(hipMemcpyAsync(b->h_bits.data(), b->bits.p, N * mb, hipMemcpyDeviceToHost, s));
     FMRX_HIP(hipMemcpyAsync(b->h_n_bits.data(), b->n_bits.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    const size_t yp = static_cast<size_t>(b->ypitch) * sizeof(double);
-    if (rrc_i) FMRX_HIP(hipMemcpy2DAsync(rrc_i, no * sizeof(double), b->yi.p, yp, no * sizeof(double), N, hipMemcpyDeviceToHost, s));
-    if (rrc_q) FMRX_HIP(hipMemcpy2DAsync(rrc_q, no * sizeof(double), b->yq.p, yp, no * sizeof(double), N, hipMemcpyDeviceToHost, s));
+    const size_t yp = static_cast<size_t>(b->c.ypitch) * sizeof(double);
+    if (rrc_i) FMRX_HIP(hipMemcpy2DAsync(rrc_i, no * sizeof(double), b->c.yi.p, yp, no * sizeof(double), N, hipMemcpyDeviceToHost, s));
+    if (rrc_q) FMRX_HIP(hipMemcpy2DAsync(rrc_q, no * sizeof(double), b->c.yq.p, yp, no * sizeof(double), N, hipMemcpyDeviceToHost, s));
     FMRX_HIP(hipStreamSynchronize(s));
     // fmMonoBlock.py:283-297, per channel: frame synchronisation over the bits kept so far
     for (size_t c = 0; c < N; c++) {
@@ -668,11 +733,7 @@ int fmrx_rds_bank_collect(fmrx_rds_bank *b, double *rrc_i, double *rrc_q, uint8_
         const uint8_t *d = b->h_bits.data() + c * mb;
         if (bits) std::memcpy(bits + c * mb, d, nb);
         if (n_bits) n_bits[c] = nb;
-        std::vector<uint8_t> &dec = b->decoded[c];
-        dec.insert(dec.end(), d, d + nb);
-        size_t next = 0;
-        const char *off = frame_sync(dec.data(), dec.size(), &next);
-        dec.erase(dec.begin(), dec.begin() + static_cast<long>(std::min(next, dec.size())));
+        const char *off = frame_sync_append(b->decoded[c], d, nb);
         if (offset_type) std::strcpy(offset_type + 8 * c, off);
     }
     return FMRX_OK;
@@ -682,8 +743,8 @@ int fmrx_rds_bank_process(fmrx_rds_bank *b, const float *demod, double *rrc_i, d
 {
     if (!b || !demod) return fail(FMRX_EINVAL, "rds_bank_process: null argument");
     if (b->pending) return fail(FMRX_EINVAL, "rds_bank_process: the previous call has not been collected (fmrx_rds_bank_collect)");
-    FMRX_HIP(hipSetDevice(b->device));
-    const size_t n = static_cast<size_t>(b->block), N = static_cast<size_t>(b->n_channels);
+    FMRX_HIP(hipSetDevice(b->c.device));
+    const size_t n = static_cast<size_t>(b->c.block), N = static_cast<size_t>(b->c.n_channels);
     FMRX_TRY(b->in.ensure(n * N));
     FMRX_HIP(hipMemcpyAsync(b->in.p, demod, n * N * sizeof(float), hipMemcpyHostToDevice, b->stream));
     FMRX_TRY(fmrx_rds_bank_process_dev(b, b->in.p, n, b->stream));
@@ -693,28 +754,8 @@ int fmrx_rds_bank_process(fmrx_rds_bank *b, const float *demod, double *rrc_i, d
 int fmrx_rds_bank_read_tap(fmrx_rds_bank *b, int channel, int which, double *out, size_t *n)
 {
     if (!b || !n) return fail(FMRX_EINVAL, "rds_bank_read_tap: null argument");
-    if (channel < 0 || channel >= b->n_channels) return fail(FMRX_EINVAL, "rds_bank_read_tap: channel %d of %d", channel, b->n_channels);
-    const long c = channel;
-    const size_t last_n = b->calls ? static_cast<size_t>(b->block) : 0, last_out = b->calls ? static_cast<size_t>(b->n_out) : 0;
-    const double *src = nullptr;
-    size_t cnt = 0;
-    switch (which) {
-    case FMRX_RDS_TAP_CHANNEL: src = b->ch.p + c * b->cpitch + b->Hc; cnt = last_n; break;   // after the tail copy the block region is intact
-    case FMRX_RDS_TAP_CARRIER: src = b->car.p + c * b->apitch; cnt = last_n; break;
-    case FMRX_RDS_TAP_PLL_I: src = b->nco_i.p + c * b->npitch; cnt = last_n ? last_n + 1 : 0; break;
-    case FMRX_RDS_TAP_PLL_Q: src = b->nco_q.p + c * b->npitch; cnt = last_n ? last_n + 1 : 0; break;
-    case FMRX_RDS_TAP_RESAMPLED_I: src = b->ri.p + c * b->rpitch + b->Hr; cnt = last_out; break;
-    case FMRX_RDS_TAP_RRC_I: src = b->yi.p + c * b->ypitch; cnt = last_out; break;
-    case FMRX_RDS_TAP_RRC_Q: src = b->yq.p + c * b->ypitch; cnt = last_out; break;
-    case FMRX_RDS_TAP_PLL_STATE: src = b->state.p + 8 * c; cnt = 7; break;
-    default: return fail(FMRX_EINVAL, "rds_bank_read_tap: unknown tap %d", which);
-    }
-    *n = cnt;
-    if (!out || cnt == 0) return FMRX_OK;
-    FMRX_HIP(hipSetDevice(b->device));
-    FMRX_HIP(hipDeviceSynchronize());
-    FMRX_HIP(hipMemcpy(out, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
-    return FMRX_OK;
+    if (channel < 0 || channel >= b->c.n_channels) return fail(FMRX_EINVAL, "rds_bank_read_tap: channel %d of %d", channel, b->c.n_channels);
+    return b->c.tap("rds_bank_read_tap", channel, which, out, n);
 }
 
 }  // extern "C"

@@ -144,5 +144,14 @@ const char *frame_sync(const uint8_t *bits, size_t n, size_t *next_index)
     return off;
 }
 
+const char *frame_sync_append(std::vector<uint8_t> &kept, const uint8_t *bits, size_t nb)
+{
+    kept.insert(kept.end(), bits, bits + nb);
+    size_t next = 0;
+    const char *off = frame_sync(kept.data(), kept.size(), &next);
+    kept.erase(kept.begin(), kept.begin() + static_cast<long>(std::min(next, kept.size())));
+    return off;
+}
+
 }  // namespace rds
 }  // namespace fmrx

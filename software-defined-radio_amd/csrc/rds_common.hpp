@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace fmrx {
 namespace rds {
@@ -21,6 +22,10 @@ size_t cdr(const double *x, size_t n, int sps, int block_count, double *state, u
 // fmSupportLib.py:30-100: the last offset word recognised in bits[0, n) ("A", "B", "C", "C_apos", "D" or " ") and the index
 // the next call starts from
 const char *frame_sync(const uint8_t *bits, size_t n, size_t *next_index);
+
+// fmMonoBlock.py:283-297: frame synchronisation over the bits kept so far.  Appends a block's nb decoded bits to `kept`, returns
+// the offset word frame_sync finds in them and drops the bits in front of the index the next block starts from.
+const char *frame_sync_append(std::vector<uint8_t> &kept, const uint8_t *bits, size_t nb);
 
 }  // namespace rds
 }  // namespace fmrx

@@ -4,7 +4,7 @@ rds_signal.py sends random information words; a station decoder needs real group
 (RadioText) of one PI and PTY, with their checkwords and offset words (IEC 62106; C' = 0x350 for version-B groups).  The bits
 are modulated as rds_signal.rds_demod_signal does (differential encoding, biphase chips, half-sine chip shape on a 57 kHz
 subcarrier locked to the pilot, plus a mono programme), with the chip rate as an argument: a transmitter off by +-150 ppm
-exercises the decoder's chip timing.  station_iq_u8 turns the multiplex into u8 I/Q at 2.4 MS/s as test_gpu_rds_bank.rds_iq_u8
+exercises the decoder's chip timing.  station_iq_u8 turns the multiplex into u8 I/Q at 2.4 MS/s as _rds_util.rds_iq_u8
 does."""
 import numpy as np
 

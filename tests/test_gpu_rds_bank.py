@@ -1,67 +1,28 @@
 """RDS banks (fmrx_rds_bank_*, RdsBank): the RDS chain of N channels per device call.
 
-The bank's arithmetic is the single-stream handle's (fmrx_rds), so every channel is compared with np.array_equal (no
-tolerance) against an Rds handle fed the same rows; against the reference's model (tests/golden/rds.npz) with the tolerances
-of test_gpu_rds.py; and behind a receiver bank on the device, against the oracle (oracle pipeline -> oracle/rds_oracle.py)."""
+The bank and the single-stream handle (fmrx_rds) run the same device chain, so every channel is compared with np.array_equal
+(no tolerance) against an Rds handle fed the same rows: that pins a channel in any lane to a chain of one channel, and the
+device's bit recovery to the host's.  Also: against the stage model (tests/_rds_stage_model.py), against the reference's
+model (tests/golden/rds.npz) with the tolerances of test_gpu_rds.py, and behind a receiver bank on the device, against the
+oracle (oracle pipeline -> oracle/rds_oracle.py)."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
+from _rds_stage_model import stage_model
+from _rds_util import BLOCK, N, ROOT, SMALL, bank_streams, ht, rds_iq_u8, rel, same
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
 G = np.load(os.path.join(ROOT, "tests", "golden", "rds.npz"))
-BLOCK = 9600                     # IF samples per call: the receiver banks' block_bytes 192 000 at rf_decim 10
-N = 70                           # a full wave of lanes and a partial one
-
-
-def rds_iq_u8(n_blocks, seed=5, amplitude=0.06, chip_offset=600.0):
-    """u8 I/Q at 2.4 MS/s of an FM transmitter whose multiplex carries RDS: rds_demod_signal sampled at the RF rate is the
-    phase increment per IF sample, so a tenth of it per RF sample; 192 000 bytes per block.  -> (iq, transmitted bits)."""
-    from rds_signal import rds_demod_signal
-    n_rf = BLOCK * 10 * n_blocks
-    x, bits = rds_demod_signal(n_rf, 2.4e6, seed=seed, amplitude=amplitude, chip_offset=chip_offset)
-    phi = np.cumsum(x.astype(np.float64) / 10.0)
-    iq = np.empty(2 * n_rf, np.uint8)
-    iq[0::2] = np.clip(np.floor(128.0 + 127.0 * 0.8 * np.cos(phi) + 0.5), 0, 255)
-    iq[1::2] = np.clip(np.floor(128.0 + 127.0 * 0.8 * np.sin(phi) + 0.5), 0, 255)
-    return iq, bits
-
-
-def bank_streams(n_blocks, n=N):
-    """n discriminator streams: different seeds, chip offsets, amplitudes and noise; channel 5 all zeros, channel 9 zeros
-    for the first two and a half blocks, then signal."""
-    from rds_signal import rds_demod_signal
-    rows = []
-    for c in range(n):
-        x, _ = rds_demod_signal(n_blocks * BLOCK, 240e3, seed=100 + c, amplitude=0.03 + 0.01 * (c % 7), chip_offset=float((37 * c) % 101),
-                                noise=0.002 * (c % 4))
-        rows.append(x)
-    rows = np.stack(rows)
-    rows[5] = 0.0
-    rows[9, :5 * BLOCK // 2] = 0.0
-    return rows
-
-
-def same(a, b, msg):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8)), msg
-
-
-def ht(a, n=256):
-    return a if len(a) <= 2 * n else np.concatenate([a[:n], a[-n:]])
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+TAPS = ("channel", "carrier", "pll_i", "pll_q", "resampled_i", "pll_state")
 
 
 @pytest.mark.parametrize("mode", [0, 2])
 def test_bank_equals_single_stream_handles(fmrx, mode):
+    """Both sides run the same kernels, so this proves two things, bit for bit: channel c of a 70-channel bank (a lane other
+    than 0, the second wave only partly filled) equals a chain of one channel; and the device's clock and data recovery
+    (rdsb_cdr_kernel, which only the bank runs) equals the host's cdr(), which the single-stream handle calls."""
     nb = 6
     rows = bank_streams(nb)
     bank = fmrx.RdsBank(mode, N, BLOCK)
@@ -77,9 +38,51 @@ def test_bank_equals_single_stream_handles(fmrx, mode):
             assert got["offset_type"][c] == want["offset_type"], (mode, b, c)
             synced += want["offset_type"] != " "
             if c in (0, 9, 63, 64, 69):
-                for tap in ("channel", "carrier", "pll_i", "pll_q", "resampled_i", "pll_state"):
+                for tap in TAPS:
                     same(bank.read_tap(c, tap), singles[c].read_tap(tap), f"mode {mode} block {b} channel {c}: tap {tap}")
     assert synced > N, "the fixture must exercise frame synchronisation"
+    bank.close()
+
+
+def test_bank_remainder_paths_in_every_lane(fmrx):
+    """A block of 333 samples (no rate change) leaves 13 samples to the PLL lanes' remainder loop and one to the FIR's last
+    quad: 70 channels over three blocks against 70 single-stream handles, bit for bit."""
+    n, nb = 333, 3
+    rows = bank_streams(nb, block=n)
+    p = fmrx.RdsParams(*SMALL)
+    bank = fmrx.RdsBank(params=p, n_channels=N, block=n)
+    singles = [fmrx.Rds(params=p, max_block=n) for _ in range(N)]
+    for b in range(nb):
+        blk = rows[:, b * n:(b + 1) * n]
+        got = bank.process(blk)
+        for c in range(N):
+            want = singles[c].process(blk[c])
+            for k in ("rrc_i", "rrc_q", "diff_bits"):
+                same(got[k][c], want[k], f"block {b} channel {c}: {k}")
+            assert got["offset_type"][c] == want["offset_type"], (b, c)
+            if c in (0, 9, 63, 64, 69):
+                for tap in TAPS:
+                    same(bank.read_tap(c, tap), singles[c].read_tap(tap), f"block {b} channel {c}: tap {tap}")
+    bank.close()
+
+
+def test_bank_stages_equal_the_stage_model(fmrx):
+    """Channels 0, 63 and 69 of 70 (the first and last lane of a full wave, the last of a partial one) at block 333 against
+    tests/_rds_stage_model.py, bit for bit, over two blocks (the second runs on carried histories)."""
+    n, nb = 333, 2
+    rows = bank_streams(nb, block=n)
+    p = fmrx.RdsParams(*SMALL)
+    bank = fmrx.RdsBank(params=p, n_channels=N, block=n)
+    models = {c: stage_model(fmrx, p) for c in (0, 63, 69)}
+    for b in range(nb):
+        blk = rows[:, b * n:(b + 1) * n]
+        got = bank.process(blk)
+        for c, m in models.items():
+            dev = {k: bank.read_tap(c, k) for k in TAPS}
+            dev.update(rrc_i=got["rrc_i"][c], rrc_q=got["rrc_q"][c])
+            for k, want in m.step(blk[c], dev).items():
+                same(dev[k], want, f"block {b} channel {c}: {k}")
+            assert dev["pll_state"][5] == (b + 1) * n
     bank.close()
 
 

@@ -1,39 +1,13 @@
 """RDS station decoding on the device: the single-stream handle's matched-filter rows into the host decoder, and the RDS bank's
 lane-per-channel decoder (fmrx_rds_bank_set_stations / _stations), whose station and group records must equal, byte for byte,
 what the host decoder (fmrx_rds_station_feed_rrc) makes of the same channel's rows as collect returns them."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
+import rds_groups as RG
+from _rds_util import BLOCK, LATE, N, SILENT, channel_station, station_rows
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-
-import rds_groups as RG  # noqa: E402
-
-BLOCK = 9600
-N = 70                           # a full wave of lanes and a partial one
-SILENT, LATE = 5, 9
-
-
-def channel_station(c):
-    return dict(pi=0x1000 + 37 * c, pty=c % 32, ps=f"ST{c:03d}  ".ljust(8)[:8], rt=f"CHANNEL {c} RADIOTEXT"[:20])
-
-
-def bank_rows(n_blocks, n=N):
-    """n stations, each with its own PI, PS, RT, amplitude, noise and chip offset (and chip rate); SILENT all zeros; LATE
-    zeros for the first 5.5 calls."""
-    rows = []
-    for c in range(n):
-        s = channel_station(c)
-        rows.append(RG.station_demod(n_blocks * BLOCK, amplitude=0.04 + 0.01 * (c % 5), noise=0.002 * (c % 4), chip_offset=float((53 * c) % 211),
-                                     chip_rate=2375.0 * (1 + (c % 7 - 3) * 40e-6), seed=300 + c, **s))
-    rows = np.stack(rows)
-    rows[SILENT] = 0.0
-    rows[LATE, :11 * BLOCK // 2] = 0.0
-    return rows
 
 
 def run_bank_and_host(fmrx, mode, rows, n_blocks, reset_at=None):
@@ -69,7 +43,7 @@ def test_single_stream_handle_and_host_decoder(fmrx):
 @pytest.mark.parametrize("mode", [0, 2])
 def test_bank_stations_equal_the_host_decoder(fmrx, mode):
     nb = 36
-    rows = bank_rows(nb)
+    rows = station_rows(nb)
     bank, recs = run_bank_and_host(fmrx, mode, rows, nb)
     st = [fmrx.rds_station_dict(r) for r in recs]
     for c in range(N):
@@ -84,7 +58,7 @@ def test_bank_stations_equal_the_host_decoder(fmrx, mode):
 
 def test_bank_reset_of_one_channel(fmrx):
     nb = 30
-    rows = bank_rows(nb)
+    rows = station_rows(nb)
     bank, recs = run_bank_and_host(fmrx, 0, rows, nb, reset_at=(6, 7))    # equality with a host decoder reset at the same call
     st = fmrx.rds_station_dict(recs[7])
     assert st["ps"] == channel_station(7)["ps"]
@@ -104,7 +78,7 @@ def test_bank_reset_of_one_channel(fmrx):
 
 def test_stations_off_changes_nothing(fmrx):
     nb = 4
-    rows = bank_rows(nb)
+    rows = station_rows(nb)
     for mode in (0, 2):
         off, on = fmrx.RdsBank(mode, N, BLOCK), fmrx.RdsBank(mode, N, BLOCK)
         on.set_stations(True)

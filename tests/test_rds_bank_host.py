@@ -62,7 +62,7 @@ def test_receiver_bank_rds_fixture_is_meaningful(oracle):
     bit) and the oracle's RDS chain: within a block the recovered bits ARE the transmitted ones (>= 97 %, as
     test_rds_chain_against_the_reference_model checks for rds.npz), and the frame synchroniser finds offset words."""
     import rds_oracle as R
-    from test_gpu_rds_bank import rds_iq_u8
+    from _rds_util import rds_iq_u8
     nb = 4
     for c in range(3):
         iq, tx = rds_iq_u8(nb, seed=5 + c, chip_offset=600.0 + 97 * c)

@@ -1,7 +1,8 @@
 """oracle/rds_oracle.py (numpy / Python restatement of the reference's RDS path) against tests/golden/rds.npz, the output of
 the reference's OWN Python model (model/fmSupportLib.py imported in the build container by tests/golden/make_golden_rds.py).
 Coefficients and bit-level results exact; float64 signal stages to 1e-12 of full scale (scipy's lfilter and a plain
-convolution sum in different orders)."""
+convolution sum in different orders).  Also: the stage model of the device chain (tests/_rds_stage_model.py) against the
+oracle, stage by stage."""
 import hashlib
 import os
 import sys
@@ -51,6 +52,25 @@ def test_rds_chain_and_bits():
         fs = G[f"b{b}_framesync"]
         assert (ord(out["offset_type"][0]), len(out["offset_type"]), out["next_index"]) == tuple(int(v) for v in fs)
     close(np.array(chain.pll, float), G["pll_state"], 1e-9, "PLL state")
+
+
+def test_stage_model_against_the_oracle():
+    """tests/_rds_stage_model.py, fed the oracle's output of each stage, gives the oracle's next stage to 1e-12 of full scale:
+    the same arithmetic, summed in the device's order instead of np.convolve's.  Shapes: the block sequences of
+    test_gpu_rds.py (mode 0 and the chain without rate change, blocks that are no multiple of 32 or 4)."""
+    from _rds_stage_model import StageModel
+    from rds_signal import rds_demod_signal
+    x, _ = rds_demod_signal(9600, 240e3, seed=21, chip_offset=66.0, noise=0.01)
+    for (U, D), blocks in (((247, 960), (960, 2880, 960, 1920)), ((1, 1), (333, 270, 303, 332))):
+        o = R.RdsChain(upsamp=U, decim=D)
+        m = StageModel(U, D, o.h_ch, o.h_car, o.h_rs, o.h_rrc)
+        at = 0
+        for n in blocks:
+            want = o.process(x[at:at + n])
+            got = m.step(x[at:at + n], want)
+            for k in ("channel", "carrier", "resampled_i", "rrc_i", "rrc_q"):
+                close(got[k], want[k], 1e-12, f"U/D {U}/{D} block at {at} {k}")
+            at += n
 
 
 def test_bit_recovery_corner_cases():

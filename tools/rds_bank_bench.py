@@ -14,8 +14,9 @@ twice, the second time with the bank's station decoders on (fmrx_rds_bank_set_st
   stations_ms              host time of the fmrx_rds_bank_stations call (records + groups D2H), preallocated buffers
   collect_c_ms             host time of the fmrx_rds_bank_collect call on the same bank, preallocated buffers, no rows
   ps_right                 channels whose decoded PS name is the transmitted one after the last call
-and, once: float64 operations per IF sample counted from the shapes, and the single-stream handle (fmrx_rds) on one of the same
-streams: process_dev device time and fmrx_rds_process host time per block.  Channel counts that do not fit the device's free
+and, once: float64 operations per IF sample counted from the shapes, and the single-stream handle (fmrx_rds: the bank's chain
+with one channel, without the CDR lanes) on one of the same streams: process_dev device time and fmrx_rds_process host time per
+block (input H2D, the chain, the matched-filter rows D2H, host CDR and frame synchronisation).  Channel counts that do not fit the device's free
 memory are reported as skipped."""
 from __future__ import annotations
 
@@ -135,7 +136,7 @@ def main() -> int:
     d_src = torch.from_numpy(src).cuda()
     results = {"mode": a.mode, "block": block, "block_ms": 1e3 * period_s, "f64_ops_per_if_sample": f64_ops_per_if_sample(p), "sweep": []}
 
-    # the single-stream handle, for comparison
+    # the single-stream handle (the same chain, one channel, host bit recovery), for comparison
     r = fmrx.Rds(a.mode, max_block=block)
     stream = torch.cuda.Stream()
     dev_ms, host_ms = [], []
