@@ -158,6 +158,32 @@ FMRX_API int fmrx_all_pass(const float *in, size_t n, float *state, size_t nstat
  * csrc/glibc_libm.hpp and pinned against it): bit-identical to the reference. */
 FMRX_API int fmrx_fm_pll(const float *in, size_t n, float *nco_out, float *state, float freq, float Fs,
                          float ncoScale, float phaseAdjust, float normBandwidth);
+/* The pilot PLL as the specialised stereo pipeline runs it (pll_mode 0): parallel in time, fast math -- one lane per segment
+ * of L samples started W samples early, seams judged against the merge tolerances, unmerged segments walked again serially
+ * (csrc/kernels_pll.hip).  Runs exactly what a warm pipeline's PLL stage runs, with the process-wide options "pll_start",
+ * "pll_warmup" and "pll_segment", the serial fast kernel below 4 L samples included; off_hint = IF samples of the stream in
+ * front of this call (< 0: unknown), as the pipeline counts them.  nco_out[n+1]; state[6] in/out as fmrx_fm_pll.  The entry
+ * owns the kernels' input contract (aligned device input, readable zero floats behind it) and starts from a zeroed work area:
+ * no drift record of an earlier call (pll_start 0), diagnostics of this call alone.
+ * Optional outputs, for tests and diagnostics (NULL = not wanted), sized for fmrx_pll_parallel_max_segments(n) segments:
+ *   records[nseg][FMRX_PLL_RECORD_FLOATS]  per segment: its end state {integrator, phaseEst, feedbackI, feedbackQ, lastOut,
+ *                trigOffset}, the (integrator, phaseEst) its outputs were computed from -- the lane's state after its warm-up,
+ *                or the predecessor's end state the repair walked it from --, and how many times the repair walked it
+ *   mask[nseg / 64 + 1]                    the final mismatch mask, bit s % 64 of word s / 64 = segment s (all zero after a call)
+ * info->nseg == 0: the block was shorter than 4 L, the serial kernel ran, records and mask are untouched. */
+typedef struct fmrx_pll_parallel_info {
+    int L, W;                      /* samples per lane; warm-up samples per lane */
+    int lti;                       /* 1 = the lanes started from the linear system's state (pll_start 1, trigArg below 2^22 rad) */
+    size_t nseg;                   /* segments */
+    unsigned repaired;             /* segment walks of the repair */
+    float max_dphase, max_dinteg;  /* largest differences accepted as merged at a seam */
+    float tol_phase, tol_integ;    /* the merge tolerances of this call */
+} fmrx_pll_parallel_info;
+#define FMRX_PLL_RECORD_FLOATS 9
+#define fmrx_pll_parallel_max_segments(n) ((size_t)(n) / 32 + 2)
+FMRX_API int fmrx_fm_pll_parallel(const float *in, size_t n, float *nco_out, float *state, float freq, float Fs,
+                                  float ncoScale, float phaseAdjust, float normBandwidth, double off_hint,
+                                  fmrx_pll_parallel_info *info, float *records, uint64_t *mask);
 /* replaces the mixer and L/R combine loops  src/project.cpp:246-248, 277-280 */
 FMRX_API int fmrx_stereo_mix(const float *stereo_filt, const float *pll, size_t n, float *mixer);
 FMRX_API int fmrx_stereo_combine(const float *stereo_final, const float *mono, size_t n, float *left, float *right);
@@ -296,9 +322,10 @@ FMRX_API int fmrx_pipeline_set_keep_intermediates(fmrx_pipeline *pl, int on);
 /* Stereo only.  In the specialised pipeline the pilot PLL (fmPLL, src/filter.cpp:32-80) runs parallel
  * in time (segments with warm-up, checked against the neighbouring segment within a tolerance, serial
  * repair where the loop was not locked); it agrees with the serial recurrence to within the float32
- * grid of its phase argument, not bit for bit (see set_force_generic for the bit-exact mode).  Cumulative since creation: segments that had to
- * be re-run serially, and the largest phase / integrator difference accepted as
- * "merged" at a segment boundary. */
+ * grid of its phase argument, not bit for bit (see set_force_generic for the bit-exact mode).  Cumulative since creation: segment walks
+ * of the serial repair (a repaired segment whose predecessor is repaired again with another result is walked again
+ * and counts each time), and the largest phase / integrator difference
+ * accepted as "merged" at a segment boundary, by the lanes' first judging or after a repair. */
 FMRX_API int fmrx_pipeline_pll_diagnostics(fmrx_pipeline *pl, unsigned *repaired_segments, float *max_dphase,
                                            float *max_dinteg);
 /* force the parameter-generic kernels (1) or allow the specialised ones (0).  on = 1 is the BIT-EXACT

@@ -91,6 +91,18 @@ _sig("fmrx_all_pass", [_f32p, _sz, _f32p, _sz, _f32p])
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _sig("fmrx_fm_demod_arctan", [_f64p, _f64p, _f64p, _sz, C.POINTER(C.c_double)])
 _sig("fmrx_fm_pll", [_f32p, _sz, _f32p, _f32p, _flt, _flt, _flt, _flt, _flt])
+
+
+class PllParallelInfo(C.Structure):
+    """struct fmrx_pll_parallel_info (include/fmrx.h)."""
+    _fields_ = [("L", _int), ("W", _int), ("lti", _int), ("nseg", _sz), ("repaired", _uint), ("max_dphase", _flt),
+                ("max_dinteg", _flt), ("tol_phase", _flt), ("tol_integ", _flt)]
+
+
+PLL_RECORD_FLOATS = 9
+_u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
+_sig("fmrx_fm_pll_parallel", [_f32p, _sz, _f32p, _f32p, _flt, _flt, _flt, _flt, _flt, C.c_double, C.POINTER(PllParallelInfo),
+                              _f32p, _u64p])
 _sig("fmrx_stereo_mix", [_f32p, _f32p, _sz, _f32p])
 _sig("fmrx_stereo_combine", [_f32p, _f32p, _sz, _f32p, _f32p])
 _sig("fmrx_pcm16", [_f32p, _sz, _i16p, _int])
@@ -368,6 +380,33 @@ def fmPLL(PLLIn, state, freq, Fs, ncoScale=2.0, phaseAdjust=0.0, normBandwidth=0
     out = np.zeros(len(x) + 1, np.float32)
     _check(lib.fmrx_fm_pll(x, len(x), out, st, freq, Fs, ncoScale, phaseAdjust, normBandwidth))
     return out, st
+
+
+def fmPllParallel(PLLIn, state, freq, Fs, ncoScale=2.0, phaseAdjust=0.0, normBandwidth=0.01, off_hint=-1.0):
+    """The parallel-in-time fast PLL of the specialised stereo pipeline as a stage (fmrx_fm_pll_parallel), under the
+    process-wide options pll_start / pll_warmup / pll_segment -> (ncoOut[len+1], new_state[6], info, records).
+
+    info: dict of L, W, lti, nseg, repaired, max_dphase, max_dinteg, tol_phase, tol_integ and "mask" (bool per segment: the
+    final mismatch flags).  records: dict of float32 arrays per segment -- "end" [nseg, 6], "basis" [nseg, 2] (the integrator
+    and phase the segment's outputs were computed from) -- and "walks" [nseg] (times the repair walked the segment).  A block
+    shorter than 4 L runs the serial kernel: nseg = 0, empty records."""
+    x, st = _f32(PLLIn), _f32(state).copy()
+    if len(st) != 6:
+        raise FmrxError(EINVAL, "PLL state has 6 elements")
+    out = np.zeros(len(x) + 1, np.float32)
+    cap = len(x) // 32 + 2
+    rec = np.zeros((cap, PLL_RECORD_FLOATS), np.float32)
+    words = np.zeros(cap // 64 + 1, np.uint64)
+    inf = PllParallelInfo()
+    _check(lib.fmrx_fm_pll_parallel(x, len(x), out, st, freq, Fs, ncoScale, phaseAdjust, normBandwidth, off_hint, C.byref(inf), rec,
+                                    words))
+    info = {f: getattr(inf, f) for f, _ in PllParallelInfo._fields_}
+    nseg = info["nseg"]
+    info["lti"] = bool(info["lti"])
+    info["mask"] = np.unpackbits(words.view(np.uint8), bitorder="little")[:nseg].astype(bool)
+    rec = rec[:nseg]
+    records = {"end": rec[:, :6].copy(), "basis": rec[:, 6:8].copy(), "walks": rec[:, 8].astype(np.int64)}
+    return out, st, info, records
 
 
 def stereoMix(stereo_filt, pll) -> np.ndarray:

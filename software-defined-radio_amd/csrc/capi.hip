@@ -7,6 +7,8 @@
 // No stage has a CPU implementation: without a device they return FMRX_ENODEV.
 #include "fmrx_internal.hpp"
 #include "rds_station.hpp"
+#include <vector>
+
 #include "build_id.hpp"   // FMRX_SRC_HASH: written by the Makefile (SHA-256 over the library's sources)
 
 namespace fmrx {
@@ -455,6 +457,62 @@ int fmrx_fm_pll(const float *in, size_t n, float *nco_out, float *state, float f
     FMRX_TRY(k_fm_pll(s.a.p, n, s.b.p, s.c.p, freq, Fs, ncoScale, phaseAdjust, normBandwidth, 0, nullptr));
     FMRX_TRY(d2h(nco_out, s.b.p, (n + 1) * sizeof(float)));
     return d2h(state, s.c.p, 6 * sizeof(float));
+}
+
+// The parallel-in-time PLL exactly as pll_stage (pipeline.hip) runs it for a warm pipeline, with what it left in its scratch
+// area.  The host contract of k_fm_pll_parallel lives here: the device input is a fresh allocation (16-byte aligned) with 16
+// zero floats behind in[n-1]; the scratch area starts zeroed (no drift record, diagnostics of this call alone).
+int fmrx_fm_pll_parallel(const float *in, size_t n, float *nco_out, float *state, float freq, float Fs, float ncoScale,
+                         float phaseAdjust, float normBandwidth, double off_hint, fmrx_pll_parallel_info *info, float *records,
+                         uint64_t *mask)
+{
+    if ((!in && n) || !nco_out || !state) return fail(FMRX_EINVAL, "fm_pll_parallel: null buffer");
+    if (!(Fs > 0)) return fail(FMRX_EINVAL, "fm_pll_parallel: Fs must be positive");
+    FMRX_TRY(require_device());
+    Scratch &s = scratch();
+    const size_t n_scratch = pll_parallel_scratch_floats(n);
+    FMRX_TRY(s.a.ensure(n + 16));
+    FMRX_TRY(s.b.ensure(n + 17));
+    FMRX_TRY(s.c.ensure(8));
+    FMRX_TRY(s.d.ensure(n_scratch));
+    FMRX_TRY(h2d(s.a.p, in, n * sizeof(float)));
+    FMRX_HIP(hipMemset(s.a.p + n, 0, 16 * sizeof(float)));
+    FMRX_HIP(hipMemset(s.d.p, 0, n_scratch * sizeof(float)));
+    FMRX_TRY(h2d(s.c.p, state, 6 * sizeof(float)));
+    const float trig_offset = state[5];
+    const Options o = options_snapshot();
+    PllParallelShape sh{};
+    FMRX_TRY(k_fm_pll_parallel(s.a.p, n, s.b.p, s.c.p, freq, Fs, ncoScale, phaseAdjust, normBandwidth, s.d.p, o, nullptr, off_hint, 3,
+                               nullptr, &sh));
+    FMRX_TRY(d2h(nco_out, s.b.p, (n + 1) * sizeof(float)));
+    FMRX_TRY(d2h(state, s.c.p, 6 * sizeof(float)));
+    const size_t nseg = static_cast<size_t>(sh.nseg);
+    if (info) {
+        unsigned hdr[8];
+        FMRX_TRY(d2h(hdr, s.d.p, sizeof(hdr)));
+        info->L = sh.L;
+        info->W = sh.W;
+        info->lti = sh.lti ? 1 : 0;
+        info->nseg = nseg;
+        info->repaired = hdr[2];
+        std::memcpy(&info->max_dphase, &hdr[3], sizeof(float));
+        std::memcpy(&info->max_dinteg, &hdr[4], sizeof(float));
+        pll_parallel_tolerances(trig_offset, n, freq, Fs, normBandwidth, sh.lti, &info->tol_phase, &info->tol_integ);
+    }
+    if (nseg == 0) return FMRX_OK;
+    if (records) {
+        std::vector<float> seg(nseg * 16);
+        FMRX_TRY(d2h(seg.data(), s.d.p + 8, seg.size() * sizeof(float)));
+        for (size_t i = 0; i < nseg; i++) {
+            float *r = records + i * FMRX_PLL_RECORD_FLOATS;
+            for (int u = 0; u < 6; u++) r[u] = seg[i * 16 + u];
+            r[6] = seg[i * 16 + 8];
+            r[7] = seg[i * 16 + 9];
+            r[8] = seg[i * 16 + 10];
+        }
+    }
+    if (mask) FMRX_TRY(d2h(mask, s.d.p + 8 + (nseg + 1) * 16, (nseg / 64 + 1) * sizeof(uint64_t)));
+    return FMRX_OK;
 }
 
 int fmrx_stereo_mix(const float *stereo_filt, const float *pll, size_t n, float *mixer)

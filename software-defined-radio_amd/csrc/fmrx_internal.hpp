@@ -266,14 +266,24 @@ constexpr int kPllHead = 1024;   // samples of a stream's first call walked seri
 // merge tolerance between a lane's warmed-up state and the true state (see kernels_pll.hip)
 constexpr float kPllTolPhase = 1e-2f, kPllTolInteg = 1e-4f;
 size_t pll_parallel_scratch_floats(size_t n);
+// what a call of k_fm_pll_parallel ran: samples and warm-up samples per lane, whether the lanes started from the linear
+// system, and its segments (0: the block was shorter than 4 L and the serial fast kernel ran)
+struct PllParallelShape {
+    int L, W;
+    bool lti;
+    long nseg;
+};
 int k_fm_pll_parallel(const float *d_in, size_t n, float *d_out, float *d_state, float freq, float Fs, float ncoScale,
                       float phaseAdjust, float normBandwidth, float *d_scratch, const Options &o, hipStream_t s,
                       double off_hint = -1.0,    // off_hint: IF samples of the stream in front of this call (the state's trigOffset), < 0 = unknown
-                      int phases = 3, float *d_lti = nullptr);
+                      int phases = 3, float *d_lti = nullptr, PllParallelShape *shape = nullptr);
 // phases: 1 = only what depends on the input alone (the linear system's chunk records), 2 = the lanes and the repair, 3 = both;
 // d_lti: where the chunk records live (pll_parallel_lti_floats(n) floats, 8-byte aligned) if not inside d_scratch -- a caller
 // that runs phase 1 of its next call on another stream while phase 2 of this one reads them keeps two
 size_t pll_parallel_lti_floats(size_t n);
+// the merge tolerances pll_segments_kernel / pll_repair_kernel compute for a block of n samples whose state carries trig_offset
+void pll_parallel_tolerances(float trig_offset, size_t n, float freq, float Fs, float normBandwidth, bool lti, float *tol_phase,
+                             float *tol_integ);
 // many channels, lane = channel, the exact serial recurrence (kernels_pll.hip); rows [channel][pitch], state 8 floats per channel
 int k_fm_pll_channels(const float *d_in, long pitch_in, size_t n, int n_ch, float *d_trig, long pitch_trig, float *d_state,
                       float *d_nco0, float freq, float Fs, float ncoScale, float phaseAdjust, float normBandwidth, hipStream_t s,

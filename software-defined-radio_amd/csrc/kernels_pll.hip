@@ -425,7 +425,9 @@ __device__ __forceinline__ float pll_integ_tol(float base, const float *state, l
 // chunk records in registers (the register budget of a kernel follows its largest legal workgroup)
 constexpr int kSegThreads = 64;
 // seg[s*16 + 0..5]  state at the END of segment s      (after sample a_s + L - 1; fbI/fbQ/last finished)
-// seg[s*16 + 8..9]  (integ, phase) this lane had at the START of segment s (after its warm-up)
+// seg[s*16 + 8..9]  (integ, phase) segment s's outputs were computed from: what this lane had at the START of segment s
+//                   (after its warm-up); pll_repair_kernel puts the state it re-walks a segment from in its place
+// seg[s*16 + 10]    written by pll_repair_kernel only, where a segment is flagged: times it walked segment s
 __global__ __launch_bounds__(kSegThreads) void pll_segments_kernel(const float *__restrict__ in, long n, float *__restrict__ out,
                                     const float *__restrict__ state, PllCoef c, int L, int W, long nseg,
                                     float *__restrict__ seg, float *hdr, const double *__restrict__ lti_rec,
@@ -637,6 +639,11 @@ __global__ __launch_bounds__(kRepairThreads) void pll_repair_kernel(
     auto is_bad = [&](long sg) { return (__atomic_load_n(badmask + sg / 64, __ATOMIC_RELAXED) >> (sg % 64)) & 1ull; };
     unsigned repaired = 0;
     const bool nothing_to_do = !flagged;                   // the common case: every segment merged
+    if (!nothing_to_do) {                                  // slot 10 of a record: times the rounds below walked the segment
+        for (long sg = threadIdx.x; sg < nseg; sg += kRepairThreads) seg[sg * 16 + 10] = 0.0f;
+        __threadfence_block();
+        __syncthreads();
+    }
     for (; !nothing_to_do;) {
         if (threadIdx.x == 0) any_todo = 0;
         __syncthreads();
@@ -653,6 +660,13 @@ __global__ __launch_bounds__(kRepairThreads) void pll_repair_kernel(
         for (int i = 0; i < nt; i++) {
             const long sg = todo[i];
             PllState s = load_state(seg + (sg - 1) * 16);   // true state at the start of segment sg
+            // What this segment's outputs now stand on takes the place of its lane's warm-up start, and the segment counts as
+            // walked: should the predecessor be repaired again in a later round, the re-judge below compares its new end
+            // with THIS, not with a start the outputs no longer come from.  (The successor is not in this round: nobody
+            // else reads or writes these slots now.)
+            seg[sg * 16 + 8] = s.integ;
+            seg[sg * 16 + 9] = s.phase;
+            seg[sg * 16 + 10] += 1.0f;                      // times walked (zeroed above)
             const long a = sg * L, b = a + L < n ? a + L : n;
             float vn = a < b ? in[a] : 0.0f;
             for (long k = a; k < b; k++) {
@@ -666,11 +680,23 @@ __global__ __launch_bounds__(kRepairThreads) void pll_repair_kernel(
             repaired++;
             atomicAnd(badmask + sg / 64, ~(1ull << (sg % 64)));
             if (sg + 1 < nseg) {
-                // does the successor's lane stand on the repaired state?  (its outputs are finished values either way)
-                const bool merged = pll_phase_dist(seg[(sg + 1) * 16 + 9], s.phase) <= tol_phase &&
-                                    fabsf(seg[(sg + 1) * 16 + 8] - s.integ) <= tol_integ;
-                if (merged) atomicAnd(badmask + (sg + 1) / 64, ~(1ull << ((sg + 1) % 64)));
-                else atomicOr(badmask + (sg + 1) / 64, 1ull << ((sg + 1) % 64));
+                // Do the successor's outputs stand on the repaired state?  Slots 8..9 hold what they were computed from.  A
+                // successor in its own lane merges to the tolerance, as at the first judging: its warm-up has put it on the
+                // locked loop's trajectory.  A successor that was walked from this segment's EARLIER end is part of one serial
+                // walk: it stays only if that end came out the same bit for bit, and is walked again otherwise -- two walks
+                // of a loop that is not locked need not stay as close as they start, so a tolerance says nothing there, and
+                // a repaired stretch is the serial recurrence from its first segment on.
+                const float b_integ = seg[(sg + 1) * 16 + 8], b_phase = seg[(sg + 1) * 16 + 9];
+                const float dp = pll_phase_dist(b_phase, s.phase), di = fabsf(b_integ - s.integ);
+                const bool walked = seg[(sg + 1) * 16 + 10] != 0.0f;
+                const bool merged = walked ? __float_as_uint(b_integ) == __float_as_uint(s.integ) &&
+                                                 __float_as_uint(b_phase) == __float_as_uint(s.phase)
+                                           : dp <= tol_phase && di <= tol_integ;
+                if (merged) {
+                    atomicAnd(badmask + (sg + 1) / 64, ~(1ull << ((sg + 1) % 64)));
+                    atomicMax(diag + 3, __float_as_uint(dp));   // accepted here as at the first judging: part of the diagnostics
+                    atomicMax(diag + 4, __float_as_uint(di));
+                } else atomicOr(badmask + (sg + 1) / 64, 1ull << ((sg + 1) % 64));
             }
         }
         __threadfence();
@@ -946,6 +972,23 @@ int k_libm_eval(int fn, const float *d_a, const float *d_b, size_t n, float *d_o
     return FMRX_OK;
 }
 
+// pll_phase_tol / pll_integ_tol on the host, for a caller that reports what the kernels judge by: the same float operations
+// (this file is built under fp contract(off) on both sides; every product with the power of two `ulp` is exact)
+void pll_parallel_tolerances(float trig_offset, size_t n, float freq, float Fs, float normBandwidth, bool lti, float *tol_phase,
+                             float *tol_integ)
+{
+    const PllCoef c = make_coef(freq, Fs, 1.0f, 0.0f, normBandwidth);
+    const float top = static_cast<float>(c.w * (static_cast<double>(trig_offset) + static_cast<double>(static_cast<long>(n))));
+    uint32_t bits;
+    std::memcpy(&bits, &top, sizeof(bits));
+    bits &= 0x7f800000u;
+    float ulp;
+    std::memcpy(&ulp, &bits, sizeof(ulp));
+    ulp *= 1.1920929e-7f;
+    *tol_phase = kPllTolPhase + 2.0f * ulp;
+    *tol_integ = kPllTolInteg + (lti ? kPllIntegTolUlpsLti : c.integ_tol_ulps) * c.Ki * ulp;
+}
+
 size_t pll_parallel_scratch_floats(size_t n)
 {
     const size_t nseg = n / kPllSegmentMin + 2;
@@ -961,7 +1004,7 @@ size_t pll_parallel_lti_floats(size_t n)
 
 int k_fm_pll_parallel(const float *d_in, size_t n, float *d_out, float *d_state, float freq, float Fs, float ncoScale,
                       float phaseAdjust, float normBandwidth, float *d_scratch, const Options &o, hipStream_t s, double off_hint,
-                      int phases, float *d_lti)
+                      int phases, float *d_lti, PllParallelShape *shape)
 {
     int L = kPllSegment, W = kPllWarmup;
     if (o.pll_warmup >= 0 && o.pll_warmup <= 65536) W = o.pll_warmup / 4 * 4;                    // tuning: warm-up samples per lane
@@ -981,6 +1024,7 @@ int k_fm_pll_parallel(const float *d_in, size_t n, float *d_out, float *d_state,
     if (reinterpret_cast<uintptr_t>(d_in) % 16)
         return fail(FMRX_EINVAL, "fm_pll_parallel: input must be 16-byte aligned (the lanes fetch 16-byte groups)");
     if (d_lti && reinterpret_cast<uintptr_t>(d_lti) % 8) return fail(FMRX_EINVAL, "fm_pll_parallel: chunk records must be 8-byte aligned");
+    if (shape) *shape = PllParallelShape{L, W, lti, 0};
     if (n < static_cast<size_t>(4 * L)) {   // nothing to gain
         if (!(phases & 2)) return FMRX_OK;
         return k_fm_pll(d_in, n, d_out, d_state, freq, Fs, ncoScale, phaseAdjust, normBandwidth, 1, s);
@@ -1010,6 +1054,7 @@ int k_fm_pll_parallel(const float *d_in, size_t n, float *d_out, float *d_state,
         lti_rec = rec;
         lti_wgtot = wgtot;
     }
+    if (shape) shape->nseg = nseg;
     if (!(phases & 2)) return FMRX_OK;
     hipLaunchKernelGGL(pll_segments_kernel, dim3(grid), dim3(kSegThreads), 0, s, d_in, static_cast<long>(n), d_out, d_state, c, L, W,
                        nseg, seg, d_scratch, lti_rec, lti_wgtot, badmask, kPllTolPhase, kPllTolInteg);
