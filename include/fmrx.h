@@ -83,6 +83,9 @@ FMRX_API int fmrx_set_device(int device);
  *                      stay complete in the order of the stream passed to the call; results are bit-identical.  Default 0
  *   "tuner_variant"    wideband tuner: 0 = matrix-core kernel (default; FMRX_TUNER_VARIANT=mfma), 1 = generic kernel (=generic)
  *   "pll_warmup", "pll_segment"               lane shape of the parallel-in-time PLL (-1 = built-in)
+ *   "deemph_warmup", "deemph_segment"         lane shape of the parallel-in-time de-emphasis filter (-1 = built-in 256 / 256;
+ *                      warm-up >= 0, segment >= 1): any shape gives the same bits, only the misses change
+ *   "deemph_mode"      de-emphasis: 0 = parallel in time (default), 1 = one lane per row, serially (same bits; measurements)
  *   "pll_start"        where the parallel PLL's lanes start: 1 (default) = the locked loop solved as a linear system of the
  *                      input's signs + 64 true steps, 0 = the block's initial state plus drift + 512 true steps
  *   "pll_mode"         stereo PLL of the specialised pipeline: 0 = parallel in time, fast math (default),
@@ -191,6 +194,30 @@ FMRX_API int fmrx_stereo_combine(const float *stereo_final, const float *mono, s
  * NaN -> 0 else (short)(a*16384).  wrap != 0 reproduces the compiled
  * reference on overflow (int32 truncation, low 16 bits); wrap == 0 saturates. */
 FMRX_API int fmrx_pcm16(const float *audio, size_t n, int16_t *out, int wrap);
+
+/* ------------------------------------------------------------------ */
+/* de-emphasis                                                          */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference (it has no de-emphasis stage).  Coefficients of the one-pole de-emphasis filter for the
+ * sample rate fs (Hz) and the time constant tau_us (microseconds: 50 in Europe and Asia, 75 in the Americas and Korea; any
+ * value is allowed): the bilinear transform of 1 / (1 + s tau), pre-warped at the corner, in float64, rounded to float32:
+ *   k = -tan(1 / (2 fs tau)),  p = (1 + k) / (1 - k),  b0 = (1 - p) / 2        (DC gain 1)
+ * Host only: works without a GPU.  FMRX_EINVAL unless fs, tau_us > 0 and 1 / (2 fs tau) < pi / 4 (so that 0 < p < 1). */
+FMRX_API int fmrx_deemph_design(double fs, double tau_us, float *p, float *b0);
+/* No counterpart in the reference.  The filter on host buffers, rows [rows][pitch] of n samples each (pitch >= n), out of place:
+ *   u = x[n] + x_prev;  v = b0 * u;  y = fmaf(p, y_prev, v);  if |y| < 2^-126: y = +0       (float32, per row)
+ * state [rows][2] = {x_prev, y_prev}, zeros at the start of a stream, updated.  The device walks it parallel in time -- lanes
+ * own segments of `deemph_segment` samples and start `deemph_warmup` samples early from y = 0 (process-wide options; -1 = the
+ * built-in 256 / 256), a verify step compares every segment's start with its predecessor's true end and walks the misses
+ * again -- with the serial walk's bits whatever the shape; option deemph_mode = 1: one lane per row, serially.  *missed (may
+ * be NULL): the segments that were walked again. */
+FMRX_API int fmrx_deemph(float *y, const float *x, size_t rows, size_t n, size_t pitch, float p, float b0, float *state,
+                         unsigned *missed);
+/* No counterpart in the reference.  The same on DEVICE buffers, asynchronous on `stream` (a hipStream_t): d_state [rows][2] is read
+ * and left updated, *d_missed (device memory, the caller zeroes it) is incremented by the segments walked again.  The entry point
+ * the kernels are measured on (tools/deemph_bench.py). */
+FMRX_API int fmrx_deemph_dev(float *d_y, const float *d_x, size_t rows, size_t n, size_t pitch, float p, float b0, float *d_state,
+                             unsigned long long *d_missed, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* diagnostics                                                          */
@@ -336,6 +363,17 @@ FMRX_API int fmrx_pipeline_pll_diagnostics(fmrx_pipeline *pl, unsigned *repaired
 FMRX_API int fmrx_pipeline_set_force_generic(fmrx_pipeline *pl, int on);
 /* per-handle run-time option, names as for fmrx_set_option */
 FMRX_API int fmrx_pipeline_set_option(fmrx_pipeline *pl, const char *name, long value);
+/* No counterpart in the reference.  De-emphasis of the audio outputs (fmrx_deemph at the handle's audio_Fs): tau_us = 0 turns it
+ * off, which is the default -- the call then launches exactly the kernels it launches without this entry point.  With it on,
+ * the producing stage writes float32 rows of the handle's own (channels * the largest call's n_audio floats, allocated when it is
+ * first turned on, and as many again for callers that take PCM only) and one more pass writes audio_f32 and / or pcm16; every tap
+ * (FMRX_TAP_MONO among them) keeps showing the signal in front of it.  Turning it on or changing tau zeroes the filter's state,
+ * and so does fmrx_pipeline_reset.  While it is on, fmrx_pipeline_state_size / get_state / set_state carry {x_prev, y_prev} per
+ * audio channel, appended at the end. */
+FMRX_API int fmrx_pipeline_set_deemphasis(fmrx_pipeline *pl, double tau_us);
+/* No counterpart in the reference.  Cumulative since creation: segments the verify step has checked (every segment of a call but
+ * each row's first, which is exact) and how many of them were walked again (either may be NULL). */
+FMRX_API int fmrx_pipeline_deemph_diagnostics(fmrx_pipeline *pl, unsigned long long *segments, unsigned long long *missed);
 
 /* ------------------------------------------------------------------ */
 /* many mono channels per device call                                   */
@@ -388,6 +426,13 @@ FMRX_API int fmrx_channels_reset(fmrx_channels *c, int channel);
 FMRX_API int fmrx_channels_load_dev(fmrx_channels *c, const uint8_t *d_iq, void *stream);
 FMRX_API int fmrx_channels_process(fmrx_channels *c, const uint8_t *iq, float *audio_f32, int16_t *pcm16, int pcm_policy);
 FMRX_API int fmrx_channels_process_dev(fmrx_channels *c, float *d_audio_f32, int16_t *d_pcm16, int pcm_policy, void *stream);
+/* No counterpart in the reference.  De-emphasis for every bank flavour (fused mono, exact and fast, mono and stereo, all modes), as
+ * fmrx_pipeline_set_deemphasis: tau_us = 0 = off (default).  With it on, the bank's output stage writes a float32 buffer of the
+ * handle's own, [n_channels][audio_channels][n_audio] -- 4 * n_channels * audio_channels * n_audio bytes, allocated when it is first
+ * turned on, and as many again for callers that take PCM only -- and one pass over its n_channels * audio_channels rows, after
+ * the bank's streams have joined, writes the caller's arrays.  fmrx_channels_reset(c, ch) zeroes that channel's rows only. */
+FMRX_API int fmrx_channels_set_deemphasis(fmrx_channels *c, double tau_us);
+FMRX_API int fmrx_channels_deemph_diagnostics(fmrx_channels *c, unsigned long long *segments, unsigned long long *missed);
 
 /* ------------------------------------------------------------------ */
 /* RDS path                                          */

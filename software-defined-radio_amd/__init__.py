@@ -106,6 +106,14 @@ _sig("fmrx_fm_pll_parallel", [_f32p, _sz, _f32p, _f32p, _flt, _flt, _flt, _flt, 
 _sig("fmrx_stereo_mix", [_f32p, _f32p, _sz, _f32p])
 _sig("fmrx_stereo_combine", [_f32p, _f32p, _sz, _f32p, _f32p])
 _sig("fmrx_pcm16", [_f32p, _sz, _i16p, _int])
+_sig("fmrx_deemph_design", [C.c_double, C.c_double, C.POINTER(_flt), C.POINTER(_flt)])
+_sig("fmrx_deemph", [_f32p, _f32p, _sz, _sz, _sz, _flt, _flt, _f32p, C.POINTER(_uint)])
+_sig("fmrx_deemph_dev", [_vp, _vp, _sz, _sz, _sz, _flt, _flt, _vp, _vp, _vp])
+_ull = C.c_ulonglong
+_sig("fmrx_pipeline_set_deemphasis", [_vp, C.c_double])
+_sig("fmrx_pipeline_deemph_diagnostics", [_vp, C.POINTER(_ull), C.POINTER(_ull)])
+_sig("fmrx_channels_set_deemphasis", [_vp, C.c_double])
+_sig("fmrx_channels_deemph_diagnostics", [_vp, C.POINTER(_ull), C.POINTER(_ull)])
 _sig("fmrx_estimate_psd", [_f32p, _f32p, _f32p, _sz, _flt, _int])
 _sig("fmrx_diag_libm", [_int, _f32p, _vp, _sz, _f32p])
 _sig("fmrx_diag_stream_read_dev", [_vp, _sz, _int, _vp])
@@ -454,6 +462,35 @@ def pcm16(audio, wrap=True) -> np.ndarray:
     return out
 
 
+def deemphasisCoeffs(Fs, tau_us):
+    """(p, b0) of the de-emphasis filter as float32 (fmrx_deemph_design; host only, works without a GPU)."""
+    p, b0 = _flt(0), _flt(0)
+    _check(lib.fmrx_deemph_design(float(Fs), float(tau_us), C.byref(p), C.byref(b0)))
+    return np.float32(p.value), np.float32(b0.value)
+
+
+def deemphasis(x, p, b0, state=None, pitch=None):
+    """The de-emphasis filter on rows x [rows, n] (or one row [n]) -> (y, state [rows, 2], missed segments).  pitch: floats
+    between the rows on the device (default n)."""
+    x = _f32(x)
+    one = x.ndim == 1
+    x2 = x.reshape(1, -1) if one else x
+    rows, n = x2.shape
+    pitch = int(pitch or n)
+    xs, ys = np.zeros((rows, pitch), np.float32), np.zeros((rows, pitch), np.float32)
+    xs[:, :n] = x2
+    st = np.zeros((rows, 2), np.float32) if state is None else _f32(state).reshape(rows, 2).copy()
+    missed = _uint(0)
+    _check(lib.fmrx_deemph(ys.reshape(-1), xs.reshape(-1), rows, n, pitch, float(p), float(b0), st.reshape(-1), C.byref(missed)))
+    y = np.ascontiguousarray(ys[:, :n])
+    return (y[0] if one else y), st, missed.value
+
+
+def deemphasis_dev(d_y_ptr, d_x_ptr, rows, n, pitch, p, b0, d_state_ptr, d_missed_ptr, stream=None):
+    """fmrx_deemph_dev on raw device addresses (state [rows, 2] float32, missed one uint64 the caller zeroes); async on `stream`."""
+    _check(lib.fmrx_deemph_dev(d_y_ptr, d_x_ptr, rows, n, pitch, float(p), float(b0), d_state_ptr, d_missed_ptr, stream))
+
+
 def frontEndFIR(iq_u8, h, decim, hist=None, force_generic=False):
     """Fused front end on host buffers -> (if_i, if_q, new_hist).  hist: u8[2*(taps-1)] or None."""
     iq, h = _u8(iq_u8), _f32(h)
@@ -517,6 +554,16 @@ class Pipeline:
         r, dp, di = _uint(0), _flt(0), _flt(0)
         _check(lib.fmrx_pipeline_pll_diagnostics(self._h, C.byref(r), C.byref(dp), C.byref(di)))
         return r.value, dp.value, di.value
+
+    def set_deemphasis(self, tau_us):
+        """De-emphasis of the audio outputs with the time constant tau_us (50 or 75, any positive value); 0 = off (default)."""
+        _check(lib.fmrx_pipeline_set_deemphasis(self._h, float(tau_us)))
+
+    def deemph_diagnostics(self):
+        """(segments checked, segments walked again) of the de-emphasis pass, cumulative since creation."""
+        sg, ms = _ull(0), _ull(0)
+        _check(lib.fmrx_pipeline_deemph_diagnostics(self._h, C.byref(sg), C.byref(ms)))
+        return sg.value, ms.value
 
     def set_force_generic(self, on=True):
         """on: the bit-exact mode (reference evaluation order everywhere, serial PLL with glibc's functions)."""
@@ -611,6 +658,16 @@ class Channels:
 
     def reset(self, channel=-1):
         _check(lib.fmrx_channels_reset(self._h, channel))
+
+    def set_deemphasis(self, tau_us):
+        """De-emphasis of every channel's audio with the time constant tau_us (50 or 75, any positive value); 0 = off (default)."""
+        _check(lib.fmrx_channels_set_deemphasis(self._h, float(tau_us)))
+
+    def deemph_diagnostics(self):
+        """(segments checked, segments walked again) of the de-emphasis pass, cumulative since creation."""
+        sg, ms = _ull(0), _ull(0)
+        _check(lib.fmrx_channels_deemph_diagnostics(self._h, C.byref(sg), C.byref(ms)))
+        return sg.value, ms.value
 
     def input_layout(self):
         """(device address of channel 0's block, pitch in bytes between channels)."""

@@ -63,6 +63,9 @@ bool option_ref(Options &o, const char *name, long **as_long, int **as_int)
     else if (n == "tuner_variant") *as_int = &o.tuner_variant;
     else if (n == "resample_chains") *as_int = &o.resample_chains;
     else if (n == "overlap_calls") *as_int = &o.overlap_calls;
+    else if (n == "deemph_warmup") *as_int = &o.deemph_warmup;
+    else if (n == "deemph_segment") *as_int = &o.deemph_segment;
+    else if (n == "deemph_mode") *as_int = &o.deemph_mode;
     else return false;
     return true;
 }
@@ -82,6 +85,9 @@ Options &default_options()
         if (const char *e = std::getenv("FMRX_PLL_SEGMENT")) d.pll_segment = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_START")) d.pll_start = std::atoi(e);
         if (const char *e = std::getenv("FMRX_PLL_MODE")) d.pll_mode = std::atoi(e);
+        if (const char *e = std::getenv("FMRX_DEEMPH_WARMUP")) d.deemph_warmup = std::atoi(e);
+        if (const char *e = std::getenv("FMRX_DEEMPH_SEGMENT")) d.deemph_segment = std::atoi(e);
+        if (const char *e = std::getenv("FMRX_DEEMPH_MODE")) d.deemph_mode = std::atoi(e);
         if (const char *e = std::getenv("FMRX_TUNER_VARIANT")) d.tuner_variant = std::strcmp(e, "generic") == 0 ? 1 : 0;
         if (const char *e = std::getenv("FMRX_DEMOD")) d.demod = std::strcmp(e, "arctan") == 0 ? 1 : std::atoi(e);
         return d;
@@ -110,6 +116,9 @@ int set_option_in(Options &o, const char *name, long value)
     if (pi == &o.tuner_variant && value != 0 && value != 1) return fail(FMRX_EINVAL, "option tuner_variant: 0 (mfma) or 1 (generic)");
     if (pi == &o.pll_mode && (value < 0 || value > 2)) return fail(FMRX_EINVAL, "option pll_mode: 0, 1 or 2");
     if (pi == &o.demod && value != 0 && value != 1) return fail(FMRX_EINVAL, "option demod: 0 (the C++ reference's discriminator) or 1 (arctan)");
+    if (pi == &o.deemph_warmup && (value < -1 || value > (1 << 20))) return fail(FMRX_EINVAL, "option deemph_warmup: -1 (built-in) or 0 .. 2^20");
+    if (pi == &o.deemph_segment && (value < -1 || value == 0 || value > (1 << 20))) return fail(FMRX_EINVAL, "option deemph_segment: -1 (built-in) or 1 .. 2^20");
+    if (pi == &o.deemph_mode && value != 0 && value != 1) return fail(FMRX_EINVAL, "option deemph_mode: 0 (parallel in time) or 1 (serial)");
     if (pl) *pl = value;
     else *pi = static_cast<int>(value);
     return FMRX_OK;
@@ -543,6 +552,85 @@ int fmrx_stereo_combine(const float *stereo_final, const float *mono, size_t n, 
     FMRX_TRY(k_combine(s.a.p, s.b.p, n, s.c.p, s.d.p, nullptr));
     FMRX_TRY(d2h(left, s.c.p, n * sizeof(float)));
     return d2h(right, s.d.p, n * sizeof(float));
+}
+
+// ---- de-emphasis (no counterpart in the reference) -------------------------------------------
+int fmrx_deemph_design(double fs, double tau_us, float *p, float *b0)
+{
+    if (!p || !b0) return fail(FMRX_EINVAL, "deemph_design: null argument");
+    if (!(fs > 0.0) || !(tau_us > 0.0)) return fail(FMRX_EINVAL, "deemph_design: fs and tau must be positive");
+    // bilinear transform of 1 / (1 + s tau), pre-warped at the corner; float64 throughout, rounded to float32 at the end
+    const double tau = tau_us * 1e-6;
+    const double a = 1.0 / (2.0 * fs * tau);
+    if (!(a < 0.78539816339744830962)) return fail(FMRX_EINVAL, "deemph_design: 1 / (2 fs tau) = %g must be below pi / 4 (0 < p < 1)", a);
+    const double k = -tan(a);
+    const double pd = (1.0 + k) / (1.0 - k);
+    *p = static_cast<float>(pd);
+    *b0 = static_cast<float>((1.0 - pd) / 2.0);
+    return FMRX_OK;
+}
+
+int fmrx_deemph(float *y, const float *x, size_t rows, size_t n, size_t pitch, float p, float b0, float *state, unsigned *missed)
+{
+    if (!y || !x || !state) return fail(FMRX_EINVAL, "deemph: null buffer");
+    if (pitch < n) return fail(FMRX_EINVAL, "deemph: pitch %zu < n %zu", pitch, n);
+    if (missed) *missed = 0;
+    if (rows == 0 || n == 0) return FMRX_OK;
+    FMRX_TRY(require_device());
+    Scratch &s = scratch();
+    const Options o = options_snapshot();
+    static thread_local DevBuf<unsigned long long> cnt;
+    FMRX_TRY(s.a.ensure(rows * pitch));
+    FMRX_TRY(s.b.ensure(rows * pitch));
+    FMRX_TRY(s.c.ensure(2 * rows));
+    FMRX_TRY(s.d.ensure(deemph_scratch_floats(rows, n, o)));
+    FMRX_TRY(cnt.ensure(1));
+    FMRX_TRY(h2d(s.a.p, x, rows * pitch * sizeof(float)));
+    FMRX_TRY(h2d(s.b.p, y, rows * pitch * sizeof(float)));   // (what lies between the rows of y stays the caller's)
+    FMRX_TRY(h2d(s.c.p, state, 2 * rows * sizeof(float)));
+    FMRX_HIP(hipMemset(cnt.p, 0, sizeof(unsigned long long)));
+    DeemphArgs a;
+    a.x = s.a.p;
+    a.y = s.b.p;
+    a.pitch_x = a.pitch_y = static_cast<long>(pitch);
+    a.rows = rows;
+    a.n = n;
+    a.p = p;
+    a.b0 = b0;
+    a.state = s.c.p;
+    a.seg = s.d.p;
+    a.missed = cnt.p;
+    FMRX_TRY(deemph_launch(a, o, false, nullptr, nullptr));
+    FMRX_TRY(sync0());
+    FMRX_TRY(d2h(y, s.b.p, rows * pitch * sizeof(float)));
+    FMRX_TRY(d2h(state, s.c.p, 2 * rows * sizeof(float)));
+    unsigned long long m = 0;
+    FMRX_TRY(d2h(&m, cnt.p, sizeof(m)));
+    if (missed) *missed = static_cast<unsigned>(m);
+    return FMRX_OK;
+}
+
+int fmrx_deemph_dev(float *d_y, const float *d_x, size_t rows, size_t n, size_t pitch, float p, float b0, float *d_state,
+                    unsigned long long *d_missed, void *stream)
+{
+    if (!d_y || !d_x || !d_state || !d_missed) return fail(FMRX_EINVAL, "deemph_dev: null buffer");
+    if (pitch < n) return fail(FMRX_EINVAL, "deemph_dev: pitch %zu < n %zu", pitch, n);
+    FMRX_TRY(require_device());
+    const Options o = options_snapshot();
+    static thread_local DevBuf<float> seg;   // (grows with the shape: a device-wide wait then, not per call)
+    FMRX_TRY(seg.ensure(deemph_scratch_floats(rows, n, o)));
+    DeemphArgs a;
+    a.x = d_x;
+    a.y = d_y;
+    a.pitch_x = a.pitch_y = static_cast<long>(pitch);
+    a.rows = rows;
+    a.n = n;
+    a.p = p;
+    a.b0 = b0;
+    a.state = d_state;
+    a.seg = seg.p;
+    a.missed = d_missed;
+    return deemph_launch(a, o, false, static_cast<hipStream_t>(stream), nullptr);
 }
 
 // ---- diagnostics ---------------------------------------------------------------------------

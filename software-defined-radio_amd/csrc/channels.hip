@@ -40,6 +40,10 @@ struct fmrx_channels {
     // banks in the reference's evaluation order, and every stereo bank: bank.hip
     int audio_channels = 1, exact = 0;
     Bank *bank = nullptr;
+    // de-emphasis (kernels_deemph.hip; off by default): while it is on, the bank writes f32 [n_channels][audio_channels][n_audio]
+    // into de.in and no PCM; one pass over its n_channels * audio_channels rows, behind the bank's call, writes the caller's arrays
+    Deemph de;
+    double de_tau = 0.0;
 };
 
 namespace {
@@ -220,17 +224,17 @@ int fmrx_channels_reset(fmrx_channels *c, int channel)
     if (!c) return fail(FMRX_EINVAL, "channels_reset: null handle");
     if (channel >= c->n_channels) return fail(FMRX_EINVAL, "channels_reset: channel %d of %d", channel, c->n_channels);
     FMRX_HIP(hipSetDevice(c->device));
-    if (c->bank) return bank_reset(c->bank, channel);
     FMRX_HIP(hipDeviceSynchronize());
+    FMRX_TRY(c->de.reset(channel < 0 ? 0 : static_cast<long>(channel) * c->audio_channels,
+                         static_cast<long>(channel < 0 ? c->n_channels : 1) * c->audio_channels, nullptr));
+    FMRX_HIP(hipDeviceSynchronize());
+    if (c->bank) return bank_reset(c->bank, channel);
     if (channel < 0) return k_fill_u8(c->slots.p, c->slot_bytes * c->n_channels, 128, nullptr);
     return k_fill_u8(c->slots.p + static_cast<size_t>(channel) * c->slot_bytes, c->hist_bytes, 128, nullptr);
 }
 
-int fmrx_channels_process_dev(fmrx_channels *c, float *d_audio_f32, int16_t *d_pcm16, int pcm_policy, void *stream)
+static int process_bank(fmrx_channels *c, float *d_audio_f32, int16_t *d_pcm16, int pcm_policy, hipStream_t s)
 {
-    if (!c) return fail(FMRX_EINVAL, "channels_process_dev: null handle");
-    FMRX_HIP(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (c->bank) return bank_process_dev(c->bank, d_audio_f32, d_pcm16, pcm_policy, s);
     const size_t total = c->slot_bytes * c->n_channels;
     const float *zend = c->zeros.p + c->p.audio_taps + 32;     // "one past the previous block's last discriminator sample": zeros
@@ -245,6 +249,36 @@ int fmrx_channels_process_dev(fmrx_channels *c, float *d_audio_f32, int16_t *d_p
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FMRX_EHIP, "launch channels_finish_kernel: %s", hipGetErrorString(e));
     return FMRX_OK;
+}
+
+int fmrx_channels_process_dev(fmrx_channels *c, float *d_audio_f32, int16_t *d_pcm16, int pcm_policy, void *stream)
+{
+    if (!c) return fail(FMRX_EINVAL, "channels_process_dev: null handle");
+    FMRX_HIP(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c->de.on) return process_bank(c, d_audio_f32, d_pcm16, pcm_policy, s);
+    // de-emphasis: the bank writes the handle's f32 rows; behind it (its internal streams have joined s) the pass writes the caller's
+    FMRX_TRY(process_bank(c, c->de.in.p, nullptr, pcm_policy, s));
+    return c->de.run(c->n_audio, d_audio_f32, d_pcm16, c->audio_channels, pcm_policy, c->opt, false, s);
+}
+
+int fmrx_channels_set_deemphasis(fmrx_channels *c, double tau_us)
+{
+    if (!c) return fail(FMRX_EINVAL, "channels_set_deemphasis: null handle");
+    if (!(tau_us >= 0.0)) return fail(FMRX_EINVAL, "channels_set_deemphasis: tau must be positive, or 0 for off");
+    if (c->de.on && tau_us == c->de_tau) return FMRX_OK;
+    FMRX_HIP(hipSetDevice(c->device));
+    FMRX_HIP(hipDeviceSynchronize());
+    FMRX_TRY(c->de.set(static_cast<double>(c->p.audio_Fs), tau_us, static_cast<size_t>(c->n_channels) * c->audio_channels, c->n_audio, c->opt));
+    c->de_tau = c->de.on ? tau_us : 0.0;
+    return FMRX_OK;
+}
+
+int fmrx_channels_deemph_diagnostics(fmrx_channels *c, unsigned long long *segments, unsigned long long *missed)
+{
+    if (!c) return fail(FMRX_EINVAL, "channels_deemph_diagnostics: null handle");
+    FMRX_HIP(hipSetDevice(c->device));
+    return c->de.diagnostics(segments, missed);
 }
 
 int fmrx_channels_load_dev(fmrx_channels *c, const uint8_t *d_iq, void *stream)

@@ -59,6 +59,9 @@ struct Options {
                                    //   linear system of the input's signs, then 64 true warm-up steps; 0 = the block's initial state plus drift, 512 steps
     int pll_mode = 0;              // "pll_mode" / FMRX_PLL_MODE: stereo PLL of the specialised pipeline: 0 = parallel in time, fast math
                                    //   (default); 1 = serial, fast math; 2 = serial, glibc math (the cause-by-cause variants of DESIGN 2)
+    int deemph_warmup = -1;        // "deemph_warmup" / FMRX_DEEMPH_WARMUP: warm-up samples per lane of the parallel de-emphasis filter (-1 = built-in)
+    int deemph_segment = -1;       // "deemph_segment" / FMRX_DEEMPH_SEGMENT: samples per lane (-1 = built-in)
+    int deemph_mode = 0;           // "deemph_mode" / FMRX_DEEMPH_MODE: 0 = parallel in time (default), 1 = one lane per row walks it serially (same bits)
     int tuner_variant = 0;         // "tuner_variant" / FMRX_TUNER_VARIANT: wideband tuner (tuner.hip): 0 = matrix-core kernel ("mfma"), 1 = generic kernel ("generic");
                                    //   read when a tuner is created
     int demod = 0;                 // "demod" / FMRX_DEMOD: 0 = the C++ reference's discriminator (fmDemod, src/filter.cpp:248-266; default),
@@ -297,6 +300,45 @@ int k_downsample(const float *d_in, size_t n_out, float *d_out, int ds, hipStrea
 int k_fill_u8(uint8_t *d, size_t n, uint8_t v, hipStream_t s);
 // diagnostics: out[i] = sinf / cosf / atan2f (fn 0 / 1 / 2) of a[i] (, b[i]) as the device evaluates glibc_libm.hpp
 int k_libm_eval(int fn, const float *d_a, const float *d_b, size_t n, float *d_out, hipStream_t s);
+
+// ---- de-emphasis (kernels_deemph.hip): y = one-pole IIR of x per row, parallel in time, bit-identical to the serial walk ----
+constexpr int kDeemphSegment = 256, kDeemphWarmup = 256;   // built-in lane shape: samples per lane, warm-up samples in front
+struct DeemphShape {
+    int L = 0, W = 0;
+    long nseg = 0;
+};
+DeemphShape deemph_shape(const Options &o, size_t n);
+size_t deemph_scratch_floats(size_t rows, size_t n, const Options &o);
+struct DeemphArgs {
+    const float *x = nullptr;            // [rows][pitch_x], n samples per row
+    long pitch_x = 0;
+    float *y = nullptr;                  // [rows][pitch_y]; never x: the repair reads x again
+    long pitch_y = 0;
+    int16_t *pcm = nullptr;              // optional: [rows / ac][n][ac]
+    int ac = 1, wrap = 0;
+    size_t rows = 0, n = 0;
+    float p = 0.0f, b0 = 0.0f;
+    float *state = nullptr;              // [rows][2] = x_prev, y_prev: read, then left for the next call
+    float *seg = nullptr;                // deemph_scratch_floats(): the segments' start and end y
+    unsigned long long *missed = nullptr;   // += segments that were walked again
+};
+// serial: the one-lane-per-row kernel (also under option deemph_mode = 1); *segments += the segments the verify step checked
+int deemph_launch(const DeemphArgs &a, const Options &o, bool serial, hipStream_t s, unsigned long long *segments);
+// what a handle with de-emphasis owns: rows [rows][n] the producing stage writes (n = the call's samples per row), rows of y
+// for callers that take PCM only (allocated by the first such call), the carried state, scratch, counters.  Nothing is allocated
+// until it is first turned on.
+struct Deemph {
+    bool on = false, counted = false;
+    float p = 0.0f, b0 = 0.0f;
+    size_t rows = 0, n_max = 0;
+    DevBuf<float> in, out, state, seg;
+    DevBuf<unsigned long long> counter;
+    unsigned long long segments = 0;
+    int set(double fs, double tau_us, size_t rows, size_t n_max, const Options &o);   // tau_us 0 = off; on / a new tau: state zeroed
+    int reset(long first_row, long n_rows, hipStream_t s);   // asynchronous on s
+    int run(size_t n, float *d_f32, int16_t *d_pcm, int ac, int wrap, const Options &o, bool serial, hipStream_t s);
+    int diagnostics(unsigned long long *segments, unsigned long long *missed);
+};
 
 // ---- measurement aid (kernels_diag.hip): one pure streaming read of the buffer; method 0 registers (non-temporal), 1 LDS-DMA ring
 int k_stream_read(const void *d_buf, size_t bytes, int method, unsigned *d_sink, hipStream_t s);

@@ -29,6 +29,9 @@
 //                         reference's float32 evaluation order, serial PLL with glibc's functions --
 //                         stereo output equal to the reference's bit for bit for any stream length
 //   --saturate            clamp PCM instead of the reference's wrap-around
+//   --deemph US           de-emphasis of the audio with the time constant US microseconds (50: Europe, Asia; 75: the
+//                         Americas, Korea; any positive value): fmrx_pipeline_set_deemphasis.  The reference has no such
+//                         stage; without the flag the output is what it always was
 //   --device N            HIP device ordinal
 //   --compat-exit         exit status 1 at EOF, like the reference
 #include <condition_variable>
@@ -61,7 +64,9 @@ struct BlockQueue {
 {
     std::fprintf(stderr,
                  "Usage: %s [<mode 0-3> [<channels 1-2>]] [--rf-taps N] [--audio-taps N] [--stereo-taps N]\n"
-                 "          [--like project|threadMonoOnly] [--blocks-per-call K] [--exact] [--saturate] [--device N] [--compat-exit]\n",
+                 "          [--like project|threadMonoOnly] [--blocks-per-call K] [--exact] [--saturate] [--deemph US] [--device N]\n"
+                 "          [--compat-exit]\n"
+                 "  --deemph US  de-emphasis time constant in microseconds (50: Europe, Asia; 75: the Americas, Korea); default: none\n",
                  argv0);
     std::exit(1);
 }
@@ -71,6 +76,7 @@ int main(int argc, char *argv[])
 {
     int mode = 0, channels = 1, rf_taps = 101, audio_taps = 101, stereo_taps = 101, device = 0, per_call = 1;
     bool saturate = false, compat_exit = false, exact = false;
+    double deemph_us = 0.0;
     std::vector<std::string> pos;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -89,6 +95,12 @@ int main(int argc, char *argv[])
             if (w == "project") rf_taps = audio_taps = stereo_taps = 13;            // src/project.cpp:46, 424-429
             else if (w == "threadMonoOnly") { rf_taps = 151; audio_taps = 101; }    // src/threadMonoOnly.cpp:66, 229-232
             else usage(argv[0]);
+        }
+        else if (a == "--deemph") {
+            if (i + 1 >= argc) usage(argv[0]);
+            char *end = nullptr;
+            deemph_us = std::strtod(argv[++i], &end);
+            if (end == argv[i] || *end != '\0' || !(deemph_us > 0.0)) usage(argv[0]);
         }
         else if (a == "--exact") exact = true;
         else if (a == "--saturate") saturate = true;
@@ -124,6 +136,11 @@ int main(int argc, char *argv[])
         return 2;
     }
     if (exact && fmrx_pipeline_set_force_generic(pl, 1) != FMRX_OK) {
+        std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
+        return 2;
+    }
+
+    if (deemph_us > 0.0 && fmrx_pipeline_set_deemphasis(pl, deemph_us) != FMRX_OK) {
         std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
         return 2;
     }

@@ -87,6 +87,10 @@ struct fmrx_pipeline {
     int mix_cur = 0;
     DevBuf<float> out_f32;
     DevBuf<int16_t> out_pcm;
+    // de-emphasis (kernels_deemph.hip; off by default): while it is on, the producing stage of a call writes f32 into de.in
+    // ([channels][n_audio]) instead of the caller's buffers and no PCM; one pass behind it writes the caller's
+    Deemph de;
+    double de_tau = 0.0;
     // asynchronous host-buffer calls (fmrx_pipeline_submit / _wait): two slots, each with its own stream and device staging
     // buffers (slot 0 = `stream`, `in`, `out_f32`, `out_pcm` above): block i+1's copy to the device runs under block i's kernels
     // and block i-1's copy back.  Only the kernels of consecutive blocks are ordered (they carry the state): ev_kern.
@@ -193,6 +197,7 @@ int reset_state(fmrx_pipeline *pl)
         FMRX_HIP(hipMemcpyAsync(pl->pll_state.p, init, sizeof(init), hipMemcpyHostToDevice, s));
         FMRX_HIP(hipMemsetAsync(pl->pll_scratch.p + 5, 0, 3 * sizeof(float), s));   // no phase-slope history yet
     }
+    FMRX_TRY(pl->de.reset(0, pl->channels, s));
     FMRX_HIP(hipStreamSynchronize(s));
     pl->fe_cur = pl->prev_cur = pl->mix_cur = 0;
     pl->prev_override = false;
@@ -357,6 +362,25 @@ int fmrx_pipeline_set_option(fmrx_pipeline *pl, const char *name, long value)
     return set_option_in(pl->opt, name, value);
 }
 
+int fmrx_pipeline_set_deemphasis(fmrx_pipeline *pl, double tau_us)
+{
+    if (!pl) return fail(FMRX_EINVAL, "null handle");
+    if (!(tau_us >= 0.0)) return fail(FMRX_EINVAL, "set_deemphasis: tau must be positive, or 0 for off");
+    if (pl->de.on && tau_us == pl->de_tau) return FMRX_OK;
+    FMRX_HIP(hipSetDevice(pl->device));
+    FMRX_HIP(hipDeviceSynchronize());   // nothing in flight sees the change under it
+    FMRX_TRY(pl->de.set(static_cast<double>(pl->p.audio_Fs), tau_us, pl->channels, n_audio_of(pl, pl->max_bytes) + 1, pl->opt));
+    pl->de_tau = pl->de.on ? tau_us : 0.0;
+    return FMRX_OK;
+}
+
+int fmrx_pipeline_deemph_diagnostics(fmrx_pipeline *pl, unsigned long long *segments, unsigned long long *missed)
+{
+    if (!pl) return fail(FMRX_EINVAL, "null handle");
+    FMRX_HIP(hipSetDevice(pl->device));
+    return pl->de.diagnostics(segments, missed);
+}
+
 int fmrx_pipeline_set_keep_intermediates(fmrx_pipeline *pl, int on)
 {
     if (!pl) return fail(FMRX_EINVAL, "null handle");
@@ -415,6 +439,10 @@ struct Call {
     bool fused;                  // the fused mono kernel does the whole call
     bool prof;                   // the call records the event quadruple ev
     hipEvent_t *ev;
+    // de-emphasis on: audio_f32 above is the handle's own rows and pcm16 null; these are the caller's
+    bool de;
+    float *user_f32;
+    int16_t *user_pcm;
 };
 
 // profiling: event k of the call's quadruple {start, after the front end, after the audio stage, end}, on the caller's stream
@@ -509,6 +537,23 @@ static int overlap_begin(fmrx_pipeline *pl, Call &c)
         FMRX_HIP(hipStreamWaitEvent(c.so, pl->ov_entry, 0));
     }
     return FMRX_OK;
+}
+
+// de-emphasis on: the stages below write f32 rows of the handle's own and no PCM (every stage already serves such a caller)
+static void deemph_redirect(fmrx_pipeline *pl, Call &c)
+{
+    c.de = pl->de.on;
+    if (!c.de) return;
+    c.user_f32 = c.audio_f32;
+    c.user_pcm = c.pcm16;
+    c.audio_f32 = pl->de.in.p;
+    c.pcm16 = nullptr;
+}
+
+// ... and this pass writes the caller's buffers, on the stream of the stage that wrote the rows
+static int deemph_stage(fmrx_pipeline *pl, const Call &c, hipStream_t s)
+{
+    return pl->de.run(c.n_au, c.user_f32, c.user_pcm, pl->channels, c.pcm_policy, pl->opt, pl->force_generic, s);
 }
 
 // ---- RF_FrontEnd + RF_MONO of modes 0/1 in one kernel (kernels_fe_mfma.hip): the discriminator output stays on chip;
@@ -676,6 +721,7 @@ static int stereo_back_end(fmrx_pipeline *pl, const Call &c)
                                    c.audio_f32 ? c.audio_f32 : (c.pcm16 ? nullptr : pl->left.p),
                                    c.audio_f32 ? c.audio_f32 + c.n_au : (c.pcm16 ? nullptr : pl->right.p), c.pcm16,
                                    c.pcm_policy, pl->keep_if ? mixer : nullptr, c.so));
+        if (c.de && c.ovl) FMRX_TRY(deemph_stage(pl, c, c.so));   // in front of the event the caller's stream waits for
         if (c.ovl) {   // the caller's stream sees the call's output in its own order, as always
             FMRX_HIP(hipEventRecord(pl->ov_done[2][c.cur], c.so));
             if (c.so != c.s) FMRX_HIP(hipStreamWaitEvent(c.s, pl->ov_done[2][c.cur], 0));
@@ -702,6 +748,7 @@ int fmrx_pipeline_process_dev(fmrx_pipeline *pl, const uint8_t *d_iq, size_t n_b
     FMRX_TRY(check_block(pl, n_bytes));
     FMRX_HIP(hipSetDevice(pl->device));   // the handle's buffers live there, whatever the caller's current device
     Call c{d_iq, n_bytes, d_audio_f32, d_pcm16, pcm_policy, static_cast<hipStream_t>(stream)};
+    deemph_redirect(pl, c);
     FMRX_TRY(call_setup(pl, c));
     FMRX_TRY(overlap_begin(pl, c));
     if (c.fused) {
@@ -710,6 +757,7 @@ int fmrx_pipeline_process_dev(fmrx_pipeline *pl, const uint8_t *d_iq, size_t n_b
         FMRX_TRY(front_end(pl, c));
         FMRX_TRY(pl->channels == 1 ? mono_back_end(pl, c) : stereo_back_end(pl, c));
     }
+    if (c.de && !c.ovl) FMRX_TRY(deemph_stage(pl, c, c.s));
     FMRX_TRY(mark(c, 3));
     if (c.prof) pl->calls++;
     return FMRX_OK;
@@ -838,6 +886,7 @@ size_t fmrx_pipeline_state_size(const fmrx_pipeline *pl)
     if (!pl) return 0;
     size_t n = 2 * (pl->p.rf_taps - 1) + 2 + pl->Ha;
     if (pl->channels == 2) n += 2 * (pl->St - 1) + pl->Ha + pl->delay + 6;
+    if (pl->de.on) n += 2 * pl->channels;   // de-emphasis: x_prev, y_prev per audio channel
     return n;
 }
 
@@ -872,6 +921,7 @@ int fmrx_pipeline_get_state(fmrx_pipeline *pl, float *state, size_t n)
         std::memcpy(o, dend - pl->delay, pl->delay * sizeof(float)); o += pl->delay;        // state_allpass
         FMRX_HIP(hipMemcpy(o, pl->pll_state.p, 6 * sizeof(float), hipMemcpyDeviceToHost)); o += 6;
     }
+    if (pl->de.on) FMRX_HIP(hipMemcpy(o, pl->de.state.p, 2 * pl->channels * sizeof(float), hipMemcpyDeviceToHost));
     return FMRX_OK;
 }
 
@@ -922,6 +972,7 @@ int fmrx_pipeline_set_state(fmrx_pipeline *pl, const float *state, size_t n)
     pl->prev_override = true;   // the fused front end would otherwise recompute IF[-1] from the byte history
     pl->pll_warm = false;
     if (pl->channels == 2) FMRX_HIP(hipMemset(pl->pll_scratch.p + 5, 0, 3 * sizeof(float)));
+    if (pl->de.on) FMRX_HIP(hipMemcpy(pl->de.state.p, o, 2 * pl->channels * sizeof(float), hipMemcpyHostToDevice));
     return FMRX_OK;
 }
 
