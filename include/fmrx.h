@@ -272,6 +272,11 @@ typedef struct fmrx_pipeline fmrx_pipeline;
  * be passed to process (device buffers are sized once, here).  device: HIP
  * device ordinal.  The handle owns all device memory and the carried state
  * (I/Q FIR history, prev I/Q, audio FIR histories, all-pass delay, PLL). */
+/* Parameters: any tap counts in 2..65535 and any decimations (the parameter-generic kernels run where no specialised one
+ * exists); with a resampler (audio_upsamp > 0) audio_taps must be a multiple of audio_upsamp, FMRX_EINVAL otherwise (and from
+ * fmrx_channels_create_ex): the reference writes its resampler state in slots upsamp-1 :: upsamp (src/filter.cpp:218-222) and
+ * reads slots taps-1 - d*upsamp (:207), the same slots only when upsamp divides taps -- otherwise its output depends on where
+ * the blocks are cut and no stream equals it. */
 FMRX_API int fmrx_pipeline_create(fmrx_pipeline **out, const fmrx_params *p, int channels, size_t max_block_bytes,
                                   int device);
 FMRX_API int fmrx_pipeline_destroy(fmrx_pipeline *pl);
@@ -325,7 +330,13 @@ FMRX_API int fmrx_pipeline_read_tap(fmrx_pipeline *pl, int which, float *out, si
  *   (+ stereo: state_stereo[St-1], state_carrier[St-1], state_stereofilt[Ha],
  *    state_allpass[(St-1)/2], state_PLL[6])
  * where Ha = audio history in INPUT samples (audio_taps-1, or
- * (audio_taps-1)/upsamp for modes 2,3).  n = number of floats. */
+ * (audio_taps-1)/upsamp for modes 2,3: the live slots upsamp-1 :: upsamp of the reference's upsampled-space vectors).
+ * n = number of floats.  The handle keeps ONE discriminator history, of which state_stereo, state_carrier (the same samples),
+ * state_allpass (their last (St-1)/2) and state_mono (the Ha samples in front of those) are windows; get_state writes them all.
+ * set_state returns FMRX_EINVAL and leaves the handle unchanged for a wrong n, an I_state / Q_state value that is not
+ * (u8-128)/128, or windows that disagree where they overlap (a state no stream produces).  A handle resumed from get_state
+ * continues bit for bit, whatever it had processed before, wherever the receiver is deterministic: mono, and stereo with the
+ * serial PLL (set_force_generic, pll_mode 1 or 2); the default parallel PLL re-acquires (within its usual bounds). */
 FMRX_API size_t fmrx_pipeline_state_size(const fmrx_pipeline *pl);
 FMRX_API int fmrx_pipeline_get_state(fmrx_pipeline *pl, float *state, size_t n);
 FMRX_API int fmrx_pipeline_set_state(fmrx_pipeline *pl, const float *state, size_t n);

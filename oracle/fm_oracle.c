@@ -500,6 +500,68 @@ size_t fmo_pipeline_intermediate(const fmo_pipeline *pl, int which, const float 
     }
 }
 
+/* ---- carried state, serialised in the order of include/fmrx.h (fmrx_pipeline_state_size):
+ *   I_state[rf_taps-1], Q_state[rf_taps-1], prev_i, prev_q, state_mono[Ha]
+ *   (+ stereo: state_stereo[St-1], state_carrier[St-1], state_stereofilt[Ha], state_allpass[(St-1)/2], state_PLL[6])
+ * These are the oracle's own vectors (project.cpp:61-65, 446-458), copied, not derived.  The audio-stage vectors of the
+ * resampling modes live in the upsampled index space, where only slots == upsamp-1 (mod upsamp) are ever read or written
+ * (filter.cpp:199, 218-222): those Ha = (audio_taps-1)/upsamp slots are what is serialised. */
+static size_t fmo_audio_hist(const fmo_pipeline *pl)
+{
+    const size_t ns = (size_t)pl->p.audio_taps - 1;
+    return pl->p.audio_upsamp ? ns / (size_t)pl->p.audio_upsamp : ns;
+}
+
+size_t fmo_pipeline_state_size(const fmo_pipeline *pl)
+{
+    const size_t Ha = fmo_audio_hist(pl), St1 = (size_t)pl->p.stereo_taps - 1;
+    size_t n = 2 * ((size_t)pl->p.rf_taps - 1) + 2 + Ha;
+    if (pl->channels == 2)
+        n += 2 * St1 + Ha + St1 / 2 + 6;
+    return n;
+}
+
+/* dir 0: vector -> *s (get); dir 1: *s -> vector (set); stride > 1: the live slots stride-1 :: stride of vec */
+static void fmo_state_copy(float **s, float *vec, size_t n, size_t stride, int dir)
+{
+    for (size_t k = 0; k < n; k++) {
+        float *v = stride > 1 ? &vec[stride - 1 + k * stride] : &vec[k];
+        if (dir) *v = (*s)[k]; else (*s)[k] = *v;
+    }
+    *s += n;
+}
+
+static int fmo_state_walk(fmo_pipeline *pl, float *state, size_t n, int dir)
+{
+    if (!pl || !state || n != fmo_pipeline_state_size(pl)) return -1;
+    const size_t Tr = (size_t)pl->p.rf_taps - 1, Ha = fmo_audio_hist(pl), St1 = (size_t)pl->p.stereo_taps - 1;
+    const size_t U = pl->p.audio_upsamp ? (size_t)pl->p.audio_upsamp : 1;
+    float *s = state;
+    fmo_state_copy(&s, pl->i_state, Tr, 1, dir);
+    fmo_state_copy(&s, pl->q_state, Tr, 1, dir);
+    fmo_state_copy(&s, &pl->prev_i, 1, 1, dir);
+    fmo_state_copy(&s, &pl->prev_q, 1, 1, dir);
+    fmo_state_copy(&s, pl->state_mono, Ha, U, dir);
+    if (pl->channels == 2) {
+        fmo_state_copy(&s, pl->state_stereo, St1, 1, dir);
+        fmo_state_copy(&s, pl->state_carrier, St1, 1, dir);
+        fmo_state_copy(&s, pl->state_stereofilt, Ha, U, dir);
+        fmo_state_copy(&s, pl->state_allpass, St1 / 2, 1, dir);
+        fmo_state_copy(&s, pl->state_pll, 6, 1, dir);
+    }
+    return 0;
+}
+
+int fmo_pipeline_get_state(const fmo_pipeline *pl, float *state, size_t n)
+{
+    return fmo_state_walk((fmo_pipeline *)pl, state, n, 0);
+}
+
+int fmo_pipeline_set_state(fmo_pipeline *pl, const float *state, size_t n)
+{
+    return fmo_state_walk(pl, (float *)state, n, 1);
+}
+
 void fmo_libm(int fn, const float *a, const float *b, size_t n, float *out)
 {
     for (size_t i = 0; i < n; i++) out[i] = fn == 0 ? sinf(a[i]) : fn == 1 ? cosf(a[i]) : atan2f(a[i], b[i]);

@@ -110,6 +110,16 @@ size_t fmo_pipeline_n_audio(const fmo_pipeline *pl, size_t n_bytes);
  * 4 allpass, 5 mono_filt, 6 stereo_final.  Returns length. */
 size_t fmo_pipeline_intermediate(const fmo_pipeline *pl, int which, const float **ptr);
 
+/* The carried state (project.cpp:61-65, 446-458), serialised as floats in the order of include/fmrx.h
+ * (fmrx_pipeline_state_size): I_state[rf_taps-1], Q_state[rf_taps-1], prev_i, prev_q, state_mono[Ha] (+ stereo:
+ * state_stereo[St-1], state_carrier[St-1], state_stereofilt[Ha], state_allpass[(St-1)/2], state_PLL[6]), Ha = audio_taps-1, or
+ * (audio_taps-1)/upsamp for the resampling modes: there state_mono and state_stereofilt are given compact, as the slots
+ * upsamp-1 :: upsamp of the upsampled-space vector (the only ones filter.cpp:199, 218-222 reads or writes).  The oracle's own
+ * vectors are copied, each for itself.  get / set return 0, or -1 when n is not the size. */
+size_t fmo_pipeline_state_size(const fmo_pipeline *pl);
+int fmo_pipeline_get_state(const fmo_pipeline *pl, float *state, size_t n);
+int fmo_pipeline_set_state(fmo_pipeline *pl, const float *state, size_t n);
+
 /* ---- diagnostics ----------------------------------- */
 /* src/fourier.cpp:44-128 estimatePSD: Bartlett average of Hann-windowed
  * nfft-point DFTs (src/fourier.cpp:15-23), in dB; nfft = NFFT = 512

@@ -26,6 +26,17 @@ int main(void)
                 size_t na = fmo_pipeline_process(pl, iq, nb, NULL, NULL, dm, al, ch == 2 ? ar : NULL);
                 if (na != fmo_pipeline_n_audio(pl, nb)) return 2;
             }
+            /* state accessors: exact-size vector out, into a fresh handle, out again; a wrong length is refused */
+            const size_t ns = fmo_pipeline_state_size(pl);
+            float *st = (float *)malloc(sizeof(float) * ns), *st2 = (float *)malloc(sizeof(float) * ns);
+            fmo_pipeline *pl2 = fmo_pipeline_create(&p, ch);
+            if (fmo_pipeline_get_state(pl, st, ns) || fmo_pipeline_set_state(pl2, st, ns) || fmo_pipeline_get_state(pl2, st2, ns)) return 4;
+            if (memcmp(st, st2, sizeof(float) * ns)) return 5;
+            if (fmo_pipeline_get_state(pl, st, ns - 1) != -1 || fmo_pipeline_set_state(pl2, st, ns + 1) != -1) return 6;
+            fmo_synth_fm_u8(iq, nb / 2, p.rf_Fs, 7, (uint64_t)nb);
+            fmo_pipeline_process(pl2, iq, nb, NULL, NULL, dm, al, ch == 2 ? ar : NULL);
+            fmo_pipeline_destroy(pl2);
+            free(st2); free(st);
             int16_t *pcm = (int16_t *)malloc(sizeof(int16_t) * fmo_pipeline_n_audio(pl, nb));
             fmo_pcm16(al, fmo_pipeline_n_audio(pl, nb), pcm, 1);
             fmo_pcm16(al, fmo_pipeline_n_audio(pl, nb), pcm, 0);

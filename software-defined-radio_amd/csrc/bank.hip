@@ -134,6 +134,8 @@ int bank_create(Bank **out, const fmrx_params &p, int n_channels, int audio_chan
     const bool stereo = audio_channels == 2;
     if (!exact && !stereo && p.audio_upsamp == 0)
         return fail(FMRX_EINVAL, "channels: the fast mono bank of the integer-decimation modes is fmrx_channels_create's");
+    if (p.audio_upsamp > 0 && p.audio_taps % p.audio_upsamp != 0)   // as fmrx_pipeline_create: the reference is a stream only then
+        return fail(FMRX_EINVAL, "channels: audio_taps %d is not a multiple of audio_upsamp %d", p.audio_taps, p.audio_upsamp);
     std::unique_ptr<Bank> b(new Bank);   // (a failure below frees what was built so far)
     if (!bank_resolve(p, audio_channels, exact, b->k))
         return fail(FMRX_EINVAL, "channels (exact): no reference-order kernels for rf %d/%d, audio %d/%d, stereo %d taps (modes 0 and 1 of the "

@@ -242,6 +242,11 @@ int fmrx_pipeline_create(fmrx_pipeline **out, const fmrx_params *p, int channels
     if (channels == 2 && (p->stereo_taps < 2 || p->stereo_taps > 65535))
         return fail(FMRX_EINVAL, "pipeline_create: bad stereo_taps");
     if (max_block_bytes < 2) return fail(FMRX_EINVAL, "pipeline_create: max_block_bytes too small");
+    // the reference's resampler refreshes its state in steps of upsamp from slot upsamp-1 (src/filter.cpp:218-222) and reads
+    // it at taps-1 - d*upsamp (:207): the two meet only when upsamp divides taps.  Otherwise the reference is not a stream (its
+    // output depends on where the blocks are cut), and the stream this handle computes would differ from it silently
+    if (p->audio_upsamp > 0 && p->audio_taps % p->audio_upsamp != 0)
+        return fail(FMRX_EINVAL, "pipeline_create: audio_taps %d is not a multiple of audio_upsamp %d", p->audio_taps, p->audio_upsamp);
     FMRX_TRY(require_device());
     FMRX_HIP(hipSetDevice(device));
 
@@ -941,9 +946,7 @@ int fmrx_pipeline_set_state(fmrx_pipeline *pl, const float *state, size_t n)
                 return fail(FMRX_EINVAL, "set_state: front-end state holds a value that is not (u8-128)/128");
             hist[hb - live + 2 * i + c] = static_cast<uint8_t>(v);
         }
-    FMRX_HIP(hipMemcpy(pl->fe_hist[pl->fe_cur].p, hist.data(), hb, hipMemcpyHostToDevice));
-    FMRX_HIP(hipMemcpy(pl->prev_iq[pl->prev_cur].p, o, 2 * sizeof(float), hipMemcpyHostToDevice));
-    o += 2;
+    const float *s_prev = o; o += 2;
     std::vector<float> dh(pl->Hd, 0.0f);
     float *dend = dh.data() + pl->Hd;
     const float *s_mono = o; o += pl->Ha;
@@ -956,7 +959,16 @@ int fmrx_pipeline_set_state(fmrx_pipeline *pl, const float *state, size_t n)
         std::memcpy(dend - pl->delay - pl->Ha, s_mono, pl->Ha * sizeof(float));
         std::memcpy(dend - pl->delay, s_ap, pl->delay * sizeof(float));
         std::memcpy(dend - (pl->St - 1), s_st, (pl->St - 1) * sizeof(float));
-        (void)s_car;  // identical to state_stereo by construction (same input stream)
+        // every consumer of the discriminator output reads ONE history here, of which the reference's vectors are windows
+        // (state_carrier and state_stereo the same one): a state whose windows disagree is not a state of this receiver
+        const int St1 = pl->St - 1;
+        const int wm = St1 - pl->delay < pl->Ha ? St1 - pl->delay : pl->Ha;   // state_mono's samples inside state_stereo's window
+        // (checked before anything is written: a refused state leaves the handle as it was)
+        if (std::memcmp(s_car, s_st, St1 * sizeof(float)) != 0 ||
+            std::memcmp(s_ap, s_st + St1 - pl->delay, pl->delay * sizeof(float)) != 0 ||
+            std::memcmp(s_mono + pl->Ha - wm, s_st + St1 - pl->delay - wm, wm * sizeof(float)) != 0)
+            return fail(FMRX_EINVAL, "set_state: state_stereo, state_carrier, state_allpass and state_mono are windows of one "
+                                     "discriminator history and must agree where they overlap");
         FMRX_HIP(hipMemset(pl->mix_tail[pl->mix_cur].p, 0, pl->Hm * sizeof(float)));
         FMRX_HIP(hipMemcpy(pl->mix_tail[pl->mix_cur].p + (pl->Hm - pl->Ha), s_sf, pl->Ha * sizeof(float), hipMemcpyHostToDevice));
         FMRX_HIP(hipMemcpy(pl->pll_state.p, o, 6 * sizeof(float), hipMemcpyHostToDevice));
@@ -965,6 +977,8 @@ int fmrx_pipeline_set_state(fmrx_pipeline *pl, const float *state, size_t n)
     } else {
         std::memcpy(dend - pl->Ha, s_mono, pl->Ha * sizeof(float));
     }
+    FMRX_HIP(hipMemcpy(pl->fe_hist[pl->fe_cur].p, hist.data(), hb, hipMemcpyHostToDevice));
+    FMRX_HIP(hipMemcpy(pl->prev_iq[pl->prev_cur].p, s_prev, 2 * sizeof(float), hipMemcpyHostToDevice));
     FMRX_HIP(hipMemcpy(pl->demod_buf[0].p, dh.data(), pl->Hd * sizeof(float), hipMemcpyHostToDevice));
     pl->demod_last = 0;
     pl->demod_n_last = 0;

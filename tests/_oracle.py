@@ -163,6 +163,9 @@ class Oracle(_FirFamily):
         self._sig("fmo_pipeline_n_if", C.c_size_t, [C.c_void_p, C.c_size_t])
         self._sig("fmo_pipeline_n_audio", C.c_size_t, [C.c_void_p, C.c_size_t])
         self._sig("fmo_pipeline_intermediate", C.c_size_t, [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_float))])
+        self._sig("fmo_pipeline_state_size", C.c_size_t, [C.c_void_p])
+        self._sig("fmo_pipeline_get_state", C.c_int, [C.c_void_p, f32p, C.c_size_t])
+        self._sig("fmo_pipeline_set_state", C.c_int, [C.c_void_p, f32p, C.c_size_t])
         self._sig("fmo_synth_fm_u8", None, [u8p, C.c_size_t, C.c_double, C.c_uint64, C.c_uint64])
         self._sig("fmo_estimate_psd", C.c_int, [f32p, f32p, f32p, C.c_size_t, C.c_float, C.c_int])
         self._sig("fmo_libm", None, [C.c_int, f32p, f32p, C.c_size_t, f32p])
@@ -242,6 +245,22 @@ class OraclePipeline:
         pp = C.POINTER(C.c_float)()
         n = self.o.lib.fmo_pipeline_intermediate(self.h, self.NAMES[name], C.byref(pp))
         return np.ctypeslib.as_array(pp, shape=(n,)).copy()
+
+
+    def state_size(self) -> int:
+        return self.o.lib.fmo_pipeline_state_size(self.h)
+
+    def get_state(self) -> np.ndarray:
+        """The carried state in the order of include/fmrx.h (fmrx_pipeline_get_state)."""
+        st = np.zeros(self.state_size(), np.float32)
+        if self.o.lib.fmo_pipeline_get_state(self.h, st, len(st)) != 0:
+            raise ValueError("fmo_pipeline_get_state")
+        return st
+
+    def set_state(self, st) -> None:
+        st = _f32(st)
+        if self.o.lib.fmo_pipeline_set_state(self.h, st, len(st)) != 0:
+            raise ValueError(f"fmo_pipeline_set_state: {len(st)} floats, expected {self.state_size()}")
 
 
 class Ref(_FirFamily):
