@@ -71,6 +71,9 @@ FMRX_API int fmrx_set_device(int device);
  * FMRX_<NAME IN CAPITALS>; fmrx_set_option changes the defaults afterwards.  A pipeline handle copies the
  * defaults when it is created and keeps its own set (fmrx_pipeline_set_option); the stage functions use the
  * defaults.  Nothing on a per-block path reads the environment.
+ * A value outside an option's range is FMRX_EINVAL and changes nothing: the ranges are given below; where none is given, any int
+ * (for "fused_min_audio", any long).  An environment value is one of the option's names (=mfma, ...) or a whole base-10 integer
+ * and passes the same check; one that does not is ignored with one line on stderr, and the built-in value stays.
  *   "fe_variant"       0 = matrix-core front-end kernels (default; FMRX_FE_VARIANT=mfma), 1 = vector-ALU kernels (=valu)
  *   "fused_min_audio"  audio samples per call from which the fused mono kernel is used (default 65536; 0 = always)
  *   "resample_l2"      1 = the L2-table resampler kernel also for large calls
@@ -84,14 +87,15 @@ FMRX_API int fmrx_set_device(int device);
  *   "tuner_variant"    wideband tuner: 0 = matrix-core kernel (default; FMRX_TUNER_VARIANT=mfma), 1 = generic kernel (=generic)
  *   "pll_warmup", "pll_segment"               lane shape of the parallel-in-time PLL (-1 = built-in)
  *   "deemph_warmup", "deemph_segment"         lane shape of the parallel-in-time de-emphasis filter (-1 = built-in 256 / 256;
- *                      warm-up >= 0, segment >= 1): any shape gives the same bits, only the misses change
+ *                      warm-up 0 .. 2^20, segment 1 .. 2^20): any shape gives the same bits, only the misses change
  *   "deemph_mode"      de-emphasis: 0 = parallel in time (default), 1 = one lane per row, serially (same bits; measurements)
  *   "pll_start"        where the parallel PLL's lanes start: 1 (default) = the locked loop solved as a linear system of the
  *                      input's signs + 64 true steps, 0 = the block's initial state plus drift + 512 true steps
  *   "pll_mode"         stereo PLL of the specialised pipeline: 0 = parallel in time, fast math (default),
  *                      1 = serial, fast math, 2 = serial, glibc's functions (cause-by-cause variants)
- *   "demod"            0 (default) = the C++ reference's discriminator fmDemod (src/filter.cpp:248-266); 1 = the Python model's
- *                      arctangent demodulator fmDemodArctan (model/fmSupportLib.py:502-531, float64 atan2 + unwrap): the pipeline
+ *   "demod"            0 (default; FMRX_DEMOD=discriminator) = the C++ reference's discriminator fmDemod (src/filter.cpp:248-266);
+ *                      1 (=arctan) = the Python model's arctangent demodulator fmDemodArctan
+ *                      (model/fmSupportLib.py:502-531, float64 atan2 + unwrap): the pipeline
  *                      then runs its unfused kernels (front end -> IF stream -> arctan -> audio / stereo stages) */
 FMRX_API int fmrx_set_option(const char *name, long value);
 FMRX_API int fmrx_get_option(const char *name, long *value);

@@ -233,13 +233,23 @@ def set_device(dev: int) -> None:
     _check(lib.fmrx_set_device(dev))
 
 
-_FE_VARIANTS = {"mfma": 0, "valu": 1, "generic": 1, "discriminator": 0, "arctan": 1}   # option values that have names
+# option values that have names, per option (the same names as the table in csrc/options.cpp)
+_OPTION_NAMES = {"fe_variant": {"mfma": 0, "valu": 1}, "tuner_variant": {"mfma": 0, "generic": 1},
+                 "demod": {"discriminator": 0, "arctan": 1}}
+
+
+def _option_value(name: str, value) -> int:
+    names = _OPTION_NAMES.get(name, {})
+    if isinstance(value, str) and value not in names:
+        raise FmrxError(EINVAL, f"option {name}: '{value}' is not one of its named values {sorted(names)}")
+    return names[value] if isinstance(value, str) else int(value)
 
 
 def set_option(name: str, value) -> None:
     """Process-wide default of a run-time option (include/fmrx.h: fmrx_set_option); pipelines created
-    afterwards start from it.  fe_variant also takes "mfma" / "valu", tuner_variant "mfma" / "generic"."""
-    _check(lib.fmrx_set_option(name.encode(), int(_FE_VARIANTS.get(value, value))))
+    afterwards start from it.  fe_variant also takes "mfma" / "valu", tuner_variant "mfma" / "generic",
+    demod "discriminator" / "arctan"."""
+    _check(lib.fmrx_set_option(name.encode(), _option_value(name, value)))
 
 
 def get_option(name: str) -> int:
@@ -571,7 +581,7 @@ class Pipeline:
 
     def set_option(self, name: str, value):
         """Per-handle run-time option (fmrx_pipeline_set_option); fe_variant also takes "mfma" / "valu"."""
-        _check(lib.fmrx_pipeline_set_option(self._h, name.encode(), int(_FE_VARIANTS.get(value, value))))
+        _check(lib.fmrx_pipeline_set_option(self._h, name.encode(), _option_value(name, value)))
 
     def process(self, iq_u8, want_pcm=True, wrap=True):
         """One block of interleaved u8 I/Q (host) -> dict(audio=..., [audio_l, audio_r], pcm16=...)."""

@@ -3,7 +3,7 @@
 // primitive (include/filter.h:18-43, include/iofunc.h:36 under /root/reference).
 //
 // Every stage function: validate (the reference's unchecked preconditions
-// become FMRX_EINVAL) -> H2D into per-thread scratch -> HIP kernel(s) -> D2H.
+// become FMRX_EINVAL) -> H2D into per-thread scratch (Stage) -> HIP kernel(s) -> D2H.
 // No stage has a CPU implementation: without a device they return FMRX_ENODEV.
 #include "fmrx_internal.hpp"
 #include "rds_station.hpp"
@@ -15,14 +15,6 @@ namespace fmrx {
 
 // ---- error plumbing ----------------------------------------------------------
 static thread_local char g_err[512] = "";
-
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
 
 int fail(int code, const char *fmt, ...)
 {
@@ -45,116 +37,61 @@ int require_device()
     return FMRX_OK;
 }
 
-// ---- run-time options -----------------------------------------------------------
-bool option_ref(Options &o, const char *name, long **as_long, int **as_int)
-{
-    *as_long = nullptr;
-    *as_int = nullptr;
-    const std::string n = name ? name : "";
-    if (n == "fused_min_audio") *as_long = &o.fused_min_audio;
-    else if (n == "fe_variant") *as_int = &o.fe_variant;
-    else if (n == "resample_l2") *as_int = &o.resample_l2;
-    else if (n == "resample_exact") *as_int = &o.resample_exact;
-    else if (n == "pll_warmup") *as_int = &o.pll_warmup;
-    else if (n == "pll_segment") *as_int = &o.pll_segment;
-    else if (n == "pll_start") *as_int = &o.pll_start;
-    else if (n == "pll_mode") *as_int = &o.pll_mode;
-    else if (n == "demod") *as_int = &o.demod;
-    else if (n == "tuner_variant") *as_int = &o.tuner_variant;
-    else if (n == "resample_chains") *as_int = &o.resample_chains;
-    else if (n == "overlap_calls") *as_int = &o.overlap_calls;
-    else if (n == "deemph_warmup") *as_int = &o.deemph_warmup;
-    else if (n == "deemph_segment") *as_int = &o.deemph_segment;
-    else if (n == "deemph_mode") *as_int = &o.deemph_mode;
-    else return false;
-    return true;
-}
-
-// built-in values, overridden once by the environment (first use; thread-safe static initialisation)
-Options &default_options()
-{
-    static Options o = [] {
-        Options d;
-        if (const char *e = std::getenv("FMRX_FE_VARIANT")) d.fe_variant = std::strcmp(e, "valu") == 0 ? 1 : 0;
-        if (const char *e = std::getenv("FMRX_FUSED_MIN_AUDIO")) d.fused_min_audio = std::atol(e);
-        if (std::getenv("FMRX_RESAMPLE_L2")) d.resample_l2 = 1;
-        if (const char *e = std::getenv("FMRX_RESAMPLE_EXACT")) d.resample_exact = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_RESAMPLE_CHAINS")) d.resample_chains = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_OVERLAP_CALLS")) d.overlap_calls = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_PLL_WARMUP")) d.pll_warmup = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_PLL_SEGMENT")) d.pll_segment = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_PLL_START")) d.pll_start = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_PLL_MODE")) d.pll_mode = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_DEEMPH_WARMUP")) d.deemph_warmup = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_DEEMPH_SEGMENT")) d.deemph_segment = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_DEEMPH_MODE")) d.deemph_mode = std::atoi(e);
-        if (const char *e = std::getenv("FMRX_TUNER_VARIANT")) d.tuner_variant = std::strcmp(e, "generic") == 0 ? 1 : 0;
-        if (const char *e = std::getenv("FMRX_DEMOD")) d.demod = std::strcmp(e, "arctan") == 0 ? 1 : std::atoi(e);
-        return d;
-    }();
-    return o;
-}
-
-std::mutex &options_mutex()
-{
-    static std::mutex m;
-    return m;
-}
-
-Options options_snapshot()
-{
-    std::lock_guard<std::mutex> lock(options_mutex());
-    return default_options();
-}
-
-int set_option_in(Options &o, const char *name, long value)
-{
-    long *pl = nullptr;
-    int *pi = nullptr;
-    if (!option_ref(o, name, &pl, &pi)) return fail(FMRX_EINVAL, "unknown option '%s'", name ? name : "(null)");
-    if (pi == &o.fe_variant && value != 0 && value != 1) return fail(FMRX_EINVAL, "option fe_variant: 0 (mfma) or 1 (valu)");
-    if (pi == &o.tuner_variant && value != 0 && value != 1) return fail(FMRX_EINVAL, "option tuner_variant: 0 (mfma) or 1 (generic)");
-    if (pi == &o.pll_mode && (value < 0 || value > 2)) return fail(FMRX_EINVAL, "option pll_mode: 0, 1 or 2");
-    if (pi == &o.demod && value != 0 && value != 1) return fail(FMRX_EINVAL, "option demod: 0 (the C++ reference's discriminator) or 1 (arctan)");
-    if (pi == &o.deemph_warmup && (value < -1 || value > (1 << 20))) return fail(FMRX_EINVAL, "option deemph_warmup: -1 (built-in) or 0 .. 2^20");
-    if (pi == &o.deemph_segment && (value < -1 || value == 0 || value > (1 << 20))) return fail(FMRX_EINVAL, "option deemph_segment: -1 (built-in) or 1 .. 2^20");
-    if (pi == &o.deemph_mode && value != 0 && value != 1) return fail(FMRX_EINVAL, "option deemph_mode: 0 (parallel in time) or 1 (serial)");
-    if (pl) *pl = value;
-    else *pi = static_cast<int>(value);
-    return FMRX_OK;
-}
-
 namespace {
 
-// per-thread device scratch for the host-buffer stage functions
-struct Scratch {
-    DevBuf<float> a, b, c, d, h;
-    DevBuf<uint8_t> u, uh;
-    DevBuf<int16_t> s16;
-};
-Scratch &scratch()
-{
-    static thread_local Scratch s;
-    return s;
-}
+// Per-thread device scratch of the stage functions: one set of slots, each its own allocation (so growing one never moves
+// another, and each keeps hipMalloc's alignment), grown on demand and typed by whoever asks.  A call makes one Stage and gets
+// slot k for its k-th request.  The host-buffer functions are synchronous and share the first kHostSlots; the two device-pointer
+// functions, whose kernel may still run when the next call on this thread begins, each own a slot behind those.
+constexpr int kHostSlots = 6, kDeemphDevSlot = 6, kStreamReadSlot = 7, kStageSlots = 8;
+using StageSlot = DevBuf<unsigned char>;
+thread_local StageSlot g_slots[kStageSlots];
 
-inline int h2d(void *dst, const void *src, size_t bytes)
+inline int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
 {
-    if (bytes == 0) return FMRX_OK;
-    FMRX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    if (bytes) FMRX_HIP(hipMemcpy(dst, src, bytes, kind));
     return FMRX_OK;
 }
-inline int d2h(void *dst, const void *src, size_t bytes)
-{
-    if (bytes == 0) return FMRX_OK;
-    FMRX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return FMRX_OK;
-}
+inline int h2d(void *dst, const void *src, size_t bytes) { return copy(dst, src, bytes, hipMemcpyHostToDevice); }
+inline int d2h(void *dst, const void *src, size_t bytes) { return copy(dst, src, bytes, hipMemcpyDeviceToHost); }
 inline int sync0()
 {
     FMRX_HIP(hipStreamSynchronize(nullptr));
     return FMRX_OK;
 }
+
+template <typename T>
+struct Dev {
+    T *p = nullptr;
+    size_t n = 0;   // elements asked for
+};
+struct Stage {
+    int k, end;
+    explicit Stage(int first = 0, int count = kHostSlots) : k(first), end(first + count) {}
+    // device buffer for n outputs
+    template <typename T>
+    int out(Dev<T> &d, size_t n)
+    {
+        if (k >= end) return fail(FMRX_EINVAL, "stage scratch: no slot %d for this call", k);
+        StageSlot &slot = g_slots[k++];
+        FMRX_TRY(slot.ensure(n * sizeof(T)));
+        d = {reinterpret_cast<T *>(slot.p), n};
+        return FMRX_OK;
+    }
+    // device buffer filled from this host array
+    template <typename T>
+    int in(Dev<T> &d, const T *host, size_t n)
+    {
+        FMRX_TRY(out(d, n));
+        return h2d(d.p, host, n * sizeof(T));
+    }
+    // part of a buffer (the [history | block] layouts): n elements to d
+    template <typename T>
+    static int put(T *d, const T *host, size_t n) { return h2d(d, host, n * sizeof(T)); }
+    // copy back: the whole buffer, or its first n elements
+    template <typename T>
+    static int back(T *host, const Dev<T> &d, size_t n = SIZE_MAX) { return d2h(host, d.p, (n < d.n ? n : d.n) * sizeof(T)); }
+};
 
 }  // namespace
 }  // namespace fmrx
@@ -179,11 +116,7 @@ int fmrx_set_option(const char *name, long value)
 int fmrx_get_option(const char *name, long *value)
 {
     std::lock_guard<std::mutex> lock(options_mutex());
-    long *pl = nullptr;
-    int *pi = nullptr;
-    if (!value || !option_ref(default_options(), name, &pl, &pi)) return fail(FMRX_EINVAL, "unknown option '%s'", name ? name : "(null)");
-    *value = pl ? *pl : *pi;
-    return FMRX_OK;
+    return get_option_in(default_options(), name, value);
 }
 const char *fmrx_last_error(void) { return g_err; }
 
@@ -223,38 +156,40 @@ int fmrx_u8_to_f32(const uint8_t *raw, size_t n, float *out)
 {
     if ((!raw || !out) && n) return fail(FMRX_EINVAL, "u8_to_f32: null buffer");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.u.ensure(n));
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(h2d(s.u.p, raw, n));
-    FMRX_TRY(k_u8_to_f32(s.u.p, n, s.a.p, nullptr));
-    return d2h(out, s.a.p, n * sizeof(float));
+    Stage st;
+    Dev<uint8_t> u;
+    Dev<float> a;
+    FMRX_TRY(st.in(u, raw, n));
+    FMRX_TRY(st.out(a, n));
+    FMRX_TRY(k_u8_to_f32(u.p, n, a.p, nullptr));
+    return st.back(out, a);
 }
 
 int fmrx_deinterleave(const float *iq, size_t n_pairs, float *I, float *Q)
 {
     if ((!iq || !I || !Q) && n_pairs) return fail(FMRX_EINVAL, "deinterleave: null buffer");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(2 * n_pairs));
-    FMRX_TRY(s.b.ensure(n_pairs));
-    FMRX_TRY(s.c.ensure(n_pairs));
-    FMRX_TRY(h2d(s.a.p, iq, 2 * n_pairs * sizeof(float)));
-    FMRX_TRY(k_deinterleave(s.a.p, n_pairs, s.b.p, s.c.p, nullptr));
-    FMRX_TRY(d2h(I, s.b.p, n_pairs * sizeof(float)));
-    return d2h(Q, s.c.p, n_pairs * sizeof(float));
+    Stage st;
+    Dev<float> a, b, c;
+    FMRX_TRY(st.in(a, iq, 2 * n_pairs));
+    FMRX_TRY(st.out(b, n_pairs));
+    FMRX_TRY(st.out(c, n_pairs));
+    FMRX_TRY(k_deinterleave(a.p, n_pairs, b.p, c.p, nullptr));
+    FMRX_TRY(st.back(I, b));
+    return st.back(Q, c);
 }
 
 int fmrx_pcm16(const float *audio, size_t n, int16_t *out, int wrap)
 {
     if ((!audio || !out) && n) return fail(FMRX_EINVAL, "pcm16: null buffer");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.s16.ensure(n));
-    FMRX_TRY(h2d(s.a.p, audio, n * sizeof(float)));
-    FMRX_TRY(k_pcm16(s.a.p, n, s.s16.p, wrap, nullptr));
-    return d2h(out, s.s16.p, n * sizeof(int16_t));
+    Stage st;
+    Dev<float> a;
+    Dev<int16_t> s16;
+    FMRX_TRY(st.in(a, audio, n));
+    FMRX_TRY(st.out(s16, n));
+    FMRX_TRY(k_pcm16(a.p, n, s16.p, wrap, nullptr));
+    return st.back(out, s16);
 }
 
 // ---- FIR family -----------------------------------------------------------------------
@@ -263,17 +198,17 @@ int fmrx_pcm16(const float *audio, size_t n, int16_t *out, int wrap)
 static int fir_common(float *y, size_t n_out, const float *x, size_t n, const float *h, size_t taps,
                       const float *state, size_t n_hist, size_t n_tail_zero, unsigned decim)
 {
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n_hist + n + n_tail_zero));
-    FMRX_TRY(s.h.ensure(taps));
-    FMRX_TRY(s.b.ensure(n_out));
-    if (state) FMRX_TRY(h2d(s.a.p, state, n_hist * sizeof(float)));
-    else FMRX_HIP(hipMemset(s.a.p, 0, n_hist * sizeof(float)));
-    FMRX_TRY(h2d(s.a.p + n_hist, x, n * sizeof(float)));
-    if (n_tail_zero) FMRX_HIP(hipMemset(s.a.p + n_hist + n, 0, n_tail_zero * sizeof(float)));
-    FMRX_TRY(h2d(s.h.p, h, taps * sizeof(float)));
-    FMRX_TRY(k_fir_generic(s.a.p + n_hist, n_out, s.h.p, static_cast<int>(taps), static_cast<int>(decim), s.b.p, nullptr));
-    return d2h(y, s.b.p, n_out * sizeof(float));
+    Stage st;
+    Dev<float> a, dh, b;
+    FMRX_TRY(st.out(a, n_hist + n + n_tail_zero));
+    if (state) FMRX_TRY(st.put(a.p, state, n_hist));
+    else FMRX_HIP(hipMemset(a.p, 0, n_hist * sizeof(float)));
+    FMRX_TRY(st.put(a.p + n_hist, x, n));
+    if (n_tail_zero) FMRX_HIP(hipMemset(a.p + n_hist + n, 0, n_tail_zero * sizeof(float)));
+    FMRX_TRY(st.in(dh, h, taps));
+    FMRX_TRY(st.out(b, n_out));
+    FMRX_TRY(k_fir_generic(a.p + n_hist, n_out, dh.p, static_cast<int>(taps), static_cast<int>(decim), b.p, nullptr));
+    return st.back(y, b);
 }
 
 int fmrx_convolve_fir(float *y, const float *x, size_t n, const float *h, size_t taps)
@@ -326,13 +261,13 @@ int fmrx_convolve_block_resample_fir(float *y, const float *x, size_t n, const f
     const size_t H = (taps - 1) / upsamp;
     std::vector<float> hist(H ? H : 1, 0.0f);
     for (size_t d = 1; d <= H; d++) hist[H - d] = state[taps - 1 - d * upsamp];
-    Scratch &s = scratch();
-    const size_t n_out = (n * upsamp) / decim;
+    Stage st;
+    Dev<float> a, b;
     const size_t Hp = (H + 3) / 4 * 4;   // keeps the block 16-byte aligned behind its history
-    FMRX_TRY(s.a.ensure(Hp + n));
-    FMRX_TRY(s.b.ensure(n_out));
-    FMRX_TRY(h2d(s.a.p + (Hp - H), hist.data(), H * sizeof(float)));
-    FMRX_TRY(h2d(s.a.p + Hp, x, n * sizeof(float)));
+    FMRX_TRY(st.out(a, Hp + n));
+    FMRX_TRY(st.out(b, (n * upsamp) / decim));
+    FMRX_TRY(st.put(a.p + (Hp - H), hist.data(), H));
+    FMRX_TRY(st.put(a.p + Hp, x, n));
     // polyphase-table kernels (bit-exact: the reference's operations in its order, kernels_resample.hip);
     // the LDS-resident-table form from 65 536 outputs per call unless the option resample_l2 is set
     // the plan (polyphase table, tap images: several device allocations and copies) is kept per thread and rebuilt only when
@@ -350,9 +285,9 @@ int fmrx_convolve_block_resample_fir(float *y, const float *x, size_t n, const f
         pc.decim = decim;
         pc.upsamp = upsamp;
     }
-    FMRX_TRY(resample_launch(pc.plan, s.a.p + Hp, n, 0, s.b.p, options_snapshot(), nullptr, false, /*exact=*/true));
+    FMRX_TRY(resample_launch(pc.plan, a.p + Hp, n, 0, b.p, options_snapshot(), nullptr, false, /*exact=*/true));
     FMRX_TRY(sync0());
-    FMRX_TRY(d2h(y, s.b.p, n_out * sizeof(float)));
+    FMRX_TRY(st.back(y, b));
     // state refresh exactly as src/filter.cpp:218-222 (host copy): k = U-1; for
     // i = U*n-(taps-1); i < U*n-U; i += U: state[k] = x[i/U + 1]; k += U
     {
@@ -371,12 +306,12 @@ int fmrx_upsample(const float *x, size_t n, float *xu, int up)
     if ((!x || !xu) && n) return fail(FMRX_EINVAL, "upsample: null buffer");
     if (up < 1) return fail(FMRX_EINVAL, "upsample: rate must be >= 1");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(n * up));
-    FMRX_TRY(h2d(s.a.p, x, n * sizeof(float)));
-    FMRX_TRY(k_upsample(s.a.p, n, s.b.p, up, nullptr));
-    return d2h(xu, s.b.p, n * up * sizeof(float));
+    Stage st;
+    Dev<float> a, b;
+    FMRX_TRY(st.in(a, x, n));
+    FMRX_TRY(st.out(b, n * up));
+    FMRX_TRY(k_upsample(a.p, n, b.p, up, nullptr));
+    return st.back(xu, b);
 }
 
 int fmrx_downsample(float *out, size_t *n_out, const float *in, size_t n, unsigned short ds)
@@ -387,12 +322,13 @@ int fmrx_downsample(float *out, size_t *n_out, const float *in, size_t n, unsign
     // size rule of src/filter.cpp:240: ceil(n / (float)ds), evaluated in float
     const size_t ny = static_cast<size_t>(ceilf(static_cast<float>(n) / static_cast<float>(ds)));
     *n_out = ny;
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n + ds));
-    FMRX_TRY(s.b.ensure(ny));
-    FMRX_TRY(h2d(s.a.p, in, n * sizeof(float)));
-    FMRX_TRY(k_downsample(s.a.p, ny, s.b.p, ds, nullptr));
-    return d2h(out, s.b.p, ny * sizeof(float));
+    Stage st;
+    Dev<float> a, b;
+    FMRX_TRY(st.out(a, n + ds));
+    FMRX_TRY(st.put(a.p, in, n));
+    FMRX_TRY(st.out(b, ny));
+    FMRX_TRY(k_downsample(a.p, ny, b.p, ds, nullptr));
+    return st.back(out, b);
 }
 
 // ---- demod / stereo helpers -----------------------------------------------------------
@@ -401,14 +337,13 @@ int fmrx_fm_demod(float *out, const float *I, const float *Q, size_t n, float *p
     if (!out || !I || !Q || !prev_i || !prev_q) return fail(FMRX_EINVAL, "fm_demod: null buffer");
     if (n == 0) return FMRX_OK;
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(n));
-    FMRX_TRY(s.c.ensure(n));
-    FMRX_TRY(h2d(s.a.p, I, n * sizeof(float)));
-    FMRX_TRY(h2d(s.b.p, Q, n * sizeof(float)));
-    FMRX_TRY(k_fm_demod_planar(s.a.p, s.b.p, n, *prev_i, *prev_q, s.c.p, nullptr));
-    FMRX_TRY(d2h(out, s.c.p, n * sizeof(float)));
+    Stage st;
+    Dev<float> a, b, c;
+    FMRX_TRY(st.in(a, I, n));
+    FMRX_TRY(st.in(b, Q, n));
+    FMRX_TRY(st.out(c, n));
+    FMRX_TRY(k_fm_demod_planar(a.p, b.p, n, *prev_i, *prev_q, c.p, nullptr));
+    FMRX_TRY(st.back(out, c));
     *prev_i = I[n - 1];
     *prev_q = Q[n - 1];
     return FMRX_OK;
@@ -419,15 +354,14 @@ int fmrx_fm_demod_arctan(double *out, const double *I, const double *Q, size_t n
     if (!out || !I || !Q || !prev_phase) return fail(FMRX_EINVAL, "fm_demod_arctan: null buffer");
     if (n == 0) return FMRX_OK;
     FMRX_TRY(require_device());
-    static thread_local DevBuf<double> di, dq, dout;
-    FMRX_TRY(di.ensure(n));
-    FMRX_TRY(dq.ensure(n));
-    FMRX_TRY(dout.ensure(n));
-    FMRX_TRY(h2d(di.p, I, n * sizeof(double)));
-    FMRX_TRY(h2d(dq.p, Q, n * sizeof(double)));
+    Stage st;
+    Dev<double> di, dq, dout;
+    FMRX_TRY(st.in(di, I, n));
+    FMRX_TRY(st.in(dq, Q, n));
+    FMRX_TRY(st.out(dout, n));
     // the phase in front of the block only matters modulo 2 pi (np.unwrap's mod takes care of the turns it has accumulated)
     FMRX_TRY(k_fm_demod_arctan_planar(di.p, dq.p, n, *prev_phase, dout.p, nullptr));
-    FMRX_TRY(d2h(out, dout.p, n * sizeof(double)));
+    FMRX_TRY(st.back(out, dout));
     double ph = *prev_phase;                                // the model's running (unwrapped) phase: prev + the steps, in order
     for (size_t k = 0; k < n; k++) ph += out[k];
     *prev_phase = ph;
@@ -439,14 +373,13 @@ int fmrx_all_pass(const float *in, size_t n, float *state, size_t nstate, float 
     if (!in || !state || !out) return fail(FMRX_EINVAL, "all_pass: null buffer");
     if (n < nstate) return fail(FMRX_EINVAL, "all_pass: block of %zu samples shorter than the delay %zu", n, nstate);
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(nstate));
-    FMRX_TRY(s.c.ensure(n));
-    FMRX_TRY(h2d(s.a.p, in, n * sizeof(float)));
-    FMRX_TRY(h2d(s.b.p, state, nstate * sizeof(float)));
-    FMRX_TRY(k_all_pass(s.a.p, n, s.b.p, nstate, s.c.p, nullptr));
-    FMRX_TRY(d2h(out, s.c.p, n * sizeof(float)));
+    Stage st;
+    Dev<float> a, b, c;
+    FMRX_TRY(st.in(a, in, n));
+    FMRX_TRY(st.in(b, state, nstate));
+    FMRX_TRY(st.out(c, n));
+    FMRX_TRY(k_all_pass(a.p, n, b.p, nstate, c.p, nullptr));
+    FMRX_TRY(st.back(out, c));
     std::memcpy(state, in + n - nstate, nstate * sizeof(float));
     return FMRX_OK;
 }
@@ -457,15 +390,14 @@ int fmrx_fm_pll(const float *in, size_t n, float *nco_out, float *state, float f
     if (!in || !nco_out || !state) return fail(FMRX_EINVAL, "fm_pll: null buffer");
     if (!(Fs > 0)) return fail(FMRX_EINVAL, "fm_pll: Fs must be positive");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(n + 1));
-    FMRX_TRY(s.c.ensure(6));
-    FMRX_TRY(h2d(s.a.p, in, n * sizeof(float)));
-    FMRX_TRY(h2d(s.c.p, state, 6 * sizeof(float)));
-    FMRX_TRY(k_fm_pll(s.a.p, n, s.b.p, s.c.p, freq, Fs, ncoScale, phaseAdjust, normBandwidth, 0, nullptr));
-    FMRX_TRY(d2h(nco_out, s.b.p, (n + 1) * sizeof(float)));
-    return d2h(state, s.c.p, 6 * sizeof(float));
+    Stage st;
+    Dev<float> a, b, c;
+    FMRX_TRY(st.in(a, in, n));
+    FMRX_TRY(st.out(b, n + 1));
+    FMRX_TRY(st.in(c, state, 6));
+    FMRX_TRY(k_fm_pll(a.p, n, b.p, c.p, freq, Fs, ncoScale, phaseAdjust, normBandwidth, 0, nullptr));
+    FMRX_TRY(st.back(nco_out, b));
+    return st.back(state, c);
 }
 
 // The parallel-in-time PLL exactly as pll_stage (pipeline.hip) runs it for a warm pipeline, with what it left in its scratch
@@ -478,27 +410,27 @@ int fmrx_fm_pll_parallel(const float *in, size_t n, float *nco_out, float *state
     if ((!in && n) || !nco_out || !state) return fail(FMRX_EINVAL, "fm_pll_parallel: null buffer");
     if (!(Fs > 0)) return fail(FMRX_EINVAL, "fm_pll_parallel: Fs must be positive");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    const size_t n_scratch = pll_parallel_scratch_floats(n);
-    FMRX_TRY(s.a.ensure(n + 16));
-    FMRX_TRY(s.b.ensure(n + 17));
-    FMRX_TRY(s.c.ensure(8));
-    FMRX_TRY(s.d.ensure(n_scratch));
-    FMRX_TRY(h2d(s.a.p, in, n * sizeof(float)));
-    FMRX_HIP(hipMemset(s.a.p + n, 0, 16 * sizeof(float)));
-    FMRX_HIP(hipMemset(s.d.p, 0, n_scratch * sizeof(float)));
-    FMRX_TRY(h2d(s.c.p, state, 6 * sizeof(float)));
+    Stage st;
+    Dev<float> a, b, c, d;
+    FMRX_TRY(st.out(a, n + 16));
+    FMRX_TRY(st.out(b, n + 17));
+    FMRX_TRY(st.out(c, 8));
+    FMRX_TRY(st.out(d, pll_parallel_scratch_floats(n)));
+    FMRX_TRY(st.put(a.p, in, n));
+    FMRX_HIP(hipMemset(a.p + n, 0, 16 * sizeof(float)));
+    FMRX_HIP(hipMemset(d.p, 0, d.n * sizeof(float)));
+    FMRX_TRY(st.put(c.p, state, 6));
     const float trig_offset = state[5];
     const Options o = options_snapshot();
     PllParallelShape sh{};
-    FMRX_TRY(k_fm_pll_parallel(s.a.p, n, s.b.p, s.c.p, freq, Fs, ncoScale, phaseAdjust, normBandwidth, s.d.p, o, nullptr, off_hint, 3,
-                               nullptr, &sh));
-    FMRX_TRY(d2h(nco_out, s.b.p, (n + 1) * sizeof(float)));
-    FMRX_TRY(d2h(state, s.c.p, 6 * sizeof(float)));
+    FMRX_TRY(k_fm_pll_parallel(a.p, n, b.p, c.p, freq, Fs, ncoScale, phaseAdjust, normBandwidth, d.p, o, nullptr, off_hint, 3, nullptr,
+                               &sh));
+    FMRX_TRY(st.back(nco_out, b, n + 1));
+    FMRX_TRY(st.back(state, c, 6));
     const size_t nseg = static_cast<size_t>(sh.nseg);
     if (info) {
         unsigned hdr[8];
-        FMRX_TRY(d2h(hdr, s.d.p, sizeof(hdr)));
+        FMRX_TRY(d2h(hdr, d.p, sizeof(hdr)));
         info->L = sh.L;
         info->W = sh.W;
         info->lti = sh.lti ? 1 : 0;
@@ -511,7 +443,7 @@ int fmrx_fm_pll_parallel(const float *in, size_t n, float *nco_out, float *state
     if (nseg == 0) return FMRX_OK;
     if (records) {
         std::vector<float> seg(nseg * 16);
-        FMRX_TRY(d2h(seg.data(), s.d.p + 8, seg.size() * sizeof(float)));
+        FMRX_TRY(d2h(seg.data(), d.p + 8, seg.size() * sizeof(float)));
         for (size_t i = 0; i < nseg; i++) {
             float *r = records + i * FMRX_PLL_RECORD_FLOATS;
             for (int u = 0; u < 6; u++) r[u] = seg[i * 16 + u];
@@ -520,7 +452,7 @@ int fmrx_fm_pll_parallel(const float *in, size_t n, float *nco_out, float *state
             r[8] = seg[i * 16 + 10];
         }
     }
-    if (mask) FMRX_TRY(d2h(mask, s.d.p + 8 + (nseg + 1) * 16, (nseg / 64 + 1) * sizeof(uint64_t)));
+    if (mask) FMRX_TRY(d2h(mask, d.p + 8 + (nseg + 1) * 16, (nseg / 64 + 1) * sizeof(uint64_t)));
     return FMRX_OK;
 }
 
@@ -528,30 +460,28 @@ int fmrx_stereo_mix(const float *stereo_filt, const float *pll, size_t n, float 
 {
     if ((!stereo_filt || !pll || !mixer) && n) return fail(FMRX_EINVAL, "stereo_mix: null buffer");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(n));
-    FMRX_TRY(s.c.ensure(n));
-    FMRX_TRY(h2d(s.a.p, stereo_filt, n * sizeof(float)));
-    FMRX_TRY(h2d(s.b.p, pll, n * sizeof(float)));
-    FMRX_TRY(k_mix(s.a.p, s.b.p, n, s.c.p, nullptr));
-    return d2h(mixer, s.c.p, n * sizeof(float));
+    Stage st;
+    Dev<float> a, b, c;
+    FMRX_TRY(st.in(a, stereo_filt, n));
+    FMRX_TRY(st.in(b, pll, n));
+    FMRX_TRY(st.out(c, n));
+    FMRX_TRY(k_mix(a.p, b.p, n, c.p, nullptr));
+    return st.back(mixer, c);
 }
 
 int fmrx_stereo_combine(const float *stereo_final, const float *mono, size_t n, float *left, float *right)
 {
     if ((!stereo_final || !mono || !left || !right) && n) return fail(FMRX_EINVAL, "stereo_combine: null buffer");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(n));
-    FMRX_TRY(s.c.ensure(n));
-    FMRX_TRY(s.d.ensure(n));
-    FMRX_TRY(h2d(s.a.p, stereo_final, n * sizeof(float)));
-    FMRX_TRY(h2d(s.b.p, mono, n * sizeof(float)));
-    FMRX_TRY(k_combine(s.a.p, s.b.p, n, s.c.p, s.d.p, nullptr));
-    FMRX_TRY(d2h(left, s.c.p, n * sizeof(float)));
-    return d2h(right, s.d.p, n * sizeof(float));
+    Stage st;
+    Dev<float> a, b, c, d;
+    FMRX_TRY(st.in(a, stereo_final, n));
+    FMRX_TRY(st.in(b, mono, n));
+    FMRX_TRY(st.out(c, n));
+    FMRX_TRY(st.out(d, n));
+    FMRX_TRY(k_combine(a.p, b.p, n, c.p, d.p, nullptr));
+    FMRX_TRY(st.back(left, c));
+    return st.back(right, d);
 }
 
 // ---- de-emphasis (no counterpart in the reference) -------------------------------------------
@@ -577,35 +507,20 @@ int fmrx_deemph(float *y, const float *x, size_t rows, size_t n, size_t pitch, f
     if (missed) *missed = 0;
     if (rows == 0 || n == 0) return FMRX_OK;
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    const Options o = options_snapshot();
-    static thread_local DevBuf<unsigned long long> cnt;
-    FMRX_TRY(s.a.ensure(rows * pitch));
-    FMRX_TRY(s.b.ensure(rows * pitch));
-    FMRX_TRY(s.c.ensure(2 * rows));
-    FMRX_TRY(s.d.ensure(deemph_scratch_floats(rows, n, o)));
-    FMRX_TRY(cnt.ensure(1));
-    FMRX_TRY(h2d(s.a.p, x, rows * pitch * sizeof(float)));
-    FMRX_TRY(h2d(s.b.p, y, rows * pitch * sizeof(float)));   // (what lies between the rows of y stays the caller's)
-    FMRX_TRY(h2d(s.c.p, state, 2 * rows * sizeof(float)));
+    Stage st;
+    Dev<float> dx, dy, dstate;
+    Dev<unsigned long long> cnt;
+    FMRX_TRY(st.in(dx, x, rows * pitch));
+    FMRX_TRY(st.in(dy, y, rows * pitch));   // (what lies between the rows of y stays the caller's)
+    FMRX_TRY(st.in(dstate, state, 2 * rows));
+    FMRX_TRY(st.out(cnt, 1));
     FMRX_HIP(hipMemset(cnt.p, 0, sizeof(unsigned long long)));
-    DeemphArgs a;
-    a.x = s.a.p;
-    a.y = s.b.p;
-    a.pitch_x = a.pitch_y = static_cast<long>(pitch);
-    a.rows = rows;
-    a.n = n;
-    a.p = p;
-    a.b0 = b0;
-    a.state = s.c.p;
-    a.seg = s.d.p;
-    a.missed = cnt.p;
-    FMRX_TRY(deemph_launch(a, o, false, nullptr, nullptr));
+    FMRX_TRY(fmrx_deemph_dev(dy.p, dx.p, rows, n, pitch, p, b0, dstate.p, cnt.p, nullptr));
     FMRX_TRY(sync0());
-    FMRX_TRY(d2h(y, s.b.p, rows * pitch * sizeof(float)));
-    FMRX_TRY(d2h(state, s.c.p, 2 * rows * sizeof(float)));
+    FMRX_TRY(st.back(y, dy));
+    FMRX_TRY(st.back(state, dstate));
     unsigned long long m = 0;
-    FMRX_TRY(d2h(&m, cnt.p, sizeof(m)));
+    FMRX_TRY(st.back(&m, cnt));
     if (missed) *missed = static_cast<unsigned>(m);
     return FMRX_OK;
 }
@@ -617,8 +532,8 @@ int fmrx_deemph_dev(float *d_y, const float *d_x, size_t rows, size_t n, size_t 
     if (pitch < n) return fail(FMRX_EINVAL, "deemph_dev: pitch %zu < n %zu", pitch, n);
     FMRX_TRY(require_device());
     const Options o = options_snapshot();
-    static thread_local DevBuf<float> seg;   // (grows with the shape: a device-wide wait then, not per call)
-    FMRX_TRY(seg.ensure(deemph_scratch_floats(rows, n, o)));
+    Dev<float> seg;                          // (grows with the shape: a device-wide wait then, not per call)
+    FMRX_TRY(Stage(kDeemphDevSlot, 1).out(seg, deemph_scratch_floats(rows, n, o)));
     DeemphArgs a;
     a.x = d_x;
     a.y = d_y;
@@ -639,22 +554,21 @@ int fmrx_diag_libm(int fn, const float *a, const float *b, size_t n, float *out)
     if (fn < 0 || fn > 5) return fail(FMRX_EINVAL, "diag_libm: fn must be 0 (sinf), 1 (cosf), 2 (atan2f) or 3..5 (their branch-free forms)");
     if ((!a || !out || (fn % 3 == 2 && !b)) && n) return fail(FMRX_EINVAL, "diag_libm: null buffer");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(n));
-    FMRX_TRY(s.c.ensure(n));
-    FMRX_TRY(h2d(s.a.p, a, n * sizeof(float)));
-    if (fn % 3 == 2) FMRX_TRY(h2d(s.b.p, b, n * sizeof(float)));
-    FMRX_TRY(k_libm_eval(fn, s.a.p, s.b.p, n, s.c.p, nullptr));
-    return d2h(out, s.c.p, n * sizeof(float));
+    Stage st;
+    Dev<float> da, db, dc;
+    FMRX_TRY(st.in(da, a, n));
+    FMRX_TRY(fn % 3 == 2 ? st.in(db, b, n) : st.out(db, n));
+    FMRX_TRY(st.out(dc, n));
+    FMRX_TRY(k_libm_eval(fn, da.p, db.p, n, dc.p, nullptr));
+    return st.back(out, dc);
 }
 
 int fmrx_diag_stream_read_dev(const void *d_buf, size_t bytes, int method, void *stream)
 {
     if (!d_buf || method < 0 || (method & ~0x10000) > 4096) return fail(FMRX_EINVAL, "diag_stream_read_dev: bad arguments");
     FMRX_TRY(require_device());
-    static thread_local DevBuf<unsigned> sink;
-    FMRX_TRY(sink.ensure(4));
+    Dev<unsigned> sink;
+    FMRX_TRY(Stage(kStreamReadSlot, 1).out(sink, 4));
     return k_stream_read(d_buf, bytes, method, sink.p, static_cast<hipStream_t>(stream));
 }
 
@@ -665,16 +579,17 @@ int fmrx_estimate_psd(float *freq, float *psd, const float *samples, size_t n, f
     if (n < static_cast<size_t>(nfft)) return fail(FMRX_EINVAL, "estimate_psd: %zu samples < nfft %d", n, nfft);
     if (!(Fs > 0)) return fail(FMRX_EINVAL, "estimate_psd: Fs must be positive");
     FMRX_TRY(require_device());
-    Scratch &s = scratch();
+    Stage st;
+    Dev<float> a, b, c, d;
     const size_t nseg = n / nfft, half = nfft / 2;
-    FMRX_TRY(s.a.ensure(n));
-    FMRX_TRY(s.b.ensure(nseg * half));
-    FMRX_TRY(s.c.ensure(half));
-    FMRX_TRY(s.d.ensure(half));
-    FMRX_TRY(h2d(s.a.p, samples, nseg * nfft * sizeof(float)));
-    FMRX_TRY(k_estimate_psd(s.a.p, n, Fs, nfft, s.b.p, s.c.p, s.d.p, nullptr));
-    FMRX_TRY(d2h(freq, s.c.p, half * sizeof(float)));
-    return d2h(psd, s.d.p, half * sizeof(float));
+    FMRX_TRY(st.out(a, n));
+    FMRX_TRY(st.put(a.p, samples, nseg * nfft));
+    FMRX_TRY(st.out(b, nseg * half));
+    FMRX_TRY(st.out(c, half));
+    FMRX_TRY(st.out(d, half));
+    FMRX_TRY(k_estimate_psd(a.p, n, Fs, nfft, b.p, c.p, d.p, nullptr));
+    FMRX_TRY(st.back(freq, c));
+    return st.back(psd, d);
 }
 
 // ---- fused front end as a stage ----------------------------------------------------------
@@ -711,7 +626,7 @@ int fmrx_fe_run_dev(const fmrx_fe_plan *plan, const uint8_t *d_iq, size_t n_samp
                     int force_generic, void *stream)
 {
     if (!plan || !d_iq || !d_if) return fail(FMRX_EINVAL, "fe_run_dev: null argument");
-    return fe_launch(plan->plan, d_iq, n_samples, d_hist, d_if, default_options(), static_cast<hipStream_t>(stream),
+    return fe_launch(plan->plan, d_iq, n_samples, d_hist, d_if, options_snapshot(), static_cast<hipStream_t>(stream),
                      force_generic != 0);
 }
 
@@ -726,23 +641,24 @@ int fmrx_fe_fir_decim_u8(const uint8_t *iq, size_t n_samples, const float *h, si
     FMRX_TRY(require_device());
     FePlan plan;
     FMRX_TRY(fe_plan_init(plan, h, static_cast<int>(taps), static_cast<int>(decim)));
-    Scratch &s = scratch();
+    Stage st;
+    Dev<uint8_t> u, uh;
+    Dev<float> a, b, c;
     const size_t n_out = n_samples / decim;
     const size_t hb = plan.hist_bytes, live = 2 * (taps - 1);
-    FMRX_TRY(s.u.ensure(2 * n_samples));
-    FMRX_TRY(s.uh.ensure(hb));
-    FMRX_TRY(s.a.ensure(2 * n_out));
-    FMRX_TRY(s.b.ensure(n_out));
-    FMRX_TRY(s.c.ensure(n_out));
-    FMRX_TRY(h2d(s.u.p, iq, 2 * n_samples));
+    FMRX_TRY(st.in(u, iq, 2 * n_samples));
+    FMRX_TRY(st.out(uh, hb));
+    FMRX_TRY(st.out(a, 2 * n_out));
+    FMRX_TRY(st.out(b, n_out));
+    FMRX_TRY(st.out(c, n_out));
     if (hist) {
-        FMRX_TRY(k_fill_u8(s.uh.p, hb, 128, nullptr));
-        FMRX_TRY(h2d(s.uh.p + (hb - live), hist, live));
+        FMRX_TRY(k_fill_u8(uh.p, hb, 128, nullptr));
+        FMRX_TRY(st.put(uh.p + (hb - live), hist, live));
     }
-    FMRX_TRY(fe_launch(plan, s.u.p, n_samples, hist ? s.uh.p : nullptr, s.a.p, default_options(), nullptr, force_generic != 0));
-    FMRX_TRY(k_split_if(s.a.p, n_out, s.b.p, s.c.p, nullptr));
-    if (if_i) FMRX_TRY(d2h(if_i, s.b.p, n_out * sizeof(float)));
-    if (if_q) FMRX_TRY(d2h(if_q, s.c.p, n_out * sizeof(float)));
+    FMRX_TRY(fe_launch(plan, u.p, n_samples, hist ? uh.p : nullptr, a.p, options_snapshot(), nullptr, force_generic != 0));
+    FMRX_TRY(k_split_if(a.p, n_out, b.p, c.p, nullptr));
+    if (if_i) FMRX_TRY(st.back(if_i, b));
+    if (if_q) FMRX_TRY(st.back(if_q, c));
     FMRX_TRY(sync0());
     if (hist) std::memcpy(hist, iq + 2 * n_samples - live, live);  // carry: the last taps-1 samples, as bytes
     return FMRX_OK;

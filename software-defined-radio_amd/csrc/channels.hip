@@ -43,7 +43,6 @@ struct fmrx_channels {
     // de-emphasis (kernels_deemph.hip; off by default): while it is on, the bank writes f32 [n_channels][audio_channels][n_audio]
     // into de.in and no PCM; one pass over its n_channels * audio_channels rows, behind the bank's call, writes the caller's arrays
     Deemph de;
-    double de_tau = 0.0;
 };
 
 namespace {
@@ -246,8 +245,7 @@ static int process_bank(fmrx_channels *c, float *d_audio_f32, int16_t *d_pcm16, 
                        static_cast<long>(c->slot_bytes), static_cast<long>(c->hist_bytes), c->audio_all.p, c->pcm_all.p,
                        static_cast<long>(c->junk_audio + c->n_audio), static_cast<long>(c->junk_audio), static_cast<long>(c->n_audio),
                        d_audio_f32, d_pcm16);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch channels_finish_kernel: %s", hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("channels_finish_kernel");
     return FMRX_OK;
 }
 
@@ -265,13 +263,8 @@ int fmrx_channels_process_dev(fmrx_channels *c, float *d_audio_f32, int16_t *d_p
 int fmrx_channels_set_deemphasis(fmrx_channels *c, double tau_us)
 {
     if (!c) return fail(FMRX_EINVAL, "channels_set_deemphasis: null handle");
-    if (!(tau_us >= 0.0)) return fail(FMRX_EINVAL, "channels_set_deemphasis: tau must be positive, or 0 for off");
-    if (c->de.on && tau_us == c->de_tau) return FMRX_OK;
     FMRX_HIP(hipSetDevice(c->device));
-    FMRX_HIP(hipDeviceSynchronize());
-    FMRX_TRY(c->de.set(static_cast<double>(c->p.audio_Fs), tau_us, static_cast<size_t>(c->n_channels) * c->audio_channels, c->n_audio, c->opt));
-    c->de_tau = c->de.on ? tau_us : 0.0;
-    return FMRX_OK;
+    return c->de.set(static_cast<double>(c->p.audio_Fs), tau_us, static_cast<size_t>(c->n_channels) * c->audio_channels, c->n_audio, c->opt);
 }
 
 int fmrx_channels_deemph_diagnostics(fmrx_channels *c, unsigned long long *segments, unsigned long long *missed)

@@ -16,7 +16,6 @@
 namespace fmrx {
 
 // ---- error plumbing -------------------------------------------------------
-void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
 
 #define FMRX_HIP(expr)                                                                         \
@@ -33,46 +32,36 @@ int fail(int code, const char *fmt, ...);
         if (rc_ != FMRX_OK) return rc_; \
     } while (0)
 
+// after every kernel launch: FMRX_LAUNCH_CHECK("kernel<%d,%d>", T, D) (a literal and its arguments) makes the enclosing function
+// return FMRX_EHIP, "launch kernel<101,10>: <HIP's words>", if the launch was refused
+#define FMRX_LAUNCH_CHECK(name, ...)                                                                                              \
+    do {                                                                                                                          \
+        hipError_t e_ = hipGetLastError();                                                                                        \
+        if (e_ != hipSuccess) return ::fmrx::fail(FMRX_EHIP, "launch " name ": %s", ##__VA_ARGS__, hipGetErrorString(e_));        \
+    } while (0)
+
 // true when at least one HIP device is usable; otherwise sets the error and
 // the caller returns FMRX_ENODEV.  There is deliberately no CPU path.
 int require_device();
 
-// ---- run-time options ----------------------------------------------------------
-// Process-wide defaults: the built-in values, overridden ONCE (first use) by the FMRX_* environment
-// variables named below, changed afterwards only through fmrx_set_option().  A pipeline handle copies
-// the defaults when it is created and keeps its own set (fmrx_pipeline_set_option); nothing on a
-// per-block launch path reads the environment.
+// ---- run-time options (options.cpp) ------------------------------------------------
+// Process-wide defaults: the built-in values below, overridden ONCE (first use) by the environment variable FMRX_<NAME IN
+// CAPITALS> of each, changed afterwards only through fmrx_set_option().  A pipeline handle copies the defaults when it is
+// created and keeps its own set (fmrx_pipeline_set_option); nothing on a per-block launch path reads the environment.
+// Names, ranges, named values and what each option means: the table in options.cpp (one row per member).
 struct Options {
-    int fe_variant = 0;            // "fe_variant" / FMRX_FE_VARIANT: 0 = matrix-core kernels ("mfma"), 1 = vector-ALU kernels ("valu")
-    long fused_min_audio = 65536;  // "fused_min_audio" / FMRX_FUSED_MIN_AUDIO: audio samples per call from which the fused mono kernel runs
-    int resample_l2 = 0;           // "resample_l2" / FMRX_RESAMPLE_L2: 1 = L2-table resampler kernel even for large calls
-    int resample_exact = 0;        // "resample_exact" / FMRX_RESAMPLE_EXACT: 1 = the pipeline's resampler keeps the reference's rounding sequence
-                                   //   (the bit-exact LDS-table kernel instead of the matrix-core one)
-    int overlap_calls = 0;         // "overlap_calls" / FMRX_OVERLAP_CALLS: 1 = the caller vouches that a process_dev call's input is complete when the call
-                                   //   is made (data resident in HBM): the stereo pipeline then runs front end, PLL and output stage of consecutive
-                                   //   calls on three internal streams, one call apart each; the caller's stream still waits for each call's output
-    int resample_chains = 0;       // "resample_chains" / FMRX_RESAMPLE_CHAINS: workgroups per XCD and tile group of the matrix-core resampler
-                                   //   (0 = as many as are resident at once); A/B knob
-    int pll_warmup = -1;           // "pll_warmup" / FMRX_PLL_WARMUP: warm-up samples per lane of the parallel PLL (-1 = built-in)
-    int pll_segment = -1;          // "pll_segment" / FMRX_PLL_SEGMENT: samples per lane (-1 = built-in)
-    int pll_start = 1;             // "pll_start" / FMRX_PLL_START: where the parallel PLL's lanes start: 1 (default) = the state of the locked loop as a
-                                   //   linear system of the input's signs, then 64 true warm-up steps; 0 = the block's initial state plus drift, 512 steps
-    int pll_mode = 0;              // "pll_mode" / FMRX_PLL_MODE: stereo PLL of the specialised pipeline: 0 = parallel in time, fast math
-                                   //   (default); 1 = serial, fast math; 2 = serial, glibc math (the cause-by-cause variants of DESIGN 2)
-    int deemph_warmup = -1;        // "deemph_warmup" / FMRX_DEEMPH_WARMUP: warm-up samples per lane of the parallel de-emphasis filter (-1 = built-in)
-    int deemph_segment = -1;       // "deemph_segment" / FMRX_DEEMPH_SEGMENT: samples per lane (-1 = built-in)
-    int deemph_mode = 0;           // "deemph_mode" / FMRX_DEEMPH_MODE: 0 = parallel in time (default), 1 = one lane per row walks it serially (same bits)
-    int tuner_variant = 0;         // "tuner_variant" / FMRX_TUNER_VARIANT: wideband tuner (tuner.hip): 0 = matrix-core kernel ("mfma"), 1 = generic kernel ("generic");
-                                   //   read when a tuner is created
-    int demod = 0;                 // "demod" / FMRX_DEMOD: 0 = the C++ reference's discriminator (fmDemod, src/filter.cpp:248-266; default),
-                                   //   1 = the Python model's arctangent demodulator (fmDemodArctan, model/fmSupportLib.py:502-531), float64
+    int fe_variant = 0, tuner_variant = 0, demod = 0, overlap_calls = 0;
+    long fused_min_audio = 65536;
+    int resample_l2 = 0, resample_exact = 0, resample_chains = 0;
+    int pll_warmup = -1, pll_segment = -1, pll_start = 1, pll_mode = 0;
+    int deemph_warmup = -1, deemph_segment = -1, deemph_mode = 0;
 };
-Options &default_options();
+Options &default_options();      // callers hold options_mutex()
 std::mutex &options_mutex();     // guards writes to the process-wide defaults and the copy a new handle takes
-Options options_snapshot();      // the defaults, copied under the mutex: what handle constructors use
-// name -> field; returns false for an unknown name
-bool option_ref(Options &o, const char *name, long **as_long, int **as_int);
-int set_option_in(Options &o, const char *name, long value);   // validates; FMRX_EINVAL for unknown names / values
+Options options_snapshot();      // the defaults, copied under the mutex: what handle constructors and stage functions use
+// by name, through the table; FMRX_EINVAL for an unknown name or a value outside the option's range
+int set_option_in(Options &o, const char *name, long value);
+int get_option_in(const Options &o, const char *name, long *value);
 
 // ---- small RAII device buffer ----------------------------------------------
 template <typename T>
@@ -330,11 +319,13 @@ int deemph_launch(const DeemphArgs &a, const Options &o, bool serial, hipStream_
 struct Deemph {
     bool on = false, counted = false;
     float p = 0.0f, b0 = 0.0f;
+    double tau_us = 0.0;                 // what is on (0 while off)
     size_t rows = 0, n_max = 0;
     DevBuf<float> in, out, state, seg;
     DevBuf<unsigned long long> counter;
     unsigned long long segments = 0;
-    int set(double fs, double tau_us, size_t rows, size_t n_max, const Options &o);   // tau_us 0 = off; on / a new tau: state zeroed
+    // (the handle's device is current)  tau_us 0 = off; the tau that is on: nothing happens; else waits for the device, state zeroed
+    int set(double fs, double tau_us, size_t rows, size_t n_max, const Options &o);
     int reset(long first_row, long n_rows, hipStream_t s);   // asynchronous on s
     int run(size_t n, float *d_f32, int16_t *d_pcm, int ac, int wrap, const Options &o, bool serial, hipStream_t s);
     int diagnostics(unsigned long long *segments, unsigned long long *missed);

@@ -226,8 +226,7 @@ int launch_fast(const AudioPlan &pl, const float *d_x, const float *d_hist_end, 
     const unsigned grid = static_cast<unsigned>(n_tiles < 256 * per_cu ? n_tiles : 256 * per_cu);
     hipLaunchKernelGGL((audio_fir_kernel<T, D, R, NT>), dim3(grid), dim3(NT), C::LDS_BYTES, stream, d_x, d_hist_end,
                        static_cast<long>(n_in), delay, pl.table.p, d_y, d_pcm, wrap, n_out, n_tiles);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch audio_fir_kernel<%d,%d>: %s", T, D, hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("audio_fir_kernel<%d,%d>", T, D);
     return FMRX_OK;
 }
 

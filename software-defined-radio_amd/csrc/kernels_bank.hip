@@ -53,12 +53,6 @@ typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 #define CHS_TAPS_ISSUE(hp, table, off) asm volatile("s_load_dwordx16 %0, %1, %2" : "=&s"(hp) : "s"(table), "i"(off))
 #define CHS_TAPS_WAIT(hp) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hp))
 
-#define CHS_LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) return fail(FMRX_EHIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 // ---- front end, reference order ------------------------------------------------------------------------------
 // Thread: outputs k0 .. k0+R-1 (I and Q in the two halves of v_pk_mul_f32 / v_pk_add_f32).  Window sample j
 // (j = 0: stream sample k0*D - (T-1)) meets output r with tap n = r*D + (T-1) - j.  Step u visits j = W-1-u, i.e.
@@ -960,7 +954,7 @@ int launch_fe(const Bank &b, long k_lo, long k_hi, hipStream_t s)
     hipLaunchKernelGGL((chs_fe_exact_kernel<T, D>), dim3(static_cast<unsigned>(ntiles * b.n_channels)), dim3(64), 0, s, b.slots.p,
                        static_cast<long>(b.slot_bytes), static_cast<int>(b.hist_bytes), k_lo, k_hi, ntiles, ntiles, b.fe_table.p, b.demod.p,
                        b.dpitch, b.Hd);
-    CHS_LAUNCH_CHECK("chs_fe_exact_kernel");
+    FMRX_LAUNCH_CHECK("chs_fe_exact_kernel");
     return FMRX_OK;
 }
 
@@ -978,7 +972,7 @@ int launch_bpf(const Bank &b, long k_lo, long k_hi, hipStream_t s)
     const long wgs = (k_hi - k_lo + 64 * kR - 1) / (64 * kR);
     hipLaunchKernelGGL((chs_bpf_kernel<T, EXACT>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p, b.dpitch,
                        b.Hd, k_lo, k_hi, wgs, b.bpf_table.p, b.bpf.p, b.carrier.p, b.ypitch, b.carrier8.p, b.cpitch);
-    CHS_LAUNCH_CHECK("chs_bpf_kernel");
+    FMRX_LAUNCH_CHECK("chs_bpf_kernel");
     return FMRX_OK;
 }
 
@@ -993,7 +987,7 @@ int launch_out(Bank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo, lon
     hipLaunchKernelGGL((chs_out_kernel<T, D, STEREO, EXACT>), dim3(static_cast<unsigned>(wgs * b.n_channels)), dim3(64), 0, s, b.demod.p,
                        b.dpitch, b.Hd, b.bpf.p, b.trig.p, b.ypitch, b.nco0.p, b.mixtail[b.mix_cur].p, b.mixtail[b.mix_cur ^ 1].p, b.Hm,
                        b.n_if, g_hi, b.delay, kNcoScale, kPhaseAdjust, b.out_table.p, wgs, d_audio, d_pcm, wrap, a_lo, a_hi, b.n_audio);
-    CHS_LAUNCH_CHECK("chs_out_kernel");
+    FMRX_LAUNCH_CHECK("chs_out_kernel");
     return FMRX_OK;
 }
 
@@ -1020,7 +1014,7 @@ int launch_resample(Bank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo
                                dim3(64 * kRW<STEREO>), 0, s, b.demod.p, b.dpitch, b.Hd, STEREO ? b.mixer.p : nullptr, b.mpitch, b.Hm, b.delay, b.res_table.p,
                                b.res_top.p, b.res_groups, gpw, b.res_iters, p.audio_decim, p.audio_upsamp, periods, b.n_channels, d_audio, d_pcm,
                                wrap, a_lo, b.n_audio);
-            CHS_LAUNCH_CHECK("chs_resample_lanes_kernel");
+            FMRX_LAUNCH_CHECK("chs_resample_lanes_kernel");
             done = a_lo + periods * p.audio_upsamp;
         }
     }
@@ -1029,7 +1023,7 @@ int launch_resample(Bank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo
         hipLaunchKernelGGL(chs_resample_exact_kernel<STEREO>, dim3(static_cast<unsigned>(wr * b.n_channels)), dim3(256), 0, s, b.demod.p, b.dpitch,
                            b.Hd, STEREO ? b.mixer.p : nullptr, b.mpitch, b.Hm, b.delay, b.h_res.p, p.audio_taps, p.audio_decim, p.audio_upsamp, wr,
                            d_audio, d_pcm, wrap, done, a_hi, b.n_audio);
-        CHS_LAUNCH_CHECK("chs_resample_exact_kernel");
+        FMRX_LAUNCH_CHECK("chs_resample_exact_kernel");
     }
     return FMRX_OK;
 }
@@ -1074,7 +1068,7 @@ int bank_launch_nco(bool exact, float *trig, long ypitch, int n_rows, long k_lo,
     };
     if (exact) go(std::true_type{});
     else go(std::false_type{});
-    CHS_LAUNCH_CHECK("chs_nco_kernel");
+    FMRX_LAUNCH_CHECK("chs_nco_kernel");
     return FMRX_OK;
 }
 
@@ -1083,14 +1077,14 @@ int bank_launch_finish(const Bank &b, hipStream_t s)
     hipLaunchKernelGGL(chs_finish_kernel, dim3(static_cast<unsigned>(b.n_channels)), dim3(64), 0, s, b.slots.p,
                        static_cast<long>(b.slot_bytes), static_cast<long>(b.hist_bytes), b.demod.p, b.dpitch, b.Hd, b.n_if,
                        b.resample && b.audio_channels == 2 ? b.mixer.p : nullptr, b.mpitch, b.Hm);
-    CHS_LAUNCH_CHECK("chs_finish_kernel");
+    FMRX_LAUNCH_CHECK("chs_finish_kernel");
     return FMRX_OK;
 }
 
 int bank_launch_fill_state(float *pll, long n, hipStream_t s)
 {
     hipLaunchKernelGGL(chs_fill_state_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, pll, n);
-    CHS_LAUNCH_CHECK("chs_fill_state_kernel");
+    FMRX_LAUNCH_CHECK("chs_fill_state_kernel");
     return FMRX_OK;
 }
 

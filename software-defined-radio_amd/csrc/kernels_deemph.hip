@@ -259,13 +259,6 @@ __global__ __launch_bounds__(kLanes) void deemph_serial_kernel(const float *__re
     state[2 * row + 1] = yp;
 }
 
-int launch_error(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch %s: %s", what, hipGetErrorString(e));
-    return FMRX_OK;
-}
-
 }  // namespace
 
 DeemphShape deemph_shape(const Options &o, size_t n)
@@ -293,7 +286,8 @@ int deemph_launch(const DeemphArgs &a, const Options &o, bool serial, hipStream_
     if (serial || o.deemph_mode == 1) {
         hipLaunchKernelGGL(deemph_serial_kernel, dim3(static_cast<unsigned>((rows + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, a.x, a.pitch_x,
                            a.y, a.pitch_y, a.pcm, a.ac, a.wrap, rows, n, a.p, a.b0, a.state);
-        return launch_error("deemph_serial_kernel");
+        FMRX_LAUNCH_CHECK("deemph_serial_kernel");
+        return FMRX_OK;
     }
     const DeemphShape sh = deemph_shape(o, a.n);
     if (!a.seg || !a.missed) return fail(FMRX_EINVAL, "deemph: null scratch");
@@ -301,25 +295,29 @@ int deemph_launch(const DeemphArgs &a, const Options &o, bool serial, hipStream_
     if (sh.nseg > (1L << 30) || (total + kLanes - 1) / kLanes > 0x7fffffffL) return fail(FMRX_EINVAL, "deemph: too many segments");
     hipLaunchKernelGGL(deemph_segments_kernel, dim3(static_cast<unsigned>((total + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, a.x, a.pitch_x,
                        a.y, a.pitch_y, a.pcm, a.ac, a.wrap, rows, n, static_cast<int>(sh.nseg), sh.L, sh.W, a.p, a.b0, a.state, a.seg);
-    FMRX_TRY(launch_error("deemph_segments_kernel"));
+    FMRX_LAUNCH_CHECK("deemph_segments_kernel");
     // lanes per row: enough to check a row's segments in few passes, whole waves
     const long vt = (sh.nseg + kLanes - 1) / kLanes * kLanes;
     hipLaunchKernelGGL(deemph_verify_kernel, dim3(static_cast<unsigned>(rows)), dim3(static_cast<unsigned>(vt < kVerifyMax ? vt : kVerifyMax)), 0, s, a.x, a.pitch_x, a.y, a.pitch_y, a.pcm,
                        a.ac, a.wrap, rows, n, static_cast<int>(sh.nseg), sh.L, a.p, a.b0, a.state, a.seg, a.missed);
-    FMRX_TRY(launch_error("deemph_verify_kernel"));
+    FMRX_LAUNCH_CHECK("deemph_verify_kernel");
     if (segments) *segments += static_cast<unsigned long long>(rows) * static_cast<unsigned long long>(sh.nseg - 1);
     return FMRX_OK;
 }
 
 // ---- a handle's de-emphasis: coefficients, carried state, scratch, counters ----
-int Deemph::set(double fs, double tau_us, size_t rows_, size_t n_max_, const Options &o)
+int Deemph::set(double fs, double tau_us_, size_t rows_, size_t n_max_, const Options &o)
 {
-    if (tau_us == 0.0) {
+    if (!(tau_us_ >= 0.0)) return fail(FMRX_EINVAL, "set_deemphasis: tau must be positive, or 0 for off");
+    if (on && tau_us_ == tau_us) return FMRX_OK;
+    FMRX_HIP(hipDeviceSynchronize());   // nothing in flight sees the change under it
+    if (tau_us_ == 0.0) {
         on = false;
+        tau_us = 0.0;
         return FMRX_OK;
     }
     float p_, b0_;
-    FMRX_TRY(fmrx_deemph_design(fs, tau_us, &p_, &b0_));
+    FMRX_TRY(fmrx_deemph_design(fs, tau_us_, &p_, &b0_));
     rows = rows_;
     n_max = n_max_;
     FMRX_TRY(in.ensure(rows * n_max));
@@ -332,6 +330,7 @@ int Deemph::set(double fs, double tau_us, size_t rows_, size_t n_max_, const Opt
     FMRX_HIP(hipDeviceSynchronize());
     p = p_;
     b0 = b0_;
+    tau_us = tau_us_;
     on = true;
     return FMRX_OK;
 }

@@ -91,8 +91,7 @@ int k_stream_read(const void *d_buf, size_t bytes, int method, unsigned *d_sink,
     else
         hipLaunchKernelGGL(read_dma_kernel<0>, dim3(512), dim3(256), 4 * 4 * 3072, s, static_cast<const unsigned char *>(d_buf),
                            static_cast<long>(bytes - bytes % 3072), d_sink, sweep);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch stream_read: %s", hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("stream_read");
     return FMRX_OK;
 }
 

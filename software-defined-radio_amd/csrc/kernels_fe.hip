@@ -458,8 +458,7 @@ int launch_fused(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, const 
                        static_cast<long>(2 * n_samples), pl.table.p, reinterpret_cast<const float2 *>(d_prev_override),
                        d_demod, reinterpret_cast<f2 *>(d_if), reinterpret_cast<float2 *>(d_prev_out), n_out,
                        static_cast<int>(n_wtiles), d_hist_next, pl.hist_bytes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch fe_demod_kernel<%d,%d>: %s", T, D, hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("fe_demod_kernel<%d,%d>", T, D);
     return FMRX_OK;
 }
 
@@ -479,8 +478,7 @@ int launch_fast(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, const u
         hipLaunchKernelGGL((fe_fir_kernel_pf<T, D, R, NT>), dim3(grid), dim3(NT), C::TILE_BYTES, stream, d_iq, d_hist,
                            static_cast<long>(2 * n_samples), pl.table.p, reinterpret_cast<f2 *>(d_if), n_out, n_tiles);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch fe_fir_kernel_pf<%d,%d>: %s", T, D, hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("fe_fir_kernel_pf<%d,%d>", T, D);
     return FMRX_OK;
 }
 

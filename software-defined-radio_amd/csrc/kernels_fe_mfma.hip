@@ -371,8 +371,7 @@ int launch_mfma(const FePlan &pl, const uint8_t *d_iq, size_t n_samples, const u
                        pl.scale_lo, reinterpret_cast<const float2 *>(d_prev), d_demod, d_if,
                        reinterpret_cast<float2 *>(d_prev_out), n_out, static_cast<int>(n_tiles), d_hist_next, pl.hist_bytes,
                        d_dhist_src, d_dhist_dst, dhist_n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch fe_mfma_kernel<%d,%d>: %s", T, D, hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("fe_mfma_kernel<%d,%d>", T, D);
     return FMRX_OK;
 }
 
@@ -940,9 +939,7 @@ int launch_fused_mono(const FePlan &fe, const AudioPlan &au, const uint8_t *d_iq
                        fe.scale_lo, au.mfma_table.p, reinterpret_cast<const float2 *>(d_prev), d_dhist_end, d_demod_tail,
                        tail_keep, reinterpret_cast<float2 *>(d_prev_out), d_audio, d_pcm, wrap, n_out, static_cast<int>(n_tiles),
                        n_audio, static_cast<int>(n_batches), static_cast<int>(bpw), d_hist_next, fe.hist_bytes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(FMRX_EHIP, "launch mono_fused_kernel<%d,%d,%d,%d>: %s", T, D, TA, DA, hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("mono_fused_kernel<%d,%d,%d,%d>", T, D, TA, DA);
     return FMRX_OK;
 }
 
@@ -1040,8 +1037,7 @@ int fe_mfma_bank_launch(const FePlan &pl, const uint8_t *d_slots, long total_byt
         hipLaunchKernelGGL((fe_mfma_bank_kernel<T_, D_>), dim3(static_cast<unsigned>(grid)), dim3(256), 4 * C::RING, stream,  \
                            d_slots, total_bytes, reinterpret_cast<const i4 *>(pl.a_img.p), pl.scale_lo, d_demod, bk,         \
                            static_cast<int>(n_tiles));                                                                        \
-        hipError_t e = hipGetLastError();                                                                                     \
-        if (e != hipSuccess) return fail(FMRX_EHIP, "launch fe_mfma_bank_kernel<%d,%d>: %s", T_, D_, hipGetErrorString(e)); \
+        FMRX_LAUNCH_CHECK("fe_mfma_bank_kernel<%d,%d>", T_, D_); \
         return FMRX_OK;                                                                                                       \
     }
     FMRX_FE_MFMA_CASES(X)

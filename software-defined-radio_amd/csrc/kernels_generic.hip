@@ -30,12 +30,6 @@ inline unsigned grid_for(size_t n, int per_block = kBlock)
     return static_cast<unsigned>(g ? g : 1);
 }
 
-#define FMRX_LAUNCH_CHECK(name)                                                                   \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) return fail(FMRX_EHIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 // ---- FIR, decimating, float in (src/filter.cpp:133-154, 158-188) ------------
 // One output per thread; x[-(taps-1)] .. x[-1] is the carried history.
 __global__ void fir_generic_kernel(const float *__restrict__ x, size_t n_out, const float *__restrict__ h, int taps,

@@ -913,12 +913,6 @@ PllCoef make_coef(float freq, float Fs, float ncoScale, float phaseAdjust, float
     return c;
 }
 
-#define FMRX_LAUNCH_CHECK(name)                                                                   \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) return fail(FMRX_EHIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 }  // namespace
 
 int k_fm_pll(const float *d_in, size_t n, float *d_out, float *d_state, float freq, float Fs, float ncoScale,

@@ -68,10 +68,10 @@ int k_estimate_psd(const float *d_x, size_t n, float Fs, int nfft, float *d_seg_
     const long total = static_cast<long>(nseg) * half;
     hipLaunchKernelGGL(psd_segments_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, d_x, nfft, nseg,
                        Fs, d_seg_db);
+    FMRX_LAUNCH_CHECK("psd_segments_kernel");
     hipLaunchKernelGGL(psd_average_kernel, dim3((half + 255) / 256), dim3(256), 0, s, d_seg_db, half, nseg, Fs, nfft, d_freq,
                        d_psd);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch psd kernels: %s", hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("psd_average_kernel");
     return FMRX_OK;
 }
 

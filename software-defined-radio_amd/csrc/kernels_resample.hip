@@ -366,8 +366,7 @@ static int resample_mfma_launch_ks(const ResamplePlan &pl, const float *x, size_
                        lds, stream, x, static_cast<long>(n_in), -static_cast<long>(pl.J - 1), n_per, pl.mfma_img.p,
                        pl.mfma_top.p, pl.mfma_groups.p, pl.mfma_ngroups, static_cast<int>(n_chain), pl.decim, pl.upsamp, d_y,
                        d_pcm, wrap);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch resample_mfma_kernel: %s", hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("resample_mfma_kernel");
     return FMRX_OK;
 }
 
@@ -480,8 +479,7 @@ int resample_launch(const ResamplePlan &pl, const float *d_x, size_t n_in, int d
             hipLaunchKernelGGL(resample_lds_kernel, dim3(grid), dim3(kLT), lds_bytes, stream, d_x - delay,
                                static_cast<long>(n_in), static_cast<long>(n_out), pl.table.p, pl.J, pl.JP, pl.decim,
                                pl.upsamp, pl.span_l, pass * pl.W, pl.W, pass == 0, pass == pl.npass - 1, n_tiles, d_y);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(FMRX_EHIP, "launch resample_lds_kernel: %s", hipGetErrorString(e));
+            FMRX_LAUNCH_CHECK("resample_lds_kernel");
         }
         return FMRX_OK;
     }
@@ -489,8 +487,7 @@ int resample_launch(const ResamplePlan &pl, const float *d_x, size_t n_in, int d
     hipLaunchKernelGGL(resample_poly_kernel, dim3(grid), dim3(kNT), pl.span * sizeof(float), stream, d_x - delay,
                        static_cast<long>(n_in), static_cast<long>(n_out), pl.table.p, pl.J, pl.JP, pl.decim, pl.upsamp,
                        pl.span, d_y);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch resample_poly_kernel: %s", hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("resample_poly_kernel");
     return FMRX_OK;
 }
 

@@ -121,8 +121,7 @@ int launch(const BpfPairPlan &pl, const float *d_x, size_t n, float *d_st, float
     const unsigned grid = static_cast<unsigned>((n + NT * R - 1) / (NT * R));
     hipLaunchKernelGGL((bpf_pair_kernel<T, R, NT>), dim3(grid), dim3(NT), 0, stream, d_x, static_cast<long>(n), pl.table.p,
                        d_st, d_car);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "launch bpf_pair_kernel<%d>: %s", T, hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("bpf_pair_kernel<%d>", T);
     return FMRX_OK;
 }
 
@@ -292,8 +291,7 @@ int stereo_out_launch(const float *d_demod, const float *d_bpf, const float *d_n
         hipLaunchKernelGGL((stereo_out_kernel<T_, D_, R, NT>), dim3(grid), dim3(NT), lds, stream, d_demod, d_bpf, d_nco, \
                            d_mix_tail_in, d_mix_tail_out, hm, static_cast<long>(n_if), delay, d_h, d_mono, d_st, d_left,  \
                            d_right, d_pcm, wrap, d_mixer, n_out);                                                        \
-        hipError_t e = hipGetLastError();                                                                               \
-        if (e != hipSuccess) return fail(FMRX_EHIP, "launch stereo_out_kernel<%d,%d>: %s", T_, D_, hipGetErrorString(e)); \
+        FMRX_LAUNCH_CHECK("stereo_out_kernel<%d,%d>", T_, D_); \
         return FMRX_OK;                                                                                                 \
     }
     X(101, 5) X(101, 6) X(13, 5) X(13, 6)

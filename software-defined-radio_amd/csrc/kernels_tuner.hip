@@ -568,11 +568,11 @@ int tuner_launch(const TunerLaunch &a, hipStream_t stream)
             hipLaunchKernelGGL(kernel, dim3(a.n_channels, static_cast<unsigned>((n_out + 255) / 256)), dim3(256), 0, stream, a.x, a.hist,
                                a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.R, a.T, a.front, a.n0, a.levels);
         }
-        FMRX_HIP(hipGetLastError());
+        FMRX_LAUNCH_CHECK("tuner_%s_kernel (format %d)", a.mfma ? "mfma" : "generic", a.format);
     }
     hipLaunchKernelGGL(tuner_hist_kernel, dim3((a.front * vb + 255) / 256), dim3(256), 0, stream, a.x, a.n_bytes * vb, a.hist, a.hist_next,
                        a.front * vb);
-    FMRX_HIP(hipGetLastError());
+    FMRX_LAUNCH_CHECK("tuner_hist_kernel");
     return FMRX_OK;
 }
 

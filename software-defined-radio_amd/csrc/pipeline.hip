@@ -90,7 +90,6 @@ struct fmrx_pipeline {
     // de-emphasis (kernels_deemph.hip; off by default): while it is on, the producing stage of a call writes f32 into de.in
     // ([channels][n_audio]) instead of the caller's buffers and no PCM; one pass behind it writes the caller's
     Deemph de;
-    double de_tau = 0.0;
     // asynchronous host-buffer calls (fmrx_pipeline_submit / _wait): two slots, each with its own stream and device staging
     // buffers (slot 0 = `stream`, `in`, `out_f32`, `out_pcm` above): block i+1's copy to the device runs under block i's kernels
     // and block i-1's copy back.  Only the kernels of consecutive blocks are ordered (they carry the state): ev_kern.
@@ -370,13 +369,8 @@ int fmrx_pipeline_set_option(fmrx_pipeline *pl, const char *name, long value)
 int fmrx_pipeline_set_deemphasis(fmrx_pipeline *pl, double tau_us)
 {
     if (!pl) return fail(FMRX_EINVAL, "null handle");
-    if (!(tau_us >= 0.0)) return fail(FMRX_EINVAL, "set_deemphasis: tau must be positive, or 0 for off");
-    if (pl->de.on && tau_us == pl->de_tau) return FMRX_OK;
     FMRX_HIP(hipSetDevice(pl->device));
-    FMRX_HIP(hipDeviceSynchronize());   // nothing in flight sees the change under it
-    FMRX_TRY(pl->de.set(static_cast<double>(pl->p.audio_Fs), tau_us, pl->channels, n_audio_of(pl, pl->max_bytes) + 1, pl->opt));
-    pl->de_tau = pl->de.on ? tau_us : 0.0;
-    return FMRX_OK;
+    return pl->de.set(static_cast<double>(pl->p.audio_Fs), tau_us, pl->channels, n_audio_of(pl, pl->max_bytes) + 1, pl->opt);
 }
 
 int fmrx_pipeline_deemph_diagnostics(fmrx_pipeline *pl, unsigned long long *segments, unsigned long long *missed)
@@ -467,17 +461,20 @@ static int materialise_history(fmrx_pipeline *pl, const Call &c)
 
 // after the front end: the next block's IF[-1], byte history (unless the front-end kernel wrote it: hist_done) and
 // discriminator history are this block's
-static void advance_state(fmrx_pipeline *pl, const Call &c, bool hist_done)
+static int advance_state(fmrx_pipeline *pl, const Call &c, bool hist_done)
 {
     pl->prev_cur ^= 1;
     pl->prev_override = false;
     pl->fe_cur ^= 1;
     const int hb = pl->fe.hist_bytes;
-    if (!hist_done)
+    if (!hist_done) {
         hipLaunchKernelGGL(hist_update_kernel, dim3((hb + 255) / 256), dim3(256), 0, c.sf, c.hist, c.iq,
                            static_cast<long>(c.n_bytes), hb, c.hist_next);
+        FMRX_LAUNCH_CHECK("hist_update_kernel");
+    }
     pl->demod_last = c.cur;
     pl->demod_n_last = c.n_if;
+    return FMRX_OK;
 }
 
 static int call_setup(fmrx_pipeline *pl, Call &c)
@@ -575,7 +572,7 @@ static int fused_mono(fmrx_pipeline *pl, const Call &c)
     pl->demod_valid = false;
     pl->last_mono = dst;
     FMRX_TRY(mark(c, 1));
-    advance_state(pl, c, hist_done);
+    FMRX_TRY(advance_state(pl, c, hist_done));
     return mark(c, 2);
 }
 
@@ -613,7 +610,7 @@ static int front_end(fmrx_pipeline *pl, const Call &c)
     // model's state_phase modulo 2 pi; zeros at the start of a stream: atan2(0, 0) = 0 = the model's initial phase)
     if (pl->opt.demod == 1) FMRX_TRY(k_fm_demod_arctan_if(pl->ifb.p, c.n_if, c.prev, c.demod, c.s));
     FMRX_TRY(mark(c, 1));
-    advance_state(pl, c, hist_done);
+    FMRX_TRY(advance_state(pl, c, hist_done));
     // a block shorter than the history keeps its own front valid, so that "tail of the previous
     // buffer" stays a contiguous Hd samples for whoever comes next
     if (c.n_if < static_cast<size_t>(pl->Hd)) FMRX_TRY(materialise_history(pl, c));

@@ -464,25 +464,33 @@ int Chain::run(const float *d_demod, size_t pitch, size_t n_in, hipStream_t s, c
     double *xb = x.p + Hx, *chb = ch.p + Hc, *mib = mi.p + Hm, *mqb = mq.p + Hm, *rib = ri.p + Hr, *rqb = rq.p + Hr;
     const double phase_adjust = 3 * kPi / 8;
     hipLaunchKernelGGL(rdsb_cvt_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, d_demod, static_cast<long>(pitch), n, xb, xpitch);
+    FMRX_LAUNCH_CHECK("rdsb_cvt_kernel");
     hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, xb, xb, xpitch, n, h_ch.p, p.taps, chb, chb, cpitch);
+    FMRX_LAUNCH_CHECK("rdsb_fir_kernel<false>");
     hipLaunchKernelGGL(rdsb_fir_kernel<true>, dim3(N, tiles(n, 256 * kR)), dim3(256), 0, s, chb, chb, cpitch, n, h_car.p, p.taps, car.p, car.p,
                        apitch);
+    FMRX_LAUNCH_CHECK("rdsb_fir_kernel<true>");
     hipLaunchKernelGGL(rdsb_pll_lanes_kernel, dim3(lanes), dim3(64), 0, s, car.p, apitch, n, n_channels, arg.p, state.p, nco_i.p, nco_q.p, npitch,
                        114e3, static_cast<double>(p.if_Fs), 0.002, 0.5, phase_adjust);
+    FMRX_LAUNCH_CHECK("rdsb_pll_lanes_kernel");
     hipLaunchKernelGGL(rdsb_mix_kernel, dim3(N, tiles(n, 256)), dim3(256), 0, s, arg.p, apitch, n, chb, cpitch, delay, 0.5, phase_adjust, nco_i.p,
                        nco_q.p, npitch, mib, mqb, mpitch);
+    FMRX_LAUNCH_CHECK("rdsb_mix_kernel");
     hipLaunchKernelGGL(rdsb_resample_kernel, dim3(N, tiles(no, 256)), dim3(256), 0, s, mib, mqb, mpitch, no, h_rs.p, 101 * p.upsamp, p.decim,
                        p.upsamp, rib, rqb, rpitch);
+    FMRX_LAUNCH_CHECK("rdsb_resample_kernel");
     hipLaunchKernelGGL(rdsb_fir_kernel<false>, dim3(N, tiles(no, 256 * kR), 2), dim3(256), 0, s, rib, rqb, rpitch, no, h_rrc.p, p.rrc_taps, yi.p,
                        yq.p, ypitch);
+    FMRX_LAUNCH_CHECK("rdsb_fir_kernel<false>");
     // fmMonoBlock.py:276-280 (fmrx_rds_process): the CDR state is re-made every block
-    if (cdr)
+    if (cdr) {
         hipLaunchKernelGGL(rdsb_cdr_kernel, dim3(lanes), dim3(64), 0, s, yi.p, ypitch, no, n_channels, p.sps, 0.0, 0.0, 158L, 0L, cdr->blk,
                            cdr->bits, cdr->max_bits, cdr->n_bits);
+        FMRX_LAUNCH_CHECK("rdsb_cdr_kernel");
+    }
     hipLaunchKernelGGL(rdsb_tail_kernel, dim3(N), dim3(256), 0, s, x.p, xpitch, Hx, ch.p, cpitch, Hc, mi.p, mq.p, mpitch, Hm, ri.p, rq.p, rpitch, Hr,
                        n, no);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FMRX_EHIP, "rds kernels: %s", hipGetErrorString(e));
+    FMRX_LAUNCH_CHECK("rdsb_tail_kernel");
     last_n = n_in;
     last_out = static_cast<size_t>(no);
     return FMRX_OK;
@@ -703,8 +711,7 @@ int fmrx_rds_bank_process_dev(fmrx_rds_bank *b, const float *d_demod, size_t pit
         const unsigned lanes = (static_cast<unsigned>(b->c.n_channels) + 63) / 64;
         hipLaunchKernelGGL(rdsb_station_kernel, dim3(lanes), dim3(64), (kStB + b->c.p.sps) * 64 * sizeof(double), s, b->c.yi.p, b->c.ypitch, b->n_out,
                            b->c.n_channels, b->dec.p, b->energy.p, b->st.p, b->grp.p, static_cast<int>(b->max_g), b->n_g.p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(FMRX_EHIP, "rds bank kernels: %s", hipGetErrorString(e));
+        FMRX_LAUNCH_CHECK("rdsb_station_kernel");
     }
     FMRX_HIP(hipEventRecord(b->done, s));
     b->pending = true;

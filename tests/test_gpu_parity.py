@@ -273,6 +273,38 @@ def test_pll_stage(fmrx, oracle):
     bits_equal(ya, yb)
 
 
+def test_stage_scratch_slots_are_reused_across_functions(fmrx, oracle):
+    """The host-buffer stage functions of a thread share one set of device slots, typed and sized by each call (csrc/capi.hip).
+    A sequence that asks the same slots for float taps, a PLL state, 16-bit PCM, a ten times larger block and then the first
+    shapes again: every call bit-identical to the oracle, the repeated call to the first one -- a slot handed out with a
+    stale size or type shows here and in no single-function test."""
+    rng = np.random.default_rng(23)
+    T = 101
+    h = fmrx.impulseResponseLPF(240e3, 16e3, T)
+    x1, s1 = rng.standard_normal(5000).astype(np.float32), rng.standard_normal(T - 1).astype(np.float32)
+    y1, st1 = fmrx.convolveBlockFastFIR(x1, h, s1, 5)
+    want_y1, want_st1 = oracle.convolve_block_fast_fir(x1, h, s1, 5)
+    bits_equal(y1, want_y1); bits_equal(st1, want_st1)
+
+    xp = (0.08 * np.cos(2 * np.pi * 19.002e3 * np.arange(2048) / 240e3 + 0.4) + 0.004 * rng.standard_normal(2048)).astype(np.float32)
+    sp = np.array([0, 0, 1, 0, 1, 0], np.float32)
+    yp, stp = fmrx.fmPLL(xp, sp, 19e3, 240e3)
+    want_yp, want_stp = oracle.fm_pll(xp, sp, 19e3, 240e3)
+    bits_equal(yp, want_yp); bits_equal(stp, want_stp)
+
+    au = (rng.standard_normal(3000) * 2.5).astype(np.float32)
+    bits_equal(fmrx.pcm16(au, wrap=True), oracle.pcm16(au, wrap=True))
+
+    x4, s4 = rng.standard_normal(50000).astype(np.float32), rng.standard_normal(T - 1).astype(np.float32)
+    y4, st4 = fmrx.convolveBlockFastFIR(x4, h, s4, 5)
+    want_y4, want_st4 = oracle.convolve_block_fast_fir(x4, h, s4, 5)
+    bits_equal(y4, want_y4); bits_equal(st4, want_st4)
+
+    y5, st5 = fmrx.convolveBlockFastFIR(x1, h, s1, 5)
+    bits_equal(y5, y1); bits_equal(st5, st1)
+    bits_equal(y5, want_y1)
+
+
 # ---------------------------------------------------------------------------
 # fused front end (the hot kernel)
 # ---------------------------------------------------------------------------
