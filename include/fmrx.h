@@ -229,8 +229,14 @@ FMRX_API int fmrx_deemph_dev(float *d_y, const float *d_x, size_t rows, size_t n
 /* out[i] = sinf(a[i]) (fn 0), cosf(a[i]) (fn 1) or atan2f(a[i], b[i]) (fn 2) as the DEVICE evaluates the
  * restatement of glibc 2.35's functions that fmPLL uses (csrc/glibc_libm.hpp): lets a test compare the
  * device build with the C library of the host, bit for bit.  b may be NULL for fn 0, 1.  fn 3, 4, 5: the same three
- * through the branch-free forms the receiver banks' PLL lanes run (general function where those are not defined). */
+ * through the branch-free forms the receiver banks' PLL lanes run (general function where those are not defined).
+ * fn 6: out[i] = the hardware reciprocal (v_rcp_f32) of a[i], the one operation of the fast discriminator that a host
+ * cannot restate; test hook. */
 FMRX_API int fmrx_diag_libm(int fn, const float *a, const float *b, size_t n, float *out);
+/* Test hook: the FAST discriminator of the specialised paths (csrc/device_math.hpp) on the caller's own IF.  iq: n interleaved
+ * (I, Q) pairs; out[k] from pair k and pair k - 1, out[0] from (prev_i, prev_q).  bounded 0: demod_fast; 1: demod_fast_bounded,
+ * whose precondition (every operand 0 or >= 2^-50 in magnitude) is the caller's to keep.  No pipeline calls this. */
+FMRX_API int fmrx_diag_demod_fast(float *out, const float *iq, size_t n, float prev_i, float prev_q, int bounded);
 /* Measurement aid for bench.py: ONE pure streaming read of a device buffer (>= 3 MiB, 16-byte aligned) by
  * one of the access methods the front-end kernels use -- method 0: non-temporal global loads into
  * registers, 1: LDS-DMA ring, one contiguous run per wave (the fused kernel's pattern), m >= 2: LDS-DMA ring, chunks of

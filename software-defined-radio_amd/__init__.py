@@ -116,6 +116,7 @@ _sig("fmrx_channels_set_deemphasis", [_vp, C.c_double])
 _sig("fmrx_channels_deemph_diagnostics", [_vp, C.POINTER(_ull), C.POINTER(_ull)])
 _sig("fmrx_estimate_psd", [_f32p, _f32p, _f32p, _sz, _flt, _int])
 _sig("fmrx_diag_libm", [_int, _f32p, _vp, _sz, _f32p])
+_sig("fmrx_diag_demod_fast", [_f32p, _f32p, _sz, _flt, _flt, _int])
 _sig("fmrx_diag_stream_read_dev", [_vp, _sz, _int, _vp])
 _sig("fmrx_mode_params", [_int, _int, _int, _int, C.POINTER(Params)])
 _sig("fmrx_pipeline_create", [C.POINTER(_vp), C.POINTER(Params), _int, _sz, _int])
@@ -290,6 +291,25 @@ def deviceLibm(fn: str, a, b=None, flat=False) -> np.ndarray:
     bb = _f32(b) if b is not None else None
     _check(lib.fmrx_diag_libm({"sinf": 0, "cosf": 1, "atan2f": 2}[fn] + (3 if flat else 0), a,
                               bb.ctypes.data if bb is not None else None, len(a), out))
+    return out
+
+
+def deviceRcp(a) -> np.ndarray:
+    """The hardware reciprocal (v_rcp_f32) of each element (fmrx_diag_libm, fn 6): test hook."""
+    a = _f32(a)
+    out = np.zeros(len(a), np.float32)
+    _check(lib.fmrx_diag_libm(6, a, None, len(a), out))
+    return out
+
+
+def fmDemodFast(I, Q, prev_i=0.0, prev_q=0.0, bounded=False) -> np.ndarray:
+    """The fast discriminator of the specialised paths (csrc/device_math.hpp: demod_fast; bounded: demod_fast_bounded)
+    on the caller's IF (fmrx_diag_demod_fast): test hook."""
+    I, Q = _f32(I), _f32(Q)
+    iq = np.empty(2 * len(I), np.float32)
+    iq[0::2], iq[1::2] = I, Q
+    out = np.zeros(len(I), np.float32)
+    _check(lib.fmrx_diag_demod_fast(out, iq, len(I), prev_i, prev_q, int(bool(bounded))))
     return out
 
 

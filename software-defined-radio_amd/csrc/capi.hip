@@ -551,7 +551,8 @@ int fmrx_deemph_dev(float *d_y, const float *d_x, size_t rows, size_t n, size_t 
 // ---- diagnostics ---------------------------------------------------------------------------
 int fmrx_diag_libm(int fn, const float *a, const float *b, size_t n, float *out)
 {
-    if (fn < 0 || fn > 5) return fail(FMRX_EINVAL, "diag_libm: fn must be 0 (sinf), 1 (cosf), 2 (atan2f) or 3..5 (their branch-free forms)");
+    if (fn < 0 || fn > 6)
+        return fail(FMRX_EINVAL, "diag_libm: fn must be 0 (sinf), 1 (cosf), 2 (atan2f), 3..5 (their branch-free forms) or 6 (rcp)");
     if ((!a || !out || (fn % 3 == 2 && !b)) && n) return fail(FMRX_EINVAL, "diag_libm: null buffer");
     FMRX_TRY(require_device());
     Stage st;
@@ -560,6 +561,22 @@ int fmrx_diag_libm(int fn, const float *a, const float *b, size_t n, float *out)
     FMRX_TRY(fn % 3 == 2 ? st.in(db, b, n) : st.out(db, n));
     FMRX_TRY(st.out(dc, n));
     FMRX_TRY(k_libm_eval(fn, da.p, db.p, n, dc.p, nullptr));
+    return st.back(out, dc);
+}
+
+int fmrx_diag_demod_fast(float *out, const float *iq, size_t n, float prev_i, float prev_q, int bounded)
+{
+    if ((!out || !iq) && n) return fail(FMRX_EINVAL, "diag_demod_fast: null buffer");
+    if (bounded != 0 && bounded != 1) return fail(FMRX_EINVAL, "diag_demod_fast: bounded must be 0 or 1");
+    if (n == 0) return FMRX_OK;
+    FMRX_TRY(require_device());
+    Stage st;
+    Dev<float> dz, dp, dc;
+    const float prev[2] = {prev_i, prev_q};
+    FMRX_TRY(st.in(dz, iq, 2 * n));
+    FMRX_TRY(st.in(dp, prev, 2));
+    FMRX_TRY(st.out(dc, n));
+    FMRX_TRY(k_fm_demod_if(dz.p, n, dp.p, nullptr, dc.p, bounded ? 2 : 1, nullptr));
     return st.back(out, dc);
 }
 

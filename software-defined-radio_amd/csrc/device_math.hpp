@@ -31,9 +31,14 @@ __device__ __forceinline__ float demod_exact(float i, float q, float pi, float p
 // and denominator (separately rounded products -- so degenerate cases such as
 // I*Q - Q*I stay exactly 0, which the stereo PLL's atan2 is sensitive to), but
 // a 1-ulp hardware reciprocal (v_rcp_f32) instead of the ~10-instruction IEEE
-// divide: |error| <= ~1.5 ulp of the quotient.  Tiny denominators are scaled
-// by 2^64 first (numerator too: same quotient) so v_rcp_f32 never sees a
-// denormal or overflows; branch-free.
+// divide: |error| <= 2.5 ulp of the quotient (1 ulp of the reciprocal is up to
+// 2 ulp of a quotient whose significand is near 2, plus the product's half;
+// ~1.5 ulp on the average significand).  Tiny denominators are scaled by 2^64
+// first (numerator too: same quotient) so v_rcp_f32 never sees a denormal or
+// overflows; branch-free.  Denormal squares and products are kept, not flushed
+// (no pipeline stream reaches one: an IF sample is an integer times 2^-(s+7)).
+// Pinned bit for bit, given the device's reciprocal, by tests/_demod_model.py
+// and tests/test_gpu_demod_exact.py.
 __device__ __forceinline__ float demod_fast(float i, float q, float pi, float pq)
 {
     const float ii = i * i, qq = q * q;

@@ -223,7 +223,7 @@ int k_fe_generic(const uint8_t *d_iq, const uint8_t *d_hist, int hist_bytes, siz
 int k_resample_generic(const float *d_x, size_t n_in, const float *d_h, int taps, int decim, int upsamp, float *d_y,
                        hipStream_t s);
 // demod[k] from interleaved IF (I,Q); IF[-1] = *d_prev (float2). Also stores IF[n-1] to d_prev_out when non-null.
-// fast != 0: the arithmetic of the fused audio kernel (demod_fast) instead of the reference order
+// fast 1: the arithmetic of the fused audio kernel (demod_fast) instead of the reference order; 2: demod_fast_bounded
 int k_fm_demod_if(const float *d_if, size_t n, const float *d_prev, float *d_prev_out, float *d_demod, int fast,
                   hipStream_t s);
 int k_fm_demod_planar(const float *d_i, const float *d_q, size_t n, float prev_i, float prev_q, float *d_demod,

@@ -104,7 +104,8 @@ __global__ void resample_generic_kernel(const float *__restrict__ x, size_t n_ou
 // ---- FM discriminator (src/filter.cpp:248-266) ------------------------------------
 __device__ inline float demod_one(float i, float q, float pi, float pq) { return demod_exact(i, q, pi, pq); }
 
-template <bool FAST>
+// FAST 0: the reference order; 1: demod_fast; 2: demod_fast_bounded (the caller keeps its precondition)
+template <int FAST>
 __global__ void demod_if_kernel(const float2 *__restrict__ z, size_t n, const float2 *__restrict__ prev,
                                 float2 *__restrict__ prev_out, float *__restrict__ out)
 {
@@ -112,7 +113,9 @@ __global__ void demod_if_kernel(const float2 *__restrict__ z, size_t n, const fl
     if (k >= n) return;
     const float2 c = z[k];
     const float2 p = k ? z[k - 1] : *prev;
-    out[k] = FAST ? demod_fast(c.x, c.y, p.x, p.y) : demod_exact(c.x, c.y, p.x, p.y);
+    out[k] = FAST == 2 ? demod_fast_bounded(c.x, c.y, p.x, p.y)
+           : FAST == 1 ? demod_fast(c.x, c.y, p.x, p.y)
+                       : demod_exact(c.x, c.y, p.x, p.y);
     if (prev_out && k == n - 1) *prev_out = c;
 }
 
@@ -284,12 +287,16 @@ int k_fm_demod_if(const float *d_if, size_t n, const float *d_prev, float *d_pre
                   hipStream_t s)
 {
     if (n == 0) return FMRX_OK;
-    if (fast)
-        hipLaunchKernelGGL(demod_if_kernel<true>, dim3(grid_for(n)), dim3(kBlock), 0, s,
+    if (fast == 2)
+        hipLaunchKernelGGL(demod_if_kernel<2>, dim3(grid_for(n)), dim3(kBlock), 0, s,
+                           reinterpret_cast<const float2 *>(d_if), n, reinterpret_cast<const float2 *>(d_prev),
+                           reinterpret_cast<float2 *>(d_prev_out), d_demod);
+    else if (fast)
+        hipLaunchKernelGGL(demod_if_kernel<1>, dim3(grid_for(n)), dim3(kBlock), 0, s,
                            reinterpret_cast<const float2 *>(d_if), n, reinterpret_cast<const float2 *>(d_prev),
                            reinterpret_cast<float2 *>(d_prev_out), d_demod);
     else
-        hipLaunchKernelGGL(demod_if_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, s,
+        hipLaunchKernelGGL(demod_if_kernel<0>, dim3(grid_for(n)), dim3(kBlock), 0, s,
                            reinterpret_cast<const float2 *>(d_if), n, reinterpret_cast<const float2 *>(d_prev),
                            reinterpret_cast<float2 *>(d_prev_out), d_demod);
     FMRX_LAUNCH_CHECK("demod_if");

@@ -874,6 +874,10 @@ __global__ void libm_eval_kernel(int fn, const float *__restrict__ a, const floa
 {
     const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (fn == 6) {   // the hardware reciprocal of the fast discriminator (device_math.hpp), alone
+        out[i] = __builtin_amdgcn_rcpf(a[i]);
+        return;
+    }
     if (fn <= 2) {
         out[i] = fn == 0 ? glibc235::sinf_glibc(a[i]) : fn == 1 ? glibc235::cosf_glibc(a[i]) : glibc235::atan2f_glibc(a[i], b[i]);
         return;

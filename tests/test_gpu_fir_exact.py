@@ -27,7 +27,8 @@ bit against an fmaf-chain model, by tests/test_gpu_mfma_exact.py.
 
 Out of scope, on purpose:
   * the PLL and the discriminator's v_rcp_f32 (the PLL's output is an input tap here, as the discriminator's is; the
-    fast PLL is pinned against its own model by tests/test_gpu_pll_exact.py);
+    fast PLL is pinned against its own model by tests/test_gpu_pll_exact.py, the fast discriminator sample by sample
+    against a model given the device's reciprocal by tests/test_gpu_demod_exact.py);
   * the exact banks: already bit for bit against the oracle (tests/test_gpu_channels.py)."""
 import math
 
