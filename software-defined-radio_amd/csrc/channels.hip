@@ -48,14 +48,16 @@ struct fmrx_channels {
 namespace {
 
 // per channel: history <- the slot's last hist_bytes bytes; audio / PCM of the slot, minus the junk in front,
-// -> the caller's contiguous per-channel arrays
+// -> the caller's contiguous per-channel arrays.  Workgroups [c * gx, (c + 1) * gx) serve channel c: the channel rides in the
+// grid's x, which has room for any bank (y and z end at 65 535, and a bank may have more receivers than that)
 __global__ void channels_finish_kernel(uint8_t *__restrict__ slots, long slot_bytes, long hist_bytes, const float *__restrict__ audio_all,
                                        const int16_t *__restrict__ pcm_all, long slot_audio, long junk_audio, long n_audio,
-                                       float *__restrict__ audio_out, int16_t *__restrict__ pcm_out)
+                                       float *__restrict__ audio_out, int16_t *__restrict__ pcm_out, unsigned gx)
 {
-    const long c = blockIdx.y;
+    const long c = blockIdx.x / gx;
+    const unsigned bx = blockIdx.x - static_cast<unsigned>(c) * gx;
     uint8_t *slot = slots + c * slot_bytes;
-    const long t = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x, nt = static_cast<long>(gridDim.x) * blockDim.x;
+    const long t = static_cast<long>(bx) * blockDim.x + threadIdx.x, nt = static_cast<long>(gx) * blockDim.x;
     const long so = c * slot_audio + junk_audio, dof = c * n_audio;   // first element of this channel: source, destination
     // four outputs per access where source and destination allow it (8-byte s16 / 16-byte f32 pieces): true for every reference
     // shape (52 600 / 1 024 elements per slot / channel, 28 in front)
@@ -79,8 +81,16 @@ __global__ void channels_finish_kernel(uint8_t *__restrict__ slots, long slot_by
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
     const u4 *src = reinterpret_cast<const u4 *>(slot + slot_bytes - hist_bytes);
     u4 *dst = reinterpret_cast<u4 *>(slot);
-    if (blockIdx.x == 0)
+    if (bx == 0)
         for (long i = threadIdx.x; i < hist_bytes / 16; i += blockDim.x) dst[i] = src[i];
+}
+
+// workgroups of channels_finish_kernel per channel: four outputs per thread where the shapes allow it (see the kernel), 8 at the
+// most -- times n_channels they fit the grid's x (2^31 - 1) for every bank whose slots fit a device's memory
+unsigned finish_groups(size_t n_audio)
+{
+    const size_t g = ((n_audio + 3) / 4 + 255) / 256;
+    return static_cast<unsigned>(g < 1 ? 1 : g < 8 ? g : 8);
 }
 
 // the block region of the first slot, and the slots' pitch: where a call's input goes
@@ -239,12 +249,11 @@ static int process_bank(fmrx_channels *c, float *d_audio_f32, int16_t *d_pcm16, 
     const float *zend = c->zeros.p + c->p.audio_taps + 32;     // "one past the previous block's last discriminator sample": zeros
     FMRX_TRY(mono_fused_launch(c->fe, c->audio, c->slots.p, total / 2, c->fe.silence.p, c->zeros.p, zend, nullptr, 0, nullptr,
                                d_audio_f32 ? c->audio_all.p : nullptr, c->pcm_all.p, pcm_policy, nullptr, c->opt, s));
-    const size_t per4 = (c->n_audio + 3) / 4;                  // four outputs per thread where the shapes allow it (see the kernel)
-    const unsigned gx = static_cast<unsigned>((per4 + 255) / 256 < 8 ? (per4 + 255) / 256 : 8);
-    hipLaunchKernelGGL(channels_finish_kernel, dim3(gx ? gx : 1, c->n_channels), dim3(256), 0, s, c->slots.p,
+    const unsigned gx = finish_groups(c->n_audio);
+    hipLaunchKernelGGL(channels_finish_kernel, dim3(gx * static_cast<unsigned>(c->n_channels)), dim3(256), 0, s, c->slots.p,
                        static_cast<long>(c->slot_bytes), static_cast<long>(c->hist_bytes), c->audio_all.p, c->pcm_all.p,
                        static_cast<long>(c->junk_audio + c->n_audio), static_cast<long>(c->junk_audio), static_cast<long>(c->n_audio),
-                       d_audio_f32, d_pcm16);
+                       d_audio_f32, d_pcm16, gx);
     FMRX_LAUNCH_CHECK("channels_finish_kernel");
     return FMRX_OK;
 }

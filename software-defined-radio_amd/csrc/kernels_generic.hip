@@ -30,6 +30,16 @@ inline unsigned grid_for(size_t n, int per_block = kBlock)
     return static_cast<unsigned>(g ? g : 1);
 }
 
+// One thread per element: a launch holds fewer than 2^32 work-items, and the runtime cuts a larger count to its low 32 bits
+// without an error (the elements behind it would silently stay as they were).  Every launch sized by grid_for() checks its count.
+constexpr size_t kMaxLaunch = 0xffffffffull - kBlock;
+#define FMRX_COUNT_CHECK(name, n)                                                                                      \
+    do {                                                                                                               \
+        if (static_cast<size_t>(n) > kMaxLaunch)                                                                       \
+            return ::fmrx::fail(FMRX_EINVAL, name ": %zu elements are more than one launch holds (%zu)",               \
+                                static_cast<size_t>(n), kMaxLaunch);                                                   \
+    } while (0)
+
 // ---- FIR, decimating, float in (src/filter.cpp:133-154, 158-188) ------------
 // One output per thread; x[-(taps-1)] .. x[-1] is the carried history.
 __global__ void fir_generic_kernel(const float *__restrict__ x, size_t n_out, const float *__restrict__ h, int taps,
@@ -245,10 +255,12 @@ __global__ void downsample_kernel(const float *__restrict__ in, size_t n_out, fl
     if (k < n_out) out[k] = in[k * ds];
 }
 
+// any size (a bank's slots are gigabytes): the grid is capped and walks the buffer in strides
+constexpr unsigned kFillBlocks = 1u << 16;
 __global__ void fill_u8_kernel(uint8_t *d, size_t n, uint8_t v)
 {
-    const size_t k = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (k < n) d[k] = v;
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t k = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; k < n; k += stride) d[k] = v;
 }
 
 }  // namespace
@@ -256,6 +268,7 @@ __global__ void fill_u8_kernel(uint8_t *d, size_t n, uint8_t v)
 int k_fir_generic(const float *d_x, size_t n_out, const float *d_h, int taps, int decim, float *d_y, hipStream_t s)
 {
     if (n_out == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("fir_generic_kernel", n_out);
     hipLaunchKernelGGL(fir_generic_kernel, dim3(grid_for(n_out)), dim3(kBlock), 0, s, d_x, n_out, d_h, taps, decim, d_y);
     FMRX_LAUNCH_CHECK("fir_generic");
     return FMRX_OK;
@@ -266,6 +279,7 @@ int k_fe_generic(const uint8_t *d_iq, const uint8_t *d_hist, int hist_bytes, siz
 {
     const size_t n_out = n_samples / decim;
     if (n_out == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("fe_generic_kernel", n_out);
     hipLaunchKernelGGL(fe_generic_kernel, dim3(grid_for(n_out)), dim3(kBlock), 0, s, d_iq, d_hist, hist_bytes, n_out,
                        d_h, taps, decim, reinterpret_cast<float2 *>(d_if));
     FMRX_LAUNCH_CHECK("fe_generic");
@@ -277,6 +291,7 @@ int k_resample_generic(const float *d_x, size_t n_in, const float *d_h, int taps
 {
     const size_t n_out = (n_in * static_cast<size_t>(upsamp)) / decim;
     if (n_out == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("resample_generic_kernel", n_out);
     hipLaunchKernelGGL(resample_generic_kernel, dim3(grid_for(n_out)), dim3(kBlock), 0, s, d_x, n_out, d_h, taps, decim,
                        upsamp, d_y);
     FMRX_LAUNCH_CHECK("resample_generic");
@@ -287,6 +302,7 @@ int k_fm_demod_if(const float *d_if, size_t n, const float *d_prev, float *d_pre
                   hipStream_t s)
 {
     if (n == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("demod_if_kernel", n);
     if (fast == 2)
         hipLaunchKernelGGL(demod_if_kernel<2>, dim3(grid_for(n)), dim3(kBlock), 0, s,
                            reinterpret_cast<const float2 *>(d_if), n, reinterpret_cast<const float2 *>(d_prev),
@@ -306,6 +322,7 @@ int k_fm_demod_if(const float *d_if, size_t n, const float *d_prev, float *d_pre
 int k_fm_demod_arctan_planar(const double *d_i, const double *d_q, size_t n, double prev_phase, double *d_out, hipStream_t s)
 {
     if (n == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("demod_arctan_planar_kernel", n);
     hipLaunchKernelGGL(demod_arctan_planar_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, d_i, d_q, n, prev_phase, d_out);
     FMRX_LAUNCH_CHECK("demod_arctan_planar");
     return FMRX_OK;
@@ -314,6 +331,7 @@ int k_fm_demod_arctan_planar(const double *d_i, const double *d_q, size_t n, dou
 int k_fm_demod_arctan_if(const float *d_if, size_t n, const float *d_prev, float *d_demod, hipStream_t s)
 {
     if (n == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("demod_arctan_if_kernel", n);
     hipLaunchKernelGGL(demod_arctan_if_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, reinterpret_cast<const float2 *>(d_if), n,
                        reinterpret_cast<const float2 *>(d_prev), d_demod);
     FMRX_LAUNCH_CHECK("demod_arctan_if");
@@ -324,6 +342,7 @@ int k_fm_demod_planar(const float *d_i, const float *d_q, size_t n, float prev_i
                       hipStream_t s)
 {
     if (n == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("demod_planar_kernel", n);
     hipLaunchKernelGGL(demod_planar_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, d_i, d_q, n, prev_i, prev_q, d_demod);
     FMRX_LAUNCH_CHECK("demod_planar");
     return FMRX_OK;
@@ -333,6 +352,7 @@ int k_fm_demod_planar(const float *d_i, const float *d_q, size_t n, float prev_i
     int fn                                                                                     \
     {                                                                                          \
         if ((n) == 0) return FMRX_OK;                                                          \
+        FMRX_COUNT_CHECK(#kern, n);                                                            \
         hipLaunchKernelGGL(kern, dim3(grid_for(n)), dim3(kBlock), 0, s, __VA_ARGS__);          \
         FMRX_LAUNCH_CHECK(#kern);                                                              \
         return FMRX_OK;                                                                        \
@@ -350,7 +370,14 @@ FMRX_ELEMENTWISE(k_mix(const float *d_bpf, const float *d_pll, size_t n, float *
 FMRX_ELEMENTWISE(k_combine(const float *d_st, const float *d_mono, size_t n, float *d_l, float *d_r, hipStream_t s),
                  combine_kernel, n, d_st, d_mono, n, d_l, d_r)
 FMRX_ELEMENTWISE(k_downsample(const float *d_in, size_t n, float *d_out, int ds, hipStream_t s), downsample_kernel, n, d_in, n, d_out, ds)
-FMRX_ELEMENTWISE(k_fill_u8(uint8_t *d, size_t n, uint8_t v, hipStream_t s), fill_u8_kernel, n, d, n, v)
+int k_fill_u8(uint8_t *d, size_t n, uint8_t v, hipStream_t s)
+{
+    if (n == 0) return FMRX_OK;
+    const unsigned want = grid_for(n < kMaxLaunch ? n : kMaxLaunch);
+    hipLaunchKernelGGL(fill_u8_kernel, dim3(want < kFillBlocks ? want : kFillBlocks), dim3(kBlock), 0, s, d, n, v);
+    FMRX_LAUNCH_CHECK("fill_u8_kernel");
+    return FMRX_OK;
+}
 
 int k_split_if(const float *d_if, size_t n, float *d_i, float *d_q, hipStream_t s) { return k_deinterleave(d_if, n, d_i, d_q, s); }
 
@@ -358,6 +385,7 @@ int k_upsample(const float *d_x, size_t n, float *d_xu, int up, hipStream_t s)
 {
     const size_t n_out = n * static_cast<size_t>(up);
     if (n_out == 0) return FMRX_OK;
+    FMRX_COUNT_CHECK("upsample_kernel", n_out);
     hipLaunchKernelGGL(upsample_kernel, dim3(grid_for(n_out)), dim3(kBlock), 0, s, d_x, n_out, d_xu, up);
     FMRX_LAUNCH_CHECK("upsample");
     return FMRX_OK;
