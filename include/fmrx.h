@@ -701,6 +701,90 @@ FMRX_API int fmrx_tuner_process(fmrx_tuner *t, const uint8_t *wide, size_t n_wid
 /* waits for the last call; per channel, over that call: output bytes that clamped, and sum (I-128)^2 + (Q-128)^2 */
 FMRX_API int fmrx_tuner_levels(fmrx_tuner *t, uint64_t *clipped, uint64_t *power);
 
+/* ------------------------------------------------------------------ */
+/* Signal meters: level, CNR, pilot, RDS, deviation of every channel    */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  One cheap pass over what a bank call leaves on the device -- the block region of every
+ * input slot (fmrx_channels_input_layout) and, where the bank keeps them, the discriminator rows (fmrx_channels_demod_layout)
+ * -- that says which channels hold a station, how good it is, whether it carries a pilot and RDS, how far off tune it is and
+ * how far it deviates.  A stage with a handle of its own, fed from the layout functions as the RDS bank is; it keeps no state
+ * between calls.  Defined by tests/_meters_model.py.
+ *
+ * Raw results, per channel and call (fmrx_meter):
+ *   RF group, from the n_iq = n_iq_bytes / 2 complex samples i = I - 128, q = Q - 128 of the u8 row; exact integers:
+ *     sum_i, sum_q   sum i, sum q                    m2        sum p, p = i^2 + q^2
+ *     m4             sum p^2 (room for 2^33 samples)  clipped   bytes equal to 0 or 255
+ *   MPX group, from the float32 discriminator row x[0 .. n_if) (radians per IF sample), accumulated in float64 in a fixed order
+ *   (the same input gives the same bytes):
+ *     sum_x, sum_x2, max_abs   over the n_if samples
+ *     probe[p], p < 5          sum over the segments = n_if / 1024 whole segments s of |sum_k x[1024 s + k] t_p[k]|^2 with
+ *                              t_p[k] = w[k] (cos, -sin)(2 pi f_p k / if_Fs), w[k] = 0.5 - 0.5 cos(2 pi (k + 0.5) / 1024) (Hann;
+ *                              sum w = 512); the phase restarts in every segment, only powers are used; probe[5 .. 8) = 0
+ *     f_p (fmrx_meters_probes) 17 000 and 21 000 Hz: noise, in the guard bands beside the pilot; 19 000 Hz: the pilot;
+ *                              55 812.5 and 58 187.5 Hz: RDS, the biphase spectrum's maxima at 57 kHz -+ 1 187.5 Hz
+ *   The samples past the last whole segment take part in sum_x, sum_x2 and max_abs only.
+ * The raw sums of successive calls add and max_abs takes the maximum: integration over longer periods is the caller's, by
+ * adding records field by field before fmrx_meters_derive.
+ * A row that is not finite: NaN or infinity goes into sum_x, sum_x2 and the probes of its segment as IEEE arithmetic takes it
+ * (the fields read NaN or infinity); max_abs skips NaN and reads infinity for an infinity.  The library's discriminators write
+ * 0 where I^2 + Q^2 = 0 (a noise-only channel can get there), so the rows of a bank are finite.
+ *
+ * Levels (fmrx_meter_levels; fmrx_meters_derive, host arithmetic in double).  Every dB value is clamped to [-99, 99]: -99
+ * where the numerator is not positive (0 / 0 included), 99 where only the denominator is not; the other fields read 0 where
+ * their sample count is 0.  With M2 = m2 / n_iq, M4 = m4 / n_iq, hz = if_Fs / 2 pi, M = segments:
+ *   level_dbfs      10 log10(M2 / 16384)
+ *   cnr_db          10 log10(S / (M2 - S)), S = sqrt(max(0, 2 M2^2 - M4)): the M2M4 estimator (a constant-envelope carrier in
+ *                   complex Gaussian noise has M2 = S + N, M4 = S^2 + 4 S N + 2 N^2)
+ *   clip_fraction   clipped / (2 n_iq)           dc_i, dc_q   sum_i / n_iq, sum_q / n_iq
+ *   freq_offset_hz  sum_x / n_if * hz            peak_dev_hz  max_abs * hz         mpx_rms_hz  sqrt(sum_x2 / n_if) * hz
+ *   pilot_dev_hz    4 sqrt(probe[19k] / M) / 1024 * hz  (a tone A cos gives a windowed sum of magnitude A * 1024 / 4)
+ *   pilot_db        10 log10(probe[19k] / noise), noise = (probe[17k] + probe[21k]) / 2
+ *   rds_db          10 log10(((probe[lo] + probe[hi]) / 2) / (9 noise)); 9 = (57 / 19)^2: discriminator noise rises with f^2
+ * Thresholds for a stereo or an RDS lamp are the caller's.  Two limits of the definition: cnr_db is over the slot's whole
+ * bandwidth (rf_Fs), not over a channel's 200 kHz; the noise probes sit about 8.5 bins from the pilot, so the window's leakage
+ * caps pilot_db somewhere above 60 dB. */
+#define FMRX_METERS_SEGMENT 1024
+#define FMRX_METERS_PROBES 5
+typedef struct fmrx_meter {
+    uint64_t n_iq;
+    int64_t sum_i, sum_q;
+    uint64_t m2, m4, clipped, n_if, segments;
+    double sum_x, sum_x2, max_abs, probe[8];
+} fmrx_meter;
+typedef struct fmrx_meter_levels {
+    double level_dbfs, cnr_db, clip_fraction, dc_i, dc_q, freq_offset_hz, peak_dev_hz, mpx_rms_hz, pilot_dev_hz, pilot_db, rds_db;
+} fmrx_meter_levels;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_meter) == 152, "fmrx_meter layout");
+static_assert(sizeof(fmrx_meter_levels) == 88, "fmrx_meter_levels layout");
+#else
+_Static_assert(sizeof(fmrx_meter) == 152, "fmrx_meter layout");
+_Static_assert(sizeof(fmrx_meter_levels) == 88, "fmrx_meter_levels layout");
+#endif
+typedef struct fmrx_meters fmrx_meters;
+/* host code, no device needed: the probe frequencies (hz[0 .. 5), the rest 0; *n = 5), the tone table re, im [5][1024] as
+ * the kernel uses it (built in double), and the levels of a record */
+FMRX_API int fmrx_meters_probes(double hz[8], int *n);
+FMRX_API int fmrx_meters_table(double if_Fs, double *re, double *im);
+FMRX_API int fmrx_meters_derive(double if_Fs, const fmrx_meter *m, fmrx_meter_levels *out);
+/* if_Fs: the discriminator rows' sample rate; below 120 000 the top probe would not stay under Nyquist: FMRX_EINVAL */
+FMRX_API int fmrx_meters_create(fmrx_meters **out, double if_Fs, int n_channels, int device);
+FMRX_API int fmrx_meters_destroy(fmrx_meters *m);
+/* The arguments are what fmrx_channels_input_layout (d_iq_first, iq_pitch_bytes; n_iq_bytes = the bank's block_bytes, any
+ * even count) and fmrx_channels_demod_layout (d_demod_row0, demod_pitch in floats, n_if) return: channel c's bytes at
+ * d_iq_first + c * iq_pitch_bytes, its row at d_demod_row0 + c * demod_pitch.  Any byte alignment and pitch work; 16-byte
+ * aligned rows, as a bank's, take the wide loads.  Either input may be NULL: that group reads zero with n_iq / n_if = 0 (the
+ * fused mono bank of modes 0/1 keeps no rows).  With a demod input, n_if < 1024 is FMRX_EINVAL.  Asynchronous on `stream`,
+ * after fmrx_channels_process_dev on the same stream; a second call before fmrx_meters_collect replaces the results. */
+FMRX_API int fmrx_meters_process_dev(fmrx_meters *m, const uint8_t *d_iq_first, size_t iq_pitch_bytes, size_t n_iq_bytes,
+                                     const float *d_demod_row0, size_t demod_pitch, size_t n_if, void *stream);
+/* out [n_channels]; waits for the last call (an event it recorded), not for the device */
+FMRX_API int fmrx_meters_collect(fmrx_meters *m, fmrx_meter *out);
+/* host rows (either may be NULL), synchronous: the single-stream use is n_channels = 1 with the bytes given to
+ * fmrx_pipeline_process and the row fmrx_pipeline_read_tap(FMRX_TAP_DEMOD) returns */
+FMRX_API int fmrx_meters_process(fmrx_meters *m, const uint8_t *iq, size_t iq_pitch_bytes, size_t n_iq_bytes, const float *demod,
+                                 size_t demod_pitch, size_t n_if, fmrx_meter *out);
+
 #ifdef __cplusplus
 }
 #endif

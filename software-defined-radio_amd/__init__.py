@@ -207,6 +207,14 @@ _sig("fmrx_tuner_n_out_bytes", [_vp, _sz], _sz)
 _sig("fmrx_tuner_process_dev", [_vp, _vp, _sz, _vp, _sz, _vp])
 _sig("fmrx_tuner_process", [_vp, _vp, _sz, _u8p])
 _sig("fmrx_tuner_levels", [_vp, _vp, _vp])
+_sig("fmrx_meters_probes", [_f64p, C.POINTER(_int)])
+_sig("fmrx_meters_table", [_dbl, _f64p, _f64p])
+_sig("fmrx_meters_derive", [_dbl, _vp, _vp])
+_sig("fmrx_meters_create", [C.POINTER(_vp), _dbl, _int, _int])
+_sig("fmrx_meters_destroy", [_vp])
+_sig("fmrx_meters_process_dev", [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp])
+_sig("fmrx_meters_collect", [_vp, _vp])
+_sig("fmrx_meters_process", [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp])
 
 
 def _check(rc: int):
@@ -674,6 +682,7 @@ class Channels:
         self.audio_channels = int(audio_channels)
         self.exact = bool(exact)
         self.block_bytes = int(block_bytes or self.params.block_bytes)
+        self.device = int(device)
         self._h = _vp()
         _check(lib.fmrx_channels_create_ex(C.byref(self._h), C.byref(self.params), self.n_channels, self.audio_channels,
                                            int(self.exact), self.block_bytes, device))
@@ -1064,6 +1073,103 @@ class Tuner:
         cl, pw = np.zeros(self.n_channels, np.uint64), np.zeros(self.n_channels, np.uint64)
         _check(lib.fmrx_tuner_levels(self._h, cl.ctypes.data, pw.ctypes.data))
         return cl, pw
+
+
+# --------------------------------------------------------------------------
+# Signal meters: level, CNR, pilot, RDS, deviation of every channel of a bank
+# --------------------------------------------------------------------------
+METERS_SEGMENT = 1024
+METER_DTYPE = np.dtype([("n_iq", "<u8"), ("sum_i", "<i8"), ("sum_q", "<i8"), ("m2", "<u8"), ("m4", "<u8"), ("clipped", "<u8"),
+                        ("n_if", "<u8"), ("segments", "<u8"), ("sum_x", "<f8"), ("sum_x2", "<f8"), ("max_abs", "<f8"),
+                        ("probe", "<f8", (8,))])                 # struct fmrx_meter
+METER_LEVELS_DTYPE = np.dtype([(k, "<f8") for k in ("level_dbfs", "cnr_db", "clip_fraction", "dc_i", "dc_q", "freq_offset_hz",
+                                                    "peak_dev_hz", "mpx_rms_hz", "pilot_dev_hz", "pilot_db", "rds_db")])   # struct fmrx_meter_levels
+assert METER_DTYPE.itemsize == 152 and METER_LEVELS_DTYPE.itemsize == 88
+
+
+def metersProbes() -> np.ndarray:
+    """Host only: the probe frequencies in Hz (noise low, noise high, pilot, RDS low, RDS high)."""
+    hz, n = np.zeros(8), _int(0)
+    _check(lib.fmrx_meters_probes(hz, C.byref(n)))
+    return hz[:n.value]
+
+
+def metersTable(if_Fs):
+    """Host only: the windowed tone table (re, im), float64 [5, 1024] each, as the device uses it."""
+    re, im = np.zeros((5, METERS_SEGMENT)), np.zeros((5, METERS_SEGMENT))
+    _check(lib.fmrx_meters_table(float(if_Fs), re.reshape(-1), im.reshape(-1)))
+    return re, im
+
+
+def metersDerive(if_Fs, rec) -> dict:
+    """Host only: the levels (fmrx_meter_levels, as a dict) of one METER_DTYPE record."""
+    r = np.array(rec, dtype=METER_DTYPE).reshape(1)
+    out = np.zeros(1, METER_LEVELS_DTYPE)
+    _check(lib.fmrx_meters_derive(float(if_Fs), r.ctypes.data, out.ctypes.data))
+    return {k: float(out[0][k]) for k in METER_LEVELS_DTYPE.names}
+
+
+class Meters:
+    """Per channel of a receiver bank and call: RF level, CNR and clipping of the input slot, and frequency offset,
+    deviation, pilot and RDS levels of the discriminator row (fmrx_meters_*).  One pass over what
+    the bank's call left on the device: meters = Meters.for_bank(bank); after bank.process_dev(..., stream=s),
+    meters.process_bank(stream=s); recs = meters.collect(); meters.derive(recs[c])."""
+
+    def __init__(self, if_Fs, n_channels=1, device=0):
+        self.if_Fs, self.n_channels = float(if_Fs), int(n_channels)
+        self._bank = None
+        self._h = _vp()
+        _check(lib.fmrx_meters_create(C.byref(self._h), self.if_Fs, self.n_channels, device))
+
+    @classmethod
+    def for_bank(cls, bank):
+        """The meters of a Channels bank, on the bank's device; process_bank() then passes the bank's own layouts (no
+        discriminator rows where the bank keeps none: the fused mono bank of modes 0/1)."""
+        m = cls(bank.params.if_Fs, bank.n_channels, bank.device)
+        m._bank = bank
+        return m
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_meters_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def process_dev(self, d_iq_first, iq_pitch_bytes, n_iq_bytes, d_demod_row0, demod_pitch, n_if, stream=None):
+        """Device rows as Channels.input_layout() / demod_layout() return them; either pointer may be None."""
+        _check(lib.fmrx_meters_process_dev(self._h, d_iq_first, iq_pitch_bytes, n_iq_bytes, d_demod_row0, demod_pitch, n_if, stream))
+
+    def process_bank(self, stream=None):
+        """process_dev on the layouts of the bank given to for_bank (asked again at every call: the rows' address is the last call's)."""
+        bank = self._bank
+        first, pitch = bank.input_layout()
+        try:
+            rows, row_pitch, n_if = bank.demod_layout()
+        except FmrxError as e:
+            if e.code != EINVAL:     # EINVAL: this bank keeps no rows; anything else is a failure of its own
+                raise
+            rows, row_pitch, n_if = None, 0, 0
+        self.process_dev(first, pitch, bank.block_bytes, rows, row_pitch, n_if, stream)
+
+    def collect(self) -> np.ndarray:
+        """Waits for the last call; METER_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, METER_DTYPE)
+        _check(lib.fmrx_meters_collect(self._h, out.ctypes.data))
+        return out
+
+    def process(self, iq=None, demod=None) -> np.ndarray:
+        """Host rows: iq uint8 [n_channels, n_iq_bytes] and / or demod float32 [n_channels, n_if] -> METER_DTYPE [n_channels]."""
+        iq = None if iq is None else _u8(iq).reshape(self.n_channels, -1)
+        x = None if demod is None else _f32(demod).reshape(self.n_channels, -1)
+        out = np.zeros(self.n_channels, METER_DTYPE)
+        _check(lib.fmrx_meters_process(self._h, None if iq is None else iq.ctypes.data, 0 if iq is None else iq.shape[1],
+                                       0 if iq is None else iq.shape[1], None if x is None else x.ctypes.data,
+                                       0 if x is None else x.shape[1], 0 if x is None else x.shape[1], out.ctypes.data))
+        return out
+
+    def derive(self, rec) -> dict:
+        return metersDerive(self.if_Fs, rec)
 
 
 class FrontEndPlan:

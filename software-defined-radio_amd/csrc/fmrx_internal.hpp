@@ -382,4 +382,15 @@ struct TunerLaunch {
 size_t tuner_mfma_lds_bytes(int R, int ks, int format);
 int tuner_launch(const TunerLaunch &a, hipStream_t stream);
 
+// ---- signal meters (kernels_meters.hip; handle, host arithmetic and C ABI in meters.hip) -----------------
+constexpr int kMetersSegment = FMRX_METERS_SEGMENT, kMetersProbes = FMRX_METERS_PROBES;
+constexpr int kMetersRfFields = 5;    // per channel: sum_i, sum_q, m2, m4, clipped (64-bit integers)
+constexpr int kMetersMpxFields = 8;   // per channel: sum_x, sum_x2, max_abs, probe[5] (doubles)
+// RF pass: rows iq + c * pitch of n_bytes (even) u8 I,Q bytes, any alignment -> acc[c][kMetersRfFields] += (zeroed by the caller)
+int meters_rf_launch(const uint8_t *d_iq, size_t pitch, size_t n_bytes, int n_channels, unsigned long long *d_acc, hipStream_t s);
+// MPX pass: rows x + c * pitch of n_if >= kMetersSegment floats -> out[c][kMetersMpxFields] (written, not added);
+// d_table: re [5][1024] then im [5][1024]; at most max_blocks workgroups walk the channels
+int meters_mpx_launch(const float *d_x, size_t pitch, size_t n_if, int n_channels, const double *d_table, double *d_out, int max_blocks,
+                      hipStream_t s);
+
 }  // namespace fmrx
