@@ -667,6 +667,16 @@ FMRX_API int fmrx_fe_run_dev(const fmrx_fe_plan *plan, const uint8_t *d_iq, size
  * fmrx_tuner_set_channel returns FMRX_EINVAL beyond that (gain x taps below 1e-7).  The output, the u8 I,Q slots of a bank,
  * is the same for every format; samples in front of a stream and past a call are zero samples (x = 0).
  *
+ * Rational rates (fmrx_tuner_create_rational; defined by tests/_tuner_rational_model.py): a capture
+ * at Fs_w whose rate is no integer multiple of rf_Fs -- 10, 12.5, 20 or 25 MS/s from an Airspy, an SDRplay, a HackRF or a
+ * USRP -- is tuned at rf_Fs = Fs_w * U / D, gcd(U, D) = 1, 1 <= U <= 32, 2 U <= D <= 512 (6/25: 10 -> 2.4 MS/s).  h is the
+ * prototype low-pass at U * Fs_w; with Tp = ceil(taps / U), n_m = floor(m D / U) and p_m = m D mod U,
+ *   y_c[m] = Q( e^{-j phi_c(n_m)} * sum_{j<Tp} ( g_c h[p_m + j U] e^{+j phi_c(j)} ) * x[n_m - j] ),  phi_c(n) = 2 pi (w n mod 2^32) / 2^32
+ * = zero-stuffing by U, filtering with h, keeping every D-th sample of the mixed capture.  Same w, same table, same rounding
+ * and shift; ONE s per channel over all U phases; the int16 pairs are phase-major, re[p * Tp + j]; the accumulator's worst
+ * case 128 * sum(|re| + |im|) is taken per phase.  A call takes n_wide % D == 0 samples and yields n_wide * U / D outputs per
+ * channel; the state is the last Tp - 1 wide samples and the counter.  With U = 1 this is the integer tuner with R = D.
+ *
  * fmrx_tuner_design / fmrx_tuner_table are host code (no device needed): the integers a channel uses.  design rejects
  * (FMRX_EINVAL) non-finite or all-zero gain x taps, |f_c| >= Fs_w / 2, s outside its range, and tap sets whose worst case
  * 128 * sum(|re| + |im|) does not fit int32.  table: cos_q15 / sin_q15 [4096] (either NULL: only *n is set). */
@@ -674,6 +684,10 @@ typedef struct fmrx_tuner fmrx_tuner;
 FMRX_API int fmrx_tuner_design(const float *h, int taps, double Fs_w, double f_c, double gain, uint32_t *w, int *s, int16_t *re,
                                int16_t *im);
 FMRX_API int fmrx_tuner_table(int16_t *cos_q15, int16_t *sin_q15, size_t *n);
+/* host code: the integers of a channel of a rational tuner.  re, im: [U * ceil(taps / U)], phase-major.  Rejections as
+ * fmrx_tuner_design, the accumulator's worst case per phase; U outside 1 .. 32: FMRX_EINVAL. */
+FMRX_API int fmrx_tuner_design_rational(const float *h, int taps, int U, double Fs_w, double f_c, double gain, uint32_t *w, int *s,
+                                        int16_t *re, int16_t *im);
 /* h [taps]: the prototype low-pass at Fs_w (2 .. 4096 taps; more than 256 run the generic kernel).  max_wide_samples: the
  * largest call, a multiple of R.  Every channel starts at f_c = 0, gain 1.  The option "tuner_variant" is read here. */
 FMRX_API int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int device);
@@ -683,13 +697,21 @@ FMRX_API int fmrx_tuner_create(fmrx_tuner **out, int R, const float *h, int taps
 #define FMRX_TUNER_S16 2
 FMRX_API int fmrx_tuner_create_ex(fmrx_tuner **out, int R, const float *h, int taps, int n_channels, size_t max_wide_samples, int format,
                                   int device);
+/* the tuner at rf_Fs = Fs_w * U / D.  h [taps]: the prototype low-pass at U * Fs_w (2 .. 4096 taps).  max_wide_samples: the
+ * largest call, a multiple of D.  FMRX_EINVAL (the message names the argument) for gcd(U, D) != 1, U or D out of range,
+ * D < 2 U, an unknown format.  Every other call works on the handle as on an integer one; calls take n_wide % D == 0.
+ * The matrix kernels run for U <= 24, D <= 125, ceil(taps / U) <= 256, the generic kernel otherwise and under
+ * "tuner_variant" = 1.  U = 1, D = R <= 32 builds the handle of fmrx_tuner_create_ex(R). */
+FMRX_API int fmrx_tuner_create_rational(fmrx_tuner **out, int U, int D, const float *h, int taps, int n_channels,
+                                        size_t max_wide_samples, int format, int device);
+FMRX_API int fmrx_tuner_ratio(const fmrx_tuner *t, int *U, int *D);   /* (1, R) for a handle of fmrx_tuner_create / _create_ex */
 FMRX_API int fmrx_tuner_format(const fmrx_tuner *t);            /* FMRX_TUNER_*; -1 for a null handle */
 FMRX_API size_t fmrx_tuner_sample_bytes(const fmrx_tuner *t);   /* bytes per complex wide sample: 2, 2 or 4 */
 FMRX_API int fmrx_tuner_destroy(fmrx_tuner *t);
 FMRX_API int fmrx_tuner_reset(fmrx_tuner *t);     /* start of stream: silence in front, sample counter 0; channels keep their settings */
 /* any time between calls; takes effect at the next call (which then waits once for its stream while it uploads) */
 FMRX_API int fmrx_tuner_set_channel(fmrx_tuner *t, int channel, double f_c_hz, double Fs_w, double gain);
-FMRX_API size_t fmrx_tuner_n_out_bytes(const fmrx_tuner *t, size_t n_wide);   /* 2 * n_wide / R; 0 unless n_wide % R == 0 */
+FMRX_API size_t fmrx_tuner_n_out_bytes(const fmrx_tuner *t, size_t n_wide);   /* 2 * n_wide * U / D (U / D = 1 / R); 0 unless n_wide % D == 0 */
 /* d_wide: DEVICE, 16-byte aligned, n_wide complex samples in the tuner's format (fmrx_tuner_sample_bytes * n_wide bytes),
  * n_wide % R == 0.  Channel c's bytes go to d_out_first + c * pitch_bytes
  * (both multiples of 16): exactly what fmrx_channels_input_layout returns, so tuner -> bank -> RDS bank chain on one stream;

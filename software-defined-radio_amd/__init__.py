@@ -198,6 +198,9 @@ _sig("fmrx_tuner_design", [_f32p, _int, _dbl, _dbl, _dbl, C.POINTER(C.c_uint32),
 _sig("fmrx_tuner_table", [_vp, _vp, C.POINTER(_sz)])
 _sig("fmrx_tuner_create", [C.POINTER(_vp), _int, _f32p, _int, _int, _sz, _int])
 _sig("fmrx_tuner_create_ex", [C.POINTER(_vp), _int, _f32p, _int, _int, _sz, _int, _int])
+_sig("fmrx_tuner_design_rational", [_f32p, _int, _int, _dbl, _dbl, _dbl, C.POINTER(C.c_uint32), C.POINTER(_int), _i16p, _i16p])
+_sig("fmrx_tuner_create_rational", [C.POINTER(_vp), _int, _int, _f32p, _int, _int, _sz, _int, _int])
+_sig("fmrx_tuner_ratio", [_vp, C.POINTER(_int), C.POINTER(_int)])
 _sig("fmrx_tuner_format", [_vp])
 _sig("fmrx_tuner_sample_bytes", [_vp], _sz)
 _sig("fmrx_tuner_destroy", [_vp])
@@ -996,6 +999,18 @@ def tunerLowPass(Fs_w, R, T) -> np.ndarray:
     return impulseResponseLPF(float(Fs_w), 0.5 * (128e3 + rf_Fs - 100e3), int(T))
 
 
+def tunerLowPassRational(Fs_w, U, D, T) -> np.ndarray:
+    """The default prototype filter of Tuner.rational: tunerLowPass's rule at the upsampled rate U * Fs_w, with the gain U
+    that makes the pass band unity after zero-stuffing:  U * impulseResponseLPF(U * Fs_w, Fc, T),  rf_Fs = Fs_w * U / D,
+    Fc = (128 kHz + rf_Fs - 100 kHz) / 2.  At T = 8 D (Tp = 8 D / U taps per phase, the transition the integer tuner has at
+    T = 8 R), the float32 taps' response at 128 kHz against DC and the largest response from rf_Fs - 100 kHz to U Fs_w / 2:
+        6/25, 3/25 (10, 20 -> 2.4 MS/s), 24/125 (12.5 -> 2.4), 3/10, 3/20 (8, 16 -> 2.4):  within 0.011 dB, below -62.4 dB
+        18/125 (10 -> 1.44 MS/s):                                                          -0.023 dB, -61.2 dB
+        12/125 (10 -> 0.96 MS/s, 25 -> 2.4 MS/s):                                          -0.032 dB, -54.9 dB"""
+    rf_Fs = float(Fs_w) * int(U) / int(D)
+    return (np.float32(U) * impulseResponseLPF(int(U) * float(Fs_w), 0.5 * (128e3 + rf_Fs - 100e3), int(T))).astype(np.float32)
+
+
 TUNER_FORMATS = {"u8": 0, "s8": 1, "s16": 2}                       # FMRX_TUNER_U8 / _S8 / _S16
 _TUNER_DTYPES = {"u8": np.uint8, "s8": np.int8, "s16": np.int16}
 
@@ -1017,6 +1032,43 @@ class Tuner:
         _check(lib.fmrx_tuner_create_ex(C.byref(self._h), self.R, self.h, len(self.h), self.n_channels, self.max_wide_samples,
                                         TUNER_FORMATS[fmt], device))
         self.sample_bytes = int(lib.fmrx_tuner_sample_bytes(self._h))       # per complex wide sample: 2, 2 or 4
+        self.U, self.D = 1, self.R
+
+    @classmethod
+    def rational(cls, U, D, h, n_channels, max_wide_samples, device=0, fmt="u8"):
+        """A Tuner at rf_Fs = Fs_w * U / D (gcd 1, 1 <= U <= 32, 2 U <= D <= 512): h is the prototype low-pass at U * Fs_w
+        (tunerLowPassRational), calls take a multiple of D wide samples and give n_wide * U / D outputs per channel
+        (fmrx_tuner_create_rational).  .U and .D hold the ratio; .R is D for U = 1, else None."""
+        if fmt not in TUNER_FORMATS:
+            raise ValueError(f"Tuner: fmt {fmt!r}: one of {', '.join(TUNER_FORMATS)}")
+        self = cls.__new__(cls)
+        self.U, self.D = int(U), int(D)
+        self.R = self.D if self.U == 1 else None
+        self.n_channels, self.max_wide_samples, self.fmt = int(n_channels), int(max_wide_samples), fmt
+        self.h = _f32(h)
+        self._h = _vp()
+        _check(lib.fmrx_tuner_create_rational(C.byref(self._h), self.U, self.D, self.h, len(self.h), self.n_channels, self.max_wide_samples,
+                                              TUNER_FORMATS[fmt], device))
+        self.sample_bytes = int(lib.fmrx_tuner_sample_bytes(self._h))
+        return self
+
+    def ratio(self):
+        """(U, D) as the handle reports it: (1, R) for an integer tuner"""
+        u, d = _int(0), _int(0)
+        _check(lib.fmrx_tuner_ratio(self._h, C.byref(u), C.byref(d)))
+        return u.value, d.value
+
+    @staticmethod
+    def design_rational(h, U, Fs_w, f_c, gain=1.0):
+        """Host only: (frequency word, scale exponent s, re int16[U * Tp], im int16[U * Tp]) of one channel of a rational
+        tuner, phase-major (tap j of phase p at p * Tp + j, Tp = ceil(len(h) / U))."""
+        h = _f32(h)
+        U = int(U)
+        n = U * (-(-len(h) // U)) if 1 <= U <= 32 else len(h)             # another U: the library rejects it
+        w, s = C.c_uint32(0), _int(0)
+        re, im = np.zeros(n, np.int16), np.zeros(n, np.int16)
+        _check(lib.fmrx_tuner_design_rational(h, len(h), U, Fs_w, f_c, gain, C.byref(w), C.byref(s), re, im))
+        return w.value, s.value, re, im
 
     @staticmethod
     def design(h, Fs_w, f_c, gain=1.0):
@@ -1054,14 +1106,14 @@ class Tuner:
 
     def process(self, wide):
         """wide: interleaved I,Q (host) as uint8 / int8 / int16 for fmt u8 / s8 / s16 (another dtype is a TypeError, never a
-        conversion), a multiple of R samples -> uint8 [n_channels, 2 * n_wide / R]."""
+        conversion), a multiple of R (of D for a rational tuner) samples -> uint8 [n_channels, n_out_bytes(n_wide)]."""
         if self.fmt == "u8" and not isinstance(wide, np.ndarray):
             wide = _u8(wide)
         if not isinstance(wide, np.ndarray) or wide.dtype != _TUNER_DTYPES[self.fmt]:
             raise TypeError(f"Tuner.process: a {self.fmt} tuner takes a {np.dtype(_TUNER_DTYPES[self.fmt]).name} array, not {getattr(wide, 'dtype', type(wide).__name__)}")
         x = np.ascontiguousarray(wide).reshape(-1)
         n_wide = len(x) // 2
-        out = np.zeros((self.n_channels, 2 * n_wide // self.R), np.uint8)
+        out = np.zeros((self.n_channels, self.n_out_bytes(n_wide)), np.uint8)
         _check(lib.fmrx_tuner_process(self._h, x.ctypes.data, n_wide, out.reshape(-1)))
         return out
 

@@ -381,6 +381,36 @@ struct TunerLaunch {
 };
 size_t tuner_mfma_lds_bytes(int R, int ks, int format);
 int tuner_launch(const TunerLaunch &a, hipStream_t stream);
+// the kernel that carries the history: the last front_bytes raw bytes of (old history | this call's n_raw_bytes of input)
+int tuner_hist_launch(const uint8_t *x, long n_raw_bytes, const uint8_t *hist, uint8_t *hist_next, int front_bytes, hipStream_t stream);
+
+// The same at a rational rate U / D (kernels_tuner_rational.hip): pointers and levels as in TunerLaunch.
+struct TunerRatLaunch {
+    bool mfma = true;
+    int format = 0, tiles = 1;           // tiles: the matrix kernel's tiles per wave and step (tuner_rat_plan)
+    bool via_lds = false;                // matrix kernel: a step's outputs go through an LDS buffer to whole-row stores
+    const uint8_t *x = nullptr;
+    long n_bytes = 0;                    // 2 * n_wide, n_wide a multiple of D
+    const uint8_t *hist = nullptr;
+    uint8_t *hist_next = nullptr;
+    const int8_t *a_img = nullptr;       // matrix kernel: operand image [group][image q < 8 U][ksp][64 lanes][16]
+    const int16_t *taps_re = nullptr, *taps_im = nullptr;   // generic kernel: [n_channels][U * Tp], phase-major
+    const uint2 *chan = nullptr;
+    const int2 *kconst = nullptr;        // 16-bit matrix kernel: [n_channels][U], the constant of each phase
+    const unsigned *table = nullptr;
+    uint8_t *out = nullptr;
+    long pitch = 0;
+    int n_channels = 0, U = 1, D = 2, Tp = 0, front = 0, ks = 0, ksp = 0;
+    unsigned n0 = 0;
+    unsigned long long *levels = nullptr;
+};
+struct TunerRatPlan {
+    int tiles;                           // 4, 2, 1, or 0 where the window does not fit the matrix kernel
+    bool via_lds;
+};
+size_t tuner_rat_lds_bytes(int U, int D, int ks, int format, int tiles, bool via_lds);
+TunerRatPlan tuner_rat_plan(int U, int D, int ks, int format);
+int tuner_rat_launch(const TunerRatLaunch &a, hipStream_t stream);
 
 // ---- signal meters (kernels_meters.hip; handle, host arithmetic and C ABI in meters.hip) -----------------
 constexpr int kMetersSegment = FMRX_METERS_SEGMENT, kMetersProbes = FMRX_METERS_PROBES;

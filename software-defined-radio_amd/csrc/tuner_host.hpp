@@ -153,4 +153,143 @@ inline void tuner_fill_image(int8_t *img, const TunerShape &sh, int T, int R, in
                 }
 }
 
+// ---- rational rates: rf_Fs = Fs_w * U / D (arithmetic defined by tests/_tuner_rational_model.py) ----
+// Output m of the stream has n_m = floor(m D / U) as its newest wide sample and sums phase p_m = m D mod U of the prototype
+// (designed at U * Fs_w, zero-padded to U * Tp taps, Tp = ceil(T / U)) over the Tp samples x[n_m - j].
+constexpr int kTunerMaxU = 32, kTunerMaxD = 512;
+constexpr int kTunerRatMfmaMaxU = 24, kTunerRatMfmaMaxD = 125;   // the range the matrix kernels cover (with Tp <= kTunerMfmaMaxTaps)
+
+inline int tuner_gcd(int a, int b)
+{
+    while (b) {
+        const int r = a % b;
+        a = b;
+        b = r;
+    }
+    return a;
+}
+// error text of a ratio (nullptr = accepted)
+inline const char *tuner_ratio_check(int U, int D)
+{
+    if (U < 1 || U > kTunerMaxU) return "U must be 1 .. 32";
+    if (D < 2 * U || D > kTunerMaxD) return "D must be 2 U .. 512";
+    if (tuner_gcd(U, D) != 1) return "U and D must have no common factor (gcd(U, D) = 1)";
+    return nullptr;
+}
+inline int tuner_phase_taps(int T, int U) { return (T + U - 1) / U; }   // Tp
+
+// tuner_design for the U phases: tap (p, j) = gain h[p + j U] (cos a_j, sin a_j), a_j = 2 pi ((w j mod 2^32) / 2^32), ONE s
+// for all phases, re / im phase-major [p * Tp + j]; the accumulator's worst case is per phase.
+inline const char *tuner_design_rational(const float *h, int T, int U, double Fs_w, double f_c, double gain, uint32_t *w_out, int *s_out,
+                                         int16_t *re, int16_t *im)
+{
+    if (!h || T < 2 || T > kTunerMaxTaps) return "taps: 2 .. 4096";
+    if (U < 1 || U > kTunerMaxU) return "U must be 1 .. 32";
+    if (!(Fs_w > 0.0) || !std::isfinite(Fs_w)) return "Fs_w must be positive and finite";
+    if (!std::isfinite(f_c) || !(std::fabs(f_c) < Fs_w / 2)) return "|f_c| must be below Fs_w / 2";
+    if (!std::isfinite(gain)) return "gain must be finite";
+    const uint32_t w = tuner_freq_word(f_c, Fs_w);
+    const int Tp = tuner_phase_taps(T, U);
+    const size_t n = static_cast<size_t>(U) * Tp;
+    std::vector<double> gr(n, 0.0), gi(n, 0.0);
+    double m = 0.0;
+    for (int k = 0; k < T; k++) {
+        if (!std::isfinite(h[k])) return "non-finite tap";
+        const int p = k % U, j = k / U;
+        const uint32_t ph = w * static_cast<uint32_t>(j);                       // w j mod 2^32
+        const double a = kTunerTwoPi * (static_cast<double>(ph) / 4294967296.0);
+        const double g = gain * static_cast<double>(h[k]);
+        const size_t i = static_cast<size_t>(p) * Tp + j;
+        gr[i] = g * std::cos(a);
+        gi[i] = g * std::sin(a);
+        m = std::fmax(m, std::fmax(std::fabs(gr[i]), std::fabs(gi[i])));
+    }
+    if (!std::isfinite(m) || m == 0.0) return "gain x taps are all zero or not finite";
+    int s = static_cast<int>(std::floor(std::log2(kTunerTapLimit / m)));
+    while (std::ldexp(m, s) > kTunerTapLimit) s--;
+    while (std::ldexp(m, s + 1) <= kTunerTapLimit) s++;
+    if (s < kTunerMinShift || s > kTunerMaxShift) return "gain x taps out of range (scale exponent outside -14 .. 47)";
+    long long worst = 0;
+    for (int p = 0; p < U; p++) {
+        long long sum = 0;
+        for (int j = 0; j < Tp; j++) {
+            const size_t i = static_cast<size_t>(p) * Tp + j;
+            const long long qr = std::llround(std::ldexp(gr[i], s)), qi = std::llround(std::ldexp(gi[i], s));
+            re[i] = static_cast<int16_t>(qr);
+            im[i] = static_cast<int16_t>(qi);
+            sum += std::llabs(qr) + std::llabs(qi);
+        }
+        worst = std::max(worst, sum);
+    }
+    if (128 * worst > 2147483647LL) return "worst-case accumulator of a phase, 128 * sum(|re| + |im|), does not fit int32";
+    *w_out = w;
+    *s_out = s;
+    return nullptr;
+}
+
+// Shape of the rational matrix kernel's tile.  A column is 8 U consecutive outputs of every channel of the group; its window
+// starts `front` bytes in front of the newest sample of its first output and 16 D bytes after its neighbour's.  Output q of
+// the column (image q) has phase p_q = q D mod U and its newest sample floor(q D / U) samples into the column: window byte u
+// meets tap j and part c where  u = front + 2 floor(q D / U) - 2 j + c.  Image q's taps lie in the K-steps j0[q] .. j1[q]-1.
+struct TunerRatShape {
+    int U = 1, D = 2, Tp = 0;
+    int front = 0;       // multiple of 16, >= 2 (Tp - 1) and >= 16
+    int ks = 0;          // K-steps the whole window spans
+    int ksp = 0;         // K-steps stored per image
+    std::vector<int> j0, j1;   // [8 U]
+};
+inline TunerRatShape tuner_rat_shape(int T, int U, int D)
+{
+    TunerRatShape s;
+    s.U = U;
+    s.D = D;
+    s.Tp = tuner_phase_taps(T, U);
+    s.front = std::max(16, (2 * (s.Tp - 1) + 15) / 16 * 16);   // Tp = 1 carries no history; the buffers keep one piece
+    const int nq = kTunerPhases * U;
+    s.j0.resize(nq);
+    s.j1.resize(nq);
+    for (int q = 0; q < nq; q++) {
+        const int off = 2 * (q * D / U);
+        s.j0[q] = (s.front + off - 2 * (s.Tp - 1)) / 64;
+        s.j1[q] = (s.front + off + 1) / 64 + 1;
+        s.ksp = std::max(s.ksp, s.j1[q] - s.j0[q]);
+    }
+    s.ks = s.j1[nq - 1];
+    return s;
+}
+inline size_t tuner_rat_group_image_bytes(const TunerRatShape &s) { return static_cast<size_t>(kTunerPhases) * s.U * s.ksp * 64 * 16; }
+
+// One channel's rows of its group's A-operand image: [image q][K-step - j0[q]][lane][16 bytes], rows and lanes as in
+// tuner_fill_image; re, im phase-major [U * Tp].
+inline void tuner_fill_image_rational(int8_t *img, const TunerRatShape &sh, int ch_in_group, const int16_t *re, const int16_t *im)
+{
+    const int nq = kTunerPhases * sh.U;
+    for (int q = 0; q < nq; q++) {
+        const int16_t *pre = re + static_cast<size_t>(q * sh.D % sh.U) * sh.Tp, *pim = im + static_cast<size_t>(q * sh.D % sh.U) * sh.Tp;
+        const int off = 2 * (q * sh.D / sh.U);
+        for (int jr = 0; jr < sh.ksp; jr++)
+            for (int part = 0; part < 2; part++)
+                for (int d = 0; d < kTunerDigits; d++) {
+                    const int row = 4 * ch_in_group + 2 * part + d;
+                    for (int g = 0; g < 4; g++) {
+                        int8_t *dst = img + ((static_cast<size_t>(q) * sh.ksp + jr) * 64 + (16 * g + row)) * 16;
+                        for (int b = 0; b < 16; b++) {
+                            const int u = 64 * (sh.j0[q] + jr) + 16 * g + b;
+                            const int c = u & 1;
+                            const int e = sh.front + off + c - u;            // = 2 j
+                            int8_t v = 0;
+                            if (e >= 0 && e / 2 <= sh.Tp - 1 && sh.j0[q] + jr < sh.j1[q]) {
+                                const int k = e / 2;
+                                const int t = part == 0 ? (c == 0 ? pre[k] : -pim[k]) : (c == 0 ? pim[k] : pre[k]);
+                                int8_t dig[2];
+                                tuner_digits(t, dig);
+                                v = dig[d];
+                            }
+                            dst[b] = v;
+                        }
+                    }
+                }
+    }
+}
+
 }  // namespace fmrx

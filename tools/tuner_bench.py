@@ -3,7 +3,7 @@ share of the chain capture -> tuner -> exact stereo bank -> RDS bank.
 
     python3 tools/tuner_bench.py [--channels 16,192,1024,4096] [--R 8] [--also-R 4,10,20] [--outputs 51200] [--calls 20]
                                  [--warmup 3] [--variant mfma|generic] [--format u8|s8|s16] [--chain 192] [--once N]
-                                 [--json out.json]
+                                 [--json out.json] [--ratio U/D [--taps T]]
 
 Per configuration (rf_Fs = 2.4 MS/s, Fs_w = R * rf_Fs, T = 8 R taps of tunerLowPass, channels on the 100 kHz raster; one call =
 `outputs` output samples per channel), from device events around every call after the warm-up, the median of `calls` calls:
@@ -17,7 +17,10 @@ Per configuration (rf_Fs = 2.4 MS/s, Fs_w = R * rf_Fs, T = 8 R taps of tunerLowP
 own pair of events on one stream, N channels.  --once N: a single configuration, `calls` calls and nothing else (for a
 counters-only profiler run around this script).  --format: the capture's format, for the tables, --chain and --once alike
 (s16: 4 bytes per wide sample in, two byte planes against the same operand image, so twice the matrix operations issued per
-output; the output bytes and the useful-operation count of the 8-bit formats are kept as the yardstick)."""
+output; the output bytes and the useful-operation count of the 8-bit formats are kept as the yardstick).
+--ratio U/D: a rational tuner (Tuner.rational, rf_Fs = 2.4 MS/s = Fs_w U / D, T = --taps or 8 D taps of tunerLowPassRational)
+instead of the integer one, for every N of --channels (or --once N): `outputs` is rounded down to a multiple of U, Tp =
+ceil(T / U) taps meet every output, so the useful operations are 16 Tp per channel output.  The integer path is unchanged."""
 from __future__ import annotations
 
 import argparse
@@ -98,6 +101,44 @@ def time_config(fmrx, torch, R, N, outputs, calls, warmup, fmt="u8"):
     return res
 
 
+def time_ratio(fmrx, torch, U, D, N, outputs, calls, warmup, fmt="u8", T=None):
+    """one rational configuration: as time_config, channels on the 100 kHz raster of the capture"""
+    outputs = outputs // U * U
+    n_wide = outputs // U * D
+    Fs_w = RF_FS * D / U
+    T = T or 8 * D
+    Tp = -(-T // U)
+    t = fmrx.Tuner.rational(U, D, fmrx.tunerLowPassRational(Fs_w, U, D, T), N, n_wide, fmt=fmt)
+    slots = int(Fs_w // 100e3) - 1
+    for c in range(N):
+        t.set_channel(c, ((c % slots) - slots // 2) * 100e3, Fs_w, 2.0)
+    pitch = (2 * outputs + 15) // 16 * 16
+    g = torch.Generator(device="cuda").manual_seed(D * 100003 + N)
+    d_wide = random_wide(torch, fmt, n_wide, -1.0, 1.0, g)
+    d_out = torch.zeros(N * pitch, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
+    with torch.cuda.stream(stream):
+        for _ in range(warmup):
+            t.process_dev(d_wide.data_ptr(), n_wide, d_out.data_ptr(), pitch, stream=stream.cuda_stream)
+        for a, b in ev:
+            a.record(stream)
+            t.process_dev(d_wide.data_ptr(), n_wide, d_out.data_ptr(), pitch, stream=stream.cuda_stream)
+            b.record(stream)
+    stream.synchronize()
+    ms = sorted(a.elapsed_time(b) for a, b in ev)
+    med = statistics.median(ms) * 1e-3
+    out_bytes = 2.0 * N * outputs
+    ops = 16.0 * Tp * N * outputs
+    res = dict(format=fmt, U=U, D=D, T=T, Tp=Tp, channels=N, outputs=outputs, n_wide=n_wide, calls=calls, ms_median=med * 1e3, ms_min=ms[0],
+               ms_max=ms[-1], wide_MS_s=n_wide / med / 1e6, signal_ms=outputs / RF_FS * 1e3, x_real_time=(outputs / RF_FS) / med,
+               out_GB_s=out_bytes / med / 1e9, ns_per_out_byte=med * 1e9 / out_bytes, int8_Top_s=ops / med / 1e12)
+    t.close()
+    del d_wide, d_out
+    return res
+
+
 def time_chain(fmrx, torch, N, calls, warmup, fmt="u8"):
     R, bb = 8, 192000
     outputs = bb // 2
@@ -151,6 +192,8 @@ def main() -> int:
     ap.add_argument("--chain", type=int, default=192)
     ap.add_argument("--once", type=int, default=0)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--ratio", default=None, help="U/D: a rational tuner, e.g. 6/25 for a 10 MS/s capture")
+    ap.add_argument("--taps", type=int, default=0, help="with --ratio: prototype taps (default 8 D)")
     a = ap.parse_args()
     fmrx = importlib.import_module("software-defined-radio_amd")
     import torch
@@ -159,6 +202,20 @@ def main() -> int:
         return 1
     fmrx.set_option("tuner_variant", a.variant)
     out = {"version": fmrx.version(), "variant": a.variant, "format": a.format, "configs": []}
+    if a.ratio:
+        U, D = (int(v) for v in a.ratio.split("/"))
+        for N in ([a.once] if a.once else [int(n) for n in a.channels.split(",") if n]):
+            r = time_ratio(fmrx, torch, U, D, N, a.outputs, a.calls, a.warmup, a.format, a.taps or None)
+            out["configs"].append(r)
+            print(f"{a.format:>3s} {a.variant:>7s} {U}/{D} T={r['T']} (Tp={r['Tp']}) N={N:5d}, {r['outputs']} outputs = {r['signal_ms']:.2f} ms of signal: "
+                  f"{r['ms_median']:8.4f} ms/call (min {r['ms_min']:.4f}, max {r['ms_max']:.4f}), {r['x_real_time']:8.1f} x real time, "
+                  f"{r['wide_MS_s']:9.0f} wide MS/s, out {r['out_GB_s']:7.1f} GB/s, {r['ns_per_out_byte']:.4f} ns per output byte, "
+                  f"int8 {r['int8_Top_s']:.1f} Top/s useful", flush=True)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return 0
     if a.once:
         configs = [(a.R, a.once)]
     else:
