@@ -701,7 +701,7 @@ FMRX_API int fmrx_tuner_create_ex(fmrx_tuner **out, int R, const float *h, int t
  * largest call, a multiple of D.  FMRX_EINVAL (the message names the argument) for gcd(U, D) != 1, U or D out of range,
  * D < 2 U, an unknown format.  Every other call works on the handle as on an integer one; calls take n_wide % D == 0.
  * The matrix kernels run for U <= 24, D <= 125, ceil(taps / U) <= 256, the generic kernel otherwise and under
- * "tuner_variant" = 1.  U = 1, D = R <= 32 builds the handle of fmrx_tuner_create_ex(R). */
+ * "tuner_variant" = 1.  U = 1, D = R <= 32 is the handle of fmrx_tuner_create_ex(R): one host path builds every rate. */
 FMRX_API int fmrx_tuner_create_rational(fmrx_tuner **out, int U, int D, const float *h, int taps, int n_channels,
                                         size_t max_wide_samples, int format, int device);
 FMRX_API int fmrx_tuner_ratio(const fmrx_tuner *t, int *U, int *D);   /* (1, R) for a handle of fmrx_tuner_create / _create_ex */

@@ -1024,33 +1024,26 @@ class Tuner:
     a device with 12 or 14 bits in the low end of the short takes a gain of 16 or 4)."""
 
     def __init__(self, R, h, n_channels, max_wide_samples, device=0, fmt="u8"):
-        if fmt not in TUNER_FORMATS:
-            raise ValueError(f"Tuner: fmt {fmt!r}: one of {', '.join(TUNER_FORMATS)}")
-        self.R, self.n_channels, self.max_wide_samples, self.fmt = int(R), int(n_channels), int(max_wide_samples), fmt
-        self.h = _f32(h)
-        self._h = _vp()
-        _check(lib.fmrx_tuner_create_ex(C.byref(self._h), self.R, self.h, len(self.h), self.n_channels, self.max_wide_samples,
-                                        TUNER_FORMATS[fmt], device))
-        self.sample_bytes = int(lib.fmrx_tuner_sample_bytes(self._h))       # per complex wide sample: 2, 2 or 4
-        self.U, self.D = 1, self.R
+        self._open(lib.fmrx_tuner_create_ex, (int(R),), 1, int(R), h, n_channels, max_wide_samples, device, fmt)
 
     @classmethod
     def rational(cls, U, D, h, n_channels, max_wide_samples, device=0, fmt="u8"):
         """A Tuner at rf_Fs = Fs_w * U / D (gcd 1, 1 <= U <= 32, 2 U <= D <= 512): h is the prototype low-pass at U * Fs_w
         (tunerLowPassRational), calls take a multiple of D wide samples and give n_wide * U / D outputs per channel
         (fmrx_tuner_create_rational).  .U and .D hold the ratio; .R is D for U = 1, else None."""
+        self = cls.__new__(cls)
+        self._open(lib.fmrx_tuner_create_rational, (int(U), int(D)), int(U), int(D), h, n_channels, max_wide_samples, device, fmt)
+        return self
+
+    def _open(self, create, rate_args, U, D, h, n_channels, max_wide_samples, device, fmt):
         if fmt not in TUNER_FORMATS:
             raise ValueError(f"Tuner: fmt {fmt!r}: one of {', '.join(TUNER_FORMATS)}")
-        self = cls.__new__(cls)
-        self.U, self.D = int(U), int(D)
-        self.R = self.D if self.U == 1 else None
+        self.U, self.D, self.R = U, D, D if U == 1 else None
         self.n_channels, self.max_wide_samples, self.fmt = int(n_channels), int(max_wide_samples), fmt
         self.h = _f32(h)
         self._h = _vp()
-        _check(lib.fmrx_tuner_create_rational(C.byref(self._h), self.U, self.D, self.h, len(self.h), self.n_channels, self.max_wide_samples,
-                                              TUNER_FORMATS[fmt], device))
-        self.sample_bytes = int(lib.fmrx_tuner_sample_bytes(self._h))
-        return self
+        _check(create(C.byref(self._h), *rate_args, self.h, len(self.h), self.n_channels, self.max_wide_samples, TUNER_FORMATS[fmt], device))
+        self.sample_bytes = int(lib.fmrx_tuner_sample_bytes(self._h))       # per complex wide sample: 2, 2 or 4
 
     def ratio(self):
         """(U, D) as the handle reports it: (1, R) for an integer tuner"""
@@ -1072,12 +1065,8 @@ class Tuner:
 
     @staticmethod
     def design(h, Fs_w, f_c, gain=1.0):
-        """Host only: (frequency word, scale exponent s, re int16[T], im int16[T]) of one channel."""
-        h = _f32(h)
-        w, s = C.c_uint32(0), _int(0)
-        re, im = np.zeros(len(h), np.int16), np.zeros(len(h), np.int16)
-        _check(lib.fmrx_tuner_design(h, len(h), Fs_w, f_c, gain, C.byref(w), C.byref(s), re, im))
-        return w.value, s.value, re, im
+        """Host only: (frequency word, scale exponent s, re int16[T], im int16[T]) of one channel of an integer tuner."""
+        return Tuner.design_rational(h, 1, Fs_w, f_c, gain)
 
     @staticmethod
     def table():

@@ -358,59 +358,39 @@ struct Filters {
 };
 Filters design_filters(const fmrx_params &p, bool stereo);
 
-// ---- wideband tuner (kernels_tuner.hip; handle and C ABI in tuner.hip) -----------------
-// One call's launch: the FIR + rotation kernel (matrix-core or generic) and the kernel that carries the history.
+// ---- wideband tuner (kernels_tuner.hip, kernels_tuner_rational.hip; handle and C ABI in tuner.hip) -----------------
+// One call's launch at the rate U / D: the FIR + rotation kernel (matrix-core or generic) and the kernel that carries the
+// history.  The integer tuner is U = 1, D <= 32 (tuner_integer_rate, tuner_host.hpp).
 struct TunerLaunch {
     bool mfma = true;
     int format = 0;                      // kTunerU8 / kTunerS8 / kTunerS16 (tuner_host.hpp): a value is 1, 1 or 2 raw bytes
+    int tiles = 1;                       // matrix kernel: tiles per wave and step (tuner_plan)
+    bool via_lds = false;                // matrix kernel: a step's outputs go through an LDS buffer to whole-row stores
     const uint8_t *x = nullptr;          // this call's wide samples, raw (matrix kernel: 16-byte aligned)
-    long n_bytes = 0;                    // 2 * n_wide: the call's I and Q values (the raw bytes of the 8-bit formats)
+    long n_bytes = 0;                    // 2 * n_wide: the call's I and Q values (the raw bytes of the 8-bit formats); n_wide a multiple of D
     const uint8_t *hist = nullptr;       // `front` values in front of the call, raw, 16-byte aligned
     uint8_t *hist_next = nullptr;        // receives the history the next call starts from
-    const int8_t *a_img = nullptr;       // matrix kernel: operand image [group][phase][ksp][64 lanes][16]
-    const int16_t *taps_re = nullptr, *taps_im = nullptr;   // generic kernel: [n_channels][T]
+    const int8_t *a_img = nullptr;       // matrix kernel: operand image [group][image q < 8 U][ksp][64 lanes][16]
+    const int16_t *taps_re = nullptr, *taps_im = nullptr;   // generic kernel: [n_channels][U * Tp], phase-major
     const uint2 *chan = nullptr;         // per channel {frequency word, output shift s + 15 + B}
-    const int2 *kconst = nullptr;        // 16-bit matrix kernel: per channel 128 * {sum(re - im), sum(im + re)}, what the low plane's
-                                         //   offset of 128 adds to acc
+    const int2 *kconst = nullptr;        // 16-bit matrix kernel: [n_channels][U], per phase 128 * {sum(re - im), sum(im + re)}, what the
+                                         //   low plane's offset of 128 adds to acc
     const unsigned *table = nullptr;     // rotation table, cos | sin << 16
     uint8_t *out = nullptr;
     long pitch = 0;
-    int n_channels = 0, R = 0, T = 0, front = 0, ks = 0, ksp = 0;
+    int n_channels = 0, U = 1, D = 2, Tp = 0, front = 0, ks = 0, ksp = 0;
     unsigned n0 = 0;                     // wide-sample index of the call's first sample, mod 2^32
     unsigned long long *levels = nullptr;   // [n_channels][2] = {clipped, power}, zeroed by the caller
 };
-size_t tuner_mfma_lds_bytes(int R, int ks, int format);
-int tuner_launch(const TunerLaunch &a, hipStream_t stream);
-// the kernel that carries the history: the last front_bytes raw bytes of (old history | this call's n_raw_bytes of input)
-int tuner_hist_launch(const uint8_t *x, long n_raw_bytes, const uint8_t *hist, uint8_t *hist_next, int front_bytes, hipStream_t stream);
-
-// The same at a rational rate U / D (kernels_tuner_rational.hip): pointers and levels as in TunerLaunch.
-struct TunerRatLaunch {
-    bool mfma = true;
-    int format = 0, tiles = 1;           // tiles: the matrix kernel's tiles per wave and step (tuner_rat_plan)
-    bool via_lds = false;                // matrix kernel: a step's outputs go through an LDS buffer to whole-row stores
-    const uint8_t *x = nullptr;
-    long n_bytes = 0;                    // 2 * n_wide, n_wide a multiple of D
-    const uint8_t *hist = nullptr;
-    uint8_t *hist_next = nullptr;
-    const int8_t *a_img = nullptr;       // matrix kernel: operand image [group][image q < 8 U][ksp][64 lanes][16]
-    const int16_t *taps_re = nullptr, *taps_im = nullptr;   // generic kernel: [n_channels][U * Tp], phase-major
-    const uint2 *chan = nullptr;
-    const int2 *kconst = nullptr;        // 16-bit matrix kernel: [n_channels][U], the constant of each phase
-    const unsigned *table = nullptr;
-    uint8_t *out = nullptr;
-    long pitch = 0;
-    int n_channels = 0, U = 1, D = 2, Tp = 0, front = 0, ks = 0, ksp = 0;
-    unsigned n0 = 0;
-    unsigned long long *levels = nullptr;
-};
-struct TunerRatPlan {
+struct TunerPlan {
     int tiles;                           // 4, 2, 1, or 0 where the window does not fit the matrix kernel
     bool via_lds;
 };
-size_t tuner_rat_lds_bytes(int U, int D, int ks, int format, int tiles, bool via_lds);
-TunerRatPlan tuner_rat_plan(int U, int D, int ks, int format);
-int tuner_rat_launch(const TunerRatLaunch &a, hipStream_t stream);
+// what the matrix kernel of this rate and format runs with (its LDS: tuner_lds_bytes, tuner_host.hpp)
+TunerPlan tuner_plan(int U, int D, int ks, int format);
+int tuner_launch(const TunerLaunch &a, hipStream_t stream);
+// tuner_launch's matrix-kernel launch outside the integer rates (kernels_tuner_rational.hip)
+int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, int n_steps, int steps_per_wg, dim3 grid, size_t lds, hipStream_t stream);
 
 // ---- signal meters (kernels_meters.hip; handle, host arithmetic and C ABI in meters.hip) -----------------
 constexpr int kMetersSegment = FMRX_METERS_SEGMENT, kMetersProbes = FMRX_METERS_PROBES;

@@ -1,5 +1,5 @@
-// kernels_tuner.hip -- the wideband tuner's kernels: N channels' frequency-translating decimating FIRs on ONE wide capture
-// (include/fmrx.h: fmrx_tuner_*; arithmetic defined by tests/_tuner_model.py).
+// kernels_tuner.hip -- the wideband tuner's kernels and their launch: N channels' frequency-translating decimating FIRs on ONE
+// wide capture (include/fmrx.h: fmrx_tuner_*; arithmetic defined by tests/_tuner_model.py).
 //
 //   y_c[m] = Q( e^{-j phi_c(mR)} * sum_k taps_c[k] * x[mR - k] ),   x = (u8 - 128) as complex, taps_c complex int16
 //
@@ -22,8 +22,14 @@
 // plus the filter's reach) is staged once in LDS and shared by the four groups; the rotation table sits in LDS beside it.
 // The stage is padded by 16 bytes per 16 R (the column stride) so that the 16 columns of a B read spread over the banks.
 //
-// The generic kernel (tuner_generic_kernel): one thread per (channel, output), integer loops over the taps; any T, the
-// second device implementation the tests compare with the model (option tuner_variant = 1 / FMRX_TUNER_VARIANT=generic).
+// These matrix kernels are the integer tuner's: U = 1, D = R <= 32, compiled for kTT / kTT16 tiles per wave.  Every other rate
+// U / D runs the templated ones of kernels_tuner_rational.hip; tuner_launch below, the one entry point, sends a call to either
+// or to the generic kernel, and then launches tuner_hist_kernel, which carries the stream's last `front` values to the next call.
+//
+// The generic kernel (tuner_generic_kernel), for every rate: one thread per (channel, output), integer loops over the Tp taps
+// of the output's phase p_m = m D mod U against the samples from n_m = floor(m D / U) back (U = 1: all T taps from m R back);
+// any T, U <= 32, D <= 512 -- the second device implementation the tests compare with the models (option tuner_variant = 1 /
+// FMRX_TUNER_VARIANT=generic), and what runs outside the matrix kernels' range.
 //
 // Input formats (tuner_host.hpp; tests/_tuner_formats_model.py).  Signed 8-bit: the same two kernels without the XOR and
 // with 0x00 as the zero sample (tuner_mfma_s8_kernel, tuner_generic_s8_kernel).  Signed 16-bit (tuner_mfma_s16_kernel): the
@@ -374,12 +380,12 @@ __global__ __launch_bounds__(256, 2) void tuner_mfma_s16_kernel(
 }
 
 // FMT: kTunerU8 / kTunerS8 / kTunerS16.  x, hist: raw values (bytes, or little-endian int16 for S16); the 16-bit format's sums
-// need 64 bits (|acc| < 2^40), the 8-bit formats' fit int32 as before.
+// need 64 bits (|acc| < 2^40), the 8-bit formats' fit int32.  taps_re, taps_im: [n_channels][U * Tp] phase-major.
 template <int FMT>
 __device__ __forceinline__ void tuner_generic_body(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, const int16_t *__restrict__ taps_re,
     const int16_t *__restrict__ taps_im, const uint2 *__restrict__ chan, const unsigned *__restrict__ table,
-    uint8_t *__restrict__ out, long pitch, long n_out, int R, int T, int front, unsigned n0, unsigned long long *__restrict__ levels)
+    uint8_t *__restrict__ out, long pitch, long n_out, int U, int D, int Tp, int front, unsigned n0, unsigned long long *__restrict__ levels)
 {
     using value_t = std::conditional_t<FMT == kTunerS16, int16_t, std::conditional_t<FMT == kTunerS8, int8_t, uint8_t>>;
     using acc_t = std::conditional_t<FMT == kTunerS16, long long, int>;
@@ -390,18 +396,25 @@ __device__ __forceinline__ void tuner_generic_body(
     unsigned clipped = 0;
     unsigned long long power = 0;
     if (m < n_out) {
-        const int16_t *re = taps_re + static_cast<long>(ch) * T, *im = taps_im + static_cast<long>(ch) * T;
+        long nm = m * D;                                            // the output's newest sample and its phase
+        int p = 0;
+        if (U != 1) {                                               // wave-uniform: the integer tuner skips the 64-bit division
+            const long md = nm;
+            nm = md / U;
+            p = static_cast<int>(md - nm * U);
+        }
+        const int16_t *re = taps_re + (static_cast<long>(ch) * U + p) * Tp, *im = taps_im + (static_cast<long>(ch) * U + p) * Tp;
         acc_t ar = 0, ai = 0;
-        for (int k = 0; k < T; k++) {
-            const long pos = 2 * (m * R - k);
+        for (int j = 0; j < Tp; j++) {
+            const long pos = 2 * (nm - j);
             const value_t *src = pos < 0 ? hv + front + pos : xv + pos;
             const int xr = static_cast<int>(src[0]) - kBias, xq = static_cast<int>(src[1]) - kBias;
-            const int gr = re[k], gi = im[k];
+            const int gr = re[j], gi = im[j];
             ar += static_cast<acc_t>(gr * xr) - gi * xq;            // a product is below 2^30, a difference of two is not
             ai += static_cast<acc_t>(gi * xr) + gr * xq;
         }
         const uint2 cp = chan[ch];
-        const unsigned ph = cp.x * (n0 + static_cast<unsigned>(m) * static_cast<unsigned>(R));
+        const unsigned ph = cp.x * (n0 + static_cast<unsigned>(nm));
         const Rot r = rot_of(table[ph >> (32 - kTunerTableBits)]);
         const long long yr = static_cast<long long>(ar) * r.c + static_cast<long long>(ai) * r.s;
         const long long yi = static_cast<long long>(ai) * r.c - static_cast<long long>(ar) * r.s;
@@ -419,13 +432,13 @@ __device__ __forceinline__ void tuner_generic_body(
     }
 }
 
-#define FMRX_TUNER_GENERIC(NAME, FMT)                                                                                                        \
+#define FMRX_TUNER_GENERIC(NAME, FMT)                                                                                                    \
     __global__ __launch_bounds__(256) void NAME(                                                                                             \
         const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, const int16_t *__restrict__ taps_re,                                \
         const int16_t *__restrict__ taps_im, const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, \
-        long pitch, long n_out, int R, int T, int front, unsigned n0, unsigned long long *__restrict__ levels)                               \
+        long pitch, long n_out, int U, int D, int Tp, int front, unsigned n0, unsigned long long *__restrict__ levels)                       \
     {                                                                                                                                        \
-        tuner_generic_body<FMT>(x, hist, taps_re, taps_im, chan, table, out, pitch, n_out, R, T, front, n0, levels);                         \
+        tuner_generic_body<FMT>(x, hist, taps_re, taps_im, chan, table, out, pitch, n_out, U, D, Tp, front, n0, levels);                 \
     }
 FMRX_TUNER_GENERIC(tuner_generic_kernel, kTunerU8)
 FMRX_TUNER_GENERIC(tuner_generic_s8_kernel, kTunerS8)
@@ -442,52 +455,61 @@ __global__ __launch_bounds__(256) void tuner_hist_kernel(const uint8_t *__restri
     new_hist[i] = pos < 0 ? old_hist[front + pos] : x[pos];
 }
 
+constexpr size_t kTwoPerCu = 64 * 1024, kOnePerCu = 160 * 1024;     // LDS of a workgroup: two on a CU, or one
+
 }  // namespace
 
-size_t tuner_mfma_lds_bytes(int R, int ks, int format)
+// Tiles per wave and step, and whether the outputs go through the LDS buffer.  The integer kernels are compiled for kTT / kTT16
+// tiles and store directly.  The rational ones, in order of preference: the buffer with the most tiles that keep two workgroups
+// on a CU; the buffer with one tile and one workgroup per CU; direct stores, by the same two rules.  tiles = 0: the window does
+// not fit the matrix kernel at all.
+TunerPlan tuner_plan(int U, int D, int ks, int format)
 {
-    const int tiles = format == kTunerS16 ? kTT16 : kTT, planes = format == kTunerS16 ? 2 : 1;
-    const int n_pieces = 16 * tiles * R + 4 * ks;
-    return static_cast<size_t>(kTunerTableSize) * 4 + 16u * planes * (n_pieces + n_pieces / R + 1);
+    if (tuner_integer_rate(U, D)) return {format == kTunerS16 ? kTT16 : kTT, false};
+    for (int via = 1; via >= 0; via--) {
+        for (int tiles = format == kTunerS16 ? 2 : 4; tiles >= 1; tiles >>= 1)
+            if (tuner_lds_bytes(U, D, ks, format, tiles, via) <= kTwoPerCu) return {tiles, via != 0};
+        if (tuner_lds_bytes(U, D, ks, format, 1, via) <= kOnePerCu) return {1, via != 0};
+    }
+    return {0, false};
 }
 
 int tuner_launch(const TunerLaunch &a, hipStream_t stream)
 {
-    const long n_out = a.n_bytes / (2L * a.R);
+    const long n_out = a.n_bytes / 2 / a.D * a.U;
     const int vb = tuner_value_bytes(a.format);
     if (n_out > 0) {
         if (a.mfma) {
-            const int step_out = a.format == kTunerS16 ? kStepOut16 : kStepOut;
-            const int n_steps = static_cast<int>((n_out + step_out - 1) / step_out);
+            const long cols = (n_out + kTunerPhases * a.U - 1) / (kTunerPhases * a.U);
+            const int n_steps = static_cast<int>((cols + 16 * a.tiles - 1) / (16 * a.tiles));
             const int gy = (a.n_channels + 4 * kTunerGroup - 1) / (4 * kTunerGroup);
             // enough workgroups to fill the chip a few times over, as many steps each as that leaves (the table is loaded once
             // per workgroup)
             int per = static_cast<int>((static_cast<long>(n_steps) * gy + 2047) / 2048);
             if (per < 1) per = 1;
             const int gx = (n_steps + per - 1) / per;
-            const size_t lds = tuner_mfma_lds_bytes(a.R, a.ks, a.format);
-            if (a.format == kTunerS16) {
+            const size_t lds = tuner_lds_bytes(a.U, a.D, a.ks, a.format, a.tiles, a.via_lds);
+            if (!tuner_integer_rate(a.U, a.D)) {
+                FMRX_TRY(tuner_rat_mfma_launch(a, n_out, n_steps, per, dim3(gx, gy), lds, stream));
+            } else if (a.format == kTunerS16) {
                 hipLaunchKernelGGL(tuner_mfma_s16_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x, a.hist, a.n_bytes,
-                                   reinterpret_cast<const i4 *>(a.a_img), a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels, n_out, a.R,
-                                   a.T, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+                                   reinterpret_cast<const i4 *>(a.a_img), a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels, n_out, a.D,
+                                   a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
             } else {
                 hipLaunchKernelGGL(a.format == kTunerS8 ? tuner_mfma_s8_kernel : tuner_mfma_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x,
                                    a.hist, a.n_bytes, reinterpret_cast<const i4 *>(a.a_img), a.chan, a.table, a.out, a.pitch, a.n_channels,
-                                   n_out, a.R, a.T, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+                                   n_out, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
             }
         } else {
             const auto kernel = a.format == kTunerS16 ? tuner_generic_s16_kernel : a.format == kTunerS8 ? tuner_generic_s8_kernel : tuner_generic_kernel;
             hipLaunchKernelGGL(kernel, dim3(a.n_channels, static_cast<unsigned>((n_out + 255) / 256)), dim3(256), 0, stream, a.x, a.hist,
-                               a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.R, a.T, a.front, a.n0, a.levels);
+                               a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.U, a.D, a.Tp, a.front, a.n0, a.levels);
         }
-        FMRX_LAUNCH_CHECK("tuner_%s_kernel (format %d)", a.mfma ? "mfma" : "generic", a.format);
+        FMRX_LAUNCH_CHECK("tuner_%s_kernel (format %d, %d/%d)", a.mfma ? "mfma" : "generic", a.format, a.U, a.D);
     }
-    return tuner_hist_launch(a.x, a.n_bytes * vb, a.hist, a.hist_next, a.front * vb, stream);
-}
-
-int tuner_hist_launch(const uint8_t *x, long n_raw_bytes, const uint8_t *hist, uint8_t *hist_next, int front_bytes, hipStream_t stream)
-{
-    hipLaunchKernelGGL(tuner_hist_kernel, dim3((front_bytes + 255) / 256), dim3(256), 0, stream, x, n_raw_bytes, hist, hist_next, front_bytes);
+    const int front_bytes = a.front * vb;
+    hipLaunchKernelGGL(tuner_hist_kernel, dim3((front_bytes + 255) / 256), dim3(256), 0, stream, a.x, a.n_bytes * vb, a.hist, a.hist_next,
+                       front_bytes);
     FMRX_LAUNCH_CHECK("tuner_hist_kernel");
     return FMRX_OK;
 }

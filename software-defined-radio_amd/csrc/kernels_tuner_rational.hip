@@ -1,5 +1,5 @@
-// kernels_tuner_rational.hip -- the wideband tuner at a rational rate rf_Fs = Fs_w * U / D: N channels' polyphase
-// frequency-translating FIRs on ONE wide capture (include/fmrx.h: fmrx_tuner_create_rational; DESIGN.md section 4.9.2;
+// kernels_tuner_rational.hip -- the wideband tuner's matrix kernels at a rational rate rf_Fs = Fs_w * U / D: N channels'
+// polyphase frequency-translating FIRs on ONE wide capture (include/fmrx.h: fmrx_tuner_create_rational; DESIGN.md section 4.9.2;
 // arithmetic defined by tests/_tuner_rational_model.py).  For output m of the stream, n_m = floor(m D / U), p_m = m D mod U:
 //
 //   y_c[m] = Q( e^{-j phi_c(n_m)} * sum_{j<Tp} taps_c[p_m][j] * x[n_m - j] ),   taps_c complex int16, phase-major [U][Tp]
@@ -28,13 +28,12 @@
 // per tile plus the reach, keeps two workgroups on a CU.  The 16-bit kernel stages two byte planes as tuner_mfma_s16_kernel
 // does; its constant 128 (row sum of the taps) is a pair per PHASE, U pairs per channel.
 //
-// The generic kernels (tuner_rat_generic_kernel, _s8_, _s16_): one thread per (channel, output), integer loops over the Tp
-// taps of the output's phase; any T, U <= 32, D <= 512 -- the second device implementation the tests compare with the model.
+// Launched by tuner_launch (kernels_tuner.hip) through tuner_rat_mfma_launch for every rate outside the integer tuner's
+// (U = 1, D <= 32), with the tiles and the output path tuner_plan chose.  The generic kernels and the history kernel, one set
+// for all rates, are in kernels_tuner.hip.
 #include "fmrx_internal.hpp"
 #include "tuner_host.hpp"
 #include "tuner_kernels.hpp"
-
-#include <type_traits>
 
 namespace fmrx {
 namespace {
@@ -444,67 +443,7 @@ __global__ __launch_bounds__(256, 2) void tuner_rat_mfma_s16_kernel(
     tuner_add_levels(clipped, power, ch_ok && col == 0, levels + 2 * ch);
 }
 
-// FMT: kTunerU8 / kTunerS8 / kTunerS16.  taps_re, taps_im: [n_channels][U * Tp] phase-major.
-template <int FMT>
-__device__ __forceinline__ void tuner_rat_generic_body(
-    const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, const int16_t *__restrict__ taps_re,
-    const int16_t *__restrict__ taps_im, const uint2 *__restrict__ chan, const unsigned *__restrict__ table,
-    uint8_t *__restrict__ out, long pitch, long n_out, int U, int D, int Tp, int front, unsigned n0, unsigned long long *__restrict__ levels)
-{
-    using value_t = std::conditional_t<FMT == kTunerS16, int16_t, std::conditional_t<FMT == kTunerS8, int8_t, uint8_t>>;
-    using acc_t = std::conditional_t<FMT == kTunerS16, long long, int>;
-    constexpr int kBias = FMT == kTunerU8 ? 128 : 0;
-    const value_t *xv = reinterpret_cast<const value_t *>(x), *hv = reinterpret_cast<const value_t *>(hist);
-    const int ch = blockIdx.x;
-    const long m = static_cast<long>(blockIdx.y) * 256 + threadIdx.x;
-    unsigned clipped = 0;
-    unsigned long long power = 0;
-    if (m < n_out) {
-        const long md = m * D, nm = md / U;                         // the output's newest sample and its phase
-        const int p = static_cast<int>(md - nm * U);
-        const int16_t *re = taps_re + (static_cast<long>(ch) * U + p) * Tp, *im = taps_im + (static_cast<long>(ch) * U + p) * Tp;
-        acc_t ar = 0, ai = 0;
-        for (int j = 0; j < Tp; j++) {
-            const long pos = 2 * (nm - j);
-            const value_t *src = pos < 0 ? hv + front + pos : xv + pos;
-            const int xr = static_cast<int>(src[0]) - kBias, xq = static_cast<int>(src[1]) - kBias;
-            const int gr = re[j], gi = im[j];
-            ar += static_cast<acc_t>(gr * xr) - gi * xq;            // a product is below 2^30, a difference of two is not
-            ai += static_cast<acc_t>(gi * xr) + gr * xq;
-        }
-        const uint2 cp = chan[ch];
-        const unsigned ph = cp.x * (n0 + static_cast<unsigned>(nm));
-        const Rot r = rot_of(table[ph >> (32 - kTunerTableBits)]);
-        const long long yr = static_cast<long long>(ar) * r.c + static_cast<long long>(ai) * r.s;
-        const long long yi = static_cast<long long>(ai) * r.c - static_cast<long long>(ar) * r.s;
-        const unsigned pr = tuner_round_y(yr, yi, static_cast<int>(cp.y), clipped, power);
-        *reinterpret_cast<unsigned short *>(out + static_cast<long>(ch) * pitch + 2 * m) = static_cast<unsigned short>(pr);
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        clipped += __shfl_xor(clipped, o);
-        power += __shfl_xor(power, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (clipped) atomicAdd(levels + 2 * ch, static_cast<unsigned long long>(clipped));
-        if (power) atomicAdd(levels + 2 * ch + 1, power);
-    }
-}
-
-#define FMRX_TUNER_RAT_GENERIC(NAME, FMT)                                                                                                    \
-    __global__ __launch_bounds__(256) void NAME(                                                                                             \
-        const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, const int16_t *__restrict__ taps_re,                                \
-        const int16_t *__restrict__ taps_im, const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, \
-        long pitch, long n_out, int U, int D, int Tp, int front, unsigned n0, unsigned long long *__restrict__ levels)                       \
-    {                                                                                                                                        \
-        tuner_rat_generic_body<FMT>(x, hist, taps_re, taps_im, chan, table, out, pitch, n_out, U, D, Tp, front, n0, levels);                 \
-    }
-FMRX_TUNER_RAT_GENERIC(tuner_rat_generic_kernel, kTunerU8)
-FMRX_TUNER_RAT_GENERIC(tuner_rat_generic_s8_kernel, kTunerS8)
-FMRX_TUNER_RAT_GENERIC(tuner_rat_generic_s16_kernel, kTunerS16)
-#undef FMRX_TUNER_RAT_GENERIC
-
-constexpr size_t kTwoPerCu = 64 * 1024, kOnePerCu = 160 * 1024;     // LDS of a workgroup: two on a CU, or one
+constexpr size_t kTwoPerCu = 64 * 1024;     // the LDS a kernel may ask for without the attribute
 
 template <typename K>
 int rat_lds_attr(K kernel, size_t lds)
@@ -516,85 +455,45 @@ int rat_lds_attr(K kernel, size_t lds)
 
 }  // namespace
 
-size_t tuner_rat_lds_bytes(int U, int D, int ks, int format, int tiles, bool via_lds)
+int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, int n_steps, int steps_per_wg, dim3 grid, size_t lds, hipStream_t stream)
 {
-    const int planes = format == kTunerS16 ? 2 : 1;
-    const int n_pieces = 16 * tiles * D + 4 * ks;
-    return static_cast<size_t>(kTunerTableSize) * 4 + 16u * planes * (n_pieces + n_pieces / D + 1) +
-           (via_lds ? static_cast<size_t>(4) * tiles * 4 * 256 * U : 0);
-}
-
-// Tiles per wave and step, and whether the outputs go through the LDS buffer.  In order of preference: the buffer with the
-// most tiles that keep two workgroups on a CU; the buffer with one tile and one workgroup per CU; direct stores, by the same
-// two rules.  tiles = 0: the window does not fit the matrix kernel at all.
-TunerRatPlan tuner_rat_plan(int U, int D, int ks, int format)
-{
-    for (int via = 1; via >= 0; via--) {
-        for (int tiles = format == kTunerS16 ? 2 : 4; tiles >= 1; tiles >>= 1)
-            if (tuner_rat_lds_bytes(U, D, ks, format, tiles, via) <= kTwoPerCu) return {tiles, via != 0};
-        if (tuner_rat_lds_bytes(U, D, ks, format, 1, via) <= kOnePerCu) return {1, via != 0};
+    const i4 *img = reinterpret_cast<const i4 *>(a.a_img);
+#define FMRX_RAT_8(KERNEL)                                                                                                             \
+    do {                                                                                                                               \
+        FMRX_TRY(rat_lds_attr(KERNEL, lds));                                                                                           \
+        hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.table, a.out, a.pitch,         \
+                           a.n_channels, n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, a.via_lds, a.levels); \
+    } while (0)
+#define FMRX_RAT_16(KERNEL)                                                                                                            \
+    do {                                                                                                                               \
+        FMRX_TRY(rat_lds_attr(KERNEL, lds));                                                                                           \
+        hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.kconst, a.table, a.out,        \
+                           a.pitch, a.n_channels, n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, a.via_lds, \
+                           a.levels);                                                                                                  \
+    } while (0)
+    if (a.format == kTunerS16) {
+        if (a.tiles == 2)
+            FMRX_RAT_16(tuner_rat_mfma_s16_kernel<2>);
+        else
+            FMRX_RAT_16(tuner_rat_mfma_s16_kernel<1>);
+    } else if (a.format == kTunerS8) {
+        if (a.tiles == 4)
+            FMRX_RAT_8(tuner_rat_mfma_s8_kernel<4>);
+        else if (a.tiles == 2)
+            FMRX_RAT_8(tuner_rat_mfma_s8_kernel<2>);
+        else
+            FMRX_RAT_8(tuner_rat_mfma_s8_kernel<1>);
+    } else {
+        if (a.tiles == 4)
+            FMRX_RAT_8(tuner_rat_mfma_kernel<4>);
+        else if (a.tiles == 2)
+            FMRX_RAT_8(tuner_rat_mfma_kernel<2>);
+        else
+            FMRX_RAT_8(tuner_rat_mfma_kernel<1>);
     }
-    return {0, false};
-}
-
-int tuner_rat_launch(const TunerRatLaunch &a, hipStream_t stream)
-{
-    const long n_out = a.n_bytes / 2 / a.D * a.U;
-    const int vb = tuner_value_bytes(a.format);
-    if (n_out > 0) {
-        if (a.mfma) {
-            const long cols = (n_out + kTunerPhases * a.U - 1) / (kTunerPhases * a.U);
-            const int n_steps = static_cast<int>((cols + 16 * a.tiles - 1) / (16 * a.tiles));
-            const int gy = (a.n_channels + 4 * kTunerGroup - 1) / (4 * kTunerGroup);
-            int per = static_cast<int>((static_cast<long>(n_steps) * gy + 2047) / 2048);
-            if (per < 1) per = 1;
-            const int gx = (n_steps + per - 1) / per;
-            const size_t lds = tuner_rat_lds_bytes(a.U, a.D, a.ks, a.format, a.tiles, a.via_lds);
-            const i4 *img = reinterpret_cast<const i4 *>(a.a_img);
-#define FMRX_RAT_8(KERNEL)                                                                                                                 \
-    do {                                                                                                                                   \
-        FMRX_TRY(rat_lds_attr(KERNEL, lds));                                                                                               \
-        hipLaunchKernelGGL(KERNEL, dim3(gx, gy), dim3(256), lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.table, a.out, a.pitch,     \
-                           a.n_channels, n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.via_lds, a.levels);            \
-    } while (0)
-#define FMRX_RAT_16(KERNEL)                                                                                                                \
-    do {                                                                                                                                   \
-        FMRX_TRY(rat_lds_attr(KERNEL, lds));                                                                                               \
-        hipLaunchKernelGGL(KERNEL, dim3(gx, gy), dim3(256), lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.kconst, a.table, a.out,    \
-                           a.pitch, a.n_channels, n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.via_lds, a.levels);   \
-    } while (0)
-            if (a.format == kTunerS16) {
-                if (a.tiles == 2)
-                    FMRX_RAT_16(tuner_rat_mfma_s16_kernel<2>);
-                else
-                    FMRX_RAT_16(tuner_rat_mfma_s16_kernel<1>);
-            } else if (a.format == kTunerS8) {
-                if (a.tiles == 4)
-                    FMRX_RAT_8(tuner_rat_mfma_s8_kernel<4>);
-                else if (a.tiles == 2)
-                    FMRX_RAT_8(tuner_rat_mfma_s8_kernel<2>);
-                else
-                    FMRX_RAT_8(tuner_rat_mfma_s8_kernel<1>);
-            } else {
-                if (a.tiles == 4)
-                    FMRX_RAT_8(tuner_rat_mfma_kernel<4>);
-                else if (a.tiles == 2)
-                    FMRX_RAT_8(tuner_rat_mfma_kernel<2>);
-                else
-                    FMRX_RAT_8(tuner_rat_mfma_kernel<1>);
-            }
 #undef FMRX_RAT_8
 #undef FMRX_RAT_16
-        } else {
-            const auto kernel = a.format == kTunerS16  ? tuner_rat_generic_s16_kernel
-                                : a.format == kTunerS8 ? tuner_rat_generic_s8_kernel
-                                                       : tuner_rat_generic_kernel;
-            hipLaunchKernelGGL(kernel, dim3(a.n_channels, static_cast<unsigned>((n_out + 255) / 256)), dim3(256), 0, stream, a.x, a.hist,
-                               a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.U, a.D, a.Tp, a.front, a.n0, a.levels);
-        }
-        FMRX_LAUNCH_CHECK("tuner_rat_%s_kernel (format %d, %d/%d)", a.mfma ? "mfma" : "generic", a.format, a.U, a.D);
-    }
-    return tuner_hist_launch(a.x, a.n_bytes * vb, a.hist, a.hist_next, a.front * vb, stream);
+    return FMRX_OK;
 }
 
 }  // namespace fmrx

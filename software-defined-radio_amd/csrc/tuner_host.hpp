@@ -1,7 +1,8 @@
-// tuner_host.hpp -- host-side (plain C++, no HIP) arithmetic of the wideband tuner (tuner.hip, kernels_tuner.hip):
-// frequency word, complex integer taps, the rotation table, and the matrix-core operand image of a channel group.
-// Header-only, like fe_mfma_host.hpp.  The arithmetic is DEFINED by tests/_tuner_model.py; this
-// file is the product's statement of it.
+// tuner_host.hpp -- host-side (plain C++, no HIP) arithmetic of the wideband tuner (tuner.hip, kernels_tuner.hip,
+// kernels_tuner_rational.hip): frequency word, complex integer taps per phase, the rotation table, and the matrix-core
+// operand image of a channel group.  One of each, for every rate U / D: the integer tuner is U = 1.
+// Header-only, like fe_mfma_host.hpp.  The arithmetic is DEFINED by tests/_tuner_model.py and, for U > 1,
+// tests/_tuner_rational_model.py (DESIGN.md sections 4.9 and 4.9.2); this file is the product's statement of it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -42,120 +43,10 @@ inline uint32_t tuner_freq_word(double f_c, double Fs_w)
     return static_cast<uint32_t>(static_cast<unsigned long long>(r) & 0xffffffffULL);
 }
 
-// error texts of tuner_design (nullptr = accepted)
-inline const char *tuner_design(const float *h, int T, double Fs_w, double f_c, double gain, uint32_t *w_out, int *s_out, int16_t *re,
-                                int16_t *im)
-{
-    if (!h || T < 2 || T > kTunerMaxTaps) return "taps: 2 .. 4096";
-    if (!(Fs_w > 0.0) || !std::isfinite(Fs_w)) return "Fs_w must be positive and finite";
-    if (!std::isfinite(f_c) || !(std::fabs(f_c) < Fs_w / 2)) return "|f_c| must be below Fs_w / 2";
-    if (!std::isfinite(gain)) return "gain must be finite";
-    const uint32_t w = tuner_freq_word(f_c, Fs_w);
-    std::vector<double> gr(T), gi(T);
-    double m = 0.0;
-    for (int k = 0; k < T; k++) {
-        if (!std::isfinite(h[k])) return "non-finite tap";
-        const uint32_t ph = w * static_cast<uint32_t>(k);                       // w k mod 2^32
-        const double a = kTunerTwoPi * (static_cast<double>(ph) / 4294967296.0);
-        const double g = gain * static_cast<double>(h[k]);
-        gr[k] = g * std::cos(a);
-        gi[k] = g * std::sin(a);
-        m = std::fmax(m, std::fmax(std::fabs(gr[k]), std::fabs(gi[k])));
-    }
-    if (!std::isfinite(m) || m == 0.0) return "gain x taps are all zero or not finite";
-    int s = static_cast<int>(std::floor(std::log2(kTunerTapLimit / m)));
-    while (std::ldexp(m, s) > kTunerTapLimit) s--;
-    while (std::ldexp(m, s + 1) <= kTunerTapLimit) s++;
-    if (s < kTunerMinShift || s > kTunerMaxShift) return "gain x taps out of range (scale exponent outside -14 .. 47)";
-    long long worst = 0;
-    for (int k = 0; k < T; k++) {
-        const long long qr = std::llround(std::ldexp(gr[k], s)), qi = std::llround(std::ldexp(gi[k], s));
-        re[k] = static_cast<int16_t>(qr);
-        im[k] = static_cast<int16_t>(qi);
-        worst += std::llabs(qr) + std::llabs(qi);
-    }
-    if (128 * worst > 2147483647LL) return "worst-case accumulator 128 * sum(|re| + |im|) does not fit int32";
-    *w_out = w;
-    *s_out = s;
-    return nullptr;
-}
-
-inline void tuner_table(int16_t *c, int16_t *s)
-{
-    for (int i = 0; i < kTunerTableSize; i++) {
-        const double a = kTunerTwoPi * (static_cast<double>(i) / kTunerTableSize);
-        c[i] = static_cast<int16_t>(std::llround(32767.0 * std::cos(a)));
-        s[i] = static_cast<int16_t>(std::llround(32767.0 * std::sin(a)));
-    }
-}
-
-// q = d0 + 256 d1, both digits in [-128, 127] (|q| <= 32512)
-inline void tuner_digits(int q, int8_t *dig)
-{
-    const int d0 = ((q + 128) & 255) - 128;
-    dig[0] = static_cast<int8_t>(d0);
-    dig[1] = static_cast<int8_t>((q - d0) / 256);
-}
-
-// Shape of the matrix kernel's tile for (T, R).  A column of the tile is 8 consecutive outputs (phases p = 0..7) of every
-// channel of the group; its window starts `front` bytes in front of the newest sample of its first output, so byte u of the
-// window meets, for phase p, tap k and part c (0 = I, 1 = Q):  u = front + 2 R p - 2 k + c.  Phase p's taps lie in the K-steps
-// j0[p] .. j1[p]-1 (64 bytes each); only those are stored (ksp = the largest count) and multiplied.
-struct TunerShape {
-    int front = 0;       // multiple of 16, >= 2 (T - 1)
-    int ks = 0;          // K-steps the whole window spans
-    int ksp = 0;         // K-steps stored per phase
-    int j0[kTunerPhases] = {}, j1[kTunerPhases] = {};
-};
-inline TunerShape tuner_shape(int T, int R)
-{
-    TunerShape s;
-    s.front = (2 * (T - 1) + 15) / 16 * 16;
-    for (int p = 0; p < kTunerPhases; p++) {
-        s.j0[p] = (s.front + 2 * R * p - 2 * (T - 1)) / 64;
-        s.j1[p] = (s.front + 2 * R * p + 1) / 64 + 1;
-        s.ksp = std::max(s.ksp, s.j1[p] - s.j0[p]);
-    }
-    s.ks = s.j1[kTunerPhases - 1];
-    return s;
-}
-inline size_t tuner_group_image_bytes(const TunerShape &s) { return static_cast<size_t>(kTunerPhases) * s.ksp * 64 * 16; }
-
-// One channel's rows of its group's A-operand image of v_mfma_i32_16x16x64_i8: [phase][K-step - j0[phase]][lane][16 bytes],
-// lane (row = lane & 15, quarter g = lane >> 4) holding what row `row` applies to window bytes 64 j + 16 g + 0..15.
-// Row = 4 * (channel in group) + 2 * part + digit, part 0 = real, 1 = imaginary part of the accumulator:
-//   real:  I bytes meet re[k], Q bytes meet -im[k];   imaginary:  I bytes meet im[k], Q bytes meet re[k].
-// The C layout (row = 4 (lane >> 4) + register) then hands lane (column, g) channel g's four rows of one output time.
-inline void tuner_fill_image(int8_t *img, const TunerShape &sh, int T, int R, int ch_in_group, const int16_t *re, const int16_t *im)
-{
-    for (int p = 0; p < kTunerPhases; p++)
-        for (int jr = 0; jr < sh.ksp; jr++)
-            for (int part = 0; part < 2; part++)
-                for (int d = 0; d < kTunerDigits; d++) {
-                    const int row = 4 * ch_in_group + 2 * part + d;
-                    for (int g = 0; g < 4; g++) {
-                        int8_t *dst = img + ((static_cast<size_t>(p) * sh.ksp + jr) * 64 + (16 * g + row)) * 16;
-                        for (int b = 0; b < 16; b++) {
-                            const int u = 64 * (sh.j0[p] + jr) + 16 * g + b;
-                            const int c = u & 1;
-                            const int e = sh.front + 2 * R * p + c - u;      // = 2 k
-                            int8_t v = 0;
-                            if (e >= 0 && e / 2 <= T - 1 && sh.j0[p] + jr < sh.j1[p]) {
-                                const int k = e / 2;
-                                const int q = part == 0 ? (c == 0 ? re[k] : -im[k]) : (c == 0 ? im[k] : re[k]);
-                                int8_t dig[2];
-                                tuner_digits(q, dig);
-                                v = dig[d];
-                            }
-                            dst[b] = v;
-                        }
-                    }
-                }
-}
-
-// ---- rational rates: rf_Fs = Fs_w * U / D (arithmetic defined by tests/_tuner_rational_model.py) ----
-// Output m of the stream has n_m = floor(m D / U) as its newest wide sample and sums phase p_m = m D mod U of the prototype
-// (designed at U * Fs_w, zero-padded to U * Tp taps, Tp = ceil(T / U)) over the Tp samples x[n_m - j].
+// Rates: rf_Fs = Fs_w * U / D (DESIGN.md sections 4.9 and 4.9.2; arithmetic defined by tests/_tuner_rational_model.py, which
+// at U = 1 is tests/_tuner_model.py).  Output m of the stream has n_m = floor(m D / U) as its newest wide sample and sums phase
+// p_m = m D mod U of the prototype (designed at U * Fs_w, zero-padded to U * Tp taps, Tp = ceil(T / U)) over the Tp samples
+// x[n_m - j].  U = 1 is plain decimation by D: one phase, the whole filter, n_m = m D.
 constexpr int kTunerMaxU = 32, kTunerMaxD = 512;
 constexpr int kTunerRatMfmaMaxU = 24, kTunerRatMfmaMaxD = 125;   // the range the matrix kernels cover (with Tp <= kTunerMfmaMaxTaps)
 
@@ -177,11 +68,14 @@ inline const char *tuner_ratio_check(int U, int D)
     return nullptr;
 }
 inline int tuner_phase_taps(int T, int U) { return (T + U - 1) / U; }   // Tp
+// the rates the integer matrix kernels (kernels_tuner.hip) are written for; every other rate runs the rational ones
+inline bool tuner_integer_rate(int U, int D) { return U == 1 && D <= kTunerMaxR; }
 
-// tuner_design for the U phases: tap (p, j) = gain h[p + j U] (cos a_j, sin a_j), a_j = 2 pi ((w j mod 2^32) / 2^32), ONE s
-// for all phases, re / im phase-major [p * Tp + j]; the accumulator's worst case is per phase.
-inline const char *tuner_design_rational(const float *h, int T, int U, double Fs_w, double f_c, double gain, uint32_t *w_out, int *s_out,
-                                         int16_t *re, int16_t *im)
+// One channel's integers: tap (p, j) = gain h[p + j U] (cos a_j, sin a_j), a_j = 2 pi ((w j mod 2^32) / 2^32), ONE s for all
+// phases, re / im phase-major [p * Tp + j] (U = 1: re[k], im[k] of tap k); the accumulator's worst case is per phase.  Returns
+// the error text (nullptr = accepted).
+inline const char *tuner_design(const float *h, int T, int U, double Fs_w, double f_c, double gain, uint32_t *w_out, int *s_out, int16_t *re,
+                                int16_t *im)
 {
     if (!h || T < 2 || T > kTunerMaxTaps) return "taps: 2 .. 4096";
     if (U < 1 || U > kTunerMaxU) return "U must be 1 .. 32";
@@ -227,20 +121,39 @@ inline const char *tuner_design_rational(const float *h, int T, int U, double Fs
     return nullptr;
 }
 
-// Shape of the rational matrix kernel's tile.  A column is 8 U consecutive outputs of every channel of the group; its window
-// starts `front` bytes in front of the newest sample of its first output and 16 D bytes after its neighbour's.  Output q of
-// the column (image q) has phase p_q = q D mod U and its newest sample floor(q D / U) samples into the column: window byte u
-// meets tap j and part c where  u = front + 2 floor(q D / U) - 2 j + c.  Image q's taps lie in the K-steps j0[q] .. j1[q]-1.
-struct TunerRatShape {
+inline void tuner_table(int16_t *c, int16_t *s)
+{
+    for (int i = 0; i < kTunerTableSize; i++) {
+        const double a = kTunerTwoPi * (static_cast<double>(i) / kTunerTableSize);
+        c[i] = static_cast<int16_t>(std::llround(32767.0 * std::cos(a)));
+        s[i] = static_cast<int16_t>(std::llround(32767.0 * std::sin(a)));
+    }
+}
+
+// q = d0 + 256 d1, both digits in [-128, 127] (|q| <= 32512)
+inline void tuner_digits(int q, int8_t *dig)
+{
+    const int d0 = ((q + 128) & 255) - 128;
+    dig[0] = static_cast<int8_t>(d0);
+    dig[1] = static_cast<int8_t>((q - d0) / 256);
+}
+
+// Shape of the matrix kernels' tile.  A column is 8 U consecutive outputs of every channel of the group; its window starts
+// `front` bytes in front of the newest sample of its first output and 16 D bytes after its neighbour's.  Output q of the
+// column (image q) has phase p_q = q D mod U and its newest sample floor(q D / U) samples into the column: window byte u
+// meets tap j and part c (0 = I, 1 = Q) where  u = front + 2 floor(q D / U) - 2 j + c.  Image q's taps lie in the K-steps
+// j0[q] .. j1[q]-1 (64 bytes each); only those are stored (ksp = the largest count) and multiplied.  At U = 1 the 8 images are
+// the integer kernels' 8 phases: the same taps shifted by 2 D bytes each.
+struct TunerShape {
     int U = 1, D = 2, Tp = 0;
     int front = 0;       // multiple of 16, >= 2 (Tp - 1) and >= 16
     int ks = 0;          // K-steps the whole window spans
     int ksp = 0;         // K-steps stored per image
     std::vector<int> j0, j1;   // [8 U]
 };
-inline TunerRatShape tuner_rat_shape(int T, int U, int D)
+inline TunerShape tuner_shape(int T, int U, int D)
 {
-    TunerRatShape s;
+    TunerShape s;
     s.U = U;
     s.D = D;
     s.Tp = tuner_phase_taps(T, U);
@@ -257,11 +170,25 @@ inline TunerRatShape tuner_rat_shape(int T, int U, int D)
     s.ks = s.j1[nq - 1];
     return s;
 }
-inline size_t tuner_rat_group_image_bytes(const TunerRatShape &s) { return static_cast<size_t>(kTunerPhases) * s.U * s.ksp * 64 * 16; }
+// LDS of a matrix kernel's workgroup: the rotation table, a step's window (`tiles` tiles of 16 columns per wave, 16 D bytes per
+// column plus the reach, padded by one 16-byte piece per D; two byte planes for S16) and, with via_lds, the four waves' output
+// buffers of tiles x 4 channels x 256 U bytes.
+inline size_t tuner_lds_bytes(int U, int D, int ks, int format, int tiles, bool via_lds)
+{
+    const int planes = format == kTunerS16 ? 2 : 1;
+    const int n_pieces = 16 * tiles * D + 4 * ks;
+    return static_cast<size_t>(kTunerTableSize) * 4 + 16u * planes * (n_pieces + n_pieces / D + 1) +
+           (via_lds ? static_cast<size_t>(4) * tiles * 4 * 256 * U : 0);
+}
+inline size_t tuner_group_image_bytes(const TunerShape &s) { return static_cast<size_t>(kTunerPhases) * s.U * s.ksp * 64 * 16; }
 
-// One channel's rows of its group's A-operand image: [image q][K-step - j0[q]][lane][16 bytes], rows and lanes as in
-// tuner_fill_image; re, im phase-major [U * Tp].
-inline void tuner_fill_image_rational(int8_t *img, const TunerRatShape &sh, int ch_in_group, const int16_t *re, const int16_t *im)
+// One channel's rows of its group's A-operand image of v_mfma_i32_16x16x64_i8: [image q][K-step - j0[q]][lane][16 bytes],
+// lane (row = lane & 15, quarter g = lane >> 4) holding what row `row` applies to window bytes 64 j + 16 g + 0..15.
+// Row = 4 * (channel in group) + 2 * part + digit, part 0 = real, 1 = imaginary part of the accumulator:
+//   real:  I bytes meet re[j], Q bytes meet -im[j];   imaginary:  I bytes meet im[j], Q bytes meet re[j].
+// The C layout (row = 4 (lane >> 4) + register) then hands lane (column, g) channel g's four rows of one output time.
+// re, im: phase-major [U * Tp], as tuner_design writes them.
+inline void tuner_fill_image(int8_t *img, const TunerShape &sh, int ch_in_group, const int16_t *re, const int16_t *im)
 {
     const int nq = kTunerPhases * sh.U;
     for (int q = 0; q < nq; q++) {

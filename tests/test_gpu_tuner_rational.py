@@ -259,6 +259,32 @@ def test_u_1_is_the_integer_tuner(fmrx, oracle, variant, R, fmt):
     assert cb[2] > 0
 
 
+@pytest.mark.parametrize("fmt", FORMATS, ids=ids)
+@pytest.mark.parametrize("T", [2, 256])
+@pytest.mark.parametrize("D", [32, 33])
+def test_both_sides_of_the_integer_kernels_boundary(fmrx, oracle, variant, D, T, fmt):
+    """U = 1 with D = 32, the last rate the integer matrix kernels run (T = 256, S16: their largest window, 52,320 bytes of
+    LDS), and D = 33, the first that runs the rational ones; three calls on one handle, so history and counter carry"""
+    N = 5
+    Fs_w, h = prototype(oracle, 1, D, T)
+    tuner, model = pair(fmrx, 1, D, h, N, 700 * D, fmt)
+    same = fmrx.Tuner(D, h, N, 700 * D, fmt=FMT_NAMES[fmt]) if D == 32 else None
+    rng = np.random.default_rng(1000 * D + 10 * T + fmt)
+    for c, (f_c, gain) in enumerate(channel_plan(N, Fs_w, rng)):
+        set_both(fmrx, tuner, model, c, h, Fs_w, f_c, gain)
+        if same:
+            same.set_channel(c, f_c, Fs_w, gain)
+    for n_out in (7, 700, 130):
+        values = random_raw(rng, 2 * D * n_out, fmt)
+        got, want = tuner.process(values), model.process(values)
+        assert np.array_equal(got, want), f"call of {n_out} outputs: bytes differ from the model"
+        cl, pw = tuner.levels()
+        assert np.array_equal(cl, model.clipped) and np.array_equal(pw, model.power), f"call of {n_out} outputs: levels"
+        if same:
+            assert np.array_equal(same.process(values), got), f"call of {n_out} outputs: bytes differ from Tuner({D}, ...)"
+        assert model.clipped[2] > 0, "the clipping gain did not clip"
+
+
 def test_argument_checks(fmrx, oracle):
     Fs_w, h = prototype(oracle, 6, 25, 200)
     E = fmrx.FmrxError
