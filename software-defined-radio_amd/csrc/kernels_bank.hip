@@ -1005,6 +1005,7 @@ int launch_resample(Bank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo
             const long cgs = (b.n_channels + 63) / 64;
             // a wave takes `gpw` consecutive groups of a period (neighbouring groups share most of their window): as many as leave
             // the chip >= 8 waves per SIMD
+            // (tests/test_gpu_mono_banks_exact.py: groups_per_wave() states this rule and derives its multi-group shapes from it)
             int gpw = b.res_groups;
             constexpr int NW = kRW<STEREO>;
             while (gpw > NW && cgs * periods * ((b.res_groups + gpw - 1) / gpw) * NW < 8192) gpw = (gpw + 1) / 2;

@@ -241,16 +241,27 @@ def audio_mfma_table(h, decim):
     return tab
 
 
-def fused_audio(x, h, decim, k0=0, n_out=None, kq_order=MFMA_K_ORDER):
+def fused_audio(x, h, decim, k0=0, n_out=None, kq_order=MFMA_K_ORDER, row0=0):
     """The audio FIR inside mono_fused_kernel (kernels_fe_mfma.hip): outputs k0 .. k0 + n_out - 1 of ONE block whose
     first output is k0 (row i of an output = its index in the block mod 16).  Output o, row i: window sample w carries
     tap DA i + TA-1 - w and meets x[DA o - (DA i + TA-1 - w)].  K-step j feeds y0 (j even) or y1 (j odd), each an fmaf
     chain from +0 over j ascending, kq in `kq_order` inside each MFMA, padding K-steps included; y = y0 + y1 (one f32
-    add).  x: the discriminator stream from its start (samples before it are 0)."""
-    tab = audio_mfma_table(h, decim)
+    add).  x: the discriminator stream from its start (samples before it are 0).
+
+    row0: the row of output k0 where the block does not start a launch -- the fused mono bank (channels.hip) runs all
+    slots as one launch, so channel c's first kept output sits at row (c * slot_audio + junk_audio) mod 16.  The row
+    decides which K-steps carry an output's taps, hence which products land in the even and which in the odd chain.  It
+    is the block that starts row0 outputs earlier, those outputs dropped (16 DA zeros in front keep them in the
+    stream: in front of the filter's reach only zero taps meet them)."""
     TA, DA = len(h), int(decim)
     if n_out is None:
         n_out = len(x) // DA - k0
+    row0 = int(row0)
+    assert 0 <= row0 < 16
+    if row0:
+        xz = np.concatenate([np.zeros(16 * DA, F32), np.asarray(x, F32)])
+        return fused_audio(xz, h, DA, k0 + 16 - row0, n_out + row0, kq_order)[row0:]
+    tab = audio_mfma_table(h, decim)
     assert n_out == 0 or DA * (k0 + n_out - 1) < len(x), "outputs outside the stream"
     AK = tab.shape[0]
     n16 = -(-n_out // 16)
@@ -266,6 +277,15 @@ def fused_audio(x, h, decim, k0=0, n_out=None, kq_order=MFMA_K_ORDER):
             xv = xp[base + w:base + w + step * (n16 - 1) + 1:step]
             y[j & 1] = _round_sum(xv[:, None] * tab[j, 16 * kq:16 * kq + 16].astype(F64), y[j & 1]).astype(F64)
     return (y[0].astype(F32) + y[1].astype(F32)).ravel()[:n_out]
+
+
+def row_phase_changes_bits(decim, row0):
+    """Whether fused_audio(row0=r) can differ in bits from row0 = 0.  Row i applies tap k to window sample
+    w = DA i + TA-1 - k; K-step j = 4 (w / 16) + w % 4 and kq = (w / 4) % 4 place it.  Moving an output by r rows moves
+    every w by DA r: a multiple of 16 moves every tap by whole groups of four K-steps -- the same chain (j keeps its
+    parity), the same order inside it, only zero products in front -- so the bits stay.  At DA = 6 that is r = 8 (and
+    r = 12 equals r = 4); at DA = 5 no phase but 0."""
+    return (int(decim) * int(row0)) % 16 != 0
 
 
 def resample_mfma_plan(taps, upsamp, decim):

@@ -184,6 +184,77 @@ def test_fma_chain_differs_from_reference_order(oracle, mode):
         assert (bits(fm.fma_chain(x, taps["bpf_st"], fm.ascending(T))) != bits(fm.fma_chain(x, taps["bpf_st"], fm.descending(T)))).any()
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_fused_audio_row_phase(oracle, mode):
+    """fused_audio(row0=r): the rows the fused mono bank gives a channel whose first kept output is not at a multiple of
+    16 in the launch.  row0 = 0 is the model of the single-stream pipeline, unchanged; r = 4, 8, 12 equal the block that
+    starts r outputs earlier with those outputs dropped (also at the start of the stream, where there is no earlier
+    output), stay within gamma(4 AK + 1) sum|h x| of the float64 FIR, and differ in bits from row0 = 0 -- except
+    where the rows' windows lie a whole number of MFMA groups apart (16 samples: DA r a multiple of 16, which is r = 8 at
+    DA = 6): every tap then keeps its chain and its place in it, and the bits are those of row0 = 0."""
+    x, p = demod_stream(oracle, mode)
+    DA = p.audio_decim
+    n_all = len(x) // DA
+    for TA in (101, 13):
+        h = oracle.impulse_response_lpf(float(p.if_Fs), 16e3, TA)
+        y0 = fm.fused_audio(x, h, DA)
+        np.testing.assert_array_equal(bits(fm.fused_audio(x, h, DA, row0=0)), bits(y0))
+        np.testing.assert_array_equal(bits(fm.fused_audio(x, h, DA, 1024, 1024, row0=0)), bits(fm.fused_audio(x, h, DA, 1024, 1024)))
+        y64, a = fm.fir64(x, h, DA)
+        bound = fm.gamma(4 * fm.audio_mfma_ksteps(TA, DA) + 1) * a
+        for r in (4, 8, 12):
+            y = fm.fused_audio(x, h, DA, row0=r)
+            assert len(y) == n_all
+            assert (np.abs(y.astype(np.float64) - y64) <= bound).all(), (mode, TA, r)
+            assert fm.row_phase_changes_bits(DA, r) == bool((bits(y) != bits(y0)).any()), (mode, TA, r)
+            # a later block: the same as starting r outputs earlier
+            k0, n = 1024 + 28, 1024
+            np.testing.assert_array_equal(bits(fm.fused_audio(x, h, DA, k0, n, row0=r)), bits(fm.fused_audio(x, h, DA, k0 - r, n + r)[r:]))
+            assert fm.row_phase_changes_bits(DA, r) == bool((bits(fm.fused_audio(x, h, DA, k0, n, row0=r)) != bits(fm.fused_audio(x, h, DA, k0, n))).any())
+    assert [r for r in (0, 4, 8, 12) if fm.row_phase_changes_bits(DA, r)] == {5: [4, 8, 12], 6: [4, 12]}[DA]
+
+
+def rms(a, b):
+    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_mono_tolerance_is_blind_to_seam_and_phase_errors(oracle, mode):
+    """What the mono tolerance (RMS 2e-6 over a block) cannot see and the bit comparison of
+    tests/test_gpu_mono_banks_exact.py can, on one 1024-output block of a bank channel (row phase 4, production taps):
+      a. the oldest sample the block reads -- the first one in front of the filter's reach into the history -- is a
+         neighbour's full-scale discriminator value (a history one sample short, a junk count off by one);
+      b. the row phase is wrong by 4 (the outputs landed on other rows of the launch than the model's);
+      c. one history sample at the far end of the filter's reach is zero (a history byte not moved).
+    Each differs from the model in bits and stays below 2e-6 RMS: h[TA-1] is about 5e-5 of the peak tap, and a row phase
+    only regroups the rounding.  For contrast, the sample directly in front of the block meets every fifth (sixth) tap:
+    that one the tolerance does see."""
+    x, p = demod_stream(oracle, mode)
+    DA, TA = p.audio_decim, 101
+    h = oracle.impulse_response_lpf(float(p.if_Fs), 16e3, TA)
+    k0, n, row = 1024, 1024, 4
+    y = fm.fused_audio(x, h, DA, k0, n, row0=row)
+    full_scale = F32(np.pi)                                  # the discriminator's range: |x| <= pi (times a gain below 1)
+    assert np.abs(x).max() <= full_scale
+    far = DA * k0 - (TA - 1)                                 # x[DA k0 - n], n = TA-1: the oldest sample output k0 reads
+    variants = {}
+    xa = x.copy()
+    xa[far] = full_scale
+    variants["a neighbour's sample at the far end of the reach"] = fm.fused_audio(xa, h, DA, k0, n, row0=row)
+    variants["row phase wrong by 4"] = fm.fused_audio(x, h, DA, k0, n, row0=row + 4)
+    xc = x.copy()
+    assert xc[far + 1] != 0
+    xc[far + 1] = 0
+    variants["a zeroed history sample at the far end of the reach"] = fm.fused_audio(xc, h, DA, k0, n, row0=row)
+    for name, v in variants.items():
+        assert (bits(v) != bits(y)).any(), name + ": the same bits"
+        assert rms(v, y) < 2e-6, (name, rms(v, y))
+        assert np.abs(oracle.pcm16(v).astype(np.int32) - oracle.pcm16(y).astype(np.int32)).max() <= 1, name
+    xd = x.copy()
+    xd[DA * k0 - 1] = full_scale
+    assert rms(fm.fused_audio(xd, h, DA, k0, n, row0=row), y) > 1e-3
+
+
 def test_mixer_and_combine_helpers():
     sf = np.array([1.5, -3.0, 2.0 ** -140, 7.0], F32)
     pll = np.array([0.25, -1.0, 0.5, 0.1, 9.0], F32)
@@ -225,6 +296,26 @@ def test_gpu_tests_cover_every_shape():
     assert {(t[1], {0: 5, 1: 6}[m]) for m, t, _, _ in g.BANK_CONFIGS} == set(g.CHS_OUT_SHAPES)
     assert {s for _, a, s in g.STEREO_CASES} == set(g.BPF_TAPS)
     assert {(a, {0: 5, 1: 6}[m]) for m, a, _ in g.STEREO_CASES if m in (0, 1)} == set(g.STEREO_OUT_SHAPES)
+
+
+def test_mono_bank_tests_cover_every_shape_and_state_the_launch_rule():
+    """tests/test_gpu_mono_banks_exact.py runs every fused shape, the full list at 101/101 taps in both modes, and its
+    groups_per_wave() is launch_resample's rule: the loop as kernels_bank.hip has it, and the thresholds it gives."""
+    import test_gpu_mfma_exact as m
+    import test_gpu_mono_banks_exact as g
+    assert {c[:4] for c in g.FUSED_BANK_CASES} == set(m.FUSED_CASES)
+    for shape in ((101, 10, 101, 5), (101, 5, 101, 6)):
+        assert {c[4:] for c in g.FUSED_BANK_CASES if c[:4] == shape} == {(n, k) for n in (1, 7, 70) for k in g.BLOCK_KINDS}
+    with open(os.path.join(CSRC, "kernels_bank.hip")) as f:
+        src = f.read()
+    assert "while (gpw > NW && cgs * periods * ((b.res_groups + gpw - 1) / gpw) * NW < 8192) gpw = (gpw + 1) / 2;" in src
+    assert "gpw = (gpw + NW - 1) / NW * NW;" in src and "template <bool STEREO> constexpr int kRW = STEREO ? 3 : 7;" in src
+    assert "test_gpu_mono_banks_exact.py" in src
+
+    def first(U, stereo, groups):
+        return next(X for X in range(1, 2000) if g.groups_per_wave(64 * X, 1, U, stereo)[1] >= groups)
+    assert (first(441, False, 2), first(441, False, 3), first(147, False, 2), first(441, True, 2)) == (147, 293, 586, 171)
+    assert g.groups_per_wave(65, 7, 441, False) == (14, 1) and g.groups_per_wave(40000, 7, 147, False)[1] > 1
 
 
 def test_resample_chain_equals_sequential_exact_fma():

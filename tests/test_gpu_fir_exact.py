@@ -23,13 +23,17 @@ short-block tail), blocks spanning several workgroups, ~1 024 000-sample blocks,
 audio_fir_kernel has persistent workgroups (each of those walks two tiles).
 
 The f32 matrix-core sums (the audio FIR inside mono_fused_kernel, resample_mfma_kernel) are pinned the same way, bit for
-bit against an fmaf-chain model, by tests/test_gpu_mfma_exact.py.
+bit against an fmaf-chain model, by tests/test_gpu_mfma_exact.py; the two fast MONO banks -- the fused mono bank of modes
+0/1 (mono_fused_kernel over all slots, at each channel's row phase, with channels_finish_kernel) and
+chs_resample_lanes_kernel<STEREO = false> of modes 2/3 -- by tests/test_gpu_mono_banks_exact.py, which also runs the lane
+resampler, mono and stereo, with more than one group per wave.
 
 Out of scope, on purpose:
   * the PLL and the discriminator's v_rcp_f32 (the PLL's output is an input tap here, as the discriminator's is; the
     fast PLL is pinned against its own model by tests/test_gpu_pll_exact.py, the fast discriminator sample by sample
     against a model given the device's reciprocal by tests/test_gpu_demod_exact.py);
-  * the exact banks: already bit for bit against the oracle (tests/test_gpu_channels.py)."""
+  * the exact banks: already bit for bit against the oracle (tests/test_gpu_channels.py);
+  * the fast mono banks (tests/test_gpu_mono_banks_exact.py, above)."""
 import math
 
 import numpy as np

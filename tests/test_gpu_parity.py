@@ -1113,7 +1113,9 @@ def test_many_channels_per_call(fmrx, oracle, mode, taps):
     """fmrx_channels: the current reference-size block of N independent mono channels in ONE kernel launch (a channel's
     carried state is its last ~1 400 input bytes pairs, kept in front of its block).  Seven channels with different
     signals, five blocks each, every channel against the oracle streaming that channel alone: audio within the mono
-    tolerance, s16 within 1 LSB; then one channel is reset (start of a new stream) while the others carry on."""
+    tolerance, s16 within 1 LSB; then one channel is reset (start of a new stream) while the others carry on.  (What a
+    tolerance cannot see -- a neighbour's sample at a seam, a wrong history byte, the junk count -- is pinned bit for bit
+    against the kernel's own arithmetic by tests/test_gpu_mono_banks_exact.py.)"""
     p = oracle.mode_params(mode, taps[0], taps[1], 101)
     N, nblk, bb = 7, 5, p.block_bytes
     streams = [oracle.synth_fm_u8(bb // 2 * (nblk + 2), rf_Fs=p.rf_Fs, seed=900 + 13 * c) for c in range(N)]

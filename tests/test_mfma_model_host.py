@@ -31,15 +31,15 @@ def stream_with_edges(rng, n, scale=1.0):
     return x
 
 
-def fused_sequential(x, h, DA, k0, n_out, kq_order=fm.MFMA_K_ORDER):
+def fused_sequential(x, h, DA, k0, n_out, kq_order=fm.MFMA_K_ORDER, row0=0):
     """mono_fused_kernel's audio FIR read straight off its description, one exact fma at a time: output o (row
-    i = (o - k0) mod 16), K-step j, K index kq: window sample w = 16 (j/4) + 4 kq + j%4, tap k = DA i + TA-1 - w (0 outside
+    i = (o - k0 + row0) mod 16), K-step j, K index kq: window sample w = 16 (j/4) + 4 kq + j%4, tap k = DA i + TA-1 - w (0 outside
     the filter) times x[DA o - k] (0 outside the stream); y0 takes even j, y1 odd j; y = y0 + y1."""
     TA = len(h)
     AK = fm.audio_mfma_ksteps(TA, DA)
     out = []
     for o in range(k0, k0 + n_out):
-        i = (o - k0) % 16
+        i = (o - k0 + row0) % 16
         y = [F32(0.0), F32(0.0)]
         for j in range(AK):
             for kq in kq_order:
@@ -87,6 +87,11 @@ def test_fused_audio_equals_sequential_exact_fma(TA, DA):
         got = fm.fused_audio(x, h, DA, k0, n_out)
         want = fused_sequential(x, h, DA, k0, n_out)
         np.testing.assert_array_equal(bits(got), bits(want), err_msg=f"TA {TA} DA {DA} k0 {k0}")
+        # the fused bank's row phases: the first output of the block sits at row 4, 8 or 12 of its launch
+        for row0 in (4, 8, 12):
+            got = fm.fused_audio(x, h, DA, k0, n_out, row0=row0)
+            want = fused_sequential(x, h, DA, k0, n_out, row0=row0)
+            np.testing.assert_array_equal(bits(got), bits(want), err_msg=f"TA {TA} DA {DA} k0 {k0} row0 {row0}")
     # a stream of tiny values: products and sums underflow to signed zeros and subnormals
     xs = (stream_with_edges(rng, DA * 40) * F32(2.0 ** -100)).astype(F32)
     hs = (rng.standard_normal(TA) * 2.0 ** -40).astype(F32)
