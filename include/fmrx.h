@@ -531,15 +531,47 @@ typedef struct fmrx_rds_station {
 typedef struct fmrx_rds_group {
     uint16_t block[4];    /* information words of slots A, B, C/C', D (0 where the slot failed) */
     uint8_t ok_mask;      /* bit s: slot s passed its syndrome; bit 4: slot 2 carried offset C' */
-    uint8_t reserved[3];  /* 0 */
+    uint8_t reserved[3];  /* [0]: corrected mask, bit s: slot s passed after burst error correction (0 with correction off);
+                             [1], [2]: 0 */
     uint32_t bit_index;   /* index of the group's first bit in the decoder's bit stream (mod 2^32) */
 } fmrx_rds_group;
+/* The extension record: what burst error correction did, and the station data beyond PS and RadioText (IEC 62106 groups 0A
+ * alternative frequencies, 0A/0B decoder identification, 1A country code / language / programme item number, 4A clock time,
+ * 10A programme type name).  Rules: rds_station.hpp.  A fresh record is all zeros but ptyn (spaces), ptyn_ab (2) and
+ * max_burst (the option). */
+typedef struct fmrx_rds_station_ext {
+    uint32_t corrected_blocks; /* blocks accepted after correction (a subset of fmrx_rds_station.good_blocks) */
+    uint32_t burst_hist[5];    /* of which with a burst of length 1..5 */
+    uint32_t sync_losses;      /* times block sync was lost */
+    uint32_t group_types;      /* bit 2*type + version (A 0, B 1): a group of that type arrived with block B passed */
+    uint32_t af_bits[8];       /* alternative frequencies (0A): bit c of the 256-bit set = code c = 87.5 + 0.1 c MHz, c in 1..204 */
+    uint32_t ct_mjd;           /* clock time (4A), the last valid one: modified Julian day (17 bits) */
+    uint32_t ct_bit_index;     /* bit_index of the group that carried it: the minute's edge in the bit stream */
+    uint32_t ct_count;         /* 4A groups accepted (B, C and D passed, hour < 24, minute < 60) */
+    char ptyn[8];              /* programme type name (10A), spaces where not yet received; cleared when its A/B flag changes */
+    uint16_t pin;              /* programme item number (1A block D), raw */
+    uint16_t lang;             /* language code (1A variant 3), 12 bits */
+    uint8_t ecc;               /* extended country code (1A variant 0) */
+    uint8_t ext_seen;          /* bit 0: ecc valid, bit 1: lang valid, bit 2: pin valid */
+    uint8_t max_burst;         /* the correction option the decoder runs with, 0..5 */
+    uint8_t di;                /* decoder identification (0A/0B): bit 3 = d3 ... bit 0 = d0 */
+    uint8_t di_mask;           /* which of its bits have been received */
+    uint8_t af_announced;      /* number of alternative frequencies the station announces (code 224 + n), 0..25 */
+    uint8_t ct_hour;           /* UTC hour 0..23 */
+    uint8_t ct_minute;         /* 0..59 */
+    uint8_t ct_offset;         /* local time offset, raw: bit 5 = sign (1: negative), bits 4..0 = half hours */
+    uint8_t ptyn_mask;         /* PTYN segments (4 characters each) received */
+    uint8_t ptyn_ab;           /* A/B flag of the name held; 2 = no group 10A yet */
+    uint8_t reserved[29];      /* 0 */
+} fmrx_rds_station_ext;
 #ifdef __cplusplus
 static_assert(sizeof(fmrx_rds_station) == 96, "fmrx_rds_station layout");
 static_assert(sizeof(fmrx_rds_group) == 16, "fmrx_rds_group layout");
+static_assert(sizeof(fmrx_rds_station_ext) == 128, "fmrx_rds_station_ext layout");
 #else
 _Static_assert(sizeof(fmrx_rds_station) == 96, "fmrx_rds_station layout");
 _Static_assert(sizeof(fmrx_rds_group) == 16, "fmrx_rds_group layout");
+_Static_assert(sizeof(fmrx_rds_station_ext) == 128, "fmrx_rds_station_ext layout");
 #endif
 typedef struct fmrx_rds_station_decoder fmrx_rds_station_decoder;
 /* sps: matched-filter samples per chip, 2..64 (fmrx_rds_params.sps: 26 in mode 0, 43 in mode 2) */
@@ -555,6 +587,19 @@ FMRX_API int fmrx_rds_station_feed_rrc(fmrx_rds_station_decoder *d, const double
 /* The same from differentially decoded bits (0 / 1): block sync and groups alone. */
 FMRX_API int fmrx_rds_station_feed_bits(fmrx_rds_station_decoder *d, const uint8_t *bits, size_t n, fmrx_rds_group *g, size_t max_g,
                                         size_t *n_g, fmrx_rds_station *st);
+/* Burst error correction (IEC 62106 annex B: the (26,16) code repairs any one burst of up to 5 bits): max_burst 0..5 = the
+ * longest burst a block that failed its syndrome while sync is held may be repaired from; 0 (the default) = none.  One wrong
+ * chip pair on the air is a 2-bit burst after differential decoding; 2 is the recommended setting.  A word of 26 random bits
+ * is taken for a block with probability (correctable syndromes + 1) / 1024: 0.1 % at 0, 2.6 % at 1, 5.1 % at 2, 9.8 % at 3,
+ * 18.8 % at 4, 35.9 % at 5.  Only on a decoder that has been fed nothing since create or reset: FMRX_EINVAL otherwise.  The
+ * option outlives fmrx_rds_station_reset. */
+FMRX_API int fmrx_rds_station_set_correction(fmrx_rds_station_decoder *d, int max_burst);
+/* The extension record as of the last feed. */
+FMRX_API int fmrx_rds_station_ext_get(const fmrx_rds_station_decoder *d, fmrx_rds_station_ext *ext);
+/* One block on its own: word26 = 26 bits, first received in bit 25; offset 0 A, 1 B, 2 C, 3 C', 4 D.  -> 0 clean, 1 corrected
+ * (a burst of *burst_len <= max_burst bits), 2 uncorrectable, -1 bad argument.  *info: the information word (of the repaired
+ * block where corrected; of the word as received where uncorrectable).  info / burst_len may be NULL. */
+FMRX_API int fmrx_rds_block_correct(uint32_t word26, int offset, int max_burst, uint16_t *info, int *burst_len);
 
 /* ------------------------------------------------------------------ */
 /* RDS banks: the RDS chain of N channels per device call               */
@@ -595,6 +640,14 @@ FMRX_API size_t fmrx_rds_bank_max_groups(const fmrx_rds_bank *b);
  * every channel's station record and the groups its last call completed, exactly what an fmrx_rds_station_decoder fed the
  * channel's rrc_i rows produces */
 FMRX_API int fmrx_rds_bank_stations(fmrx_rds_bank *b, fmrx_rds_station *st, fmrx_rds_group *g, size_t *n_g);
+/* Options of the bank's station decoders: max_burst as fmrx_rds_station_set_correction; ext != 0 keeps an extension record
+ * per channel on the device.  Only with stations on and under the rule of fmrx_rds_bank_set_stations (before the first call
+ * or right after fmrx_rds_bank_reset(b, -1)).  A bank on which this was never called runs what it ran before it existed. */
+FMRX_API int fmrx_rds_bank_set_station_options(fmrx_rds_bank *b, int max_burst, int ext);
+/* waits for the last process_dev as fmrx_rds_bank_stations does (and takes it off the "not collected" rule likewise);
+ * ext [n_channels]: exactly what fmrx_rds_station_ext_get reports for a host decoder with the same option fed the channel's
+ * rrc_i rows.  FMRX_EINVAL when the extension records are off.  fmrx_rds_bank_reset(b, c) clears channel c's record too. */
+FMRX_API int fmrx_rds_bank_stations_ext(fmrx_rds_bank *b, fmrx_rds_station_ext *ext);
 /* Receiver banks that keep discriminator rows (stereo banks, exact banks, the resampling modes' banks): where the last
  * call's rows are, for fmrx_rds_bank_process_dev on the same stream.  FMRX_EINVAL for the fused mono bank of modes 0/1.
  * A call leaves its rows intact (only the history in front of each row is rewritten) until the next fmrx_channels_process*;

@@ -688,14 +688,30 @@ struct fmrx_rds_station_decoder {
     fmrx::rdsst::Dec d;
     double E[fmrx::rdsst::kMaxSps];
     fmrx_rds_station rec;
+    fmrx_rds_station_ext ext;
+    int max_burst = 0;
+    bool fed = false;                              // something has been fed since create / reset: the option is fixed
 };
 
 namespace {
+// the correction table of rds_station.hpp, built at the first use
+const uint32_t *burst_table()
+{
+    static const std::vector<uint32_t> tab = [] {
+        std::vector<uint32_t> t(fmrx::rdsst::kBurstTableSize);
+        if (fmrx::rdsst::build_burst_table(t.data()) != 367) std::abort();   // (the code's own property: cannot happen)
+        return t;
+    }();
+    return tab.data();
+}
+
 void station_reset(fmrx_rds_station_decoder *d, int sps)
 {
-    fmrx::rdsst::init(d->d, sps);
+    fmrx::rdsst::init(d->d, sps, d->max_burst);
     for (double &e : d->E) e = 0.0;
     fmrx::rdsst::clear_record(&d->rec);
+    fmrx::rdsst::clear_ext(&d->ext, d->max_burst);
+    d->fed = false;
 }
 
 template <typename F>
@@ -703,9 +719,12 @@ int station_feed(fmrx_rds_station_decoder *d, size_t n, fmrx_rds_group *g, size_
 {
     if (!d || !st) return fail(FMRX_EINVAL, "rds_station_feed: null argument");
     if ((g == nullptr) != (n_g == nullptr)) return fail(FMRX_EINVAL, "rds_station_feed: g and n_g go together");
-    fmrx::rdsst::Out o{&d->rec, g, g ? static_cast<uint32_t>(std::min<size_t>(max_g, 0xFFFFFFFFu)) : 0u, 0u};
+    fmrx::rdsst::Out o{&d->rec, g, g ? static_cast<uint32_t>(std::min<size_t>(max_g, 0xFFFFFFFFu)) : 0u, 0u,
+                       d->max_burst ? burst_table() : nullptr, &d->ext};
+    if (n) d->fed = true;
     for (size_t i = 0; i < n; i++) each(i, o);
     fmrx::rdsst::finish(d->d, &d->rec);
+    fmrx::rdsst::finish_ext(d->d, &d->ext);
     *st = d->rec;
     if (n_g) *n_g = o.n_g;
     return FMRX_OK;
@@ -754,6 +773,35 @@ int fmrx_rds_station_feed_bits(fmrx_rds_station_decoder *d, const uint8_t *bits,
 {
     if (n && !bits) return fail(FMRX_EINVAL, "rds_station_feed_bits: null bits");
     return station_feed(d, n, g, max_g, n_g, st, [&](size_t i, fmrx::rdsst::Out &o) { fmrx::rdsst::feed_bit(d->d, bits[i] ? 1 : 0, o); });
+}
+
+int fmrx_rds_station_set_correction(fmrx_rds_station_decoder *d, int max_burst)
+{
+    if (!d) return fail(FMRX_EINVAL, "rds_station_set_correction: null handle");
+    if (max_burst < 0 || max_burst > fmrx::rdsst::kMaxBurst)
+        return fail(FMRX_EINVAL, "rds_station_set_correction: max_burst %d not in 0..%d", max_burst, fmrx::rdsst::kMaxBurst);
+    if (d->fed) return fail(FMRX_EINVAL, "rds_station_set_correction: only on a decoder fed nothing since create or reset");
+    d->max_burst = max_burst;
+    station_reset(d, d->d.sps);
+    return FMRX_OK;
+}
+
+int fmrx_rds_station_ext_get(const fmrx_rds_station_decoder *d, fmrx_rds_station_ext *ext)
+{
+    if (!d || !ext) return fail(FMRX_EINVAL, "rds_station_ext_get: null argument");
+    *ext = d->ext;
+    return FMRX_OK;
+}
+
+int fmrx_rds_block_correct(uint32_t word26, int offset, int max_burst, uint16_t *info, int *burst_len)
+{
+    if (offset < 0 || offset > 4 || max_burst < 0 || max_burst > fmrx::rdsst::kMaxBurst || (word26 >> 26)) return -1;
+    uint32_t w = word26;
+    const uint32_t sx = fmrx::rdsst::syndrome(w) ^ fmrx::rdsst::syndrome_of_offset(offset);
+    const int len = sx ? fmrx::rdsst::correct_block(w, sx, max_burst, burst_table()) : 0;
+    if (info) *info = static_cast<uint16_t>(w >> 10);
+    if (burst_len) *burst_len = len;
+    return sx == 0 ? 0 : len ? 1 : 2;
 }
 
 }  // extern "C"

@@ -294,10 +294,13 @@ __global__ __launch_bounds__(64) void rdsb_cdr_kernel(const double *__restrict__
 // matched-filter row.  The row arrives a batch ahead through registers into LDS, as in rdsb_pll_lanes_kernel; the per-phase
 // energies live in LDS for the call (they are indexed by the sample's phase); the decoder's scalars stay in registers.  Station
 // records (text as it arrives, the scalars at the end) and group records go out with ordinary vector stores.
+// tab: the burst-correction table in global memory (one cached load per failed block; null with correction off); ext: the
+// extension records (null = none kept).  A bank without station options passes both null and does what it did before them.
 // Dynamic LDS: (kStB + sps) * 64 doubles, [sample][lane] then [phase][lane].  Rows are 16-byte aligned (even pitches).
 __global__ __launch_bounds__(64) void rdsb_station_kernel(const double *__restrict__ y, long ypitch, long n, int n_ch, rdsst::Dec *__restrict__ dec,
                                                           double *__restrict__ energy, fmrx_rds_station *__restrict__ st,
-                                                          fmrx_rds_group *__restrict__ grp, int max_g, uint32_t *__restrict__ n_g)
+                                                          fmrx_rds_group *__restrict__ grp, int max_g, uint32_t *__restrict__ n_g,
+                                                          const uint32_t *__restrict__ tab, fmrx_rds_station_ext *__restrict__ ext)
 {
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(64) void rdsb_station_kernel(const double *__restri
     const int sps = d.sps;
     double *er = energy + ch * rdsst::kMaxSps;
     for (int p = 0; p < sps; p++) E[p * 64] = er[p];
-    rdsst::Out o{st + ch, grp + ch * max_g, static_cast<uint32_t>(max_g), 0u};
+    rdsst::Out o{st + ch, grp + ch * max_g, static_cast<uint32_t>(max_g), 0u, tab, ext ? ext + ch : nullptr};
     const double *row = y + ch * ypitch;
     const d2 *row2 = reinterpret_cast<const d2 *>(row);
     const long nb = n / kStB;
@@ -332,6 +335,7 @@ __global__ __launch_bounds__(64) void rdsb_station_kernel(const double *__restri
     }
     for (long k = nb * kStB; k < n; k++) rdsst::feed_sample(d, E, 64, row[k], o);
     rdsst::finish(d, st + ch);
+    if (ext) rdsst::finish_ext(d, ext + ch);
     dec[ch] = d;
     for (int p = 0; p < sps; p++) er[p] = E[p * 64];
     n_g[ch] = o.n_g;
@@ -544,6 +548,9 @@ struct fmrx_rds_bank {
     DevBuf<fmrx_rds_group> grp;                    // [N][max_g] the last call's groups
     DevBuf<uint32_t> n_g;                          // [N] how many
     std::vector<uint32_t> h_n_g;
+    int max_burst = 0;                             // station options (fmrx_rds_bank_set_station_options)
+    DevBuf<uint32_t> tab;                          // [1024] the burst-correction table, where max_burst > 0 was asked for
+    DevBuf<fmrx_rds_station_ext> ext;              // [N] extension records, where asked for
 };
 
 namespace {
@@ -559,8 +566,13 @@ int bank_reset(fmrx_rds_bank *b, int lo, int hi)
         std::vector<rdsst::Dec> d(cnt);
         std::vector<fmrx_rds_station> r(cnt);
         for (size_t c = 0; c < cnt; c++) {
-            rdsst::init(d[c], b->c.p.sps);
+            rdsst::init(d[c], b->c.p.sps, b->max_burst);
             rdsst::clear_record(&r[c]);
+        }
+        if (b->ext.p) {
+            std::vector<fmrx_rds_station_ext> x(cnt);
+            for (size_t c = 0; c < cnt; c++) rdsst::clear_ext(&x[c], b->max_burst);
+            FMRX_HIP(hipMemcpy(b->ext.p + lo, x.data(), cnt * sizeof(fmrx_rds_station_ext), hipMemcpyHostToDevice));
         }
         FMRX_HIP(hipMemcpy(b->dec.p + lo, d.data(), cnt * sizeof(rdsst::Dec), hipMemcpyHostToDevice));
         FMRX_HIP(hipMemcpy(b->st.p + lo, r.data(), cnt * sizeof(fmrx_rds_station), hipMemcpyHostToDevice));
@@ -670,6 +682,41 @@ int fmrx_rds_bank_set_stations(fmrx_rds_bank *b, int on)
     return FMRX_OK;
 }
 
+int fmrx_rds_bank_set_station_options(fmrx_rds_bank *b, int max_burst, int ext)
+{
+    if (!b) return fail(FMRX_EINVAL, "rds_bank_set_station_options: null handle");
+    if (!b->stations) return fail(FMRX_EINVAL, "rds_bank_set_station_options: stations are off (fmrx_rds_bank_set_stations)");
+    if (!b->fresh)
+        return fail(FMRX_EINVAL, "rds_bank_set_station_options: only before the first call or right after fmrx_rds_bank_reset(b, -1)");
+    if (max_burst < 0 || max_burst > rdsst::kMaxBurst)
+        return fail(FMRX_EINVAL, "rds_bank_set_station_options: max_burst %d not in 0..%d", max_burst, rdsst::kMaxBurst);
+    FMRX_HIP(hipSetDevice(b->c.device));
+    if (max_burst > 0 && !b->tab.p) {
+        std::vector<uint32_t> t(rdsst::kBurstTableSize);
+        if (rdsst::build_burst_table(t.data()) != 367) return fail(FMRX_EINVAL, "rds_bank_set_station_options: correction table");
+        FMRX_TRY(b->tab.alloc(t.size()));
+        FMRX_HIP(hipMemcpy(b->tab.p, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (ext && !b->ext.p) FMRX_TRY(b->ext.alloc(static_cast<size_t>(b->c.n_channels)));
+    if (!ext) b->ext.release();
+    b->max_burst = max_burst;
+    return bank_reset(b, 0, b->c.n_channels);       // the decoders start over with the option
+}
+
+int fmrx_rds_bank_stations_ext(fmrx_rds_bank *b, fmrx_rds_station_ext *ext)
+{
+    if (!b || !ext) return fail(FMRX_EINVAL, "rds_bank_stations_ext: null argument");
+    if (!b->stations || !b->ext.p)
+        return fail(FMRX_EINVAL, "rds_bank_stations_ext: the extension records are off (fmrx_rds_bank_set_station_options)");
+    FMRX_HIP(hipSetDevice(b->c.device));
+    b->pending = false;
+    hipStream_t s = b->stream;
+    FMRX_HIP(hipStreamWaitEvent(s, b->done, 0));
+    FMRX_HIP(hipMemcpyAsync(ext, b->ext.p, static_cast<size_t>(b->c.n_channels) * sizeof(fmrx_rds_station_ext), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipStreamSynchronize(s));
+    return FMRX_OK;
+}
+
 size_t fmrx_rds_bank_max_groups(const fmrx_rds_bank *b) { return b ? static_cast<size_t>(b->max_g) : 0; }
 
 int fmrx_rds_bank_stations(fmrx_rds_bank *b, fmrx_rds_station *st, fmrx_rds_group *g, size_t *n_g)
@@ -710,7 +757,8 @@ int fmrx_rds_bank_process_dev(fmrx_rds_bank *b, const float *d_demod, size_t pit
     if (b->stations) {
         const unsigned lanes = (static_cast<unsigned>(b->c.n_channels) + 63) / 64;
         hipLaunchKernelGGL(rdsb_station_kernel, dim3(lanes), dim3(64), (kStB + b->c.p.sps) * 64 * sizeof(double), s, b->c.yi.p, b->c.ypitch, b->n_out,
-                           b->c.n_channels, b->dec.p, b->energy.p, b->st.p, b->grp.p, static_cast<int>(b->max_g), b->n_g.p);
+                           b->c.n_channels, b->dec.p, b->energy.p, b->st.p, b->grp.p, static_cast<int>(b->max_g), b->n_g.p,
+                           b->max_burst > 0 ? b->tab.p : nullptr, b->ext.p);
         FMRX_LAUNCH_CHECK("rdsb_station_kernel");
     }
     FMRX_HIP(hipEventRecord(b->done, s));

@@ -19,17 +19,51 @@
 //   block sync    syndrome of the last 26 bits with frame_sync's parity matrix (offsets A 0x3D8, B 0x3D4, C 0x25C, C' 0x3CC,
 //                 D 0x258).  Not synced: two offset matches 26 bits apart in sequence (A->B, B->C/C', C/C'->D, D->A) acquire
 //                 sync.  Synced: one block every 26 bits against the expected offset (C and C' both pass in slot 2); sync is
-//                 lost after kSyncLossBad bad blocks in a row.  No burst error correction.
+//                 lost after kSyncLossBad bad blocks in a row.
+//   correction    option max_burst 0..5 (0 = off, the default), only while sync is held (acquisition always wants two CLEAN
+//                 matches).  A block whose syndrome is not a pass gets s = syndrome ^ syndrome-of-the-expected-offset looked up
+//                 in a 1024-entry table (build_burst_table) that holds, for every syndrome that exactly one burst of length
+//                 <= 5 inside the 26 bits produces, that burst's pattern and length.  The (26,16) code tells all bursts up to
+//                 length 5 apart: bursts of length <= 1, 2, 3, 4, 5 have 26, 51, 99, 191, 367 distinct non-zero syndromes
+//                 (length 6 collides), so the table is well defined up to 5 and no further.  Length <= max_burst: the pattern
+//                 is XORed in and the block counts as CORRECTED: used exactly like a clean one (good_blocks, ok_mask, station
+//                 data), and marked in the group's corrected mask (fmrx_rds_group.reserved[0], bit s = slot s).  Expected
+//                 offset: slots 0, 1, 3: A, B, D.  Slot 2: a clean C or C' passes as ever; correction aims at C or C' by the
+//                 version bit of block B when slot 1 passed (clean or corrected), and is not tried when slot 1 failed.
+//                 Flywheel: a clean block clears the bad-block count, a failed one adds to it, a corrected one leaves it alone
+//                 (evidence neither way).  The price: 26 random bits are taken for a block with probability
+//                 (correctable syndromes + 1) / 1024 -- 0.1 % at max_burst 0, 2.6 % at 1, 5.1 % at 2, 9.8 % at 3, 18.8 % at 4
+//                 and 35.9 % at 5, which is what a decoder that has lost the block grid but not yet its sync flag is fed.
+//                 The offset words' syndromes themselves differ by burst syndromes (A/B 2 bits, C/D 1, A/D 2, B/C' 2, A/C' 3,
+//                 C'/D 3, B/C 4, B/D 4, C/C' 5; A/C none): a block of one offset with that burst IS a clean block of the other,
+//                 which is why correction aims at the expected offset only -- and why, from max_burst 4 on, a lock on the right
+//                 block grid with the slots one off (A for B, B for C, C for D, D for A: 2, 4, 1, 2 bits) corrects every block
+//                 and holds; corrected_blocks == good_blocks gives it away.  Up to 3 such a lock fails slots 1 and 2 of every
+//                 group and is dropped after three groups.
+//                 One wrong chip pair is a 2-bit burst after differential decoding: 2 is the recommended setting.
 //   groups        one record per four block slots (emitted at slot 3): {block[4], ok_mask, bit_index}; ok_mask bit s = slot s
 //                 passed, bit 4 = slot 2 carried C'.  bit_index = index of the group's first bit in the decoded bit stream.
 //   station       updated at each group from the blocks that passed: PI (A, or C' of version-B groups), PTY / TP (B);
 //                 groups 0A/0B: TA, MS, two PS characters from D at segment B & 3 (+ ps_mask); groups 2A/2B: RadioText, 2A four
 //                 characters from C and D (both must pass), 2B two from D; rt_mask per segment; a change of the A/B flag clears
 //                 the text (to spaces) and the mask.
-// Not decoded: every other group type (clock time, alternative frequencies, EON, TMC, open data applications).
+//   extension     fmrx_rds_station_ext, where the caller keeps one (Out::ext), from groups whose block B passed:
+//                 group_types bit 2*type + version.  0A/0B: decoder identification, bit (B>>2)&1 at position 3 - (B&3) of di,
+//                 the same position set in di_mask.  0A with C passed: two alternative-frequency codes, high byte first: 1..204
+//                 set that bit of the 256-bit set af_bits (87.5 + 0.1 code MHz); 224 + n sets af_announced = n (n <= 25); 250
+//                 in the high byte (an LF/MF frequency follows) makes the low byte ignored; everything else (205 the filler,
+//                 250 in the low byte, unassigned codes) is ignored.  1A with C passed: variant (C>>12)&7 = 0: ecc = C & 0xFF,
+//                 3: lang = C & 0xFFF; 1A with D passed (C or not): pin = D; ext_seen bits 0, 1, 2 say which are valid.  4A
+//                 with C and D passed: ct_mjd = ((B&3)<<15) | (C>>1), ct_hour = ((C&1)<<4) | (D>>12), ct_minute = (D>>6)&63,
+//                 ct_offset = D&63, ct_bit_index = the group's bit_index, ct_count + 1 -- all only if hour < 24 and minute < 60.
+//                 10A: a change of the A/B flag (B>>4)&1 clears ptyn (to spaces) and ptyn_mask; with C and D passed, four
+//                 characters at segment B&1.  The counters (corrected_blocks, burst_hist, sync_losses) are carried in Dec
+//                 and written by finish_ext.
+// Not decoded: EON (14A), TMC (8A), open data applications (3A and their groups), 2A/2B beyond the text, 1A's other variants.
 //
 // Floating point: fabs, add, multiply and compare only, in a fixed order, FP contraction off -- host and device compute the
-// same bits.  tests/_rds_station_model.py restates this file in Python.
+// same bits.  tests/_rds_station_model.py restates this file in Python, tests/_rds_station_ext_model.py its correction and
+// extension record.
 #pragma once
 #include <stdint.h>
 
@@ -59,11 +93,17 @@ constexpr double kPairHyst = 1.25;          // the other pairing must beat the c
 constexpr int kSyncLossBad = 6;             // bad blocks in a row that lose block sync
 constexpr uint32_t kSynA = 0x3D8, kSynB = 0x3D4, kSynC = 0x25C, kSynCp = 0x3CC, kSynD = 0x258;
 constexpr uint32_t kMask26 = (1u << 26) - 1, kMask27 = (1u << 27) - 1;
+constexpr int kMaxBurst = 5;                // the longest burst the (26,16) code locates uniquely
+constexpr int kBurstTableSize = 1024;       // one entry per syndrome: pattern in bits 0..25, burst length in bits 26..28 (0: none)
 
 // offset codes: 0 A, 1 B, 2 C, 3 C', 4 D, -1 none
 FMRX_SHD int offset_of(uint32_t syn)
 {
     return syn == kSynA ? 0 : syn == kSynB ? 1 : syn == kSynC ? 2 : syn == kSynCp ? 3 : syn == kSynD ? 4 : -1;
+}
+FMRX_SHD uint32_t syndrome_of_offset(int off)
+{
+    return off == 0 ? kSynA : off == 1 ? kSynB : off == 2 ? kSynC : off == 3 ? kSynCp : kSynD;
 }
 
 // the parity matrix of frame_sync (rds_common.cpp), row k for the k-th bit of the block (first received first)
@@ -75,6 +115,37 @@ FMRX_SHD uint32_t syndrome(uint32_t w)
 #pragma unroll
     for (int k = 0; k < 26; k++) s ^= ((w >> (25 - k)) & 1u) ? P[k] : 0u;
     return s;
+}
+
+// The correction table, by enumeration: every burst of length 1..5 that lies inside the 26 bits (first and last bit of the
+// burst wrong, the ones between either way), shortest first.  Host only, once; the kernel reads it from global memory.
+// Returns the number of entries filled (367), or -1 if two bursts met in one syndrome (they do not).
+inline int build_burst_table(uint32_t *t)
+{
+    for (int i = 0; i < kBurstTableSize; i++) t[i] = 0u;
+    int n = 0;
+    for (int len = 1; len <= kMaxBurst; len++)
+        for (int lo = 0; lo + len <= 26; lo++)                     // lo: the burst's last received bit, counted from bit 0
+            for (uint32_t mid = 0; mid < (len > 2 ? 1u << (len - 2) : 1u); mid++) {
+                const uint32_t ends = len == 1 ? 1u : (1u | (1u << (len - 1)));
+                const uint32_t pat = (ends | (mid << 1)) << lo;
+                const uint32_t s = syndrome(pat);
+                if (s == 0u || t[s] != 0u) return -1;
+                t[s] = pat | (static_cast<uint32_t>(len) << 26);
+                n++;
+            }
+    return n;
+}
+
+// A block that did not pass: sx = its syndrome ^ the expected offset's.  Repairs w and returns the burst's length where
+// exactly one burst of at most max_burst bits explains sx; 0 otherwise.
+FMRX_SHD int correct_block(uint32_t &w, uint32_t sx, int max_burst, const uint32_t *__restrict__ tab)
+{
+    const uint32_t e = tab[sx & 1023u];
+    const int len = static_cast<int>(e >> 26);
+    if (len == 0 || len > max_burst) return 0;
+    w ^= e & kMask26;
+    return len;
 }
 
 // Everything carried across calls except the per-phase energies E[sps] (the host decoder keeps them next to this struct, the
@@ -91,15 +162,19 @@ struct Dec {
     uint32_t hA, hB, hC, hCp, hD;          // per offset: matches over the last 27 bits (bit 26 = 26 bits ago)
     uint32_t blocks, good, groups;         // counters of the station record
     uint32_t pi, pty, tp, ta, ms, seen, ps_mask, rt_mask, rt_ab;
+    uint32_t max_burst;                    // the correction option, 0..5
+    uint32_t corr, bh1, bh2, bh3, bh4, bh5, losses;   // corrected blocks, by burst length; sync losses
 };
 
 struct Out {
     fmrx_rds_station *st;                  // PS / RT are written here as groups arrive; the rest by finish()
     fmrx_rds_group *g;                     // room for max_g records of this call
     uint32_t max_g, n_g;
+    const uint32_t *tab = nullptr;         // the correction table (build_burst_table); needed where max_burst > 0
+    fmrx_rds_station_ext *ext = nullptr;   // the extension record, written as groups arrive; may be null (nothing kept)
 };
 
-FMRX_SHD void init(Dec &d, int sps)
+FMRX_SHD void init(Dec &d, int sps, int max_burst = 0)
 {
     d.sps = sps; d.ph = 0; d.countdown = 0; d.cpar = 0;
     d.pair = 0; d.dprev = 0; d.synced = 0; d.slot = 0;
@@ -109,6 +184,8 @@ FMRX_SHD void init(Dec &d, int sps)
     d.hA = 0; d.hB = 0; d.hC = 0; d.hCp = 0; d.hD = 0;
     d.blocks = 0; d.good = 0; d.groups = 0;
     d.pi = 0; d.pty = 0; d.tp = 0; d.ta = 0; d.ms = 0; d.seen = 0; d.ps_mask = 0; d.rt_mask = 0; d.rt_ab = 2;
+    d.max_burst = static_cast<uint32_t>(max_burst);
+    d.corr = 0; d.bh1 = 0; d.bh2 = 0; d.bh3 = 0; d.bh4 = 0; d.bh5 = 0; d.losses = 0;
 }
 
 // the station record of a fresh decoder: zeros, PS and RT all spaces, rt_ab = 2 (no group 2 seen)
@@ -118,6 +195,31 @@ FMRX_SHD void clear_record(fmrx_rds_station *st)
     for (int i = 0; i < 6; i++) w[i] = 0u;
     for (int i = 6; i < 24; i++) w[i] = 0x20202020u;
     st->rt_ab = 2;
+}
+
+// the extension record of a fresh decoder: zeros, ptyn all spaces, ptyn_ab = 2 (no group 10A seen), the option echoed
+FMRX_SHD void clear_ext(fmrx_rds_station_ext *x, int max_burst)
+{
+    uint32_t *w = reinterpret_cast<uint32_t *>(x);
+    for (int i = 0; i < 32; i++) w[i] = 0u;
+    w[19] = 0x20202020u;
+    w[20] = 0x20202020u;
+    x->ptyn_ab = 2;
+    x->max_burst = static_cast<uint8_t>(max_burst);
+}
+
+// the counters of the extension record from the state (everything else is written as it arrives)
+FMRX_SHD void finish_ext(const Dec &d, fmrx_rds_station_ext *x)
+{
+    uint32_t *w = reinterpret_cast<uint32_t *>(x);
+    w[0] = d.corr;
+    w[1] = d.bh1;
+    w[2] = d.bh2;
+    w[3] = d.bh3;
+    w[4] = d.bh4;
+    w[5] = d.bh5;
+    w[6] = d.losses;
+    x->max_burst = static_cast<uint8_t>(d.max_burst);
 }
 
 // the scalar fields of the record from the state (the text is written as it arrives)
@@ -139,6 +241,71 @@ FMRX_SHD void put_block(Dec &d, int slot, uint32_t word, int off)
     d.ok |= 1u << slot;
     if (off == 3) d.ok |= 0x10u;
     d.good++;
+}
+
+// one alternative-frequency code of a group 0A
+FMRX_SHD void ext_af_code(fmrx_rds_station_ext *x, uint32_t code)
+{
+    if (code >= 1u && code <= 204u) x->af_bits[code >> 5] |= 1u << (code & 31u);
+    else if (code >= 224u && code <= 249u) x->af_announced = static_cast<uint8_t>(code - 224u);
+}
+
+// a group whose block B passed into the extension record (at most once per group: everything lives in memory)
+FMRX_SHD void ext_group(fmrx_rds_station_ext *x, uint32_t B, uint32_t Cw, uint32_t D, uint32_t ok, uint32_t gbit)
+{
+    const uint32_t gt = B >> 12, ver = (B >> 11) & 1u;
+    x->group_types |= 1u << (2u * gt + ver);
+    if (gt == 0) {
+        const uint32_t pos = 3u - (B & 3u);
+        x->di = static_cast<uint8_t>((x->di & ~(1u << pos)) | (((B >> 2) & 1u) << pos));
+        x->di_mask = static_cast<uint8_t>(x->di_mask | (1u << pos));
+        if (ver == 0 && (ok & 4u)) {
+            const uint32_t hi = Cw >> 8, lo = Cw & 0xFFu;
+            ext_af_code(x, hi);
+            if (hi != 250u) ext_af_code(x, lo);
+        }
+    } else if (ver != 0) {
+        return;                                                  // the rest are version-A groups
+    } else if (gt == 1) {
+        if (ok & 4u) {
+            const uint32_t var = (Cw >> 12) & 7u;
+            if (var == 0) {
+                x->ecc = static_cast<uint8_t>(Cw & 0xFFu);
+                x->ext_seen |= 1u;
+            } else if (var == 3) {
+                x->lang = static_cast<uint16_t>(Cw & 0xFFFu);
+                x->ext_seen |= 2u;
+            }
+        }
+        if (ok & 8u) {
+            x->pin = static_cast<uint16_t>(D);
+            x->ext_seen |= 4u;
+        }
+    } else if (gt == 4) {
+        const uint32_t hour = ((Cw & 1u) << 4) | (D >> 12), minute = (D >> 6) & 63u;
+        if ((ok & 0xCu) == 0xCu && hour < 24u && minute < 60u) {
+            x->ct_mjd = ((B & 3u) << 15) | (Cw >> 1);
+            x->ct_hour = static_cast<uint8_t>(hour);
+            x->ct_minute = static_cast<uint8_t>(minute);
+            x->ct_offset = static_cast<uint8_t>(D & 63u);
+            x->ct_bit_index = gbit;
+            x->ct_count++;
+        }
+    } else if (gt == 10) {
+        const uint32_t ab = (B >> 4) & 1u, seg = B & 1u;
+        if (ab != x->ptyn_ab) {
+            for (int i = 0; i < 8; i++) x->ptyn[i] = ' ';
+            x->ptyn_mask = 0;
+            x->ptyn_ab = static_cast<uint8_t>(ab);
+        }
+        if ((ok & 0xCu) == 0xCu) {
+            x->ptyn[4 * seg] = static_cast<char>(Cw >> 8);
+            x->ptyn[4 * seg + 1] = static_cast<char>(Cw & 0xFF);
+            x->ptyn[4 * seg + 2] = static_cast<char>(D >> 8);
+            x->ptyn[4 * seg + 3] = static_cast<char>(D & 0xFF);
+            x->ptyn_mask = static_cast<uint8_t>(x->ptyn_mask | (1u << seg));
+        }
+    }
 }
 
 FMRX_SHD void end_group(Dec &d, Out &o)
@@ -197,6 +364,7 @@ FMRX_SHD void end_group(Dec &d, Out &o)
             d.rt_mask |= 1u << seg;
         }
     }
+    if (o.ext) ext_group(o.ext, B, Cw, D, ok, d.gbit);
 }
 
 // one differentially decoded bit into block sync and group assembly
@@ -205,7 +373,8 @@ FMRX_SHD void feed_bit(Dec &d, int bit, Out &o)
     d.sr = (d.sr << 1) | static_cast<uint64_t>(bit & 1);
     d.nbits++;
     const uint32_t w = static_cast<uint32_t>(d.sr) & kMask26;
-    const int off = offset_of(syndrome(w));
+    const uint32_t syn = syndrome(w);
+    const int off = offset_of(syn);
     d.hA = ((d.hA << 1) | (off == 0 ? 1u : 0u)) & kMask27;
     d.hB = ((d.hB << 1) | (off == 1 ? 1u : 0u)) & kMask27;
     d.hC = ((d.hC << 1) | (off == 2 ? 1u : 0u)) & kMask27;
@@ -248,11 +417,30 @@ FMRX_SHD void feed_bit(Dec &d, int bit, Out &o)
         put_block(d, slot, w, off);
         d.bad = 0;
     } else {
-        d.bad++;
+        int len = 0, want = slot == 3 ? 4 : slot;
+        if (d.max_burst != 0u && (slot != 2 || (d.ok & 2u))) {
+            if (slot == 2) want = ((d.blk >> 27) & 1u) ? 3 : 2;     // the version bit of block B
+            uint32_t fixed = w;
+            len = correct_block(fixed, syn ^ syndrome_of_offset(want), static_cast<int>(d.max_burst), o.tab);
+            if (len) {
+                put_block(d, slot, fixed, want);
+                d.ok |= 0x100u << slot;                             // the corrected mask, fmrx_rds_group.reserved[0]
+                d.corr++;
+                d.bh1 += len == 1;
+                d.bh2 += len == 2;
+                d.bh3 += len == 3;
+                d.bh4 += len == 4;
+                d.bh5 += len == 5;
+            }
+        }
+        if (!len) d.bad++;
     }
     if (slot == 3) end_group(d, o);
     d.slot = (slot + 1) & 3;
-    if (d.bad >= static_cast<uint32_t>(kSyncLossBad)) d.synced = 0;
+    if (d.bad >= static_cast<uint32_t>(kSyncLossBad)) {
+        d.synced = 0;
+        d.losses++;
+    }
 }
 
 // one chip: pairing energies, pairing decision, and a bit when the chip completes a pair

@@ -1,7 +1,7 @@
 """RDS banks (fmrx_rds_bank_*): time per call against the number of channels, device-resident discriminator rows.
 
     python3 tools/rds_bank_bench.py [--mode 0] [--block 9600] [--channels 64,1024,4096,16384,65536] [--calls 8] [--warmup 2]
-                                    [--stations] [--json out.json]
+                                    [--stations [--max-burst 0..5] [--ext]] [--json out.json]
 
 Per channel count, reported separately:
   process_dev  device-event time of fmrx_rds_bank_process_dev (the whole signal chain + CDR lanes, on one stream)
@@ -14,6 +14,9 @@ twice, the second time with the bank's station decoders on (fmrx_rds_bank_set_st
   stations_ms              host time of the fmrx_rds_bank_stations call (records + groups D2H), preallocated buffers
   collect_c_ms             host time of the fmrx_rds_bank_collect call on the same bank, preallocated buffers, no rows
   ps_right                 channels whose decoded PS name is the transmitted one after the last call
+--max-burst B runs those decoders with burst error correction (fmrx_rds_bank_set_station_options); --ext keeps the extension
+records and adds
+  stations_ext_ms          host time of the fmrx_rds_bank_stations_ext call (records D2H), preallocated buffer
 and, once: float64 operations per IF sample counted from the shapes, and the single-stream handle (fmrx_rds: the bank's chain
 with one channel, without the CDR lanes) on one of the same streams: process_dev device time and fmrx_rds_process host time per
 block (input H2D, the chain, the matched-filter rows D2H, host CDR and frame synchronisation).  Channel counts that do not fit the device's free
@@ -66,8 +69,12 @@ def stations_leg(fmrx, a, p, n, block, calls, d_src, S, stream, ps_of) -> dict:
     (alternate calls; either takes a call off the not-collected rule)."""
     import torch
     bank = fmrx.RdsBank(a.mode, n, block)
-    bank.set_stations(True)
+    if a.max_burst or a.ext:
+        bank.set_stations(True, max_burst=a.max_burst, ext=a.ext)
+    else:
+        bank.set_stations(True)                      # no station options: the bank as it runs without them
     L, h = fmrx.lib, bank._h
+    xr = np.zeros(n, fmrx.RDS_STATION_EXT_DTYPE) if a.ext else None
     mg = bank.max_groups
     st = np.zeros(n, fmrx.RDS_STATION_DTYPE)
     g = np.zeros((n, mg), fmrx.RDS_GROUP_DTYPE)
@@ -77,7 +84,7 @@ def stations_leg(fmrx, a, p, n, block, calls, d_src, S, stream, ps_of) -> dict:
     off = ctypes.create_string_buffer(8 * n)
     rows = torch.empty((n, block), dtype=torch.float32, device="cuda")
     idx = torch.arange(n, device="cuda") % S
-    pd, t_st, t_co = [], [], []
+    pd, t_st, t_co, t_x = [], [], [], []
     for k in range(calls):
         rows.copy_(d_src[idx, k * block:(k + 1) * block])
         torch.cuda.synchronize()
@@ -90,6 +97,11 @@ def stations_leg(fmrx, a, p, n, block, calls, d_src, S, stream, ps_of) -> dict:
         if k % 2 == 0 or k == calls - 1:
             fmrx._check(L.fmrx_rds_bank_stations(h, st.ctypes.data, g.ctypes.data, ng.ctypes.data))
             dt, lst = 1e3 * (time.perf_counter() - t0), t_st
+            if a.ext:
+                t1 = time.perf_counter()
+                fmrx._check(L.fmrx_rds_bank_stations_ext(h, xr.ctypes.data))
+                if k >= a.warmup:
+                    t_x.append(1e3 * (time.perf_counter() - t1))
         else:
             fmrx._check(L.fmrx_rds_bank_collect(h, None, None, bits.ctypes.data, nb.ctypes.data, off))
             dt, lst = 1e3 * (time.perf_counter() - t0), t_co
@@ -99,8 +111,14 @@ def stations_leg(fmrx, a, p, n, block, calls, d_src, S, stream, ps_of) -> dict:
     ps_right = sum(bytes(st[c]["ps"]).decode("latin-1") == ps_of[c % S] for c in range(n))
     bank.close()
     del rows
-    return {"process_dev_stations_ms": statistics.median(pd), "stations_ms": statistics.median(t_st),
-            "collect_c_ms": statistics.median(t_co) if t_co else None, "max_groups": int(mg), "ps_right": int(ps_right)}
+    out = {"process_dev_stations_ms": statistics.median(pd), "stations_ms": statistics.median(t_st),
+           "collect_c_ms": statistics.median(t_co) if t_co else None, "max_groups": int(mg), "ps_right": int(ps_right)}
+    if a.max_burst or a.ext:
+        out["max_burst"], out["ext"] = a.max_burst, bool(a.ext)
+    if a.ext:
+        out["stations_ext_ms"] = statistics.median(t_x)
+        out["corrected_blocks"] = int(xr["corrected_blocks"].sum())
+    return out
 
 
 def main() -> int:
@@ -111,6 +129,8 @@ def main() -> int:
     ap.add_argument("--calls", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--stations", action="store_true")
+    ap.add_argument("--max-burst", type=int, default=0, help="with --stations: burst error correction of the station decoders")
+    ap.add_argument("--ext", action="store_true", help="with --stations: keep and read the extension records")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
 
