@@ -860,6 +860,91 @@ FMRX_API int fmrx_meters_collect(fmrx_meters *m, fmrx_meter *out);
 FMRX_API int fmrx_meters_process(fmrx_meters *m, const uint8_t *iq, size_t iq_pitch_bytes, size_t n_iq_bytes, const float *demod,
                                  size_t demod_pitch, size_t n_if, fmrx_meter *out);
 
+/* ------------------------------------------------------------------ */
+/* Stereo blend and soft mute, driven by the meters                     */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  The last stage behind a bank: from the pilot and guard-band noise powers the meters leave
+ * on the device it decides, per channel and call, a stereo lamp, how far to blend left and right towards mono, and how far
+ * to mute -- and applies both, ramped across the call, to the audio the bank wrote.  capture -> tuner -> bank -> meters ->
+ * blend on one stream, no host round trip.  A stage with a handle of its own; it changes nothing in front of it.
+ * Defined by tests/_blend_model.py; host and device equal that model bit for bit.
+ *
+ * Control (float64, per channel and call; every step one IEEE operation, no fused multiply-add, no sqrt, no log).  From
+ * the MPX group of the channel's meter record:
+ *   noise = (probe[17k] + probe[21k]) * 0.5       pilot ratio r_p = probe[19k] / noise       quieting r_q = ref / noise,
+ *   ref = ((2 pi 7500 / if_Fs) * 256)^2 * segments: the windowed power a nominal pilot of 7.5 kHz deviation reads.
+ *   drive d = plog2(r) = e + (m - 1) with r = m 2^e, m in [1, 2) (Mitchell's pseudo-logarithm through frexp: exact pieces,
+ *   one rounded addition; within 0.0861 of log2 r, which is 0.26 dB).  Edge rule, as the meters' dB values: a numerator that
+ *   is not > 0 (NaN included) gives d = -infinity; otherwise a denominator that is not > 0 gives d = +infinity; a quotient
+ *   that underflows to 0 (or is not a number) reads -infinity, one that overflows +infinity.
+ *   Thresholds are given in dB and divided by the literal 3.010299956639812 on the host; ramp(d; lo, hi) =
+ *   clamp((d - lo) * (1 / (hi - lo)), 0, 1).
+ *   lamp      hysteresis on d_p: on at d_p >= pilot_on, off at d_p < pilot_off, otherwise kept (off at the start)
+ *   targets   separation t_b = lamp ? ramp(d_p; blend_lo, blend_hi) : 0;  gain t_m = floor + (1 - floor) * ramp(d_q; mute_lo, mute_hi)
+ *   smoothing first call after create / reset: s = t.  Afterwards s = s + c * (t - s), c = attack where t < s and release
+ *             otherwise; then s = t where |t - s| <= 2^-10 (a station that recovers reaches exactly 1).
+ *   end points (float32): mono1 = (float)(1 - s_b), gain1 = (float)s_m; mono0, gain0 = the previous call's (the first call: equal)
+ * Apply (float32, sample k of the call's n = n_audio; inv_n = (float)(1.0 / n)):
+ *   a[k] = clamp(fmaf((float)(k + 1), (mono1 - mono0) * inv_n, mono0), 0, 1), m[k] likewise from gain0, gain1;
+ *   D = 0.5f * (L - R);  l = a[k] == 0 ? L : fmaf(-a[k], D, L);  r = a[k] == 0 ? R : fmaf(a[k], D, R);  L' = m[k] * l, R' = m[k] * r.
+ *   Full separation and full gain return the input bit for bit (-0 included); mono rows (audio_channels = 1) take the gain only.
+ *   PCM: the library's pack of L', R' (pcm_policy), interleaved [n_channels][n_audio][audio_channels] as the banks write it.
+ *
+ * Defaults (fmrx_blend_defaults) -- design choices, not measurements of any receiver: lamp on / off at 20 / 14 dB of pilot
+ * ratio; blend from mono at 20 dB to full separation at 32 dB; mute from the floor at 10 dB of quieting to full gain at
+ * 24 dB; mute_floor 0 (silence between stations); attack 1 (a call that reads worse takes effect at once, ramped across
+ * that call), release 0.25 per call.  fmrx_blend_create / fmrx_blend_control return FMRX_EINVAL unless blend_hi > blend_lo,
+ * mute_hi > mute_lo, pilot_on >= pilot_off, 0 <= mute_floor <= 1, 0 < attack, release <= 1 and everything is finite. */
+typedef struct fmrx_blend_params {
+    double pilot_on, pilot_off, blend_lo, blend_hi, mute_lo, mute_hi;   /* dB */
+    double mute_floor, attack, release;
+} fmrx_blend_params;
+/* Per channel: what the last call decided, and the state the next one starts from.  pilot_db / quiet_db: the drives times
+ * 3.010299956639812 (pseudo-dB; -+infinity by the edge rule). */
+typedef struct fmrx_blend_status {
+    double pilot_db, quiet_db;
+    double sep_target, gain_target;   /* t_b, t_m */
+    double sep, gain;                 /* s_b, s_m */
+    float mono0, gain0, mono1, gain1; /* the last call's ramps: from (mono0, gain0) to (mono1, gain1) */
+    uint32_t lamp, reserved;
+    uint64_t calls;                   /* since create / reset; 0 = the next call is a first call */
+} fmrx_blend_status;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_blend_params) == 72, "fmrx_blend_params layout");
+static_assert(sizeof(fmrx_blend_status) == 80, "fmrx_blend_status layout");
+#else
+_Static_assert(sizeof(fmrx_blend_params) == 72, "fmrx_blend_params layout");
+_Static_assert(sizeof(fmrx_blend_status) == 80, "fmrx_blend_status layout");
+#endif
+typedef struct fmrx_blend fmrx_blend;
+FMRX_API int fmrx_blend_defaults(fmrx_blend_params *p);
+/* Host code, no device needed: one channel's control step on one record (only probe[0 .. 5) and segments are read); *state
+ * is read and replaced.  A zeroed status is a fresh channel.  The function the control kernel runs (blend_control.hpp). */
+FMRX_API int fmrx_blend_control(const fmrx_blend_params *p, double if_Fs, const fmrx_meter *rec, fmrx_blend_status *state_in_out);
+/* n_audio: samples per row and call (fmrx_channels_n_audio); audio_channels 1 or 2 */
+FMRX_API int fmrx_blend_create(fmrx_blend **out, const fmrx_blend_params *p, double if_Fs, int n_channels, int audio_channels,
+                               size_t n_audio, int device);
+FMRX_API int fmrx_blend_destroy(fmrx_blend *b);
+/* channel < 0: all.  Waits for the handle's last call; the rows are clear when it returns, for a later call on any stream. */
+FMRX_API int fmrx_blend_reset(fmrx_blend *b, int channel);
+/* Asynchronous on `stream`, after fmrx_meters_process_dev on the same stream: reads the MPX results of m's last call where
+ * they lie on the device.  FMRX_EINVAL where that call had no discriminator rows (n_if = 0: the fused mono bank of modes 0/1
+ * keeps none) or m has another channel count or device.  d_in [n_channels][audio_channels][n_audio] as
+ * fmrx_channels_process_dev writes it; d_out the same shape, d_out == d_in allowed (no other overlap); d_pcm16
+ * [n_channels][n_audio][audio_channels]; d_out or d_pcm16 may be NULL, not both.  Stereo rows that are 16-byte aligned
+ * (d_in, d_out and d_pcm16 are, and n_audio is a multiple of 4) move in 16-byte pieces; all others 4 bytes at a time, the
+ * same arithmetic. */
+FMRX_API int fmrx_blend_process_dev(fmrx_blend *b, const fmrx_meters *m, const float *d_in, float *d_out, int16_t *d_pcm16,
+                                    int pcm_policy, void *stream);
+/* Host rows and host records [n_channels], synchronous (it first waits for the handle's last call, whatever stream that was
+ * on): the records' MPX groups are uploaded in the meters' layout and the
+ * same two kernels run (the single-stream use: n_channels = 1 with fmrx_meters_process's record).  out == in allowed (the
+ * device pass then runs in place); the device copies keep each host pointer's address modulo 16, so a host row that is not
+ * 16-byte aligned takes the 4-byte path. */
+FMRX_API int fmrx_blend_process(fmrx_blend *b, const fmrx_meter *recs, const float *in, float *out, int16_t *pcm16, int pcm_policy);
+/* out [n_channels]; waits for the handle's last call (an event it recorded), not for the device */
+FMRX_API int fmrx_blend_status_get(fmrx_blend *b, fmrx_blend_status *out);
+
 #ifdef __cplusplus
 }
 #endif

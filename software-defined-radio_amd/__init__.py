@@ -1285,6 +1285,123 @@ class Meters:
         return metersDerive(self.if_Fs, rec)
 
 
+# --------------------------------------------------------------------------
+# Stereo blend and soft mute behind a bank, driven by the meters
+# --------------------------------------------------------------------------
+class BlendParams(C.Structure):
+    """struct fmrx_blend_params: thresholds in dB, mute_floor in [0, 1], attack / release per call in (0, 1].  BlendParams()
+    holds the library's defaults; keyword arguments replace single fields."""
+    _fields_ = [(k, C.c_double) for k in ("pilot_on", "pilot_off", "blend_lo", "blend_hi", "mute_lo", "mute_hi", "mute_floor",
+                                          "attack", "release")]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(lib.fmrx_blend_defaults(C.byref(self)))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"BlendParams has no field {k!r}")
+            setattr(self, k, float(v))
+
+
+BLEND_STATUS_DTYPE = np.dtype([("pilot_db", "<f8"), ("quiet_db", "<f8"), ("sep_target", "<f8"), ("gain_target", "<f8"), ("sep", "<f8"),
+                               ("gain", "<f8"), ("mono0", "<f4"), ("gain0", "<f4"), ("mono1", "<f4"), ("gain1", "<f4"), ("lamp", "<u4"),
+                               ("reserved", "<u4"), ("calls", "<u8")])                 # struct fmrx_blend_status
+assert BLEND_STATUS_DTYPE.itemsize == 80 and C.sizeof(BlendParams) == 72
+_sig("fmrx_blend_defaults", [C.POINTER(BlendParams)])
+_sig("fmrx_blend_control", [C.POINTER(BlendParams), _dbl, _vp, _vp])
+_sig("fmrx_blend_create", [C.POINTER(_vp), C.POINTER(BlendParams), _dbl, _int, _int, _sz, _int])
+_sig("fmrx_blend_destroy", [_vp])
+_sig("fmrx_blend_reset", [_vp, _int])
+_sig("fmrx_blend_process_dev", [_vp, _vp, _vp, _vp, _vp, _int, _vp])
+_sig("fmrx_blend_process", [_vp, _vp, _vp, _vp, _vp, _int])
+_sig("fmrx_blend_status_get", [_vp, _vp])
+
+
+def blendControl(params, if_Fs, rec, state=None) -> np.ndarray:
+    """Host only: one channel's control step (fmrx_blend_control) on one METER_DTYPE record; state: the BLEND_STATUS_DTYPE
+    record the last step returned (None or zeros: a fresh channel) -> the new one."""
+    r = np.array(rec, dtype=METER_DTYPE).reshape(1)
+    st = np.zeros(1, BLEND_STATUS_DTYPE) if state is None else np.array(state, dtype=BLEND_STATUS_DTYPE).reshape(1).copy()
+    p = params if params is not None else BlendParams()
+    _check(lib.fmrx_blend_control(C.byref(p), float(if_Fs), r.ctypes.data, st.ctypes.data))
+    return st[0]
+
+
+class Blend:
+    """Stereo lamp, blend towards mono and soft mute per channel of a receiver bank, decided from the meters' pilot and noise
+    powers of the same call and applied to the bank's audio (fmrx_blend_*).  blend = Blend.for_bank(bank,
+    meters); after bank.process_dev(d_audio, ..., stream=s) and meters.process_bank(stream=s):
+    blend.process_bank(d_audio, d_out, d_pcm, stream=s); blend.status()."""
+
+    def __init__(self, if_Fs, n_channels=1, audio_channels=2, n_audio=1920, params: BlendParams | None = None, device=0):
+        self.if_Fs, self.n_channels, self.audio_channels, self.n_audio = float(if_Fs), int(n_channels), int(audio_channels), int(n_audio)
+        self.params = params if params is not None else BlendParams()
+        self._meters = None
+        self._h = _vp()
+        _check(lib.fmrx_blend_create(C.byref(self._h), C.byref(self.params), self.if_Fs, self.n_channels, self.audio_channels,
+                                     self.n_audio, device))
+
+    @classmethod
+    def for_bank(cls, bank, meters, params: BlendParams | None = None):
+        """The blend stage of a Channels bank and of the Meters made for it, on the bank's device."""
+        b = cls(bank.params.if_Fs, bank.n_channels, bank.audio_channels, bank.n_audio, params, bank.device)
+        b._meters = meters
+        return b
+
+    @staticmethod
+    def coef(tau_s, call_s) -> float:
+        """The attack / release coefficient of a time constant tau_s at one call every call_s seconds: 1 - exp(-call_s / tau_s)."""
+        return 1.0 - float(np.exp(-float(call_s) / float(tau_s)))
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_blend_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, channel=-1):
+        _check(lib.fmrx_blend_reset(self._h, channel))
+
+    def process_dev(self, meters, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
+        """Device rows [n_channels, audio_channels, n_audio] float32 -> d_out (may be d_in) and / or d_pcm [n_channels, n_audio,
+        audio_channels] int16, asynchronous on `stream` behind meters.process_dev on the same stream."""
+        _check(lib.fmrx_blend_process_dev(self._h, meters._h, d_in, d_out, d_pcm, PCM_WRAP if wrap else PCM_SATURATE, stream))
+
+    def process_bank(self, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
+        """process_dev with the Meters given to for_bank."""
+        self.process_dev(self._meters, d_in, d_out, d_pcm, stream, wrap)
+
+    def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True, in_place=False):
+        """Host records METER_DTYPE [n_channels] and host rows float32 [n_channels, audio_channels, n_audio], synchronous ->
+        dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]); in_place: the device pass writes over its input (audio
+        is then an array of its own, never the caller's).  The rows keep their host address modulo 16 on the device."""
+        r = np.ascontiguousarray(recs, dtype=METER_DTYPE).reshape(self.n_channels)
+        shape = (self.n_channels, self.audio_channels, self.n_audio)
+        x = _f32(audio).reshape(shape)
+        f = s = None
+        if want_f32:
+            if in_place:
+                pad = np.zeros(x.size + 4, np.float32)           # a copy at the caller's address modulo 16
+                o = ((x.ctypes.data - pad.ctypes.data) % 16) // 4
+                f = pad[o:o + x.size].reshape(shape)
+                f[...] = x
+                x = f
+            else:
+                f = np.zeros(shape, np.float32)
+        if want_pcm:
+            s = np.zeros((self.n_channels, self.n_audio, self.audio_channels), np.int16)
+        _check(lib.fmrx_blend_process(self._h, r.ctypes.data, x.ctypes.data, None if f is None else f.ctypes.data,
+                                      None if s is None else s.ctypes.data, PCM_WRAP if wrap else PCM_SATURATE))
+        return {"audio": f, "pcm16": s}
+
+    def status(self) -> np.ndarray:
+        """Waits for the last call; BLEND_STATUS_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, BLEND_STATUS_DTYPE)
+        _check(lib.fmrx_blend_status_get(self._h, out.ctypes.data))
+        return out
+
+
 class FrontEndPlan:
     """Reusable device-side tap tables for the fused front-end kernel (fmrx_fe_plan)."""
 

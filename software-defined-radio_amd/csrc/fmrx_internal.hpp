@@ -402,5 +402,26 @@ int meters_rf_launch(const uint8_t *d_iq, size_t pitch, size_t n_bytes, int n_ch
 // d_table: re [5][1024] then im [5][1024]; at most max_blocks workgroups walk the channels
 int meters_mpx_launch(const float *d_x, size_t pitch, size_t n_if, int n_channels, const double *d_table, double *d_out, int max_blocks,
                       hipStream_t s);
+// what a meters handle's last call left on the device, for a stage behind it on the same stream (blend.hip): the MPX
+// results [n_channels][kMetersMpxFields], and that call's n_if (0: no discriminator rows were given; ran false: no call yet)
+struct MetersMpx {
+    const double *d_mpx;
+    size_t n_if;
+    int n_channels, device;
+    bool ran;
+};
+MetersMpx meters_mpx(const fmrx_meters *m);
+
+// ---- stereo blend and soft mute (kernels_blend.hip; control step in blend_control.hpp; handle and C ABI in blend.hip) -----------------
+namespace blend {
+struct Control;
+}
+// one lane per channel: d_status[c] <- control_step on d_mpx[c]'s probes; segments from d_seg_each[c], or seg_all where that is NULL
+int blend_control_launch(const blend::Control &c, const double *d_mpx, const unsigned long long *d_seg_each, unsigned long long seg_all,
+                         fmrx_blend_status *d_status, int n_channels, hipStream_t s);
+// d_in [n_channels][audio_channels][n_audio] -> d_out (the same shape; may be d_in or NULL) and d_pcm [n_channels][n_audio][audio_channels]
+// (may be NULL), ramped between the end points in d_status; float rows 4-byte aligned, n_audio <= 2^26
+int blend_apply_launch(const float *d_in, float *d_out, int16_t *d_pcm, const fmrx_blend_status *d_status, int n_channels, int audio_channels,
+                       size_t n_audio, float inv_n, int wrap, hipStream_t s);
 
 }  // namespace fmrx

@@ -62,6 +62,8 @@ double mean(double a, double n) { return n > 0.0 ? a / n : 0.0; }
 
 }  // namespace
 
+fmrx::MetersMpx fmrx::meters_mpx(const fmrx_meters *m) { return MetersMpx{m->d_mpx.p, m->n_if, m->n_channels, m->device, m->ran}; }
+
 extern "C" {
 
 int fmrx_meters_probes(double hz[8], int *n)
