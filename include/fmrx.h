@@ -945,6 +945,95 @@ FMRX_API int fmrx_blend_process(fmrx_blend *b, const fmrx_meter *recs, const flo
 /* out [n_channels]; waits for the handle's last call (an event it recorded), not for the device */
 FMRX_API int fmrx_blend_status_get(fmrx_blend *b, fmrx_blend_status *out);
 
+/* ------------------------------------------------------------------ */
+/* Variable high-cut, driven by the meters                              */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  The third thing a receiver does with a weak signal, behind the blend (or directly behind a
+ * bank): a one-pole low-pass per audio row whose corner moves with the channel's quieting, from above Nyquist (transparent)
+ * down to fc_min.  capture -> tuner -> bank -> meters -> blend -> high-cut on one stream, no host round trip.  A stage with a
+ * handle of its own; it changes nothing in front of it.  Defined by tests/_highcut_model.py; host and
+ * device equal that model bit for bit.
+ *
+ * Design (host, float64): p_max_d = exp(-2 pi fc_min / audio_Fs), p_max = (float)p_max_d; FMRX_EINVAL unless fc_min and
+ * audio_Fs are finite and > 0 and p_max <= 0.875 (beyond that pole the built-in lanes of the parallel walk start to miss on
+ * ordinary audio; at 48 kHz that is fc_min >= 1 020.1 Hz).  The pole moves linearly with the cut: 0 is transparent, p_max
+ * has its -3 dB corner at fc_min.  No transcendental function runs on the device.
+ * Control (float64, per channel and call; the blend's arithmetic and edge rules, one IEEE operation per step):
+ *   noise and the quieting drive d_q exactly as the blend forms them (ref * segments / noise through plog2);
+ *   openness target t_o = (1 - cut_max) + cut_max * ramp(d_q; hc_lo, hc_hi);
+ *   smoothing as the blend's: a first call takes s_o = t_o; attack where t_o < s_o, release otherwise; the 2^-10 snap;
+ *   end points (float32): p1 = (float)((1 - s_o) * p_max_d); p0 = the previous call's p1 (a first call: equal).
+ * Apply (float32, per row; both rows of a stereo channel use the channel's poles; y_prev = +0 at the start of a stream, carried
+ * across calls; sample k of the call's n = n_audio, inv_n = (float)(1.0 / n)):
+ *   p[k] = clamp(fmaf((float)(k + 1), (p1 - p0) * inv_n, p0), 0, p_max)
+ *   q = 1 - p[k];  v = q * x[k];  y = fmaf(p[k], y_prev, v);  if |y| < 2^-126: y = +0
+ *   y[k] = p[k] == 0 ? x[k] : y;  y_prev = y[k]
+ *   A channel at cut 0 returns its input bit for bit (-0, subnormals and NaN included: two NaNs are the same value).
+ *   PCM: the library's pack of y (pcm_policy), interleaved [n_channels][n_audio][audio_channels] as the banks write it.
+ * The device walks the recurrence parallel in time (lanes of `segment` samples that start `warmup` samples early, a verify
+ * step, a serial repair of the misses) and returns the serial walk's bits whatever the lane shape.
+ *
+ * Defaults (fmrx_highcut_defaults) -- design choices, not measurements of any receiver: fc_min 2 500 Hz; no cut from 36 dB of
+ * quieting (hc_hi), full cut at 16 dB (hc_lo); cut_max 1; attack 1 (a call that reads worse takes effect at once, ramped
+ * across that call), release 0.25 per call; warmup and segment -1 (the built-in lane shape, 256 and 256).
+ * fmrx_highcut_create / fmrx_highcut_control return FMRX_EINVAL unless hc_hi > hc_lo, 0 <= cut_max <= 1, 0 < attack,
+ * release <= 1, warmup in -1 .. 2^20, segment -1 or 1 .. 2^20, the design's conditions hold and everything is finite. */
+typedef struct fmrx_highcut_params {
+    double fc_min;          /* Hz: the corner at full cut */
+    double hc_lo, hc_hi;    /* dB of quieting: full cut at and below hc_lo, none from hc_hi */
+    double cut_max, attack, release;
+    int32_t warmup, segment;   /* the parallel walk's lane shape; -1 = built-in */
+} fmrx_highcut_params;
+/* Per channel: what the last call decided, and the state the next one starts from.  quiet_db as fmrx_blend_status's. */
+typedef struct fmrx_highcut_status {
+    double quiet_db;
+    double open_target, open;   /* t_o, s_o: 1 = no cut */
+    float p0, p1;               /* the last call's pole ramp */
+    uint64_t calls;             /* since create / reset; 0 = the next call is a first call */
+} fmrx_highcut_status;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_highcut_params) == 56, "fmrx_highcut_params layout");
+static_assert(sizeof(fmrx_highcut_status) == 40, "fmrx_highcut_status layout");
+#else
+_Static_assert(sizeof(fmrx_highcut_params) == 56, "fmrx_highcut_params layout");
+_Static_assert(sizeof(fmrx_highcut_status) == 40, "fmrx_highcut_status layout");
+#endif
+typedef struct fmrx_highcut fmrx_highcut;
+FMRX_API int fmrx_highcut_defaults(fmrx_highcut_params *p);
+/* Host code, no device needed: one channel's control step on one record (only probe[0 .. 5) and segments are read); *state
+ * is read and replaced.  A zeroed status is a fresh channel.  The function the control kernel runs (highcut_control.hpp). */
+FMRX_API int fmrx_highcut_control(const fmrx_highcut_params *p, double if_Fs, double audio_Fs, const fmrx_meter *rec,
+                                  fmrx_highcut_status *state_in_out);
+/* Host code: the design alone, *p_max = the float32 pole at full cut; FMRX_EINVAL as stated above */
+FMRX_API int fmrx_highcut_design(double fc_min, double audio_Fs, float *p_max);
+/* n_audio: samples per row and call (fmrx_channels_n_audio); audio_channels 1 or 2 */
+FMRX_API int fmrx_highcut_create(fmrx_highcut **out, const fmrx_highcut_params *p, double if_Fs, double audio_Fs, int n_channels,
+                                 int audio_channels, size_t n_audio, int device);
+FMRX_API int fmrx_highcut_destroy(fmrx_highcut *h);
+/* channel < 0: all.  Clears the status row and the filter state of the channel's rows.  Waits for the handle's last call; the
+ * rows are clear when it returns, for a later call on any stream. */
+FMRX_API int fmrx_highcut_reset(fmrx_highcut *h, int channel);
+/* on != 0: every later call walks its rows serially, one lane per row (the kernel the parallel walk is measured against); the
+ * bits are the same, fmrx_highcut_diagnostics counts nothing for such calls.  Waits for the handle's last call. */
+FMRX_API int fmrx_highcut_set_force(fmrx_highcut *h, int on);
+/* Asynchronous on `stream`, after fmrx_meters_process_dev on the same stream (and after the blend, where there is one): reads
+ * the MPX results of m's last call where they lie on the device.  FMRX_EINVAL where that call had no discriminator rows
+ * (n_if = 0: the fused mono bank of modes 0/1 keeps none) or m has another channel count or device.  Shapes and alignment as
+ * fmrx_blend_process_dev: d_in [n_channels][audio_channels][n_audio], d_out the same shape, d_out == d_in allowed (no other
+ * overlap; the call then filters a copy of the rows it keeps in the handle); d_pcm16 [n_channels][n_audio][audio_channels];
+ * d_out or d_pcm16 may be NULL, not both; float rows 4-byte aligned, PCM 2-byte. */
+FMRX_API int fmrx_highcut_process_dev(fmrx_highcut *h, const fmrx_meters *m, const float *d_in, float *d_out, int16_t *d_pcm16,
+                                      int pcm_policy, void *stream);
+/* Host rows and host records [n_channels], synchronous (it first waits for the handle's last call): the single-stream use is
+ * n_channels = 1 with fmrx_meters_process's record.  out == in allowed; the device copies keep each host pointer's address
+ * modulo 16. */
+FMRX_API int fmrx_highcut_process(fmrx_highcut *h, const fmrx_meter *recs, const float *in, float *out, int16_t *pcm16, int pcm_policy);
+/* out [n_channels]; waits for the handle's last call (an event it recorded), not for the device */
+FMRX_API int fmrx_highcut_status_get(fmrx_highcut *h, fmrx_highcut_status *out);
+/* Since create: the segment boundaries the verify step checked and the segments it walked again (as
+ * fmrx_channels_deemph_diagnostics); waits for the handle's last call.  Either pointer may be NULL. */
+FMRX_API int fmrx_highcut_diagnostics(fmrx_highcut *h, unsigned long long *segments, unsigned long long *missed);
+
 #ifdef __cplusplus
 }
 #endif

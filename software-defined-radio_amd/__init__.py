@@ -1402,6 +1402,140 @@ class Blend:
         return out
 
 
+# --------------------------------------------------------------------------
+# Variable high-cut behind the blend (or a bank), driven by the meters
+# --------------------------------------------------------------------------
+class HighCutParams(C.Structure):
+    """struct fmrx_highcut_params: fc_min in Hz, hc_lo / hc_hi in dB of quieting, cut_max in [0, 1], attack / release per call in
+    (0, 1], warmup / segment the parallel walk's lane shape (-1 = built-in).  HighCutParams() holds the library's defaults;
+    keyword arguments replace single fields."""
+    _fields_ = [(k, C.c_double) for k in ("fc_min", "hc_lo", "hc_hi", "cut_max", "attack", "release")] + \
+               [("warmup", C.c_int32), ("segment", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _check(lib.fmrx_highcut_defaults(C.byref(self)))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError(f"HighCutParams has no field {k!r}")
+            setattr(self, k, int(v) if kinds[k] is C.c_int32 else float(v))
+
+
+HIGHCUT_STATUS_DTYPE = np.dtype([("quiet_db", "<f8"), ("open_target", "<f8"), ("open", "<f8"), ("p0", "<f4"), ("p1", "<f4"),
+                                 ("calls", "<u8")])                                 # struct fmrx_highcut_status
+assert HIGHCUT_STATUS_DTYPE.itemsize == 40 and C.sizeof(HighCutParams) == 56
+_sig("fmrx_highcut_defaults", [C.POINTER(HighCutParams)])
+_sig("fmrx_highcut_design", [_dbl, _dbl, C.POINTER(C.c_float)])
+_sig("fmrx_highcut_control", [C.POINTER(HighCutParams), _dbl, _dbl, _vp, _vp])
+_sig("fmrx_highcut_create", [C.POINTER(_vp), C.POINTER(HighCutParams), _dbl, _dbl, _int, _int, _sz, _int])
+_sig("fmrx_highcut_destroy", [_vp])
+_sig("fmrx_highcut_reset", [_vp, _int])
+_sig("fmrx_highcut_set_force", [_vp, _int])
+_sig("fmrx_highcut_process_dev", [_vp, _vp, _vp, _vp, _vp, _int, _vp])
+_sig("fmrx_highcut_process", [_vp, _vp, _vp, _vp, _vp, _int])
+_sig("fmrx_highcut_status_get", [_vp, _vp])
+_sig("fmrx_highcut_diagnostics", [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
+
+
+def highCutDesign(fc_min, audio_Fs) -> np.float32:
+    """Host only: the float32 pole at full cut, float32(exp(-2 pi fc_min / audio_Fs)); FmrxError where it exceeds 0.875."""
+    p = C.c_float()
+    _check(lib.fmrx_highcut_design(float(fc_min), float(audio_Fs), C.byref(p)))
+    return np.float32(p.value)
+
+
+def highCutControl(params, if_Fs, audio_Fs, rec, state=None) -> np.ndarray:
+    """Host only: one channel's control step (fmrx_highcut_control) on one METER_DTYPE record; state: the HIGHCUT_STATUS_DTYPE
+    record the last step returned (None or zeros: a fresh channel) -> the new one."""
+    r = np.array(rec, dtype=METER_DTYPE).reshape(1)
+    st = np.zeros(1, HIGHCUT_STATUS_DTYPE) if state is None else np.array(state, dtype=HIGHCUT_STATUS_DTYPE).reshape(1).copy()
+    p = params if params is not None else HighCutParams()
+    _check(lib.fmrx_highcut_control(C.byref(p), float(if_Fs), float(audio_Fs), r.ctypes.data, st.ctypes.data))
+    return st[0]
+
+
+class HighCut:
+    """A one-pole low-pass per audio row of a receiver bank whose corner follows the channel's quieting, decided from the
+    meters' noise powers of the same call (fmrx_highcut_*).  hc = HighCut.for_bank(bank, meters); after
+    bank.process_dev, meters.process_bank and (where there is one) blend.process_bank on stream s:
+    hc.process_bank(d_audio, d_out, d_pcm, stream=s); hc.status(); hc.diagnostics()."""
+
+    def __init__(self, if_Fs, audio_Fs=48000.0, n_channels=1, audio_channels=2, n_audio=1920, params: HighCutParams | None = None, device=0):
+        self.if_Fs, self.audio_Fs = float(if_Fs), float(audio_Fs)
+        self.n_channels, self.audio_channels, self.n_audio = int(n_channels), int(audio_channels), int(n_audio)
+        self.params = params if params is not None else HighCutParams()
+        self._meters = None
+        self._h = _vp()
+        _check(lib.fmrx_highcut_create(C.byref(self._h), C.byref(self.params), self.if_Fs, self.audio_Fs, self.n_channels,
+                                       self.audio_channels, self.n_audio, device))
+
+    @classmethod
+    def for_bank(cls, bank, meters, params: HighCutParams | None = None):
+        """The high-cut stage of a Channels bank and of the Meters made for it, on the bank's device."""
+        h = cls(bank.params.if_Fs, bank.params.audio_Fs, bank.n_channels, bank.audio_channels, bank.n_audio, params, bank.device)
+        h._meters = meters
+        return h
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_highcut_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, channel=-1):
+        _check(lib.fmrx_highcut_reset(self._h, channel))
+
+    def force_serial(self, on=True):
+        """Later calls walk their rows serially, one lane per row: the same bits, nothing counted in diagnostics()."""
+        _check(lib.fmrx_highcut_set_force(self._h, int(bool(on))))
+
+    def process_dev(self, meters, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
+        """Device rows [n_channels, audio_channels, n_audio] float32 -> d_out (may be d_in) and / or d_pcm [n_channels, n_audio,
+        audio_channels] int16, asynchronous on `stream` behind meters.process_dev on the same stream."""
+        _check(lib.fmrx_highcut_process_dev(self._h, meters._h, d_in, d_out, d_pcm, PCM_WRAP if wrap else PCM_SATURATE, stream))
+
+    def process_bank(self, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
+        """process_dev with the Meters given to for_bank."""
+        self.process_dev(self._meters, d_in, d_out, d_pcm, stream, wrap)
+
+    def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True, in_place=False):
+        """Host records METER_DTYPE [n_channels] and host rows float32 [n_channels, audio_channels, n_audio], synchronous ->
+        dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]); in_place: the call writes over its input (audio is then an
+        array of its own, never the caller's).  The rows keep their host address modulo 16 on the device."""
+        r = np.ascontiguousarray(recs, dtype=METER_DTYPE).reshape(self.n_channels)
+        shape = (self.n_channels, self.audio_channels, self.n_audio)
+        x = _f32(audio).reshape(shape)
+        f = s = None
+        if want_f32:
+            if in_place:
+                pad = np.zeros(x.size + 4, np.float32)           # a copy at the caller's address modulo 16
+                o = ((x.ctypes.data - pad.ctypes.data) % 16) // 4
+                f = pad[o:o + x.size].reshape(shape)
+                f[...] = x
+                x = f
+            else:
+                f = np.zeros(shape, np.float32)
+        if want_pcm:
+            s = np.zeros((self.n_channels, self.n_audio, self.audio_channels), np.int16)
+        _check(lib.fmrx_highcut_process(self._h, r.ctypes.data, x.ctypes.data, None if f is None else f.ctypes.data,
+                                        None if s is None else s.ctypes.data, PCM_WRAP if wrap else PCM_SATURATE))
+        return {"audio": f, "pcm16": s}
+
+    def status(self) -> np.ndarray:
+        """Waits for the last call; HIGHCUT_STATUS_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, HIGHCUT_STATUS_DTYPE)
+        _check(lib.fmrx_highcut_status_get(self._h, out.ctypes.data))
+        return out
+
+    def diagnostics(self) -> dict:
+        """Waits for the last call; segments: the segment boundaries checked since create, missed: the segments walked again."""
+        a, b = C.c_ulonglong(), C.c_ulonglong()
+        _check(lib.fmrx_highcut_diagnostics(self._h, C.byref(a), C.byref(b)))
+        return {"segments": a.value, "missed": b.value}
+
+
 class FrontEndPlan:
     """Reusable device-side tap tables for the fused front-end kernel (fmrx_fe_plan)."""
 

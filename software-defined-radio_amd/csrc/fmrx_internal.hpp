@@ -424,4 +424,29 @@ int blend_control_launch(const blend::Control &c, const double *d_mpx, const uns
 int blend_apply_launch(const float *d_in, float *d_out, int16_t *d_pcm, const fmrx_blend_status *d_status, int n_channels, int audio_channels,
                        size_t n_audio, float inv_n, int wrap, hipStream_t s);
 
+// ---- variable high-cut (kernels_highcut.hip; control step in highcut_control.hpp; handle and C ABI in highcut.hip) -----------------
+namespace highcut {
+struct Control;
+}
+constexpr int kHighcutSegment = 256, kHighcutWarmup = 256;   // built-in lane shape: samples per lane, warm-up samples in front
+// one lane per channel: d_status[c] <- control_step on d_mpx[c]'s probes; segments from d_seg_each[c], or seg_all where that is NULL
+int highcut_control_launch(const highcut::Control &c, const double *d_mpx, const unsigned long long *d_seg_each, unsigned long long seg_all,
+                           fmrx_highcut_status *d_status, int n_channels, hipStream_t s);
+long highcut_segments(size_t n, int L);   // segments of L samples in a row of n
+struct HighcutArgs {
+    const float *x = nullptr;            // [rows][n], row = channel * ac + audio channel
+    float *y = nullptr;                  // [rows][n]; not x
+    int16_t *pcm = nullptr;              // [rows / ac][n][ac], or NULL
+    const fmrx_highcut_status *status = nullptr;   // [rows / ac]: the poles' end points
+    int ac = 1, wrap = 1;
+    size_t rows = 0, n = 0;
+    float inv_n = 0.0f, p_max = 0.0f;
+    int L = kHighcutSegment, W = kHighcutWarmup;
+    float *state = nullptr;              // [rows]: y_prev, read and replaced
+    float *seg = nullptr;                // 2 * rows * highcut_segments(n, L): the segments' start and end y (not for the serial walk)
+    unsigned long long *missed = nullptr;   // += the segments walked again
+};
+// serial: the one-lane-per-row kernel; otherwise segments + verify, and *segments += the boundaries the verify step checked
+int highcut_apply_launch(const HighcutArgs &a, bool serial, hipStream_t s, unsigned long long *segments);
+
 }  // namespace fmrx

@@ -1,0 +1,161 @@
+"""Variable high-cut (fmrx_highcut_*): device time of one pass behind a fast stereo bank of mode 0, its meters and the blend,
+against the number of channels, and of one long row.
+
+    python3 tools/highcut_bench.py [--channels 192,4096,65536] [--long 1048576] [--calls 20] [--warmup 3] [--json out.json]
+
+Per channel count, on one stream, one 192 000-byte block per channel (1 920 audio samples per row), random bytes in the
+slots -- every channel is noise, so every row is filtered at full cut --, from device events around every call after the
+warm-up, the median of `calls` calls.  The bank's call and the meters' run in front of every timed call, outside its pair
+of events, as in the loop the stage is for.
+  highcut_ms    fmrx_highcut_process_dev out of place with float and PCM output: the control kernel, the segment lanes and
+                the verify step
+  inplace_ms, f32_ms, pcm_ms   the same call in place (it filters a copy), and with only the float / only the PCM output
+  serial_ms     the same call through the serial kernel, one lane per row (fmrx_highcut_set_force)
+  blend_ms      fmrx_blend_process_dev on the same rows, float and PCM
+  copy_ms       hipMemcpyAsync, device to device, of as many bytes as highcut_ms reads plus writes (20 per stereo sample)
+  bank_ms       fmrx_channels_process_dev of the same bank
+The long row: one mono row of `--long` samples of noise behind a one-channel Meters whose record reads full cut:
+  long_ms, long_serial_ms, deemph_ms   the parallel walk, the serial kernel, and fmrx_deemph_dev (75 us) on the same row"""
+from __future__ import annotations
+
+import argparse
+import importlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
+
+from blend_bench import BLOCK_BYTES, loaded_hip_runtime, median_ms  # noqa: E402
+
+
+def time_config(fmrx, torch, N, calls, warmup):
+    import ctypes
+    bank = fmrx.Channels(0, N, audio_channels=2, exact=False, block_bytes=BLOCK_BYTES)
+    meters = fmrx.Meters.for_bank(bank)
+    blend = fmrx.Blend.for_bank(bank, meters)
+    hc = fmrx.HighCut.for_bank(bank, meters)
+    n = bank.n_audio
+    g = torch.Generator(device="cuda").manual_seed(N)
+    d_iq = torch.randint(0, 256, (N * BLOCK_BYTES,), dtype=torch.uint8, device="cuda", generator=g)
+    d_audio = torch.zeros(N * 2 * n, dtype=torch.float32, device="cuda")
+    d_out = torch.zeros(N * 2 * n, dtype=torch.float32, device="cuda")
+    d_bank_pcm = torch.zeros(N * 2 * n, dtype=torch.int16, device="cuda")
+    d_pcm = torch.zeros(N * 2 * n, dtype=torch.int16, device="cuda")
+    moved = N * n * 20                                   # 8 in + 8 out + 4 PCM per stereo sample
+    d_src = torch.zeros(moved // 2, dtype=torch.uint8, device="cuda")
+    d_dst = torch.zeros(moved // 2, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    s = stream.cuda_stream
+    bank.load_dev(d_iq.data_ptr(), stream=s)
+    del d_iq
+    run_bank = lambda: bank.process_dev(d_audio.data_ptr(), d_bank_pcm.data_ptr(), stream=s)
+
+    def front():
+        run_bank()
+        meters.process_bank(stream=s)
+
+    bank_ms = median_ms(torch, stream, run_bank, calls, warmup)
+    a, o, p = d_audio.data_ptr(), d_out.data_ptr(), d_pcm.data_ptr()
+    both = median_ms(torch, stream, lambda: hc.process_bank(a, o, p, stream=s), calls, warmup, front)
+    f32 = median_ms(torch, stream, lambda: hc.process_bank(a, o, None, stream=s), calls, warmup, front)
+    pcm = median_ms(torch, stream, lambda: hc.process_bank(a, None, p, stream=s), calls, warmup, front)
+    inplace = median_ms(torch, stream, lambda: hc.process_bank(a, a, p, stream=s), calls, warmup, front)
+    diag = hc.diagnostics()
+    hc.force_serial(True)
+    serial = median_ms(torch, stream, lambda: hc.process_bank(a, o, p, stream=s), calls, warmup, front)
+    hc.force_serial(False)
+    bl = median_ms(torch, stream, lambda: blend.process_bank(a, o, p, stream=s), calls, warmup, front)
+    hip = loaded_hip_runtime()
+    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+
+    def run_copy():
+        if hip.hipMemcpyAsync(d_dst.data_ptr(), d_src.data_ptr(), moved // 2, 3, s) != 0:      # 3: hipMemcpyDeviceToDevice
+            raise RuntimeError("hipMemcpyAsync failed")
+
+    copy = median_ms(torch, stream, run_copy, calls, warmup, front)
+    status = hc.status()
+    res = dict(channels=N, block_bytes=BLOCK_BYTES, n_audio=n, calls=calls, highcut_ms=both[0], highcut_ms_min=both[1], highcut_ms_max=both[2],
+               inplace_ms=inplace[0], f32_ms=f32[0], pcm_ms=pcm[0], serial_ms=serial[0], serial_over_highcut=serial[0] / both[0],
+               blend_ms=bl[0], copy_ms=copy[0], moved_bytes=float(moved), GB_s=moved / (both[0] * 1e-3) / 1e9,
+               highcut_over_copy=both[0] / copy[0], bank_ms=bank_ms[0], highcut_over_bank=both[0] / bank_ms[0],
+               channels_cut=int((status["p1"] > 0).sum()), segments=diag["segments"], missed=diag["missed"])
+    for x in (hc, blend, meters, bank):
+        x.close()
+    del d_audio, d_out, d_pcm, d_bank_pcm, d_src, d_dst
+    torch.cuda.empty_cache()
+    return res
+
+
+def time_long_row(fmrx, torch, n, calls, warmup):
+    import numpy as np
+    if_Fs, audio_Fs = 240000.0, 48000.0
+    rng = np.random.default_rng(n)
+    meters = fmrx.Meters(if_Fs, 1)
+    meters.process(demod=(0.3 * rng.standard_normal((1, 4096))).astype(np.float32))      # noise: full cut
+    hc = fmrx.HighCut(if_Fs, audio_Fs, 1, 1, n)
+    d_x = torch.from_numpy((0.3 * rng.standard_normal(n)).astype(np.float32)).cuda()
+    d_y = torch.zeros(n, dtype=torch.float32, device="cuda")
+    d_state = torch.zeros(2, dtype=torch.float32, device="cuda")
+    d_missed = torch.zeros(1, dtype=torch.int64, device="cuda")
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    s = stream.cuda_stream
+    x, y = d_x.data_ptr(), d_y.data_ptr()
+    par = median_ms(torch, stream, lambda: hc.process_dev(meters, x, y, None, stream=s), calls, warmup)
+    diag = hc.diagnostics()
+    hc.force_serial(True)
+    ser = median_ms(torch, stream, lambda: hc.process_dev(meters, x, y, None, stream=s), calls, warmup)
+    p, b0 = fmrx.deemphasisCoeffs(audio_Fs, 75.0)
+    de = median_ms(torch, stream, lambda: fmrx.deemphasis_dev(y, x, 1, n, n, p, b0, d_state.data_ptr(), d_missed.data_ptr(), stream=s), calls, warmup)
+    res = dict(n=n, calls=calls, long_ms=par[0], long_ms_min=par[1], long_ms_max=par[2], long_serial_ms=ser[0], serial_over_parallel=ser[0] / par[0],
+               deemph_ms=de[0], p1=float(hc.status()["p1"][0]), segments=diag["segments"], missed=diag["missed"])
+    for h in (hc, meters):
+        h.close()
+    return res
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--channels", default="192,4096,65536")
+    ap.add_argument("--long", type=int, default=1 << 20)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    fmrx = importlib.import_module("software-defined-radio_amd")
+    import torch
+    if fmrx.device_count() < 1 or not torch.cuda.is_available():
+        print("highcut_bench: no GPU; nothing is measured without one", file=sys.stderr)
+        return 1
+    out = {"version": fmrx.version(), "configs": [], "long_row": None}
+
+    def save():
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+
+    if a.long > 0:
+        r = out["long_row"] = time_long_row(fmrx, torch, a.long, a.calls, a.warmup)
+        print(f"one row of {r['n']} samples (pole {r['p1']:.4f}): parallel {r['long_ms']:.4f} ms/call (min {r['long_ms_min']:.4f}, max "
+              f"{r['long_ms_max']:.4f}), serial kernel {r['long_serial_ms']:.3f} ms, serial / parallel = {r['serial_over_parallel']:.1f}; "
+              f"fmrx_deemph_dev {r['deemph_ms']:.4f} ms; {r['missed']} of {r['segments']} segments walked again", flush=True)
+        save()
+    for N in [int(n) for n in a.channels.split(",") if n]:
+        r = time_config(fmrx, torch, N, a.calls, a.warmup)
+        out["configs"].append(r)
+        print(f"N={N:6d}: high-cut {r['highcut_ms']:8.4f} ms/call (min {r['highcut_ms_min']:.4f}, max {r['highcut_ms_max']:.4f}; in place "
+              f"{r['inplace_ms']:.4f}, float only {r['f32_ms']:.4f}, PCM only {r['pcm_ms']:.4f}), {r['GB_s']:7.1f} GB/s; serial kernel "
+              f"{r['serial_ms']:.4f} ms (serial / parallel = {r['serial_over_highcut']:.2f}); blend {r['blend_ms']:.4f} ms; copy of the same "
+              f"bytes {r['copy_ms']:.4f} ms (high-cut / copy = {r['highcut_over_copy']:.2f}); bank {r['bank_ms']:.3f} ms/call (high-cut / "
+              f"bank = {r['highcut_over_bank']:.4f}); {r['channels_cut']} channels cut, {r['missed']} of {r['segments']} segments walked again",
+              flush=True)
+        save()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
