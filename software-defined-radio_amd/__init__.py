@@ -1286,6 +1286,77 @@ class Meters:
 
 
 # --------------------------------------------------------------------------
+# What the stages behind the meters share
+# --------------------------------------------------------------------------
+def _params_init(self, defaults, kw):
+    """The keyword constructor of BlendParams and HighCutParams: the library's defaults, then single fields by name."""
+    C.Structure.__init__(self)
+    _check(defaults(C.byref(self)))
+    kinds = dict(self._fields_)
+    for k, v in kw.items():
+        if k not in kinds:
+            raise TypeError(f"{type(self).__name__} has no field {k!r}")
+        setattr(self, k, int(v) if kinds[k] is C.c_int32 else float(v))
+
+
+class _MeterStage:
+    """What Blend and HighCut share: a handle behind the meters on a bank's audio (csrc/meter_stage.hpp).  A subclass names its
+    fmrx_<_prefix>_* functions and its status dtype, and creates self._h."""
+    _prefix = _status_dtype = None
+
+    def _call(self, name, *args):
+        _check(getattr(lib, f"fmrx_{self._prefix}_{name}")(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            getattr(lib, f"fmrx_{self._prefix}_destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, channel=-1):
+        self._call("reset", channel)
+
+    def process_dev(self, meters, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
+        """Device rows [n_channels, audio_channels, n_audio] float32 -> d_out (may be d_in) and / or d_pcm [n_channels, n_audio,
+        audio_channels] int16, asynchronous on `stream` behind meters.process_dev on the same stream."""
+        self._call("process_dev", meters._h, d_in, d_out, d_pcm, PCM_WRAP if wrap else PCM_SATURATE, stream)
+
+    def process_bank(self, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
+        """process_dev with the Meters given to for_bank."""
+        self.process_dev(self._meters, d_in, d_out, d_pcm, stream, wrap)
+
+    def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True, in_place=False):
+        """Host records METER_DTYPE [n_channels] and host rows float32 [n_channels, audio_channels, n_audio], synchronous ->
+        dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]); in_place: the call writes over its input (audio is then an
+        array of its own, never the caller's).  The rows keep their host address modulo 16 on the device."""
+        r = np.ascontiguousarray(recs, dtype=METER_DTYPE).reshape(self.n_channels)
+        shape = (self.n_channels, self.audio_channels, self.n_audio)
+        x = _f32(audio).reshape(shape)
+        f = s = None
+        if want_f32:
+            if in_place:
+                pad = np.zeros(x.size + 4, np.float32)           # a copy at the caller's address modulo 16
+                o = ((x.ctypes.data - pad.ctypes.data) % 16) // 4
+                f = pad[o:o + x.size].reshape(shape)
+                f[...] = x
+                x = f
+            else:
+                f = np.zeros(shape, np.float32)
+        if want_pcm:
+            s = np.zeros((self.n_channels, self.n_audio, self.audio_channels), np.int16)
+        self._call("process", r.ctypes.data, x.ctypes.data, None if f is None else f.ctypes.data, None if s is None else s.ctypes.data,
+                   PCM_WRAP if wrap else PCM_SATURATE)
+        return {"audio": f, "pcm16": s}
+
+    def status(self) -> np.ndarray:
+        """Waits for the last call; the stage's status records (BLEND_STATUS_DTYPE, HIGHCUT_STATUS_DTYPE) [n_channels]."""
+        out = np.zeros(self.n_channels, self._status_dtype)
+        self._call("status_get", out.ctypes.data)
+        return out
+
+
+# --------------------------------------------------------------------------
 # Stereo blend and soft mute behind a bank, driven by the meters
 # --------------------------------------------------------------------------
 class BlendParams(C.Structure):
@@ -1295,12 +1366,7 @@ class BlendParams(C.Structure):
                                           "attack", "release")]
 
     def __init__(self, **kw):
-        super().__init__()
-        _check(lib.fmrx_blend_defaults(C.byref(self)))
-        for k, v in kw.items():
-            if k not in dict(self._fields_):
-                raise TypeError(f"BlendParams has no field {k!r}")
-            setattr(self, k, float(v))
+        _params_init(self, lib.fmrx_blend_defaults, kw)
 
 
 BLEND_STATUS_DTYPE = np.dtype([("pilot_db", "<f8"), ("quiet_db", "<f8"), ("sep_target", "<f8"), ("gain_target", "<f8"), ("sep", "<f8"),
@@ -1327,11 +1393,13 @@ def blendControl(params, if_Fs, rec, state=None) -> np.ndarray:
     return st[0]
 
 
-class Blend:
+class Blend(_MeterStage):
     """Stereo lamp, blend towards mono and soft mute per channel of a receiver bank, decided from the meters' pilot and noise
     powers of the same call and applied to the bank's audio (fmrx_blend_*).  blend = Blend.for_bank(bank,
     meters); after bank.process_dev(d_audio, ..., stream=s) and meters.process_bank(stream=s):
     blend.process_bank(d_audio, d_out, d_pcm, stream=s); blend.status()."""
+
+    _prefix, _status_dtype = "blend", BLEND_STATUS_DTYPE
 
     def __init__(self, if_Fs, n_channels=1, audio_channels=2, n_audio=1920, params: BlendParams | None = None, device=0):
         self.if_Fs, self.n_channels, self.audio_channels, self.n_audio = float(if_Fs), int(n_channels), int(audio_channels), int(n_audio)
@@ -1353,54 +1421,6 @@ class Blend:
         """The attack / release coefficient of a time constant tau_s at one call every call_s seconds: 1 - exp(-call_s / tau_s)."""
         return 1.0 - float(np.exp(-float(call_s) / float(tau_s)))
 
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_blend_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def reset(self, channel=-1):
-        _check(lib.fmrx_blend_reset(self._h, channel))
-
-    def process_dev(self, meters, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
-        """Device rows [n_channels, audio_channels, n_audio] float32 -> d_out (may be d_in) and / or d_pcm [n_channels, n_audio,
-        audio_channels] int16, asynchronous on `stream` behind meters.process_dev on the same stream."""
-        _check(lib.fmrx_blend_process_dev(self._h, meters._h, d_in, d_out, d_pcm, PCM_WRAP if wrap else PCM_SATURATE, stream))
-
-    def process_bank(self, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
-        """process_dev with the Meters given to for_bank."""
-        self.process_dev(self._meters, d_in, d_out, d_pcm, stream, wrap)
-
-    def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True, in_place=False):
-        """Host records METER_DTYPE [n_channels] and host rows float32 [n_channels, audio_channels, n_audio], synchronous ->
-        dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]); in_place: the device pass writes over its input (audio
-        is then an array of its own, never the caller's).  The rows keep their host address modulo 16 on the device."""
-        r = np.ascontiguousarray(recs, dtype=METER_DTYPE).reshape(self.n_channels)
-        shape = (self.n_channels, self.audio_channels, self.n_audio)
-        x = _f32(audio).reshape(shape)
-        f = s = None
-        if want_f32:
-            if in_place:
-                pad = np.zeros(x.size + 4, np.float32)           # a copy at the caller's address modulo 16
-                o = ((x.ctypes.data - pad.ctypes.data) % 16) // 4
-                f = pad[o:o + x.size].reshape(shape)
-                f[...] = x
-                x = f
-            else:
-                f = np.zeros(shape, np.float32)
-        if want_pcm:
-            s = np.zeros((self.n_channels, self.n_audio, self.audio_channels), np.int16)
-        _check(lib.fmrx_blend_process(self._h, r.ctypes.data, x.ctypes.data, None if f is None else f.ctypes.data,
-                                      None if s is None else s.ctypes.data, PCM_WRAP if wrap else PCM_SATURATE))
-        return {"audio": f, "pcm16": s}
-
-    def status(self) -> np.ndarray:
-        """Waits for the last call; BLEND_STATUS_DTYPE [n_channels]."""
-        out = np.zeros(self.n_channels, BLEND_STATUS_DTYPE)
-        _check(lib.fmrx_blend_status_get(self._h, out.ctypes.data))
-        return out
-
 
 # --------------------------------------------------------------------------
 # Variable high-cut behind the blend (or a bank), driven by the meters
@@ -1413,13 +1433,7 @@ class HighCutParams(C.Structure):
                [("warmup", C.c_int32), ("segment", C.c_int32)]
 
     def __init__(self, **kw):
-        super().__init__()
-        _check(lib.fmrx_highcut_defaults(C.byref(self)))
-        kinds = dict(self._fields_)
-        for k, v in kw.items():
-            if k not in kinds:
-                raise TypeError(f"HighCutParams has no field {k!r}")
-            setattr(self, k, int(v) if kinds[k] is C.c_int32 else float(v))
+        _params_init(self, lib.fmrx_highcut_defaults, kw)
 
 
 HIGHCUT_STATUS_DTYPE = np.dtype([("quiet_db", "<f8"), ("open_target", "<f8"), ("open", "<f8"), ("p0", "<f4"), ("p1", "<f4"),
@@ -1455,11 +1469,13 @@ def highCutControl(params, if_Fs, audio_Fs, rec, state=None) -> np.ndarray:
     return st[0]
 
 
-class HighCut:
+class HighCut(_MeterStage):
     """A one-pole low-pass per audio row of a receiver bank whose corner follows the channel's quieting, decided from the
     meters' noise powers of the same call (fmrx_highcut_*).  hc = HighCut.for_bank(bank, meters); after
     bank.process_dev, meters.process_bank and (where there is one) blend.process_bank on stream s:
     hc.process_bank(d_audio, d_out, d_pcm, stream=s); hc.status(); hc.diagnostics()."""
+
+    _prefix, _status_dtype = "highcut", HIGHCUT_STATUS_DTYPE
 
     def __init__(self, if_Fs, audio_Fs=48000.0, n_channels=1, audio_channels=2, n_audio=1920, params: HighCutParams | None = None, device=0):
         self.if_Fs, self.audio_Fs = float(if_Fs), float(audio_Fs)
@@ -1477,57 +1493,9 @@ class HighCut:
         h._meters = meters
         return h
 
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_highcut_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def reset(self, channel=-1):
-        _check(lib.fmrx_highcut_reset(self._h, channel))
-
     def force_serial(self, on=True):
         """Later calls walk their rows serially, one lane per row: the same bits, nothing counted in diagnostics()."""
         _check(lib.fmrx_highcut_set_force(self._h, int(bool(on))))
-
-    def process_dev(self, meters, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
-        """Device rows [n_channels, audio_channels, n_audio] float32 -> d_out (may be d_in) and / or d_pcm [n_channels, n_audio,
-        audio_channels] int16, asynchronous on `stream` behind meters.process_dev on the same stream."""
-        _check(lib.fmrx_highcut_process_dev(self._h, meters._h, d_in, d_out, d_pcm, PCM_WRAP if wrap else PCM_SATURATE, stream))
-
-    def process_bank(self, d_in, d_out=None, d_pcm=None, stream=None, wrap=True):
-        """process_dev with the Meters given to for_bank."""
-        self.process_dev(self._meters, d_in, d_out, d_pcm, stream, wrap)
-
-    def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True, in_place=False):
-        """Host records METER_DTYPE [n_channels] and host rows float32 [n_channels, audio_channels, n_audio], synchronous ->
-        dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]); in_place: the call writes over its input (audio is then an
-        array of its own, never the caller's).  The rows keep their host address modulo 16 on the device."""
-        r = np.ascontiguousarray(recs, dtype=METER_DTYPE).reshape(self.n_channels)
-        shape = (self.n_channels, self.audio_channels, self.n_audio)
-        x = _f32(audio).reshape(shape)
-        f = s = None
-        if want_f32:
-            if in_place:
-                pad = np.zeros(x.size + 4, np.float32)           # a copy at the caller's address modulo 16
-                o = ((x.ctypes.data - pad.ctypes.data) % 16) // 4
-                f = pad[o:o + x.size].reshape(shape)
-                f[...] = x
-                x = f
-            else:
-                f = np.zeros(shape, np.float32)
-        if want_pcm:
-            s = np.zeros((self.n_channels, self.n_audio, self.audio_channels), np.int16)
-        _check(lib.fmrx_highcut_process(self._h, r.ctypes.data, x.ctypes.data, None if f is None else f.ctypes.data,
-                                        None if s is None else s.ctypes.data, PCM_WRAP if wrap else PCM_SATURATE))
-        return {"audio": f, "pcm16": s}
-
-    def status(self) -> np.ndarray:
-        """Waits for the last call; HIGHCUT_STATUS_DTYPE [n_channels]."""
-        out = np.zeros(self.n_channels, HIGHCUT_STATUS_DTYPE)
-        _check(lib.fmrx_highcut_status_get(self._h, out.ctypes.data))
-        return out
 
     def diagnostics(self) -> dict:
         """Waits for the last call; segments: the segment boundaries checked since create, missed: the segments walked again."""

@@ -1,9 +1,9 @@
 // kernels_blend.hip -- the two kernels of the stereo blend / soft mute stage (include/fmrx.h: fmrx_blend_*; DESIGN.md section
 // 4.12; defined by tests/_blend_model.py).
 //
-// blend_control_kernel: one lane per channel runs control_step (blend_control.hpp) on the channel's five probe powers, where
-// the meters' MPX pass left them, and its status row: the row is state and result at once -- lamp, drives, targets, smoothed
-// values, the float32 end points (mono0, gain0, mono1, gain1) of this call's ramps, the call count.
+// blend_control_kernel: meter_stage.hpp's control kernel with control_step of blend_control.hpp.  The status row is state and
+// result at once -- lamp, drives, targets, smoothed values, the float32 end points (mono0, gain0, mono1, gain1) of this
+// call's ramps, the call count.
 //
 // blend_apply_kernel: the pass over the audio, 8 bytes in, 8 bytes out and 4 bytes of PCM per stereo sample, nothing else.
 // The channel rides in the grid's x (banks have more than 65 535 receivers), a piece of the row in its y.  A lane owns groups
@@ -17,7 +17,7 @@
 // a clamp each, per sample.
 #include "blend_control.hpp"
 #include "device_math.hpp"
-#include "fmrx_internal.hpp"
+#include "meter_stage.hpp"
 
 namespace fmrx {
 namespace {
@@ -28,17 +28,12 @@ using u4 = unsigned __attribute__((ext_vector_type(4)));
 constexpr int kThreads = 256;
 constexpr int kGroups = 2;   // groups of 4 samples per lane
 
-__global__ __launch_bounds__(kThreads) void blend_control_kernel(blend::Control c, const double *__restrict__ mpx,
-                                                                 const unsigned long long *__restrict__ seg_each,
-                                                                 unsigned long long seg_all, fmrx_blend_status *__restrict__ st,
-                                                                 unsigned n_channels)
+__global__ __launch_bounds__(meter_stage::kControlThreads) void blend_control_kernel(blend::Control c, const double *__restrict__ mpx,
+                                                                                     const unsigned long long *__restrict__ seg_each,
+                                                                                     unsigned long long seg_all,
+                                                                                     fmrx_blend_status *__restrict__ st, unsigned n_channels)
 {
-    const unsigned i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n_channels) return;
-    const double *probe = mpx + static_cast<size_t>(i) * kMetersMpxFields + 3;   // behind sum_x, sum_x2, max_abs
-    fmrx_blend_status s = st[i];
-    blend::control_step(c, probe, seg_each ? seg_each[i] : seg_all, s);
-    st[i] = s;
+    meter_stage::control_body(c, mpx, seg_each, seg_all, st, n_channels);
 }
 
 // value k of a ramp from v0: clamp(fmaf(k + 1, step, v0), 0, 1)
@@ -139,10 +134,7 @@ __global__ __launch_bounds__(kThreads) void blend_apply_kernel(const float *in, 
 int blend_control_launch(const blend::Control &c, const double *d_mpx, const unsigned long long *d_seg_each, unsigned long long seg_all,
                          fmrx_blend_status *d_status, int n_channels, hipStream_t s)
 {
-    const unsigned grid = (static_cast<unsigned>(n_channels) + kThreads - 1) / kThreads;
-    blend_control_kernel<<<grid, kThreads, 0, s>>>(c, d_mpx, d_seg_each, seg_all, d_status, static_cast<unsigned>(n_channels));
-    FMRX_LAUNCH_CHECK("blend_control_kernel");
-    return FMRX_OK;
+    return meter_stage::control_launch("blend_control_kernel", blend_control_kernel, c, d_mpx, d_seg_each, seg_all, d_status, n_channels, s);
 }
 
 int blend_apply_launch(const float *d_in, float *d_out, int16_t *d_pcm, const fmrx_blend_status *d_status, int n_channels, int audio_channels,

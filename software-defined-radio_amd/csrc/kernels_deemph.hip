@@ -4,259 +4,68 @@
 //     u = x[n] + x_prev;  v = b0 * u;  y = fmaf(p, y_prev, v);  if |y| < 2^-126: y = +0
 // with p, b0 from fmrx_deemph_design.  The flush is part of the definition: without it the state of a row in digital silence
 // sticks at the smallest subnormal (RN(p * 2^-149) = 2^-149) and a lane that starts from zero never meets it again.
+// v = b0 * (x + x_prev) does not depend on y: only the fused multiply-add and the flush are on the dependent chain.
 //
-// One kernel family on rows [rows][n] with a row pitch -- a pipeline has 1 or 2 rows, a bank n_channels * audio_channels:
-//   deemph_segments_kernel  parallel in time.  A lane owns one (row, segment of L samples): it starts W samples early with y = +0
-//                           and the true x_prev (the input is known), or at sample 0 from the carried state where its warm-up
-//                           would begin in front of the call; it remembers the y it has reached at its segment's start, writes
-//                           its L outputs (f32 and PCM) and leaves its end y.  p < 1 makes the recurrence a contraction: after
-//                           W steps the lane's y has the true one's bits, unless the input stepped by many orders of magnitude.
-//   deemph_verify_kernel    one workgroup per row (64 .. 1024 lanes, by the row's segments).  Segment c is right iff the bits of its start y equal segment c-1's true end y
-//                           (two NaNs count as equal: payloads are not part of the definition).  With every segment's start equal
-//                           to its predecessor's speculative end, all of them are true by induction from the exact segment 0: the
-//                           lanes check that in parallel.  A miss is walked again by one lane from the true state, outputs and
-//                           PCM rewritten, until a recomputed y has the stored one's bits -- everything behind is identical.  The
-//                           row's carried state is the last segment's true end.  Misses are counted.
+// One kernel family on rows [rows][n] with a row pitch -- a pipeline has 1 or 2 rows, a bank n_channels * audio_channels --,
+// the three bodies of onepole_walk.hpp (which describes the scheme, the staging and the repair) with DeemphFilter:
+//   deemph_segments_kernel  parallel in time, one lane per (row, segment)
+//   deemph_verify_kernel    one workgroup per row checks the segments' joints and walks a miss again
 //   deemph_serial_kernel    one lane per row walks the whole row (option deemph_mode = 1, set_force_generic; what the segment
 //                           kernels are measured against).
 // The stage is out of place: the repair reads x again.
 //
-// Staging (segment kernel): 64 lanes per workgroup, in batches of 32 steps.  Lanes are L samples apart, so a batch is staged
-// through LDS: 32 consecutive lanes of the wave read one lane's 32 consecutive floats (128 contiguous bytes per half wave; which
-// row, and where that lane starts, comes from its own registers by v_readlane: an LDS lookup there cost two round trips per
-// element), each lane then walks its own LDS row -- row stride 33 words, so the 64 lanes of a step hit 32 different banks twice (the minimum
-// for a 64-lane ds_read_b32) -- and leaves y in place; the same mapping stores the batch, packing PCM on the way.  v = b0 * (x +
-// x_prev) does not depend on y: only the fused multiply-add and the flush are on the dependent chain.
-//
-// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): segments 56 VGPRs, 8 448 bytes of LDS; verify 15 VGPRs, 8 bytes; serial
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): segments 57 VGPRs, 8 448 bytes of LDS; verify 15 VGPRs, 8 bytes; serial
 // 28 VGPRs, none; no kernel uses scratch.
-#include "device_math.hpp"
-#include "fmrx_internal.hpp"
+#include "onepole_walk.hpp"
 
 namespace fmrx {
 namespace {
 
-constexpr int kLanes = 64, kBatch = 32, kStride = kBatch + 1;
+using walk::kLanes;
 
-__device__ __forceinline__ float deemph_step(float x, float x_prev, float y_prev, float p, float b0)
-{
-    const float v = b0 * (x + x_prev);
-    const float y = __builtin_fmaf(p, y_prev, v);
-    return __builtin_fabsf(y) < 1.17549435e-38f ? 0.0f : y;
-}
-
-__device__ __forceinline__ bool deemph_same(float a, float b)
-{
-    return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
-}
-
-// PCM of row r, sample k: [row / ac][k][row % ac] -- mono rows (ac = 1), the pipeline's interleaved stereo (2 rows, ac = 2) and
-// a bank's [N][n][ac] are all this one layout: sample k of a row sits k * ac behind the row's first
-__device__ __forceinline__ long deemph_pcm_row(long row, int n, int ac) { return (row / ac) * n * ac + row % ac; }
-__device__ __forceinline__ void deemph_pcm(int16_t *pcm_row, int k, int ac, float y, int wrap)
-{
-    pcm_row[static_cast<long>(k) * ac] = pcm_pack(y, wrap);
-}
-
-// lane (2 it + half)'s value of v: both halves of the wave ask for one lane each, so two scalar reads and a select -- no LDS
-// lookup (and its latency) in the staging loops
-__device__ __forceinline__ int deemph_pick(int v, int it, int half)
-{
-    const int a = __builtin_amdgcn_readlane(v, 2 * it), b = __builtin_amdgcn_readlane(v, 2 * it + 1);
-    return half ? b : a;
-}
+// state [rows][2] = x_prev, y_prev; the same p, b0 for every row
+struct DeemphFilter {
+    float p, b0;
+    struct State {
+        float x_prev, y;
+    };
+    __device__ __forceinline__ State load(const float *state, long row) const { return State{state[2 * row], state[2 * row + 1]}; }
+    __device__ __forceinline__ void store(float *state, long row, State s) const
+    {
+        state[2 * row] = s.x_prev;
+        state[2 * row + 1] = s.y;
+    }
+    __device__ __forceinline__ DeemphFilter at(long) const { return *this; }
+    __device__ __forceinline__ State enter(float y, const float *x) const { return State{x[-1], y}; }
+    __device__ __forceinline__ State step(float x, int, State s) const
+    {
+        const float v = b0 * (x + s.x_prev);
+        const float y = __builtin_fmaf(p, s.y, v);
+        return State{x, __builtin_fabsf(y) < 1.17549435e-38f ? 0.0f : y};
+    }
+};
 
 __global__ __launch_bounds__(kLanes) void deemph_segments_kernel(const float *__restrict__ x, long pitch_x, float *__restrict__ y,
                                                                  long pitch_y, int16_t *__restrict__ pcm, int ac, int wrap, long rows,
                                                                  int n, int nseg, int L, int W, float p, float b0,
                                                                  const float *__restrict__ state, float *__restrict__ seg)
 {
-    __shared__ float buf[kLanes * kStride];
-    const int tid = threadIdx.x;
-    const long total = rows * nseg;
-    const long t = static_cast<long>(blockIdx.x) * kLanes + tid;
-    const bool ok = t < total;
-    const long row = ok ? t / nseg : 0;
-    const int c = ok ? static_cast<int>(t - row * nseg) : 0;
-    const int g0 = c * L - W;                      // where the warm-up would begin; <= 0: the lane starts at sample 0, exact
-    // what the staging loops need of every lane: its row, where it starts (a lane past the end: so early that it never meets
-    // sample 0), and its row's place in the PCM
-    const int lane_row = static_cast<int>(row), lane_g0 = ok ? g0 : -(1 << 30);
-    const long pcm_row = deemph_pcm_row(row, n, ac);
-    const int pcm_lo = static_cast<int>(pcm_row), pcm_hi = static_cast<int>(pcm_row >> 32);
-    const int steps = W + L;
-    float yp = 0.0f, xp = 0.0f, ystart = 0.0f;
-    if (ok) {
-        if (g0 <= 0) {
-            xp = state[2 * row];
-            yp = state[2 * row + 1];
-        } else {
-            xp = x[row * pitch_x + g0 - 1];
-        }
-    }
-    const int e = tid & (kBatch - 1), half = tid >> 5;
-    for (int j0 = 0; j0 < steps; j0 += kBatch) {
-        float in[kLanes / 2];   // all of the batch's loads in flight at once, then LDS
-#pragma unroll
-        for (int it = 0; it < kLanes / 2; it++) {
-            const long r = deemph_pick(lane_row, it, half);
-            const int j = j0 + e, g = deemph_pick(lane_g0, it, half) + j;
-            in[it] = 0.0f;
-            if (j < steps && g >= 0 && g < n) in[it] = x[r * pitch_x + g];
-        }
-#pragma unroll
-        for (int it = 0; it < kLanes / 2; it++) buf[(2 * it + half) * kStride + e] = in[it];
-        __syncthreads();
-        float xs[kBatch];   // the lane's row in registers: the LDS latency stays off the dependent chain
-#pragma unroll
-        for (int i = 0; i < kBatch; i++) xs[i] = buf[tid * kStride + i];
-#pragma unroll
-        for (int i = 0; i < kBatch; i++) {
-            const int j = j0 + i, g = g0 + j;
-            const bool act = ok && j < steps && g >= 0 && g < n;
-            ystart = j == W ? yp : ystart;
-            const float yv = deemph_step(xs[i], xp, yp, p, b0);
-            yp = act ? yv : yp;
-            xp = act ? xs[i] : xp;
-            xs[i] = yp;
-        }
-#pragma unroll
-        for (int i = 0; i < kBatch; i++) buf[tid * kStride + i] = xs[i];
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < kLanes / 2; it++) {
-            const long r = deemph_pick(lane_row, it, half);
-            const int j = j0 + e, g = deemph_pick(lane_g0, it, half) + j;
-            const long po = (static_cast<long>(deemph_pick(pcm_hi, it, half)) << 32) | static_cast<unsigned>(deemph_pick(pcm_lo, it, half));
-            const float v = buf[(2 * it + half) * kStride + e];
-            if (j >= W && j < steps && g >= 0 && g < n) {
-                y[r * pitch_y + g] = v;
-                if (pcm) deemph_pcm(pcm + po, g, ac, v, wrap);
-            }
-        }
-        __syncthreads();
-    }
-    if (ok) {
-        seg[t] = ystart;
-        seg[total + t] = yp;
-    }
+    walk::walk_segments(DeemphFilter{p, b0}, x, pitch_x, y, pitch_y, pcm, ac, wrap, rows, n, nseg, L, W, state, seg);
 }
 
-constexpr int kScan = 8;      // segments every lane checks per pass
-constexpr int kVerifyMax = 1024;   // lanes per row at most
-
-// (seg is read and written here: no __restrict__, no const)
-__global__ __launch_bounds__(kVerifyMax) void deemph_verify_kernel(const float *__restrict__ x, long pitch_x, float *y, long pitch_y,
-                                                               int16_t *pcm, int ac, int wrap, long rows, int n, int nseg, int L,
-                                                               float p, float b0, float *__restrict__ state, float *seg,
-                                                               unsigned long long *missed)
+__global__ __launch_bounds__(walk::kVerifyMax) void deemph_verify_kernel(const float *__restrict__ x, long pitch_x, float *y, long pitch_y,
+                                                                     int16_t *pcm, int ac, int wrap, long rows, int n, int nseg, int L,
+                                                                     float p, float b0, float *__restrict__ state, float *seg,
+                                                                     unsigned long long *missed)
 {
-    __shared__ int first, resume;
-    const int tid = threadIdx.x;
-    const long row = blockIdx.x;
-    const float *xr = x + row * pitch_x;
-    float *yr = y + row * pitch_y;
-    float *start = seg + row * nseg, *end = seg + rows * nseg + row * nseg;
-    int16_t *pcm_row = pcm ? pcm + deemph_pcm_row(row, n, ac) : nullptr;
-    unsigned miss = 0;
-    int from = 1;
-    while (from < nseg) {
-        const int nt = blockDim.x;
-        const int hi = from + kScan * nt < nseg ? from + kScan * nt : nseg;
-        if (tid == 0) first = nseg;
-        __syncthreads();
-        int found = nseg;
-#pragma unroll
-        for (int u = kScan - 1; u >= 0; u--) {   // (no early exit: the loads of a pass are independent)
-            const int c = from + u * nt + tid;
-            if (c < hi && !deemph_same(start[c], end[c - 1])) found = c;
-        }
-        if (found < nseg) atomicMin(&first, found);
-        __syncthreads();
-        const int f = first;
-        __syncthreads();   // (everybody has read it before lane 0 writes it again)
-        if (f >= nseg) {
-            from = hi;
-            continue;
-        }
-        if (tid == 0) {
-            // everything in front of segment f is true: walk f again from its predecessor's end, and on through the segments
-            // behind it for as long as the walk does not meet the stored values
-            int c = f;
-            float yv = end[c - 1];
-            for (;;) {
-                miss++;
-                const int g_lo = c * L, g_hi = g_lo + L < n ? g_lo + L : n;
-                float xp = xr[g_lo - 1];
-                bool met = false;
-                for (int g = g_lo; g < g_hi && !met; g += 8) {
-                    float xs[8], ys[8];   // eight samples' loads in flight at once: the walk itself is a dependent chain
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        xs[i] = g + i < g_hi ? xr[g + i] : 0.0f;
-                        ys[i] = g + i < g_hi ? yr[g + i] : 0.0f;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        if (met || g + i >= g_hi) break;
-                        yv = deemph_step(xs[i], xp, yv, p, b0);
-                        xp = xs[i];
-                        if (deemph_same(yv, ys[i])) {
-                            met = true;
-                        } else {
-                            yr[g + i] = yv;
-                            if (pcm_row) deemph_pcm(pcm_row, g + i, ac, yv, wrap);
-                        }
-                    }
-                }
-                c++;
-                if (met || c >= nseg) {
-                    if (!met) end[c - 1] = yv;
-                    break;
-                }
-                end[c - 1] = yv;
-                if (deemph_same(start[c], yv)) {   // the next segment started from exactly this: it and its end are true
-                    c++;
-                    break;
-                }
-            }
-            resume = c;
-        }
-        __syncthreads();
-        from = resume;
-    }
-    if (tid == 0) {
-        state[2 * row] = xr[n - 1];
-        state[2 * row + 1] = end[nseg - 1];
-        if (miss) atomicAdd(missed, static_cast<unsigned long long>(miss));
-    }
+    walk::walk_verify(DeemphFilter{p, b0}, x, pitch_x, y, pitch_y, pcm, ac, wrap, rows, n, nseg, L, state, seg, missed);
 }
 
 __global__ __launch_bounds__(kLanes) void deemph_serial_kernel(const float *__restrict__ x, long pitch_x, float *__restrict__ y,
                                                                long pitch_y, int16_t *__restrict__ pcm, int ac, int wrap, long rows,
                                                                int n, float p, float b0, float *__restrict__ state)
 {
-    const long row = static_cast<long>(blockIdx.x) * kLanes + threadIdx.x;
-    if (row >= rows) return;
-    const float *xr = x + row * pitch_x;
-    float *yr = y + row * pitch_y;
-    float xp = state[2 * row], yp = state[2 * row + 1];
-    int16_t *pcm_row = pcm ? pcm + deemph_pcm_row(row, n, ac) : nullptr;
-    for (int g = 0; g < n; g += 8) {
-        float xs[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) xs[i] = g + i < n ? xr[g + i] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            if (g + i >= n) break;
-            yp = deemph_step(xs[i], xp, yp, p, b0);
-            xp = xs[i];
-            yr[g + i] = yp;
-            if (pcm_row) deemph_pcm(pcm_row, g + i, ac, yp, wrap);
-        }
-    }
-    state[2 * row] = xp;
-    state[2 * row + 1] = yp;
+    walk::walk_serial(DeemphFilter{p, b0}, x, pitch_x, y, pitch_y, pcm, ac, wrap, rows, n, state);
 }
 
 }  // namespace
@@ -266,7 +75,7 @@ DeemphShape deemph_shape(const Options &o, size_t n)
     DeemphShape s;
     s.L = o.deemph_segment < 0 ? kDeemphSegment : o.deemph_segment;
     s.W = o.deemph_warmup < 0 ? kDeemphWarmup : o.deemph_warmup;
-    s.nseg = static_cast<long>((n + s.L - 1) / s.L);
+    s.nseg = walk::segments(n, s.L);
     return s;
 }
 
@@ -284,24 +93,22 @@ int deemph_launch(const DeemphArgs &a, const Options &o, bool serial, hipStream_
     const long rows = static_cast<long>(a.rows);
     const int n = static_cast<int>(a.n);
     if (serial || o.deemph_mode == 1) {
-        hipLaunchKernelGGL(deemph_serial_kernel, dim3(static_cast<unsigned>((rows + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, a.x, a.pitch_x,
-                           a.y, a.pitch_y, a.pcm, a.ac, a.wrap, rows, n, a.p, a.b0, a.state);
+        hipLaunchKernelGGL(deemph_serial_kernel, dim3(walk::serial_blocks(rows)), dim3(kLanes), 0, s, a.x, a.pitch_x, a.y, a.pitch_y, a.pcm, a.ac,
+                           a.wrap, rows, n, a.p, a.b0, a.state);
         FMRX_LAUNCH_CHECK("deemph_serial_kernel");
         return FMRX_OK;
     }
     const DeemphShape sh = deemph_shape(o, a.n);
     if (!a.seg || !a.missed) return fail(FMRX_EINVAL, "deemph: null scratch");
-    const long total = rows * sh.nseg;
-    if (sh.nseg > (1L << 30) || (total + kLanes - 1) / kLanes > 0x7fffffffL) return fail(FMRX_EINVAL, "deemph: too many segments");
-    hipLaunchKernelGGL(deemph_segments_kernel, dim3(static_cast<unsigned>((total + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, a.x, a.pitch_x,
-                       a.y, a.pitch_y, a.pcm, a.ac, a.wrap, rows, n, static_cast<int>(sh.nseg), sh.L, sh.W, a.p, a.b0, a.state, a.seg);
+    walk::Grid g;
+    FMRX_TRY(walk::grid("deemph", rows, a.n, sh.L, &g));
+    hipLaunchKernelGGL(deemph_segments_kernel, dim3(g.blocks), dim3(kLanes), 0, s, a.x, a.pitch_x, a.y, a.pitch_y, a.pcm, a.ac, a.wrap, rows, n,
+                       static_cast<int>(g.nseg), sh.L, sh.W, a.p, a.b0, a.state, a.seg);
     FMRX_LAUNCH_CHECK("deemph_segments_kernel");
-    // lanes per row: enough to check a row's segments in few passes, whole waves
-    const long vt = (sh.nseg + kLanes - 1) / kLanes * kLanes;
-    hipLaunchKernelGGL(deemph_verify_kernel, dim3(static_cast<unsigned>(rows)), dim3(static_cast<unsigned>(vt < kVerifyMax ? vt : kVerifyMax)), 0, s, a.x, a.pitch_x, a.y, a.pitch_y, a.pcm,
-                       a.ac, a.wrap, rows, n, static_cast<int>(sh.nseg), sh.L, a.p, a.b0, a.state, a.seg, a.missed);
+    hipLaunchKernelGGL(deemph_verify_kernel, dim3(static_cast<unsigned>(rows)), dim3(g.verify_lanes), 0, s, a.x, a.pitch_x, a.y, a.pitch_y, a.pcm,
+                       a.ac, a.wrap, rows, n, static_cast<int>(g.nseg), sh.L, a.p, a.b0, a.state, a.seg, a.missed);
     FMRX_LAUNCH_CHECK("deemph_verify_kernel");
-    if (segments) *segments += static_cast<unsigned long long>(rows) * static_cast<unsigned long long>(sh.nseg - 1);
+    if (segments) *segments += g.checked;
     return FMRX_OK;
 }
 
