@@ -1034,6 +1034,135 @@ FMRX_API int fmrx_highcut_status_get(fmrx_highcut *h, fmrx_highcut_status *out);
  * fmrx_channels_deemph_diagnostics); waits for the handle's last call.  Either pointer may be NULL. */
 FMRX_API int fmrx_highcut_diagnostics(fmrx_highcut *h, unsigned long long *segments, unsigned long long *missed);
 
+/* ------------------------------------------------------------------ */
+/* Audio meters: peak, RMS, BS.1770 loudness, stereo image, gating      */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  What the signal meters are for the RF and the multiplex side, for the audio that comes out
+ * the other end: per channel of a receiver bank and call, is there programme or dead air, how loud is it by ITU-R BS.1770 /
+ * EBU R 128, does the PCM clip, is the stereo signal really stereo.  capture -> tuner -> bank -> meters -> blend -> high-cut ->
+ * audio meters on one stream; a few dozen bytes per channel come back instead of the audio.  A stage with a handle of its own
+ * that only reads the rows; it needs no discriminator rows and no fmrx_meters, so it also serves the fused mono bank of modes
+ * 0 / 1.  Defined by tests/_audio_meters_model.py; host and device equal that model bit for bit (a
+ * NaN's sign and payload are the machine's).
+ *
+ * K-weighting: two biquads in float64, designed for audio_Fs by the usual closed form of the BS.1770 pre-filter, K = tan(pi f0
+ * / Fs), KQ = K / Q, K2 = K K, a0 = (1 + KQ) + K2:
+ *   shelf      f0 = 1681.974450955533, Q = 0.7071752369554196, Vh = 10^(3.999843853973347 / 20) and Vb = Vh^0.4996667741545416
+ *              as literals;  b = [((Vh + Vb KQ) + K2) / a0, (2 (K2 - Vh)) / a0, ((Vh - Vb KQ) + K2) / a0],
+ *              a = [(2 (K2 - 1)) / a0, ((1 - KQ) + K2) / a0]
+ *   high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1], not normalised, as in the standard's table; a as
+ *              the shelf's.  At 48 000 Hz the design equals the table of BS.1770-4 to 9e-16.
+ * Walk, per row and sample x, v = (double)x, for the shelf and then the high-pass (transposed direct form II; every step one
+ * IEEE double operation, no fused multiply-add; float64 denormals are kept):
+ *   o = b0 v + z1;   z1 = (b1 v - a1 o) + z2;   z2 = b2 v - a2 o
+ * Raw results per channel and call (fmrx_audio_meter; arrays of 2 for the rows L and R, mono fills index 0 only; every sum is
+ * float64, serial in sample order):
+ *   n            the call's samples per row
+ *   over[r]      samples with !(fabsf(x) < 2.0f): at or beyond what the PCM pack (short)(x * 16384) overflows on; NaN counts
+ *   peak[r]      max |x|; skips NaN, reads infinity for an infinity
+ *   sum_x[r], sum_x2[r]          sum_k2[r]   sum y^2, y the K-weighted sample          sum_lr   sum L R; 0 for mono
+ *   bins_done    the 100 ms bins this call closed
+ * Records of successive calls add field by field and peak takes the maximum, as the signal meters' records do.
+ * 100 ms bins: bin_len = (size_t)(audio_Fs / 10 + 0.5) samples.  After each sample the row's y^2 is added to bin_acc[r]; when
+ * bin_fill reaches bin_len, bin_acc[r] goes to bins[r][bins_done] and is cleared.  A call of n samples closes at most n / bin_len
+ * + 1 bins; bins straddle calls.  The state per channel -- the eight filter values, bin_acc[2] and bin_fill
+ * (fmrx_audio_meter_state; all zero is a fresh channel) -- is carried across calls.  A NaN or an infinity in a row poisons that
+ * row's filter state: sum_k2 and the bins read NaN from then on, until fmrx_audio_meters_reset.
+ *
+ * Levels (fmrx_audio_levels; fmrx_audio_meters_derive, host arithmetic in double; full_scale is the float value of 0 dBFS, 2.0
+ * for the library's PCM pack, which maps it to 32 768; fs2 = full_scale^2).  Every dB value follows the signal meters' edge
+ * rule: clamped to [-99, 99], -99 where the numerator is not positive (0 / 0 and NaN included), 99 where only the denominator is
+ * not; the other fields read 0 where they are undefined (n = 0; correlation and balance_db of a mono channel; correlation where
+ * a row is silent).
+ *   peak_dbfs[r]   10 log10(peak^2 / fs2)            rms_dbfs[r]   10 log10(sum_x2 / n / fs2)          dc[r]   sum_x / n
+ *   loudness_lkfs  -0.691 + 10 log10((sum_k2[0] + sum_k2[1]) / n / fs2): ungated, over the record (add records for longer spans)
+ *   correlation    sum_lr / sqrt(sum_x2[0] sum_x2[1])      balance_db   10 log10(sum_x2[0] / sum_x2[1])
+ *   over_fraction  (over[0] + over[1]) / (n audio_channels)
+ * Thresholds for silence, overload or a mono alarm are the caller's.
+ *
+ * The device pass: parallel over channels only -- the high-pass has its poles at 0.995, so no warm-up of practical length
+ * seeds a later start to the serial walk's bits -- one lane per channel, 64 channels per wave.  A bank fills the card from
+ * about 16 384 channels; a single stream (n_channels = 1) is one lane walking serially: correct, not fast. */
+typedef struct fmrx_audio_meter {
+    uint64_t n, over[2];
+    double peak[2], sum_x[2], sum_x2[2], sum_k2[2], sum_lr;
+    uint64_t bins_done;
+} fmrx_audio_meter;
+typedef struct fmrx_audio_meter_state {
+    double z[2][4];      /* per row: shelf z1, z2, high-pass z1, z2 */
+    double bin_acc[2];
+    uint64_t bin_fill;
+} fmrx_audio_meter_state;
+typedef struct fmrx_audio_levels {
+    double peak_dbfs[2], rms_dbfs[2], dc[2], loudness_lkfs, correlation, balance_db, over_fraction;
+} fmrx_audio_levels;
+/* Gated loudness of one channel (fmrx_loudness_read): every value by the dB edge rule, -99 where there is nothing to read yet */
+typedef struct fmrx_loudness_levels {
+    double momentary, short_term, integrated;
+    uint64_t blocks;           /* gating blocks stored */
+    uint32_t full, reserved;   /* full: max_blocks reached; later blocks are not stored (integrated stands still) */
+} fmrx_loudness_levels;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_audio_meter) == 104, "fmrx_audio_meter layout");
+static_assert(sizeof(fmrx_audio_meter_state) == 88, "fmrx_audio_meter_state layout");
+static_assert(sizeof(fmrx_audio_levels) == 80, "fmrx_audio_levels layout");
+static_assert(sizeof(fmrx_loudness_levels) == 40, "fmrx_loudness_levels layout");
+#else
+_Static_assert(sizeof(fmrx_audio_meter) == 104, "fmrx_audio_meter layout");
+_Static_assert(sizeof(fmrx_audio_meter_state) == 88, "fmrx_audio_meter_state layout");
+_Static_assert(sizeof(fmrx_audio_levels) == 80, "fmrx_audio_levels layout");
+_Static_assert(sizeof(fmrx_loudness_levels) == 40, "fmrx_loudness_levels layout");
+#endif
+typedef struct fmrx_audio_meters fmrx_audio_meters;
+typedef struct fmrx_loudness fmrx_loudness;
+/* Host code, no device needed.  design: coef [2][5] = (b0, b1, b2, a1, a2) of the shelf, then of the high-pass; audio_Fs finite,
+ * 8 000 .. 768 000, else FMRX_EINVAL (as every function here that takes audio_Fs).  bin_len / max_bins: the bin length in samples
+ * and n_audio / bin_len + 1; 0 for an audio_Fs that design refuses. */
+FMRX_API int fmrx_audio_meters_design(double audio_Fs, double *coef);
+FMRX_API size_t fmrx_audio_meters_bin_len(double audio_Fs);
+FMRX_API size_t fmrx_audio_meters_max_bins(double audio_Fs, size_t n_audio);
+/* The host reference of one channel: rows [audio_channels][row_pitch] floats of which n are walked; *state is read and replaced;
+ * *rec is written; bins [2][max_bins] doubles is written (entries past bins_done, and a mono channel's second row, 0);
+ * max_bins >= n / bin_len + 1, else FMRX_EINVAL.  The body the kernel runs (audio_meters_core.hpp). */
+FMRX_API int fmrx_audio_meters_walk(double audio_Fs, int audio_channels, const float *rows, size_t row_pitch, size_t n,
+                                    fmrx_audio_meter_state *state_in_out, fmrx_audio_meter *rec, double *bins, size_t max_bins);
+FMRX_API int fmrx_audio_meters_derive(const fmrx_audio_meter *rec, int audio_channels, double full_scale, fmrx_audio_levels *out);
+/* n_audio: the most samples per row and call (fmrx_channels_n_audio), 1 .. 2^26; audio_channels 1 or 2 */
+FMRX_API int fmrx_audio_meters_create(fmrx_audio_meters **out, double audio_Fs, int n_channels, int audio_channels, size_t n_audio,
+                                      int device);
+FMRX_API int fmrx_audio_meters_destroy(fmrx_audio_meters *m);
+/* channel < 0: all.  Clears the channel's filter state, bin_acc and bin_fill.  Waits for the handle's last call; the state is
+ * clear when it returns, for a later call on any stream. */
+FMRX_API int fmrx_audio_meters_reset(fmrx_audio_meters *m, int channel);
+/* out [n_channels]: every channel's carried state; waits for the handle's last call */
+FMRX_API int fmrx_audio_meters_state_get(fmrx_audio_meters *m, fmrx_audio_meter_state *out);
+/* Asynchronous on `stream`, behind whatever wrote the rows on the same stream: d_audio [n_channels][audio_channels][row_pitch]
+ * floats, as the banks, the blend and the high-cut write them (row_pitch = n_audio there), of which the first n <= n_audio of
+ * every row are walked; 4-byte aligned.  Rows that are 16-byte aligned (d_audio is, and row_pitch is a multiple of 4) are
+ * fetched in 16-byte pieces, all others 4 bytes at a time, the same arithmetic.  The rows are only read.  One kernel launch; a
+ * second call before fmrx_audio_meters_collect replaces the results (the state has then advanced by both). */
+FMRX_API int fmrx_audio_meters_process_dev(fmrx_audio_meters *m, const float *d_audio, size_t row_pitch, size_t n, void *stream);
+/* records [n_channels], bins [n_channels][2][max_bins] doubles (may be NULL); waits for the last call (an event it recorded),
+ * not for the device */
+FMRX_API int fmrx_audio_meters_collect(fmrx_audio_meters *m, fmrx_audio_meter *records, double *bins);
+/* host rows [n_channels][audio_channels][row_pitch], synchronous: the single-stream use is n_channels = 1 with the audio
+ * fmrx_pipeline_process returns */
+FMRX_API int fmrx_audio_meters_process(fmrx_audio_meters *m, const float *audio, size_t row_pitch, size_t n, fmrx_audio_meter *records,
+                                       double *bins);
+/* Gated loudness by BS.1770-4, host only, no device needed: an integrator over what fmrx_audio_meters_collect returns.  Gating
+ * blocks are 4 consecutive bins with a hop of one bin, rows summed (400 ms, 75 % overlap); a block's loudness is -0.691 + 10
+ * log10(its energy / (4 bin_len) / full_scale^2).  momentary: the last block; short_term: the last 30 bins; integrated: over the
+ * stored blocks above the absolute gate of -70 LKFS that are also above the relative gate, 10 LU under the loudness of the mean
+ * of the absolutely gated blocks.  Per channel up to max_blocks block energies are stored (8 bytes each; one hour is 36 000);
+ * at max_blocks `full` is set and nothing is overwritten: momentary and short_term go on, integrated stands still. */
+FMRX_API int fmrx_loudness_create(fmrx_loudness **out, int n_channels, size_t bin_len, size_t max_blocks, double full_scale);
+FMRX_API int fmrx_loudness_destroy(fmrx_loudness *l);
+FMRX_API int fmrx_loudness_reset(fmrx_loudness *l, int channel);   /* channel < 0: all */
+/* records [n_channels] and bins [n_channels][2][max_bins] as fmrx_audio_meters_collect returned them (only bins_done is read
+ * of a record) */
+FMRX_API int fmrx_loudness_push(fmrx_loudness *l, const fmrx_audio_meter *records, const double *bins, size_t max_bins);
+FMRX_API int fmrx_loudness_read(const fmrx_loudness *l, int channel, fmrx_loudness_levels *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1504,6 +1504,169 @@ class HighCut(_MeterStage):
         return {"segments": a.value, "missed": b.value}
 
 
+# --------------------------------------------------------------------------
+# Audio meters: peak, RMS, BS.1770 loudness, stereo image of every channel of a bank
+# --------------------------------------------------------------------------
+AUDIO_METER_DTYPE = np.dtype([("n", "<u8"), ("over", "<u8", (2,)), ("peak", "<f8", (2,)), ("sum_x", "<f8", (2,)), ("sum_x2", "<f8", (2,)),
+                              ("sum_k2", "<f8", (2,)), ("sum_lr", "<f8"), ("bins_done", "<u8")])              # struct fmrx_audio_meter
+AUDIO_METER_STATE_DTYPE = np.dtype([("z", "<f8", (2, 4)), ("bin_acc", "<f8", (2,)), ("bin_fill", "<u8")])    # struct fmrx_audio_meter_state
+AUDIO_LEVELS_DTYPE = np.dtype([("peak_dbfs", "<f8", (2,)), ("rms_dbfs", "<f8", (2,)), ("dc", "<f8", (2,)), ("loudness_lkfs", "<f8"),
+                               ("correlation", "<f8"), ("balance_db", "<f8"), ("over_fraction", "<f8")])     # struct fmrx_audio_levels
+LOUDNESS_LEVELS_DTYPE = np.dtype([("momentary", "<f8"), ("short_term", "<f8"), ("integrated", "<f8"), ("blocks", "<u8"), ("full", "<u4"),
+                                  ("reserved", "<u4")])                                                      # struct fmrx_loudness_levels
+assert AUDIO_METER_DTYPE.itemsize == 104 and AUDIO_METER_STATE_DTYPE.itemsize == 88 and AUDIO_LEVELS_DTYPE.itemsize == 80
+assert LOUDNESS_LEVELS_DTYPE.itemsize == 40
+AUDIO_FULL_SCALE = 2.0    # the float value the PCM pack maps to 32 768
+_sig("fmrx_audio_meters_design", [_dbl, _f64p])
+_sig("fmrx_audio_meters_bin_len", [_dbl], _sz)
+_sig("fmrx_audio_meters_max_bins", [_dbl, _sz], _sz)
+_sig("fmrx_audio_meters_walk", [_dbl, _int, _vp, _sz, _sz, _vp, _vp, _vp, _sz])
+_sig("fmrx_audio_meters_derive", [_vp, _int, _dbl, _vp])
+_sig("fmrx_audio_meters_create", [C.POINTER(_vp), _dbl, _int, _int, _sz, _int])
+_sig("fmrx_audio_meters_destroy", [_vp])
+_sig("fmrx_audio_meters_reset", [_vp, _int])
+_sig("fmrx_audio_meters_state_get", [_vp, _vp])
+_sig("fmrx_audio_meters_process_dev", [_vp, _vp, _sz, _sz, _vp])
+_sig("fmrx_audio_meters_collect", [_vp, _vp, _vp])
+_sig("fmrx_audio_meters_process", [_vp, _vp, _sz, _sz, _vp, _vp])
+_sig("fmrx_loudness_create", [C.POINTER(_vp), _int, _sz, _sz, _dbl])
+_sig("fmrx_loudness_destroy", [_vp])
+_sig("fmrx_loudness_reset", [_vp, _int])
+_sig("fmrx_loudness_push", [_vp, _vp, _vp, _sz])
+_sig("fmrx_loudness_read", [_vp, _int, _vp])
+
+
+def audioMetersDesign(audio_Fs) -> np.ndarray:
+    """Host only: the K-weighting biquads for audio_Fs, float64 [2, 5]: (b0, b1, b2, a1, a2) of the shelf, then of the high-pass."""
+    c = np.zeros(10)
+    _check(lib.fmrx_audio_meters_design(float(audio_Fs), c))
+    return c.reshape(2, 5)
+
+
+def audioMetersBinLen(audio_Fs) -> int:
+    """Host only: the samples of a 100 ms bin."""
+    return lib.fmrx_audio_meters_bin_len(float(audio_Fs))
+
+
+def audioMetersWalk(audio_Fs, rows, state=None):
+    """Host only: the reference walk of one channel (fmrx_audio_meters_walk) on rows float32 [audio_channels, n]; state: the
+    AUDIO_METER_STATE_DTYPE record the last call returned (None or zeros: a fresh channel) -> (record, bins [2, max_bins], state)."""
+    x = _f32(rows)
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    st = np.zeros(1, AUDIO_METER_STATE_DTYPE) if state is None else np.array(state, dtype=AUDIO_METER_STATE_DTYPE).reshape(1).copy()
+    rec = np.zeros(1, AUDIO_METER_DTYPE)
+    nb = lib.fmrx_audio_meters_max_bins(float(audio_Fs), x.shape[1])
+    bins = np.zeros((2, max(nb, 1)))
+    _check(lib.fmrx_audio_meters_walk(float(audio_Fs), x.shape[0], x.ctypes.data, x.shape[1], x.shape[1], st.ctypes.data, rec.ctypes.data,
+                                      bins.ctypes.data, bins.shape[1]))
+    return rec[0], bins, st[0]
+
+
+def audioMetersDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dict:
+    """Host only: the levels (fmrx_audio_levels, as a dict; the arrays of 2 as tuples) of one AUDIO_METER_DTYPE record."""
+    r = np.array(rec, dtype=AUDIO_METER_DTYPE).reshape(1)
+    out = np.zeros(1, AUDIO_LEVELS_DTYPE)
+    _check(lib.fmrx_audio_meters_derive(r.ctypes.data, int(audio_channels), float(full_scale), out.ctypes.data))
+    return {k: (tuple(float(v) for v in out[0][k]) if out[0][k].ndim else float(out[0][k])) for k in AUDIO_LEVELS_DTYPE.names}
+
+
+class AudioMeters:
+    """Per channel of a receiver bank and call: overs, peak, sums, K-weighted energy, the stereo cross sum and the 100 ms bins of
+    the audio rows (fmrx_audio_meters_*).  The last stage of the chain, behind whatever wrote the rows on
+    stream s: am = AudioMeters.for_bank(bank); am.process_bank(d_audio, stream=s); recs, bins = am.collect(); am.derive(recs[c]).
+    It needs no Meters, so it also works behind the fused mono bank."""
+
+    def __init__(self, audio_Fs=48000.0, n_channels=1, audio_channels=2, n_audio=1920, device=0):
+        self.audio_Fs, self.n_channels, self.audio_channels, self.n_audio = float(audio_Fs), int(n_channels), int(audio_channels), int(n_audio)
+        self._h = _vp()
+        _check(lib.fmrx_audio_meters_create(C.byref(self._h), self.audio_Fs, self.n_channels, self.audio_channels, self.n_audio, device))
+        self.bin_len = lib.fmrx_audio_meters_bin_len(self.audio_Fs)
+        self.max_bins = lib.fmrx_audio_meters_max_bins(self.audio_Fs, self.n_audio)
+
+    @classmethod
+    def for_bank(cls, bank):
+        """The audio meters of a Channels bank, on the bank's device."""
+        return cls(bank.params.audio_Fs, bank.n_channels, bank.audio_channels, bank.n_audio, bank.device)
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_audio_meters_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, channel=-1):
+        _check(lib.fmrx_audio_meters_reset(self._h, channel))
+
+    def state(self) -> np.ndarray:
+        """Waits for the last call; every channel's carried state, AUDIO_METER_STATE_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, AUDIO_METER_STATE_DTYPE)
+        _check(lib.fmrx_audio_meters_state_get(self._h, out.ctypes.data))
+        return out
+
+    def process_dev(self, d_audio, row_pitch=None, n=None, stream=None):
+        """Device rows float32 [n_channels, audio_channels, row_pitch] of which the first n samples are walked (defaults: n_audio),
+        asynchronous on `stream`; the rows are only read."""
+        n = self.n_audio if n is None else int(n)
+        _check(lib.fmrx_audio_meters_process_dev(self._h, d_audio, n if row_pitch is None else int(row_pitch), n, stream))
+
+    def process_bank(self, d_audio, stream=None):
+        """process_dev on rows as the bank, the blend or the high-cut wrote them: [n_channels, audio_channels, n_audio]."""
+        self.process_dev(d_audio, self.n_audio, self.n_audio, stream)
+
+    def collect(self):
+        """Waits for the last call; (AUDIO_METER_DTYPE [n_channels], bins float64 [n_channels, 2, max_bins])."""
+        out, bins = np.zeros(self.n_channels, AUDIO_METER_DTYPE), np.zeros((self.n_channels, 2, self.max_bins))
+        _check(lib.fmrx_audio_meters_collect(self._h, out.ctypes.data, bins.ctypes.data))
+        return out, bins
+
+    def process(self, audio):
+        """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
+        x = _f32(audio).reshape(self.n_channels, self.audio_channels, -1)
+        out, bins = np.zeros(self.n_channels, AUDIO_METER_DTYPE), np.zeros((self.n_channels, 2, self.max_bins))
+        _check(lib.fmrx_audio_meters_process(self._h, x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data, bins.ctypes.data))
+        return out, bins
+
+    def derive(self, rec, full_scale=AUDIO_FULL_SCALE) -> dict:
+        return audioMetersDerive(rec, self.audio_channels, full_scale)
+
+
+class Loudness:
+    """Gated loudness by ITU-R BS.1770-4 over the audio meters' bins (fmrx_loudness_*), host only: loud = Loudness.for_meters(am);
+    loud.push(*am.collect()); loud.read(c) -> momentary, short_term, integrated (LKFS), blocks, full."""
+
+    def __init__(self, n_channels, bin_len, max_blocks=36000, full_scale=AUDIO_FULL_SCALE):
+        self.n_channels = int(n_channels)
+        self._h = _vp()
+        _check(lib.fmrx_loudness_create(C.byref(self._h), self.n_channels, int(bin_len), int(max_blocks), float(full_scale)))
+
+    @classmethod
+    def for_meters(cls, am, max_blocks=36000, full_scale=AUDIO_FULL_SCALE):
+        return cls(am.n_channels, am.bin_len, max_blocks, full_scale)
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.fmrx_loudness_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, channel=-1):
+        _check(lib.fmrx_loudness_reset(self._h, channel))
+
+    def push(self, recs, bins):
+        """What AudioMeters.collect() returned: records [n_channels] and bins [n_channels, 2, max_bins]."""
+        r = np.ascontiguousarray(recs, dtype=AUDIO_METER_DTYPE).reshape(self.n_channels)
+        b = np.ascontiguousarray(bins, dtype=np.float64).reshape(self.n_channels, 2, -1)
+        _check(lib.fmrx_loudness_push(self._h, r.ctypes.data, b.ctypes.data, b.shape[2]))
+
+    def read(self, channel=0) -> dict:
+        out = np.zeros(1, LOUDNESS_LEVELS_DTYPE)
+        _check(lib.fmrx_loudness_read(self._h, int(channel), out.ctypes.data))
+        return dict(momentary=float(out[0]["momentary"]), short_term=float(out[0]["short_term"]), integrated=float(out[0]["integrated"]),
+                    blocks=int(out[0]["blocks"]), full=bool(out[0]["full"]))
+
+
 class FrontEndPlan:
     """Reusable device-side tap tables for the fused front-end kernel (fmrx_fe_plan)."""
 

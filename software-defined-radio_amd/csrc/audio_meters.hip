@@ -1,0 +1,302 @@
+// audio_meters.hip -- the audio meters' handle, host arithmetic and C ABI (include/fmrx.h: fmrx_audio_meters_*): per channel of a
+// receiver bank and call, peak, sums, K-weighted energy, the stereo cross sum and the 100 ms bins of the audio rows.  Kernel:
+// kernels_audio_meters.hip; one channel's walk, shared with fmrx_audio_meters_walk below: audio_meters_core.hpp; definition:
+// tests/_audio_meters_model.py.
+//
+// A handle of the signal meters' kind (meters.hip), not meter_stage.hpp's: it reads no meters and writes no audio.  It keeps
+// the channels' state on the device (field-major, see fmrx_internal.hpp), the result arrays a call writes, their pinned host
+// copies, and the event the last call recorded behind the copies; collect waits on that event, not on the device.
+#include "audio_meters_core.hpp"
+#include "fmrx_internal.hpp"
+
+#include <cmath>
+
+using namespace fmrx;
+
+struct fmrx_audio_meters {
+    int device = 0, n_channels = 0, ac = 1;
+    double audio_Fs = 0.0;
+    size_t n_audio = 0, bin_len = 0, max_bins = 0;
+    audio_meters::Coefs coef;
+    DevBuf<double> d_state, d_sums, d_bins;
+    DevBuf<unsigned> d_fill, d_counts;
+    double *h_sums = nullptr, *h_bins = nullptr;   // pinned
+    unsigned *h_counts = nullptr;                  // pinned
+    hipEvent_t done = nullptr;
+    bool ran = false;
+    size_t n = 0;                                  // of the last call
+    DevBuf<float> d_rows;                          // fmrx_audio_meters_process only
+    ~fmrx_audio_meters()
+    {
+        if (h_sums) (void)hipHostFree(h_sums);
+        if (h_bins) (void)hipHostFree(h_bins);
+        if (h_counts) (void)hipHostFree(h_counts);
+        if (done) (void)hipEventDestroy(done);
+    }
+};
+
+namespace {
+
+bool good_fs(double Fs) { return std::isfinite(Fs) && Fs >= audio_meters::kMinFs && Fs <= audio_meters::kMaxFs; }
+
+// the signal meters' edge rule: offset + 10 log10(num / den) clamped to [-99, 99]; -99 where num is not positive (0 / 0 and NaN
+// included), 99 where only den is not
+double db(double num, double den, double offset = 0.0)
+{
+    if (!(num > 0.0)) return -99.0;
+    if (!(den > 0.0)) return 99.0;
+    const double v = offset + 10.0 * std::log10(num / den);
+    return v < -99.0 ? -99.0 : (v > 99.0 ? 99.0 : v);
+}
+
+template <int AC>
+void walk_channel(const audio_meters::Coefs &c, const float *rows, size_t pitch, size_t n, unsigned len, fmrx_audio_meter_state *st,
+                  fmrx_audio_meter *rec, double *bins, size_t max_bins)
+{
+    audio_meters::Walk<AC> w;
+    w.begin();
+    for (int r = 0; r < AC; r++) {
+        for (int i = 0; i < 4; i++) w.z[r][i] = st->z[r][i];
+        w.bin_acc[r] = st->bin_acc[r];
+    }
+    w.bin_fill = static_cast<unsigned>(st->bin_fill);
+    for (size_t k = 0; k < n; k++) {
+        const float x[2] = {rows[k], rows[(AC - 1) * pitch + k]};
+        w.sample(c, x, len, bins, max_bins);
+    }
+    w.finish(bins, max_bins);
+    std::memset(rec, 0, sizeof *rec);
+    rec->n = n;
+    for (int r = 0; r < AC; r++) {
+        for (int i = 0; i < 4; i++) st->z[r][i] = w.z[r][i];
+        st->bin_acc[r] = w.bin_acc[r];
+        rec->over[r] = w.over[r];
+        rec->peak[r] = static_cast<double>(w.peak[r]);
+        rec->sum_x[r] = w.sum_x[r];
+        rec->sum_x2[r] = w.sum_x2[r];
+        rec->sum_k2[r] = w.sum_k2[r];
+    }
+    st->bin_fill = w.bin_fill;
+    rec->sum_lr = w.sum_lr;
+    rec->bins_done = w.bins_done;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmrx_audio_meters_design(double audio_Fs, double *coef)
+{
+    if (!coef) return fail(FMRX_EINVAL, "audio_meters_design: null argument");
+    if (!good_fs(audio_Fs)) return fail(FMRX_EINVAL, "audio_meters_design: audio_Fs %g (finite, %g .. %g)", audio_Fs, audio_meters::kMinFs, audio_meters::kMaxFs);
+    audio_meters::Coefs c;
+    audio_meters::design(audio_Fs, &c);
+    std::memcpy(coef, c.q, sizeof c.q);
+    return FMRX_OK;
+}
+
+size_t fmrx_audio_meters_bin_len(double audio_Fs) { return good_fs(audio_Fs) ? audio_meters::bin_len(audio_Fs) : 0; }
+
+size_t fmrx_audio_meters_max_bins(double audio_Fs, size_t n_audio) { return good_fs(audio_Fs) ? n_audio / audio_meters::bin_len(audio_Fs) + 1 : 0; }
+
+int fmrx_audio_meters_walk(double audio_Fs, int audio_channels, const float *rows, size_t row_pitch, size_t n, fmrx_audio_meter_state *state,
+                           fmrx_audio_meter *rec, double *bins, size_t max_bins)
+{
+    if (!rows || !state || !rec || !bins) return fail(FMRX_EINVAL, "audio_meters_walk: null argument");
+    if (!good_fs(audio_Fs)) return fail(FMRX_EINVAL, "audio_meters_walk: audio_Fs %g (finite, %g .. %g)", audio_Fs, audio_meters::kMinFs, audio_meters::kMaxFs);
+    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "audio_meters_walk: audio_channels must be 1 or 2");
+    const size_t len = audio_meters::bin_len(audio_Fs);
+    if (row_pitch < n || max_bins < n / len + 1) return fail(FMRX_EINVAL, "audio_meters_walk: a pitch shorter than its row, or %zu bins for %zu samples", max_bins, n);
+    if (state->bin_fill >= len) return fail(FMRX_EINVAL, "audio_meters_walk: the state's bin_fill %llu is not below bin_len %zu", (unsigned long long)state->bin_fill, len);
+    audio_meters::Coefs c;
+    audio_meters::design(audio_Fs, &c);
+    if (audio_channels == 2) {
+        walk_channel<2>(c, rows, row_pitch, n, static_cast<unsigned>(len), state, rec, bins, max_bins);
+    } else {
+        walk_channel<1>(c, rows, row_pitch, n, static_cast<unsigned>(len), state, rec, bins, max_bins);
+    }
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_derive(const fmrx_audio_meter *m, int audio_channels, double full_scale, fmrx_audio_levels *out)
+{
+    if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_derive: null argument");
+    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "audio_meters_derive: audio_channels must be 1 or 2");
+    if (!(full_scale > 0.0) || !std::isfinite(full_scale)) return fail(FMRX_EINVAL, "audio_meters_derive: full_scale %g", full_scale);
+    const double n = static_cast<double>(m->n), fs2 = full_scale * full_scale;
+    std::memset(out, 0, sizeof *out);
+    for (int r = 0; r < 2; r++) {
+        const bool has = r < audio_channels;
+        out->peak_dbfs[r] = has ? db(m->peak[r] * m->peak[r], fs2) : -99.0;
+        out->rms_dbfs[r] = has ? db(n > 0.0 ? m->sum_x2[r] / n : 0.0, fs2) : -99.0;
+        out->dc[r] = has && n > 0.0 ? m->sum_x[r] / n : 0.0;
+    }
+    const double k2 = m->sum_k2[0] + (audio_channels == 2 ? m->sum_k2[1] : 0.0);
+    out->loudness_lkfs = db(n > 0.0 ? k2 / n : 0.0, fs2, -0.691);
+    if (audio_channels == 2) {
+        const double den = std::sqrt(m->sum_x2[0] * m->sum_x2[1]);
+        out->correlation = den > 0.0 && std::isfinite(den) ? m->sum_lr / den : 0.0;
+        out->balance_db = db(m->sum_x2[0], m->sum_x2[1]);
+    }
+    out->over_fraction = n > 0.0 ? (static_cast<double>(m->over[0]) + static_cast<double>(m->over[1])) / (n * audio_channels) : 0.0;
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_create(fmrx_audio_meters **out, double audio_Fs, int n_channels, int audio_channels, size_t n_audio, int device)
+{
+    if (!out) return fail(FMRX_EINVAL, "audio_meters_create: null argument");
+    if (!good_fs(audio_Fs)) return fail(FMRX_EINVAL, "audio_meters_create: audio_Fs %g (finite, %g .. %g)", audio_Fs, audio_meters::kMinFs, audio_meters::kMaxFs);
+    if (n_channels < 1) return fail(FMRX_EINVAL, "audio_meters_create: n_channels must be >= 1");
+    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "audio_meters_create: audio_channels must be 1 or 2");
+    if (n_audio < 1 || n_audio > (size_t{1} << 26)) return fail(FMRX_EINVAL, "audio_meters_create: n_audio %zu (1 .. 2^26)", n_audio);
+    FMRX_TRY(require_device());
+    FMRX_HIP(hipSetDevice(device));
+    fmrx_audio_meters *m = new fmrx_audio_meters;
+    m->device = device;
+    m->n_channels = n_channels;
+    m->ac = audio_channels;
+    m->audio_Fs = audio_Fs;
+    m->n_audio = n_audio;
+    m->bin_len = audio_meters::bin_len(audio_Fs);
+    m->max_bins = n_audio / m->bin_len + 1;
+    audio_meters::design(audio_Fs, &m->coef);
+    auto body = [&]() -> int {
+        const size_t N = n_channels;
+        FMRX_TRY(m->d_state.alloc(N * kAudioMetersStateFields));
+        FMRX_TRY(m->d_fill.alloc(N));
+        FMRX_TRY(m->d_sums.alloc(N * kAudioMetersSumFields));
+        FMRX_TRY(m->d_counts.alloc(N * kAudioMetersCountFields));
+        FMRX_TRY(m->d_bins.alloc(N * 2 * m->max_bins));
+        FMRX_HIP(hipMemset(m->d_state.p, 0, m->d_state.bytes()));
+        FMRX_HIP(hipMemset(m->d_fill.p, 0, m->d_fill.bytes()));
+        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_sums), m->d_sums.bytes(), hipHostMallocDefault));
+        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_counts), m->d_counts.bytes(), hipHostMallocDefault));
+        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_bins), m->d_bins.bytes(), hipHostMallocDefault));
+        FMRX_HIP(hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
+        return FMRX_OK;
+    };
+    const int rc = body();
+    if (rc != FMRX_OK) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_destroy(fmrx_audio_meters *m)
+{
+    if (!m) return FMRX_OK;
+    (void)hipSetDevice(m->device);
+    if (m->ran) (void)hipEventSynchronize(m->done);
+    delete m;
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_reset(fmrx_audio_meters *m, int channel)
+{
+    if (!m) return fail(FMRX_EINVAL, "audio_meters_reset: null handle");
+    if (channel >= m->n_channels) return fail(FMRX_EINVAL, "audio_meters_reset: channel %d of %d", channel, m->n_channels);
+    FMRX_HIP(hipSetDevice(m->device));
+    if (m->ran) FMRX_HIP(hipEventSynchronize(m->done));
+    const size_t N = m->n_channels;
+    if (channel < 0) {
+        FMRX_HIP(hipMemset(m->d_state.p, 0, m->d_state.bytes()));
+        FMRX_HIP(hipMemset(m->d_fill.p, 0, m->d_fill.bytes()));
+    } else {   // the channel's column of the field-major state
+        FMRX_HIP(hipMemset2D(m->d_state.p + channel, N * sizeof(double), 0, sizeof(double), kAudioMetersStateFields));
+        FMRX_HIP(hipMemset(m->d_fill.p + channel, 0, sizeof(unsigned)));
+    }
+    FMRX_HIP(hipStreamSynchronize(nullptr));   // clear before this returns: a call on any stream, non-blocking ones included, finds it so
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_state_get(fmrx_audio_meters *m, fmrx_audio_meter_state *out)
+{
+    if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_state_get: null argument");
+    FMRX_HIP(hipSetDevice(m->device));
+    if (m->ran) FMRX_HIP(hipEventSynchronize(m->done));
+    const size_t N = m->n_channels;
+    std::vector<double> st(N * kAudioMetersStateFields);
+    std::vector<unsigned> fill(N);
+    FMRX_HIP(hipMemcpy(st.data(), m->d_state.p, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    FMRX_HIP(hipMemcpy(fill.data(), m->d_fill.p, fill.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < N; c++) {
+        for (int r = 0; r < 2; r++) {
+            for (int i = 0; i < 4; i++) out[c].z[r][i] = st[(r * 4 + i) * N + c];
+            out[c].bin_acc[r] = st[(8 + r) * N + c];
+        }
+        out[c].bin_fill = fill[c];
+    }
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_process_dev(fmrx_audio_meters *m, const float *d_audio, size_t row_pitch, size_t n, void *stream)
+{
+    if (!m || !d_audio) return fail(FMRX_EINVAL, "audio_meters_process_dev: null argument");
+    if (n < 1 || n > m->n_audio) return fail(FMRX_EINVAL, "audio_meters_process_dev: %zu samples per row (1 .. the handle's n_audio %zu)", n, m->n_audio);
+    if (row_pitch < n) return fail(FMRX_EINVAL, "audio_meters_process_dev: pitch of %zu floats is shorter than a row's %zu samples", row_pitch, n);
+    FMRX_HIP(hipSetDevice(m->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AudioMetersArgs a;
+    a.x = d_audio;
+    a.pitch = row_pitch;
+    a.n = n;
+    a.n_channels = m->n_channels;
+    a.ac = m->ac;
+    std::memcpy(a.coef, m->coef.q, sizeof a.coef);
+    a.bin_len = static_cast<unsigned>(m->bin_len);
+    a.max_bins = m->max_bins;
+    a.state = m->d_state.p;
+    a.fill = m->d_fill.p;
+    a.sums = m->d_sums.p;
+    a.counts = m->d_counts.p;
+    a.bins = m->d_bins.p;
+    FMRX_TRY(audio_meters_launch(a, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_sums, m->d_sums.p, m->d_sums.bytes(), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_counts, m->d_counts.p, m->d_counts.bytes(), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_bins, m->d_bins.p, m->d_bins.bytes(), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipEventRecord(m->done, s));
+    m->n = n;
+    m->ran = true;
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_collect(fmrx_audio_meters *m, fmrx_audio_meter *out, double *bins)
+{
+    if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_collect: null argument");
+    if (!m->ran) return fail(FMRX_EINVAL, "audio_meters_collect: no call to collect");
+    FMRX_HIP(hipSetDevice(m->device));
+    FMRX_HIP(hipEventSynchronize(m->done));
+    const size_t N = m->n_channels;
+    for (size_t c = 0; c < N; c++) {
+        fmrx_audio_meter &r = out[c];
+        r.n = m->n;
+        for (int k = 0; k < 2; k++) {
+            r.peak[k] = m->h_sums[(0 + k) * N + c];
+            r.sum_x[k] = m->h_sums[(2 + k) * N + c];
+            r.sum_x2[k] = m->h_sums[(4 + k) * N + c];
+            r.sum_k2[k] = m->h_sums[(6 + k) * N + c];
+            r.over[k] = m->h_counts[k * N + c];
+        }
+        r.sum_lr = m->h_sums[8 * N + c];
+        r.bins_done = m->h_counts[2 * N + c];
+    }
+    if (bins) std::memcpy(bins, m->h_bins, N * 2 * m->max_bins * sizeof(double));
+    return FMRX_OK;
+}
+
+int fmrx_audio_meters_process(fmrx_audio_meters *m, const float *audio, size_t row_pitch, size_t n, fmrx_audio_meter *out, double *bins)
+{
+    if (!m || !audio || !out) return fail(FMRX_EINVAL, "audio_meters_process: null argument");
+    if (n < 1 || n > m->n_audio) return fail(FMRX_EINVAL, "audio_meters_process: %zu samples per row (1 .. the handle's n_audio %zu)", n, m->n_audio);
+    if (row_pitch < n) return fail(FMRX_EINVAL, "audio_meters_process: a pitch shorter than its row");
+    FMRX_HIP(hipSetDevice(m->device));
+    const size_t rows = static_cast<size_t>(m->n_channels) * m->ac, dp = (n + 3) / 4 * 4;   // the device copy's rows are 16-byte aligned
+    FMRX_TRY(m->d_rows.ensure(dp * rows));
+    FMRX_HIP(hipMemcpy2D(m->d_rows.p, dp * sizeof(float), audio, row_pitch * sizeof(float), n * sizeof(float), rows, hipMemcpyHostToDevice));
+    FMRX_TRY(fmrx_audio_meters_process_dev(m, m->d_rows.p, dp, n, nullptr));
+    return fmrx_audio_meters_collect(m, out, bins);
+}
+
+}  // extern "C"

@@ -449,4 +449,24 @@ struct HighcutArgs {
 // serial: the one-lane-per-row kernel; otherwise segments + verify, and *segments += the boundaries the verify step checked
 int highcut_apply_launch(const HighcutArgs &a, bool serial, hipStream_t s, unsigned long long *segments);
 
+// ---- audio meters (kernels_audio_meters.hip; one channel's walk in audio_meters_core.hpp; handle and C ABI in audio_meters.hip) -----------------
+constexpr int kAudioMetersStateFields = 10;   // per channel: z[2][4], bin_acc[2] (doubles); bin_fill lies in an array of its own
+constexpr int kAudioMetersSumFields = 9;      // per channel: peak[2], sum_x[2], sum_x2[2], sum_k2[2], sum_lr (doubles)
+constexpr int kAudioMetersCountFields = 3;    // per channel: over[2], bins_done (32-bit)
+struct AudioMetersArgs {
+    const float *x = nullptr;            // [n_channels][ac][pitch]; only read
+    size_t pitch = 0, n = 0;             // floats per row; samples of every row to walk
+    int n_channels = 0, ac = 1;
+    double coef[2][5] = {};              // fmrx_audio_meters_design
+    unsigned bin_len = 0;
+    size_t max_bins = 0;
+    // field-major [field][n_channels], so that the lanes of a wave touch consecutive addresses
+    double *state = nullptr;             // [kAudioMetersStateFields][n_channels], read and replaced
+    unsigned *fill = nullptr;            // [n_channels]: bin_fill, read and replaced
+    double *sums = nullptr;              // [kAudioMetersSumFields][n_channels], written
+    unsigned *counts = nullptr;          // [kAudioMetersCountFields][n_channels], written
+    double *bins = nullptr;              // [n_channels][2][max_bins], written
+};
+int audio_meters_launch(const AudioMetersArgs &a, hipStream_t s);
+
 }  // namespace fmrx
