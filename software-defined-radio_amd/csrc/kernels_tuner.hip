@@ -22,9 +22,13 @@
 // plus the filter's reach) is staged once in LDS and shared by the four groups; the rotation table sits in LDS beside it.
 // The stage is padded by 16 bytes per 16 R (the column stride) so that the 16 columns of a B read spread over the banks.
 //
-// These matrix kernels are the integer tuner's: U = 1, D = R <= 32, compiled for kTT / kTT16 tiles per wave.  Every other rate
-// U / D runs the templated ones of kernels_tuner_rational.hip; tuner_launch below, the one entry point, sends a call to either
-// or to the generic kernel, and then launches tuner_hist_kernel, which carries the stream's last `front` values to the next call.
+// These matrix kernels are the integer tuner's: U = 1, D = R <= 32 (the code says D), compiled for kTT / kTT16 tiles per wave.
+// Every other rate U / D runs the templated ones of kernels_tuner_rational.hip.  Both sets are made of the pieces of
+// tuner_mfma.hpp (wave set-up, window staging, the K-step loop tuner_mac, the epilogue tuner_finish8 / tuner_finish16); what
+// the integer kernels add is the K-step ranges of the 8 phases computed once per kernel (tuner_phase_ranges), the phase word
+// as a running add of w D (tuner_phase_words) and the direct store of every piece (tuner_store_piece).  tuner_launch below,
+// the one entry point, sends a call to either set or to the generic kernel, and then launches tuner_hist_kernel, which carries
+// the stream's last `front` values to the next call.
 //
 // The generic kernel (tuner_generic_kernel), for every rate: one thread per (channel, output), integer loops over the Tp taps
 // of the output's phase p_m = m D mod U against the samples from n_m = floor(m D / U) back (U = 1: all T taps from m R back);
@@ -41,7 +45,7 @@
 // wave and step instead of four keep the accumulators at 128 registers; every A fragment still feeds four MFMAs.
 #include "fmrx_internal.hpp"
 #include "tuner_host.hpp"
-#include "tuner_kernels.hpp"
+#include "tuner_mfma.hpp"
 
 #include <type_traits>
 
@@ -51,176 +55,87 @@ namespace {
 constexpr int kTT = 4;                        // tiles (of 16 columns x 8 outputs) per wave and step
 constexpr int kStepOut = 128 * kTT;           // outputs per channel and step
 
-// kFlip: what turns a raw byte into the int8 x (0x80 for unsigned bytes, 0 for signed ones) = the raw byte of a zero sample
+// K-step range of every phase, the same in every column and step (scalars)
+__device__ __forceinline__ void tuner_phase_ranges(int (&j0)[kTunerPhases], int (&j1)[kTunerPhases], int D, int T, int front)
+{
+#pragma unroll
+    for (int p = 0; p < kTunerPhases; p++) {
+        j0[p] = (front + 2 * D * p - 2 * (T - 1)) / 64;
+        j1[p] = (front + 2 * D * p + 1) / 64 + 1;
+    }
+}
+
+// phase words of a lane's 8 outputs from output mb on: w (n0 + (mb + p) D) mod 2^32, a running add
+__device__ __forceinline__ void tuner_phase_words(unsigned (&ph)[kTunerPhases], unsigned w, unsigned n0, long mb, int D)
+{
+    ph[0] = w * (n0 + static_cast<unsigned>(mb) * static_cast<unsigned>(D));
+#pragma unroll
+    for (int p = 1; p < kTunerPhases; p++) ph[p] = ph[p - 1] + w * static_cast<unsigned>(D);
+}
+
+// kFlip: as tuner_stage_bytes'
 template <unsigned kFlip>
 __device__ __forceinline__ void tuner_mfma_body(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
     const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, long pitch, int n_channels,
-    long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    long n_out, int D, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
     unsigned long long *__restrict__ levels)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     unsigned *tab = reinterpret_cast<unsigned *>(lds_raw);
     uint8_t *stage = lds_raw + kTunerTableSize * 4;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = static_cast<int>(blockIdx.y) * 4 + wave;
-    const int n_groups = (n_channels + kTunerGroup - 1) / kTunerGroup;
-    const bool live = grp < n_groups;                               // wave-uniform
-    const int col = lane & 15, g = lane >> 4;
-    const int ch = grp * kTunerGroup + g;
-    const bool ch_ok = live && ch < n_channels;
-
-    for (int i = tid; i < kTunerTableSize; i += 256) tab[i] = table[i];
-
-    // K-step range of every phase (scalars)
+    const TunerWave tw = tuner_wave(n_channels);
+    unsigned w;
+    int sh;
+    const i4 *a_grp = tuner_wave_setup(tw, tab, table, chan, a_img, 1, ksp, w, sh);
     int j0[kTunerPhases], j1[kTunerPhases];
-#pragma unroll
-    for (int p = 0; p < kTunerPhases; p++) {
-        j0[p] = (front + 2 * R * p - 2 * (T - 1)) / 64;
-        j1[p] = (front + 2 * R * p + 1) / 64 + 1;
-    }
-    unsigned w = 0;
-    int sh = 1;
-    if (ch_ok) {
-        const uint2 cp = chan[ch];
-        w = cp.x;
-        sh = static_cast<int>(cp.y);
-    }
-    const i4 *a_grp = a_img + static_cast<size_t>(live ? grp : 0) * kTunerPhases * ksp * 64 + lane;
-    const int n_pieces = 64 * R + 4 * ks;                           // 16-byte pieces of a step's window
+    tuner_phase_ranges(j0, j1, D, T, front);
+    const int n_pieces = 16 * kTT * D + 4 * ks;                     // 16-byte pieces of a step's window
+    const uint8_t *const planes[1] = {stage};
     unsigned clipped = 0;
     unsigned long long power = 0;
 
     const int step0 = static_cast<int>(blockIdx.x) * steps_per_wg;
     for (int st = step0; st < step0 + steps_per_wg && st < n_steps; st++) {
         const long m0 = static_cast<long>(st) * kStepOut;
-        const long q0 = 2L * R * m0 - front;                        // byte position of the window's start, relative to the call
         __syncthreads();                                            // the previous step's reads are done (and the table is written)
-        for (int i = tid; i < n_pieces; i += 256) {
-            const long q = q0 + 16L * i;
-            u4 v;
-            if (q < 0) {
-                v = *reinterpret_cast<const u4 *>(hist + front + q);
-            } else if (q + 16 <= n_bytes) {
-                v = *reinterpret_cast<const u4 *>(x + q);
-            } else {
-                unsigned b[4];                                      // past the call: zero samples
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    unsigned wd = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const long pos = q + 4 * d + k;
-                        wd |= (pos < n_bytes ? static_cast<unsigned>(x[pos]) : kFlip) << (8 * k);
-                    }
-                    b[d] = wd;
-                }
-                v = u4{b[0], b[1], b[2], b[3]};
-            }
-            if (kFlip) v ^= kFlip * 0x01010101u;                    // u8 -> u8 - 128 as int8
-            *reinterpret_cast<u4 *>(stage + 16 * (i + i / R)) = v;
-        }
+        tuner_stage_bytes<kFlip>(stage, x, hist, n_bytes, front, 2L * D * m0 - front, n_pieces, D, tw.tid);
         __syncthreads();
-        if (!live) continue;
+        if (!tw.live) continue;
 
-        i4 acc[kTT][kTunerPhases];
-#pragma unroll
-        for (int tt = 0; tt < kTT; tt++)
-#pragma unroll
-            for (int p = 0; p < kTunerPhases; p++) acc[tt][p] = i4{0, 0, 0, 0};
-        // this lane's B fragment of K-step j, tile tt: piece R (16 tt + col) + 4 j + g, padded by one piece per R
-        int rem = g % R, blk = g / R;                               // (4 j + g) mod R and div R
-        for (int j = 0; j < ks; j++) {
-            i4 b[kTT];
-#pragma unroll
-            for (int tt = 0; tt < kTT; tt++)
-                b[tt] = *reinterpret_cast<const i4 *>(stage + 16 * ((R + 1) * (16 * tt + col) + 4 * j + g + blk));
-            // the 8 phases' A fragments of this K-step, issued together (a phase outside its range loads its nearest stored step)
-            i4 a[kTunerPhases];
-#pragma unroll
-            for (int p = 0; p < kTunerPhases; p++) {
-                int jr = j - j0[p];
-                jr = jr < 0 ? 0 : (jr >= ksp ? ksp - 1 : jr);
-                a[p] = a_grp[(p * ksp + jr) * 64];
-            }
-#pragma unroll
-            for (int p = 0; p < kTunerPhases; p++) {
-                if (j >= j0[p] && j < j1[p]) {
-#pragma unroll
-                    for (int tt = 0; tt < kTT; tt++) acc[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], b[tt], acc[tt][p], 0, 0, 0);
-                }
-            }
-            rem += 4;
-            while (rem >= R) {
-                rem -= R;
-                blk++;
-            }
-        }
-        if (!ch_ok) continue;
+        i4 acc[1][kTT][kTunerPhases];
+        tuner_mac<kTT, 1>(acc, planes, a_grp, j0, j1, 0, ks, ksp, D, tw.col, tw.g);
+        if (!tw.ch_ok) continue;
 #pragma unroll
         for (int tt = 0; tt < kTT; tt++) {
-            const long mb = m0 + 128 * tt + 8 * col;                // this lane's first output time of the tile
+            const long mb = m0 + 128 * tt + 8 * tw.col;             // this lane's first output time of the tile
             if (mb >= n_out) continue;
-            unsigned pr[kTunerPhases];
-            unsigned ph = w * (n0 + static_cast<unsigned>(mb) * static_cast<unsigned>(R));
-            const unsigned dph = w * static_cast<unsigned>(R);
+            unsigned ph[kTunerPhases], pr[kTunerPhases];
+            tuner_phase_words(ph, w, n0, mb, D);
             const bool whole = mb + kTunerPhases <= n_out;
-            if (sh >= 17 && sh <= 47) {
-                unsigned cl[kTunerPhases], pw[kTunerPhases];
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) {
-                    const int ar = acc[tt][p][0] + 256 * acc[tt][p][1], ai = acc[tt][p][2] + 256 * acc[tt][p][3];
-                    cl[p] = 0;
-                    pw[p] = 0;
-                    pr[p] = tuner_round_pair_fast(ar, ai, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh - 16, cl[p], pw[p]);
-                    ph += dph;
-                }
-                unsigned cs = 0, ps = 0;
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++)
-                    if (whole || mb + p < n_out) {
-                        cs += cl[p];
-                        ps += pw[p];
-                    }
-                clipped += cs;
-                power += ps;
-            } else {
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) {
-                    const int ar = acc[tt][p][0] + 256 * acc[tt][p][1], ai = acc[tt][p][2] + 256 * acc[tt][p][3];
-                    unsigned cl = 0;
-                    unsigned long long pw = 0;
-                    pr[p] = tuner_round_pair(ar, ai, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh, cl, pw);
-                    if (mb + p < n_out) {
-                        clipped += cl;
-                        power += pw;
-                    }
-                    ph += dph;
-                }
-            }
-            tuner_store_piece(out + static_cast<long>(ch) * pitch + 2 * mb, pr, whole, n_out - mb);
+            tuner_finish8(acc[0][tt], ph, tab, sh, whole, mb, n_out, pr, clipped, power);
+            tuner_store_piece(out + static_cast<long>(tw.ch) * pitch + 2 * mb, pr, whole, n_out - mb);
         }
     }
-    tuner_add_levels(clipped, power, ch_ok && col == 0, levels + 2 * ch);
+    tuner_add_levels(clipped, power, tw.ch_ok && tw.col == 0, levels + 2 * tw.ch);
 }
 
 __global__ __launch_bounds__(256, 2) void tuner_mfma_kernel(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
     const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, long pitch, int n_channels,
-    long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    long n_out, int D, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
     unsigned long long *__restrict__ levels)
 {
-    tuner_mfma_body<0x80u>(x, hist, n_bytes, a_img, chan, table, out, pitch, n_channels, n_out, R, T, front, ks, ksp, n0, n_steps, steps_per_wg, levels);
+    tuner_mfma_body<0x80u>(x, hist, n_bytes, a_img, chan, table, out, pitch, n_channels, n_out, D, T, front, ks, ksp, n0, n_steps, steps_per_wg, levels);
 }
 
 __global__ __launch_bounds__(256, 2) void tuner_mfma_s8_kernel(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
     const uint2 *__restrict__ chan, const unsigned *__restrict__ table, uint8_t *__restrict__ out, long pitch, int n_channels,
-    long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    long n_out, int D, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
     unsigned long long *__restrict__ levels)
 {
-    tuner_mfma_body<0u>(x, hist, n_bytes, a_img, chan, table, out, pitch, n_channels, n_out, R, T, front, ks, ksp, n0, n_steps, steps_per_wg, levels);
+    tuner_mfma_body<0u>(x, hist, n_bytes, a_img, chan, table, out, pitch, n_channels, n_out, D, T, front, ks, ksp, n0, n_steps, steps_per_wg, levels);
 }
 
 // ---- signed 16-bit input: two byte planes against the same operand image ------------------------------------------
@@ -232,151 +147,50 @@ constexpr int kStepOut16 = 128 * kTT16;
 __global__ __launch_bounds__(256, 2) void tuner_mfma_s16_kernel(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_values, const i4 *__restrict__ a_img,
     const uint2 *__restrict__ chan, const int2 *__restrict__ kconst, const unsigned *__restrict__ table, uint8_t *__restrict__ out,
-    long pitch, int n_channels, long n_out, int R, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
+    long pitch, int n_channels, long n_out, int D, int T, int front, int ks, int ksp, unsigned n0, int n_steps, int steps_per_wg,
     unsigned long long *__restrict__ levels)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     unsigned *tab = reinterpret_cast<unsigned *>(lds_raw);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = static_cast<int>(blockIdx.y) * 4 + wave;
-    const int n_groups = (n_channels + kTunerGroup - 1) / kTunerGroup;
-    const bool live = grp < n_groups;                               // wave-uniform
-    const int col = lane & 15, g = lane >> 4;
-    const int ch = grp * kTunerGroup + g;
-    const bool ch_ok = live && ch < n_channels;
-    const int n_pieces = 16 * kTT16 * R + 4 * ks;                   // 16-byte pieces of a step's window, per plane
+    const TunerWave tw = tuner_wave(n_channels);
+    const int n_pieces = 16 * kTT16 * D + 4 * ks;                   // 16-byte pieces of a step's window, per plane
     uint8_t *stage_l = lds_raw + kTunerTableSize * 4;
-    uint8_t *stage_h = stage_l + 16 * (n_pieces + n_pieces / R + 1);
-
-    for (int i = tid; i < kTunerTableSize; i += 256) tab[i] = table[i];
-
+    uint8_t *stage_h = stage_l + tuner_plane_bytes(n_pieces, D);
+    unsigned w;
+    int sh;
+    const i4 *a_grp = tuner_wave_setup(tw, tab, table, chan, a_img, 1, ksp, w, sh);
     int j0[kTunerPhases], j1[kTunerPhases];
-#pragma unroll
-    for (int p = 0; p < kTunerPhases; p++) {
-        j0[p] = (front + 2 * R * p - 2 * (T - 1)) / 64;
-        j1[p] = (front + 2 * R * p + 1) / 64 + 1;
-    }
-    unsigned w = 0;
-    int sh = 1, kr = 0, ki = 0;
-    if (ch_ok) {
-        const uint2 cp = chan[ch];
-        w = cp.x;
-        sh = static_cast<int>(cp.y);
-        const int2 kc = kconst[ch];
-        kr = kc.x;
-        ki = kc.y;
-    }
-    const i4 *a_grp = a_img + static_cast<size_t>(live ? grp : 0) * kTunerPhases * ksp * 64 + lane;
+    tuner_phase_ranges(j0, j1, D, T, front);
+    const int2 kc = tw.ch_ok ? kconst[tw.ch] : int2{0, 0};          // U = 1: the 8 images' phase is the channel's one
+    const uint8_t *const planes[2] = {stage_l, stage_h};
     unsigned clipped = 0;
     unsigned long long power = 0;
 
     const int step0 = static_cast<int>(blockIdx.x) * steps_per_wg;
     for (int st = step0; st < step0 + steps_per_wg && st < n_steps; st++) {
         const long m0 = static_cast<long>(st) * kStepOut16;
-        const long q0 = 2L * R * m0 - front;                        // plane position of the window's start, relative to the call
         __syncthreads();
-        for (int i = tid; i < n_pieces; i += 256) {
-            const long q = q0 + 16L * i;
-            u4 v0, v1;                                              // 16 values = 32 raw bytes -> one piece per plane
-            if (q < 0) {
-                const u4 *src = reinterpret_cast<const u4 *>(hist + 2 * (front + q));
-                v0 = src[0];
-                v1 = src[1];
-            } else if (q + 16 <= n_values) {
-                const u4 *src = reinterpret_cast<const u4 *>(x + 2 * q);
-                v0 = src[0];
-                v1 = src[1];
-            } else {
-                unsigned b[8];                                      // past the call: zero samples
-#pragma unroll
-                for (int d = 0; d < 8; d++) {
-                    unsigned wd = 0;
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const long pos = q + 2 * d + k;
-                        wd |= (pos < n_values ? static_cast<unsigned>(reinterpret_cast<const unsigned short *>(x)[pos]) : 0u) << (16 * k);
-                    }
-                    b[d] = wd;
-                }
-                v0 = u4{b[0], b[1], b[2], b[3]};
-                v1 = u4{b[4], b[5], b[6], b[7]};
-            }
-            // a raw word is (low, high) of value 2 d, (low, high) of value 2 d + 1: even bytes -> low plane, odd -> high plane
-            const u4 lo = u4{__builtin_amdgcn_perm(v0[1], v0[0], 0x06040200u), __builtin_amdgcn_perm(v0[3], v0[2], 0x06040200u),
-                             __builtin_amdgcn_perm(v1[1], v1[0], 0x06040200u), __builtin_amdgcn_perm(v1[3], v1[2], 0x06040200u)};
-            const u4 hi = u4{__builtin_amdgcn_perm(v0[1], v0[0], 0x07050301u), __builtin_amdgcn_perm(v0[3], v0[2], 0x07050301u),
-                             __builtin_amdgcn_perm(v1[1], v1[0], 0x07050301u), __builtin_amdgcn_perm(v1[3], v1[2], 0x07050301u)};
-            const int off = 16 * (i + i / R);
-            *reinterpret_cast<u4 *>(stage_l + off) = lo ^ 0x80808080u;   // low byte - 128 as int8
-            *reinterpret_cast<u4 *>(stage_h + off) = hi;
-        }
+        tuner_stage_planes(stage_l, stage_h, x, hist, n_values, front, 2L * D * m0 - front, n_pieces, D, tw.tid);
         __syncthreads();
-        if (!live) continue;
+        if (!tw.live) continue;
 
-        i4 accl[kTT16][kTunerPhases], acch[kTT16][kTunerPhases];
-#pragma unroll
-        for (int tt = 0; tt < kTT16; tt++)
-#pragma unroll
-            for (int p = 0; p < kTunerPhases; p++) accl[tt][p] = acch[tt][p] = i4{0, 0, 0, 0};
-        int rem = g % R, blk = g / R;                               // (4 j + g) mod R and div R
-        for (int j = 0; j < ks; j++) {
-            i4 bl[kTT16], bh[kTT16];
-#pragma unroll
-            for (int tt = 0; tt < kTT16; tt++) {
-                const int off = 16 * ((R + 1) * (16 * tt + col) + 4 * j + g + blk);
-                bl[tt] = *reinterpret_cast<const i4 *>(stage_l + off);
-                bh[tt] = *reinterpret_cast<const i4 *>(stage_h + off);
-            }
-            i4 a[kTunerPhases];
-#pragma unroll
-            for (int p = 0; p < kTunerPhases; p++) {
-                int jr = j - j0[p];
-                jr = jr < 0 ? 0 : (jr >= ksp ? ksp - 1 : jr);
-                a[p] = a_grp[(p * ksp + jr) * 64];
-            }
-#pragma unroll
-            for (int p = 0; p < kTunerPhases; p++) {
-                if (j >= j0[p] && j < j1[p]) {
-#pragma unroll
-                    for (int tt = 0; tt < kTT16; tt++) {
-                        accl[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], bl[tt], accl[tt][p], 0, 0, 0);
-                        acch[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], bh[tt], acch[tt][p], 0, 0, 0);
-                    }
-                }
-            }
-            rem += 4;
-            while (rem >= R) {
-                rem -= R;
-                blk++;
-            }
-        }
-        if (!ch_ok) continue;
+        i4 acc[2][kTT16][kTunerPhases];                             // low plane, high plane
+        tuner_mac<kTT16, 2>(acc, planes, a_grp, j0, j1, 0, ks, ksp, D, tw.col, tw.g);
+        if (!tw.ch_ok) continue;
 #pragma unroll
         for (int tt = 0; tt < kTT16; tt++) {
-            const long mb = m0 + 128 * tt + 8 * col;                // this lane's first output time of the tile
+            const long mb = m0 + 128 * tt + 8 * tw.col;             // this lane's first output time of the tile
             if (mb >= n_out) continue;
-            unsigned pr[kTunerPhases];
-            unsigned ph = w * (n0 + static_cast<unsigned>(mb) * static_cast<unsigned>(R));
-            const unsigned dph = w * static_cast<unsigned>(R);
+            unsigned ph[kTunerPhases], pr[kTunerPhases];
+            tuner_phase_words(ph, w, n0, mb, D);
             const bool whole = mb + kTunerPhases <= n_out;
 #pragma unroll
-            for (int p = 0; p < kTunerPhases; p++) {
-                const int lr = accl[tt][p][0] + 256 * accl[tt][p][1], li = accl[tt][p][2] + 256 * accl[tt][p][3];
-                const int hr = acch[tt][p][0] + 256 * acch[tt][p][1], hi = acch[tt][p][2] + 256 * acch[tt][p][3];
-                unsigned cl = 0;
-                unsigned long long pw = 0;
-                pr[p] = tuner_round_pair_planes(lr, li, hr, hi, kr, ki, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh, cl, pw);
-                if (whole || mb + p < n_out) {
-                    clipped += cl;
-                    power += pw;
-                }
-                ph += dph;
-            }
-            tuner_store_piece(out + static_cast<long>(ch) * pitch + 2 * mb, pr, whole, n_out - mb);
+            for (int p = 0; p < kTunerPhases; p++)
+                pr[p] = tuner_finish16(acc[0][tt][p], acc[1][tt][p], kc, ph[p], tab, sh, whole || mb + p < n_out, clipped, power);
+            tuner_store_piece(out + static_cast<long>(tw.ch) * pitch + 2 * mb, pr, whole, n_out - mb);
         }
     }
-    tuner_add_levels(clipped, power, ch_ok && col == 0, levels + 2 * ch);
+    tuner_add_levels(clipped, power, tw.ch_ok && tw.col == 0, levels + 2 * tw.ch);
 }
 
 // FMT: kTunerU8 / kTunerS8 / kTunerS16.  x, hist: raw values (bytes, or little-endian int16 for S16); the 16-bit format's sums
@@ -455,7 +269,7 @@ __global__ __launch_bounds__(256) void tuner_hist_kernel(const uint8_t *__restri
     new_hist[i] = pos < 0 ? old_hist[front + pos] : x[pos];
 }
 
-constexpr size_t kTwoPerCu = 64 * 1024, kOnePerCu = 160 * 1024;     // LDS of a workgroup: two on a CU, or one
+constexpr size_t kOnePerCu = 160 * 1024;     // LDS of a workgroup that has a CU to itself (two on a CU: kTwoPerCu)
 
 }  // namespace
 
@@ -492,13 +306,13 @@ int tuner_launch(const TunerLaunch &a, hipStream_t stream)
             if (!tuner_integer_rate(a.U, a.D)) {
                 FMRX_TRY(tuner_rat_mfma_launch(a, n_out, n_steps, per, dim3(gx, gy), lds, stream));
             } else if (a.format == kTunerS16) {
-                hipLaunchKernelGGL(tuner_mfma_s16_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x, a.hist, a.n_bytes,
-                                   reinterpret_cast<const i4 *>(a.a_img), a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels, n_out, a.D,
-                                   a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+                FMRX_TRY(tuner_launch_mfma(tuner_mfma_s16_kernel, dim3(gx, gy), lds, stream, a.x, a.hist, a.n_bytes,
+                                           reinterpret_cast<const i4 *>(a.a_img), a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels, n_out,
+                                           a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels));
             } else {
-                hipLaunchKernelGGL(a.format == kTunerS8 ? tuner_mfma_s8_kernel : tuner_mfma_kernel, dim3(gx, gy), dim3(256), lds, stream, a.x,
-                                   a.hist, a.n_bytes, reinterpret_cast<const i4 *>(a.a_img), a.chan, a.table, a.out, a.pitch, a.n_channels,
-                                   n_out, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels);
+                FMRX_TRY(tuner_launch_mfma(a.format == kTunerS8 ? tuner_mfma_s8_kernel : tuner_mfma_kernel, dim3(gx, gy), lds, stream, a.x,
+                                           a.hist, a.n_bytes, reinterpret_cast<const i4 *>(a.a_img), a.chan, a.table, a.out, a.pitch,
+                                           a.n_channels, n_out, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels));
             }
         } else {
             const auto kernel = a.format == kTunerS16 ? tuner_generic_s16_kernel : a.format == kTunerS8 ? tuner_generic_s8_kernel : tuner_generic_kernel;

@@ -4,7 +4,11 @@
 //
 //   y_c[m] = Q( e^{-j phi_c(n_m)} * sum_{j<Tp} taps_c[p_m][j] * x[n_m - j] ),   taps_c complex int16, phase-major [U][Tp]
 //
-// Integer arithmetic throughout, as in kernels_tuner.hip, whose device helpers (tuner_kernels.hpp) round and store here too.
+// Integer arithmetic throughout, as in kernels_tuner.hip.  The kernels here are made of the same pieces as the integer tuner's
+// (tuner_mfma.hpp: wave set-up, window staging, the K-step loop tuner_mac, the epilogue tuner_finish8 / tuner_finish16; rounding
+// and stores in tuner_kernels.hpp).  What this file adds: the TT template, the loop over the U blocks of a column with
+// rat_block(u)'s K-step ranges and sample offsets, the phase word w (n_b + nq[p]) and the constant of each image's phase, and
+// the output path rat_emit / rat_flush / rat_wave_sync.
 //
 // The matrix kernels (tuner_rat_mfma_kernel, _s8_, _s16_), on v_mfma_i32_16x16x64_i8:
 //   rows    (M=16) = 4 channels x {real, imaginary part of the accumulator} x 2 balanced base-256 digits of the taps
@@ -25,15 +29,15 @@
 // and after the step's last block the wave writes each row segment with whole-wave contiguous 16-byte stores (rat_flush).
 // Where that buffer (4 waves x TT x U KiB) does not fit the LDS beside the window, the pieces are stored directly.
 // A workgroup = 4 waves = 4 channel groups x TT tiles per step; TT (4, 2 or 1) is the largest whose staged window, 256 D bytes
-// per tile plus the reach, keeps two workgroups on a CU.  The 16-bit kernel stages two byte planes as tuner_mfma_s16_kernel
-// does; its constant 128 (row sum of the taps) is a pair per PHASE, U pairs per channel.
+// per tile plus the reach, keeps two workgroups on a CU.  The 16-bit kernel stages two byte planes (tuner_stage_planes); its
+// constant 128 (row sum of the taps) is a pair per PHASE, U pairs per channel.
 //
 // Launched by tuner_launch (kernels_tuner.hip) through tuner_rat_mfma_launch for every rate outside the integer tuner's
 // (U = 1, D <= 32), with the tiles and the output path tuner_plan chose.  The generic kernels and the history kernel, one set
 // for all rates, are in kernels_tuner.hip.
 #include "fmrx_internal.hpp"
 #include "tuner_host.hpp"
-#include "tuner_kernels.hpp"
+#include "tuner_mfma.hpp"
 
 namespace fmrx {
 namespace {
@@ -102,8 +106,15 @@ __device__ __forceinline__ void rat_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// kFlip: what turns a raw byte into the int8 x (0x80 for unsigned bytes, 0 for signed ones) = the raw byte of a zero sample
-// TT: tiles (of 16 columns x 8 U outputs) per wave and step
+// The phase words of block u's 8 outputs in column cidx: the images' newest samples are nq[p] samples into the column
+__device__ __forceinline__ void rat_phase_words(unsigned (&ph)[kTunerPhases], unsigned w, unsigned n0, long cidx, int D, const RatBlock &rb)
+{
+    const unsigned nb = n0 + static_cast<unsigned>(cidx) * static_cast<unsigned>(kTunerPhases * D);
+#pragma unroll
+    for (int p = 0; p < kTunerPhases; p++) ph[p] = w * (nb + static_cast<unsigned>(rb.nq[p]));
+}
+
+// kFlip: as tuner_stage_bytes';  TT: tiles (of 16 columns x 8 U outputs) per wave and step
 template <unsigned kFlip, int TT>
 __device__ __forceinline__ void tuner_rat_mfma_body(
     const uint8_t *__restrict__ x, const uint8_t *__restrict__ hist, long n_bytes, const i4 *__restrict__ a_img,
@@ -114,151 +125,49 @@ __device__ __forceinline__ void tuner_rat_mfma_body(
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     unsigned *tab = reinterpret_cast<unsigned *>(lds_raw);
     uint8_t *stage = lds_raw + kTunerTableSize * 4;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = static_cast<int>(blockIdx.y) * 4 + wave;
-    const int n_groups = (n_channels + kTunerGroup - 1) / kTunerGroup;
-    const bool live = grp < n_groups;                               // wave-uniform
-    const int col = lane & 15, g = lane >> 4;
-    const int ch = grp * kTunerGroup + g;
-    const bool ch_ok = live && ch < n_channels;
-
-    for (int i = tid; i < kTunerTableSize; i += 256) tab[i] = table[i];
-
-    unsigned w = 0;
-    int sh = 1;
-    if (ch_ok) {
-        const uint2 cp = chan[ch];
-        w = cp.x;
-        sh = static_cast<int>(cp.y);
-    }
-    const i4 *a_grp = a_img + static_cast<size_t>(live ? grp : 0) * kTunerPhases * U * ksp * 64 + lane;
+    const TunerWave tw = tuner_wave(n_channels);
+    unsigned w;
+    int sh;
+    const i4 *a_grp = tuner_wave_setup(tw, tab, table, chan, a_img, U, ksp, w, sh);
     const int n_pieces = 16 * TT * D + 4 * ks;                      // 16-byte pieces of a step's window
-    uint8_t *obuf = stage + 16 * (n_pieces + n_pieces / D + 1) + wave * (TT * 4 * 256 * U);   // this wave's output buffer (via_lds)
+    uint8_t *obuf = stage + tuner_plane_bytes(n_pieces, D) + tw.wave * (TT * 4 * 256 * U);   // this wave's output buffer (via_lds)
+    const uint8_t *const planes[1] = {stage};
     unsigned clipped = 0;
     unsigned long long power = 0;
 
     const int step0 = static_cast<int>(blockIdx.x) * steps_per_wg;
     for (int st = step0; st < step0 + steps_per_wg && st < n_steps; st++) {
         const long c0 = static_cast<long>(st) * (16 * TT);          // the step's first column
-        const long q0 = 16L * D * c0 - front;                       // byte position of the window's start, relative to the call
         __syncthreads();                                            // the previous step's reads are done (and the table is written)
-        for (int i = tid; i < n_pieces; i += 256) {
-            const long q = q0 + 16L * i;
-            u4 v;
-            if (q < 0) {
-                v = *reinterpret_cast<const u4 *>(hist + front + q);
-            } else if (q + 16 <= n_bytes) {
-                v = *reinterpret_cast<const u4 *>(x + q);
-            } else {
-                unsigned b[4];                                      // past the call: zero samples
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    unsigned wd = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const long pos = q + 4 * d + k;
-                        wd |= (pos < n_bytes ? static_cast<unsigned>(x[pos]) : kFlip) << (8 * k);
-                    }
-                    b[d] = wd;
-                }
-                v = u4{b[0], b[1], b[2], b[3]};
-            }
-            if (kFlip) v ^= kFlip * 0x01010101u;                    // u8 -> u8 - 128 as int8
-            *reinterpret_cast<u4 *>(stage + 16 * (i + i / D)) = v;
-        }
+        tuner_stage_bytes<kFlip>(stage, x, hist, n_bytes, front, 16L * D * c0 - front, n_pieces, D, tw.tid);
         __syncthreads();
-        if (!live) continue;
+        if (!tw.live) continue;
 
         for (int u = 0; u < U; u++) {
             const RatBlock rb = rat_block(u, U, D, Tp, front);
-            i4 acc[TT][kTunerPhases];
-#pragma unroll
-            for (int tt = 0; tt < TT; tt++)
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) acc[tt][p] = i4{0, 0, 0, 0};
-            // this lane's B fragment of K-step j, tile tt: piece D (16 tt + col) + 4 j + g, padded by one piece per D
-            const int jlo = rb.j0[0], jhi = rb.j1[kTunerPhases - 1];
-            int rem = (4 * jlo + g) % D, blk = (4 * jlo + g) / D;   // (4 j + g) mod D and div D
-            for (int j = jlo; j < jhi; j++) {
-                i4 b[TT];
-#pragma unroll
-                for (int tt = 0; tt < TT; tt++)
-                    b[tt] = *reinterpret_cast<const i4 *>(stage + 16 * ((D + 1) * (16 * tt + col) + 4 * j + g + blk));
-                // the 8 images' A fragments of this K-step (an image outside its range loads its nearest stored step)
-                i4 a[kTunerPhases];
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) {
-                    int jr = j - rb.j0[p];
-                    jr = jr < 0 ? 0 : (jr >= ksp ? ksp - 1 : jr);
-                    a[p] = a_grp[((kTunerPhases * u + p) * ksp + jr) * 64];
-                }
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) {
-                    if (j >= rb.j0[p] && j < rb.j1[p]) {
-#pragma unroll
-                        for (int tt = 0; tt < TT; tt++) acc[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], b[tt], acc[tt][p], 0, 0, 0);
-                    }
-                }
-                rem += 4;
-                while (rem >= D) {
-                    rem -= D;
-                    blk++;
-                }
-            }
-            if (ch_ok) {
+            i4 acc[1][TT][kTunerPhases];
+            tuner_mac<TT, 1>(acc, planes, a_grp + kTunerPhases * u * ksp * 64, rb.j0, rb.j1, rb.j0[0], rb.j1[kTunerPhases - 1], ksp, D, tw.col, tw.g);
+            if (tw.ch_ok) {
 #pragma unroll
                 for (int tt = 0; tt < TT; tt++) {
-                    const long cidx = c0 + 16 * tt + col;           // this lane's column of the call
+                    const long cidx = c0 + 16 * tt + tw.col;        // this lane's column of the call
                     const long mb = (cidx * U + u) * kTunerPhases;  // its first output time of the block
                     if (mb >= n_out) continue;
-                    unsigned pr[kTunerPhases];
-                    const unsigned nb = n0 + static_cast<unsigned>(cidx) * static_cast<unsigned>(kTunerPhases * D);
+                    unsigned ph[kTunerPhases], pr[kTunerPhases];
+                    rat_phase_words(ph, w, n0, cidx, D, rb);
                     const bool whole = mb + kTunerPhases <= n_out;
-                    if (sh >= 17 && sh <= 47) {
-                        unsigned cl[kTunerPhases], pw[kTunerPhases];
-#pragma unroll
-                        for (int p = 0; p < kTunerPhases; p++) {
-                            const int ar = acc[tt][p][0] + 256 * acc[tt][p][1], ai = acc[tt][p][2] + 256 * acc[tt][p][3];
-                            const unsigned ph = w * (nb + static_cast<unsigned>(rb.nq[p]));
-                            cl[p] = 0;
-                            pw[p] = 0;
-                            pr[p] = tuner_round_pair_fast(ar, ai, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh - 16, cl[p], pw[p]);
-                        }
-                        unsigned cs = 0, ps = 0;
-#pragma unroll
-                        for (int p = 0; p < kTunerPhases; p++)
-                            if (whole || mb + p < n_out) {
-                                cs += cl[p];
-                                ps += pw[p];
-                            }
-                        clipped += cs;
-                        power += ps;
-                    } else {
-#pragma unroll
-                        for (int p = 0; p < kTunerPhases; p++) {
-                            const int ar = acc[tt][p][0] + 256 * acc[tt][p][1], ai = acc[tt][p][2] + 256 * acc[tt][p][3];
-                            const unsigned ph = w * (nb + static_cast<unsigned>(rb.nq[p]));
-                            unsigned cl = 0;
-                            unsigned long long pw = 0;
-                            pr[p] = tuner_round_pair(ar, ai, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh, cl, pw);
-                            if (mb + p < n_out) {
-                                clipped += cl;
-                                power += pw;
-                            }
-                        }
-                    }
-                    rat_emit(obuf, via_lds, tt, g, col, u, U, out + static_cast<long>(ch) * pitch + 2 * mb, pr, whole, n_out - mb);
+                    tuner_finish8(acc[0][tt], ph, tab, sh, whole, mb, n_out, pr, clipped, power);
+                    rat_emit(obuf, via_lds, tt, tw.g, tw.col, u, U, out + static_cast<long>(tw.ch) * pitch + 2 * mb, pr, whole, n_out - mb);
                 }
             }
         }
         if (via_lds) {
             rat_wave_sync();
-            rat_flush(obuf, out, pitch, grp, n_channels, c0, n_out, U, TT, lane);
+            rat_flush(obuf, out, pitch, tw.grp, n_channels, c0, n_out, U, TT, tw.lane);
             rat_wave_sync();
         }
     }
-    tuner_add_levels(clipped, power, ch_ok && col == 0, levels + 2 * ch);
+    tuner_add_levels(clipped, power, tw.ch_ok && tw.col == 0, levels + 2 * tw.ch);
 }
 
 #define FMRX_TUNER_RAT_ARGS                                                                                                             \
@@ -295,162 +204,57 @@ __global__ __launch_bounds__(256, 2) void tuner_rat_mfma_s16_kernel(
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     unsigned *tab = reinterpret_cast<unsigned *>(lds_raw);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = static_cast<int>(blockIdx.y) * 4 + wave;
-    const int n_groups = (n_channels + kTunerGroup - 1) / kTunerGroup;
-    const bool live = grp < n_groups;                               // wave-uniform
-    const int col = lane & 15, g = lane >> 4;
-    const int ch = grp * kTunerGroup + g;
-    const bool ch_ok = live && ch < n_channels;
+    const TunerWave tw = tuner_wave(n_channels);
     const int n_pieces = 16 * TT * D + 4 * ks;                      // 16-byte pieces of a step's window, per plane
     uint8_t *stage_l = lds_raw + kTunerTableSize * 4;
-    uint8_t *stage_h = stage_l + 16 * (n_pieces + n_pieces / D + 1);
-    uint8_t *obuf = stage_h + 16 * (n_pieces + n_pieces / D + 1) + wave * (TT * 4 * 256 * U);   // this wave's output buffer (via_lds)
-
-    for (int i = tid; i < kTunerTableSize; i += 256) tab[i] = table[i];
-
-    unsigned w = 0;
-    int sh = 1;
-    if (ch_ok) {
-        const uint2 cp = chan[ch];
-        w = cp.x;
-        sh = static_cast<int>(cp.y);
-    }
-    const int2 *kc_ch = kconst + static_cast<size_t>(ch_ok ? ch : 0) * U;
-    const i4 *a_grp = a_img + static_cast<size_t>(live ? grp : 0) * kTunerPhases * U * ksp * 64 + lane;
+    uint8_t *stage_h = stage_l + tuner_plane_bytes(n_pieces, D);
+    uint8_t *obuf = stage_h + tuner_plane_bytes(n_pieces, D) + tw.wave * (TT * 4 * 256 * U);   // this wave's output buffer (via_lds)
+    unsigned w;
+    int sh;
+    const i4 *a_grp = tuner_wave_setup(tw, tab, table, chan, a_img, U, ksp, w, sh);
+    const int2 *kc_ch = kconst + static_cast<size_t>(tw.ch_ok ? tw.ch : 0) * U;
+    const uint8_t *const planes[2] = {stage_l, stage_h};
     unsigned clipped = 0;
     unsigned long long power = 0;
 
     const int step0 = static_cast<int>(blockIdx.x) * steps_per_wg;
     for (int st = step0; st < step0 + steps_per_wg && st < n_steps; st++) {
         const long c0 = static_cast<long>(st) * (16 * TT);
-        const long q0 = 16L * D * c0 - front;                       // plane position of the window's start, relative to the call
         __syncthreads();
-        for (int i = tid; i < n_pieces; i += 256) {
-            const long q = q0 + 16L * i;
-            u4 v0, v1;                                              // 16 values = 32 raw bytes -> one piece per plane
-            if (q < 0) {
-                const u4 *src = reinterpret_cast<const u4 *>(hist + 2 * (front + q));
-                v0 = src[0];
-                v1 = src[1];
-            } else if (q + 16 <= n_values) {
-                const u4 *src = reinterpret_cast<const u4 *>(x + 2 * q);
-                v0 = src[0];
-                v1 = src[1];
-            } else {
-                unsigned b[8];                                      // past the call: zero samples
-#pragma unroll
-                for (int d = 0; d < 8; d++) {
-                    unsigned wd = 0;
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const long pos = q + 2 * d + k;
-                        wd |= (pos < n_values ? static_cast<unsigned>(reinterpret_cast<const unsigned short *>(x)[pos]) : 0u) << (16 * k);
-                    }
-                    b[d] = wd;
-                }
-                v0 = u4{b[0], b[1], b[2], b[3]};
-                v1 = u4{b[4], b[5], b[6], b[7]};
-            }
-            // a raw word is (low, high) of value 2 d, (low, high) of value 2 d + 1: even bytes -> low plane, odd -> high plane
-            const u4 lo = u4{__builtin_amdgcn_perm(v0[1], v0[0], 0x06040200u), __builtin_amdgcn_perm(v0[3], v0[2], 0x06040200u),
-                             __builtin_amdgcn_perm(v1[1], v1[0], 0x06040200u), __builtin_amdgcn_perm(v1[3], v1[2], 0x06040200u)};
-            const u4 hi = u4{__builtin_amdgcn_perm(v0[1], v0[0], 0x07050301u), __builtin_amdgcn_perm(v0[3], v0[2], 0x07050301u),
-                             __builtin_amdgcn_perm(v1[1], v1[0], 0x07050301u), __builtin_amdgcn_perm(v1[3], v1[2], 0x07050301u)};
-            const int off = 16 * (i + i / D);
-            *reinterpret_cast<u4 *>(stage_l + off) = lo ^ 0x80808080u;   // low byte - 128 as int8
-            *reinterpret_cast<u4 *>(stage_h + off) = hi;
-        }
+        tuner_stage_planes(stage_l, stage_h, x, hist, n_values, front, 16L * D * c0 - front, n_pieces, D, tw.tid);
         __syncthreads();
-        if (!live) continue;
+        if (!tw.live) continue;
 
         for (int u = 0; u < U; u++) {
             const RatBlock rb = rat_block(u, U, D, Tp, front);
-            i4 accl[TT][kTunerPhases], acch[TT][kTunerPhases];
-#pragma unroll
-            for (int tt = 0; tt < TT; tt++)
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) accl[tt][p] = acch[tt][p] = i4{0, 0, 0, 0};
-            const int jlo = rb.j0[0], jhi = rb.j1[kTunerPhases - 1];
-            int rem = (4 * jlo + g) % D, blk = (4 * jlo + g) / D;   // (4 j + g) mod D and div D
-            for (int j = jlo; j < jhi; j++) {
-                i4 bl[TT], bh[TT];
-#pragma unroll
-                for (int tt = 0; tt < TT; tt++) {
-                    const int off = 16 * ((D + 1) * (16 * tt + col) + 4 * j + g + blk);
-                    bl[tt] = *reinterpret_cast<const i4 *>(stage_l + off);
-                    bh[tt] = *reinterpret_cast<const i4 *>(stage_h + off);
-                }
-                i4 a[kTunerPhases];
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) {
-                    int jr = j - rb.j0[p];
-                    jr = jr < 0 ? 0 : (jr >= ksp ? ksp - 1 : jr);
-                    a[p] = a_grp[((kTunerPhases * u + p) * ksp + jr) * 64];
-                }
-#pragma unroll
-                for (int p = 0; p < kTunerPhases; p++) {
-                    if (j >= rb.j0[p] && j < rb.j1[p]) {
-#pragma unroll
-                        for (int tt = 0; tt < TT; tt++) {
-                            accl[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], bl[tt], accl[tt][p], 0, 0, 0);
-                            acch[tt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[p], bh[tt], acch[tt][p], 0, 0, 0);
-                        }
-                    }
-                }
-                rem += 4;
-                while (rem >= D) {
-                    rem -= D;
-                    blk++;
-                }
-            }
-            if (ch_ok) {
+            i4 acc[2][TT][kTunerPhases];                            // low plane, high plane
+            tuner_mac<TT, 2>(acc, planes, a_grp + kTunerPhases * u * ksp * 64, rb.j0, rb.j1, rb.j0[0], rb.j1[kTunerPhases - 1], ksp, D, tw.col, tw.g);
+            if (tw.ch_ok) {
                 int2 kc[kTunerPhases];                              // the constants of the 8 images' phases
 #pragma unroll
                 for (int p = 0; p < kTunerPhases; p++) kc[p] = kc_ch[(kTunerPhases * u + p) * D % U];
 #pragma unroll
                 for (int tt = 0; tt < TT; tt++) {
-                    const long cidx = c0 + 16 * tt + col;
+                    const long cidx = c0 + 16 * tt + tw.col;
                     const long mb = (cidx * U + u) * kTunerPhases;
                     if (mb >= n_out) continue;
-                    unsigned pr[kTunerPhases];
-                    const unsigned nb = n0 + static_cast<unsigned>(cidx) * static_cast<unsigned>(kTunerPhases * D);
+                    unsigned ph[kTunerPhases], pr[kTunerPhases];
+                    rat_phase_words(ph, w, n0, cidx, D, rb);
                     const bool whole = mb + kTunerPhases <= n_out;
 #pragma unroll
-                    for (int p = 0; p < kTunerPhases; p++) {
-                        const int lr = accl[tt][p][0] + 256 * accl[tt][p][1], li = accl[tt][p][2] + 256 * accl[tt][p][3];
-                        const int hr = acch[tt][p][0] + 256 * acch[tt][p][1], hi = acch[tt][p][2] + 256 * acch[tt][p][3];
-                        const unsigned ph = w * (nb + static_cast<unsigned>(rb.nq[p]));
-                        unsigned cl = 0;
-                        unsigned long long pw = 0;
-                        pr[p] = tuner_round_pair_planes(lr, li, hr, hi, kc[p].x, kc[p].y, rot_of(tab[ph >> (32 - kTunerTableBits)]), sh, cl, pw);
-                        if (whole || mb + p < n_out) {
-                            clipped += cl;
-                            power += pw;
-                        }
-                    }
-                    rat_emit(obuf, via_lds, tt, g, col, u, U, out + static_cast<long>(ch) * pitch + 2 * mb, pr, whole, n_out - mb);
+                    for (int p = 0; p < kTunerPhases; p++)
+                        pr[p] = tuner_finish16(acc[0][tt][p], acc[1][tt][p], kc[p], ph[p], tab, sh, whole || mb + p < n_out, clipped, power);
+                    rat_emit(obuf, via_lds, tt, tw.g, tw.col, u, U, out + static_cast<long>(tw.ch) * pitch + 2 * mb, pr, whole, n_out - mb);
                 }
             }
         }
         if (via_lds) {
             rat_wave_sync();
-            rat_flush(obuf, out, pitch, grp, n_channels, c0, n_out, U, TT, lane);
+            rat_flush(obuf, out, pitch, tw.grp, n_channels, c0, n_out, U, TT, tw.lane);
             rat_wave_sync();
         }
     }
-    tuner_add_levels(clipped, power, ch_ok && col == 0, levels + 2 * ch);
-}
-
-constexpr size_t kTwoPerCu = 64 * 1024;     // the LDS a kernel may ask for without the attribute
-
-template <typename K>
-int rat_lds_attr(K kernel, size_t lds)
-{
-    if (lds > kTwoPerCu)
-        FMRX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    return FMRX_OK;
+    tuner_add_levels(clipped, power, tw.ch_ok && tw.col == 0, levels + 2 * tw.ch);
 }
 
 }  // namespace
@@ -458,42 +262,17 @@ int rat_lds_attr(K kernel, size_t lds)
 int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, int n_steps, int steps_per_wg, dim3 grid, size_t lds, hipStream_t stream)
 {
     const i4 *img = reinterpret_cast<const i4 *>(a.a_img);
-#define FMRX_RAT_8(KERNEL)                                                                                                             \
-    do {                                                                                                                               \
-        FMRX_TRY(rat_lds_attr(KERNEL, lds));                                                                                           \
-        hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.table, a.out, a.pitch,         \
-                           a.n_channels, n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, a.via_lds, a.levels); \
-    } while (0)
-#define FMRX_RAT_16(KERNEL)                                                                                                            \
-    do {                                                                                                                               \
-        FMRX_TRY(rat_lds_attr(KERNEL, lds));                                                                                           \
-        hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.kconst, a.table, a.out,        \
-                           a.pitch, a.n_channels, n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, a.via_lds, \
-                           a.levels);                                                                                                  \
-    } while (0)
+    const int via = a.via_lds;
     if (a.format == kTunerS16) {
-        if (a.tiles == 2)
-            FMRX_RAT_16(tuner_rat_mfma_s16_kernel<2>);
-        else
-            FMRX_RAT_16(tuner_rat_mfma_s16_kernel<1>);
-    } else if (a.format == kTunerS8) {
-        if (a.tiles == 4)
-            FMRX_RAT_8(tuner_rat_mfma_s8_kernel<4>);
-        else if (a.tiles == 2)
-            FMRX_RAT_8(tuner_rat_mfma_s8_kernel<2>);
-        else
-            FMRX_RAT_8(tuner_rat_mfma_s8_kernel<1>);
-    } else {
-        if (a.tiles == 4)
-            FMRX_RAT_8(tuner_rat_mfma_kernel<4>);
-        else if (a.tiles == 2)
-            FMRX_RAT_8(tuner_rat_mfma_kernel<2>);
-        else
-            FMRX_RAT_8(tuner_rat_mfma_kernel<1>);
+        const auto kernel = a.tiles == 2 ? tuner_rat_mfma_s16_kernel<2> : tuner_rat_mfma_s16_kernel<1>;
+        return tuner_launch_mfma(kernel, grid, lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels,
+                                 n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, via, a.levels);
     }
-#undef FMRX_RAT_8
-#undef FMRX_RAT_16
-    return FMRX_OK;
+    const auto kernel = a.format == kTunerS8
+                            ? (a.tiles == 4 ? tuner_rat_mfma_s8_kernel<4> : a.tiles == 2 ? tuner_rat_mfma_s8_kernel<2> : tuner_rat_mfma_s8_kernel<1>)
+                            : (a.tiles == 4 ? tuner_rat_mfma_kernel<4> : a.tiles == 2 ? tuner_rat_mfma_kernel<2> : tuner_rat_mfma_kernel<1>);
+    return tuner_launch_mfma(kernel, grid, lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.table, a.out, a.pitch, a.n_channels, n_out, a.U,
+                             a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, via, a.levels);
 }
 
 }  // namespace fmrx

@@ -180,6 +180,7 @@ inline size_t tuner_lds_bytes(int U, int D, int ks, int format, int tiles, bool 
     return static_cast<size_t>(kTunerTableSize) * 4 + 16u * planes * (n_pieces + n_pieces / D + 1) +
            (via_lds ? static_cast<size_t>(4) * tiles * 4 * 256 * U : 0);
 }
+constexpr size_t kTwoPerCu = 64 * 1024;   // the most that leaves two workgroups on a CU, and what a kernel gets without asking for it
 inline size_t tuner_group_image_bytes(const TunerShape &s) { return static_cast<size_t>(kTunerPhases) * s.U * s.ksp * 64 * 16; }
 
 // One channel's rows of its group's A-operand image of v_mfma_i32_16x16x64_i8: [image q][K-step - j0[q]][lane][16 bytes],

@@ -1,7 +1,9 @@
-// tuner_kernels.hpp -- device helpers shared by the wideband tuner's kernels (kernels_tuner.hip, kernels_tuner_rational.hip):
-// the rotation-table entry, the rounding of a rotated sample to (I, Q) bytes in its three forms, the 16-byte store of a lane's
-// 8 outputs and the level sums.  Every function is __forceinline__ in an anonymous namespace: a kernel file that includes this
-// header gets exactly the code it had when the helpers stood in it.
+// tuner_kernels.hpp -- the output side shared by the wideband tuner's kernels (kernels_tuner.hip, kernels_tuner_rational.hip),
+// one sample or one lane at a time: the rotation-table entry, the rounding of a rotated sample to (I, Q) bytes in its three
+// forms, the 16-byte store of a lane's 8 outputs and the level sums.  The generic kernel uses the first two; the matrix kernels
+// reach all of it through the pieces of tuner_mfma.hpp.  Every function is __forceinline__ in an anonymous namespace.  Moving
+// these helpers here left every kernel's code as it was (profiles/tuner_rational); the larger pieces of tuner_mfma.hpp do not
+// promise that: profiles/tuner_kernels has what they did to each matrix kernel's code, registers and time.
 #pragma once
 #include "fmrx_internal.hpp"
 #include "tuner_host.hpp"
