@@ -759,6 +759,20 @@ FMRX_API int fmrx_tuner_create_rational(fmrx_tuner **out, int U, int D, const fl
                                         size_t max_wide_samples, int format, int device);
 FMRX_API int fmrx_tuner_ratio(const fmrx_tuner *t, int *U, int *D);   /* (1, R) for a handle of fmrx_tuner_create / _create_ex */
 FMRX_API int fmrx_tuner_format(const fmrx_tuner *t);            /* FMRX_TUNER_*; -1 for a null handle */
+/* What a call of n_wide wide samples on this handle launches; there for tests and diagnostics.  Host arithmetic only (the same
+ * function create and the launch read, csrc/tuner_host.hpp: tuner_plan_info): no device call, nothing changes.  matrix: 1 a
+ * matrix-core kernel runs, 0 the generic kernel (then tiles, via_lds, lds_bytes, n_steps and steps_per_wg are 0 and the grid is
+ * the generic kernel's: channels x 256 outputs).  tiles: 4, 2 or 1 tiles of 16 columns per wave and step.  via_lds: 1 a step's
+ * outputs go through the per-wave LDS buffer to whole-row stores, 0 every 16-byte piece is stored directly (always 0 at an
+ * integer rate).  lds_bytes: dynamic LDS of a workgroup (at most 65 536 where two share a CU, else at most 163 840).  The grid is
+ * grid_x workgroups of steps_per_wg consecutive steps (n_steps in all) times grid_y rows of 16 channels.  FMRX_EINVAL for a null
+ * argument or an n_wide fmrx_tuner_process_dev would refuse (0, no multiple of D, more than max_wide_samples). */
+typedef struct fmrx_tuner_plan_info {
+    int matrix, tiles, via_lds;
+    size_t lds_bytes;
+    int n_steps, steps_per_wg, grid_x, grid_y;
+} fmrx_tuner_plan_info;
+FMRX_API int fmrx_tuner_plan(const fmrx_tuner *t, size_t n_wide, fmrx_tuner_plan_info *out);
 FMRX_API size_t fmrx_tuner_sample_bytes(const fmrx_tuner *t);   /* bytes per complex wide sample: 2, 2 or 4 */
 FMRX_API int fmrx_tuner_destroy(fmrx_tuner *t);
 FMRX_API int fmrx_tuner_reset(fmrx_tuner *t);     /* start of stream: silence in front, sample counter 0; channels keep their settings */

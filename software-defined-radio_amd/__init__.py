@@ -208,6 +208,15 @@ _sig("fmrx_tuner_create_rational", [C.POINTER(_vp), _int, _int, _f32p, _int, _in
 _sig("fmrx_tuner_ratio", [_vp, C.POINTER(_int), C.POINTER(_int)])
 _sig("fmrx_tuner_format", [_vp])
 _sig("fmrx_tuner_sample_bytes", [_vp], _sz)
+
+
+class TunerPlanInfo(C.Structure):
+    """fmrx_tuner_plan_info: what one call of a Tuner launches (Tuner.plan)"""
+    _fields_ = [("matrix", _int), ("tiles", _int), ("via_lds", _int), ("lds_bytes", _sz), ("n_steps", _int), ("steps_per_wg", _int),
+                ("grid_x", _int), ("grid_y", _int)]
+
+
+_sig("fmrx_tuner_plan", [_vp, _sz, C.POINTER(TunerPlanInfo)])
 _sig("fmrx_tuner_destroy", [_vp])
 _sig("fmrx_tuner_reset", [_vp])
 _sig("fmrx_tuner_set_channel", [_vp, _int, _dbl, _dbl, _dbl])
@@ -1164,6 +1173,14 @@ class Tuner:
 
     def n_out_bytes(self, n_wide):
         return lib.fmrx_tuner_n_out_bytes(self._h, n_wide)
+
+    def plan(self, n_wide):
+        """For tests and diagnostics, host only: what a call of n_wide wide samples launches, as a dict of matrix, tiles, via_lds
+        (bools and an int), lds_bytes, n_steps, steps_per_wg, grid_x, grid_y (fmrx_tuner_plan)."""
+        p = TunerPlanInfo()
+        _check(lib.fmrx_tuner_plan(self._h, int(n_wide), C.byref(p)))
+        return {"matrix": bool(p.matrix), "tiles": p.tiles, "via_lds": bool(p.via_lds), "lds_bytes": p.lds_bytes, "n_steps": p.n_steps,
+                "steps_per_wg": p.steps_per_wg, "grid_x": p.grid_x, "grid_y": p.grid_y}
 
     def process(self, wide):
         """wide: interleaved I,Q (host) as uint8 / int8 / int16 for fmt u8 / s8 / s16 (another dtype is a TypeError, never a

@@ -362,10 +362,8 @@ Filters design_filters(const fmrx_params &p, bool stereo);
 // One call's launch at the rate U / D: the FIR + rotation kernel (matrix-core or generic) and the kernel that carries the
 // history.  The integer tuner is U = 1, D <= 32 (tuner_integer_rate, tuner_host.hpp).
 struct TunerLaunch {
-    bool mfma = true;
+    bool mfma = true;                    // the handle runs the matrix kernels (tuner_plan_info's `matrix` at create)
     int format = 0;                      // kTunerU8 / kTunerS8 / kTunerS16 (tuner_host.hpp): a value is 1, 1 or 2 raw bytes
-    int tiles = 1;                       // matrix kernel: tiles per wave and step (tuner_plan)
-    bool via_lds = false;                // matrix kernel: a step's outputs go through an LDS buffer to whole-row stores
     const uint8_t *x = nullptr;          // this call's wide samples, raw (matrix kernel: 16-byte aligned)
     long n_bytes = 0;                    // 2 * n_wide: the call's I and Q values (the raw bytes of the 8-bit formats); n_wide a multiple of D
     const uint8_t *hist = nullptr;       // `front` values in front of the call, raw, 16-byte aligned
@@ -382,15 +380,11 @@ struct TunerLaunch {
     unsigned n0 = 0;                     // wide-sample index of the call's first sample, mod 2^32
     unsigned long long *levels = nullptr;   // [n_channels][2] = {clipped, power}, zeroed by the caller
 };
-struct TunerPlan {
-    int tiles;                           // 4, 2, 1, or 0 where the window does not fit the matrix kernel
-    bool via_lds;
-};
-// what the matrix kernel of this rate and format runs with (its LDS: tuner_lds_bytes, tuner_host.hpp)
-TunerPlan tuner_plan(int U, int D, int ks, int format);
+// what a call launches: kernel set, tiles per wave and step, output path, LDS and grid (tuner_plan_info, tuner_host.hpp)
+struct TunerPlanInfo;
 int tuner_launch(const TunerLaunch &a, hipStream_t stream);
 // tuner_launch's matrix-kernel launch outside the integer rates (kernels_tuner_rational.hip)
-int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, int n_steps, int steps_per_wg, dim3 grid, size_t lds, hipStream_t stream);
+int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, const TunerPlanInfo &plan, hipStream_t stream);
 
 // ---- signal meters (kernels_meters.hip; handle, host arithmetic and C ABI in meters.hip) -----------------
 constexpr int kMetersSegment = FMRX_METERS_SEGMENT, kMetersProbes = FMRX_METERS_PROBES;

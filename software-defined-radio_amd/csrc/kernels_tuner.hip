@@ -52,8 +52,7 @@
 namespace fmrx {
 namespace {
 
-constexpr int kTT = 4;                        // tiles (of 16 columns x 8 outputs) per wave and step
-constexpr int kStepOut = 128 * kTT;           // outputs per channel and step
+constexpr int kStepOut = 128 * kTT;           // outputs per channel and step (kTT tiles per wave: tuner_host.hpp)
 
 // K-step range of every phase, the same in every column and step (scalars)
 __device__ __forceinline__ void tuner_phase_ranges(int (&j0)[kTunerPhases], int (&j1)[kTunerPhases], int D, int T, int front)
@@ -139,8 +138,7 @@ __global__ __launch_bounds__(256, 2) void tuner_mfma_s8_kernel(
 }
 
 // ---- signed 16-bit input: two byte planes against the same operand image ------------------------------------------
-constexpr int kTT16 = 2;                      // tiles per wave and step: two planes of accumulators each
-constexpr int kStepOut16 = 128 * kTT16;
+constexpr int kStepOut16 = 128 * kTT16;       // kTT16 tiles per wave and step: two planes of accumulators each
 
 // x, hist: raw little-endian int16 I,Q values (n_values of them in the call, `front` in the history); a plane's byte u is
 // value u's low or high byte, so plane positions are the 8-bit kernel's byte positions and the raw position is twice that.
@@ -269,54 +267,33 @@ __global__ __launch_bounds__(256) void tuner_hist_kernel(const uint8_t *__restri
     new_hist[i] = pos < 0 ? old_hist[front + pos] : x[pos];
 }
 
-constexpr size_t kOnePerCu = 160 * 1024;     // LDS of a workgroup that has a CU to itself (two on a CU: kTwoPerCu)
-
 }  // namespace
-
-// Tiles per wave and step, and whether the outputs go through the LDS buffer.  The integer kernels are compiled for kTT / kTT16
-// tiles and store directly.  The rational ones, in order of preference: the buffer with the most tiles that keep two workgroups
-// on a CU; the buffer with one tile and one workgroup per CU; direct stores, by the same two rules.  tiles = 0: the window does
-// not fit the matrix kernel at all.
-TunerPlan tuner_plan(int U, int D, int ks, int format)
-{
-    if (tuner_integer_rate(U, D)) return {format == kTunerS16 ? kTT16 : kTT, false};
-    for (int via = 1; via >= 0; via--) {
-        for (int tiles = format == kTunerS16 ? 2 : 4; tiles >= 1; tiles >>= 1)
-            if (tuner_lds_bytes(U, D, ks, format, tiles, via) <= kTwoPerCu) return {tiles, via != 0};
-        if (tuner_lds_bytes(U, D, ks, format, 1, via) <= kOnePerCu) return {1, via != 0};
-    }
-    return {0, false};
-}
 
 int tuner_launch(const TunerLaunch &a, hipStream_t stream)
 {
     const long n_out = a.n_bytes / 2 / a.D * a.U;
     const int vb = tuner_value_bytes(a.format);
     if (n_out > 0) {
-        if (a.mfma) {
-            const long cols = (n_out + kTunerPhases * a.U - 1) / (kTunerPhases * a.U);
-            const int n_steps = static_cast<int>((cols + 16 * a.tiles - 1) / (16 * a.tiles));
-            const int gy = (a.n_channels + 4 * kTunerGroup - 1) / (4 * kTunerGroup);
-            // enough workgroups to fill the chip a few times over, as many steps each as that leaves (the table is loaded once
-            // per workgroup)
-            int per = static_cast<int>((static_cast<long>(n_steps) * gy + 2047) / 2048);
-            if (per < 1) per = 1;
-            const int gx = (n_steps + per - 1) / per;
-            const size_t lds = tuner_lds_bytes(a.U, a.D, a.ks, a.format, a.tiles, a.via_lds);
+        // which kernels, the matrix kernel's tiles, output path and LDS, and the grid: tuner_plan_info (tuner_host.hpp)
+        const TunerPlanInfo plan = tuner_plan_of_shape(a.U, a.D, a.Tp, a.ks, a.format, a.n_channels, a.n_bytes / 2, a.mfma);
+        if (plan.matrix) {
+            const int n_steps = plan.n_steps, per = plan.steps_per_wg;
+            const dim3 grid(plan.grid_x, plan.grid_y);
+            const size_t lds = plan.lds_bytes;
             if (!tuner_integer_rate(a.U, a.D)) {
-                FMRX_TRY(tuner_rat_mfma_launch(a, n_out, n_steps, per, dim3(gx, gy), lds, stream));
+                FMRX_TRY(tuner_rat_mfma_launch(a, n_out, plan, stream));
             } else if (a.format == kTunerS16) {
-                FMRX_TRY(tuner_launch_mfma(tuner_mfma_s16_kernel, dim3(gx, gy), lds, stream, a.x, a.hist, a.n_bytes,
+                FMRX_TRY(tuner_launch_mfma(tuner_mfma_s16_kernel, grid, lds, stream, a.x, a.hist, a.n_bytes,
                                            reinterpret_cast<const i4 *>(a.a_img), a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels, n_out,
                                            a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels));
             } else {
-                FMRX_TRY(tuner_launch_mfma(a.format == kTunerS8 ? tuner_mfma_s8_kernel : tuner_mfma_kernel, dim3(gx, gy), lds, stream, a.x,
+                FMRX_TRY(tuner_launch_mfma(a.format == kTunerS8 ? tuner_mfma_s8_kernel : tuner_mfma_kernel, grid, lds, stream, a.x,
                                            a.hist, a.n_bytes, reinterpret_cast<const i4 *>(a.a_img), a.chan, a.table, a.out, a.pitch,
                                            a.n_channels, n_out, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, per, a.levels));
             }
         } else {
             const auto kernel = a.format == kTunerS16 ? tuner_generic_s16_kernel : a.format == kTunerS8 ? tuner_generic_s8_kernel : tuner_generic_kernel;
-            hipLaunchKernelGGL(kernel, dim3(a.n_channels, static_cast<unsigned>((n_out + 255) / 256)), dim3(256), 0, stream, a.x, a.hist,
+            hipLaunchKernelGGL(kernel, dim3(plan.grid_x, plan.grid_y), dim3(256), 0, stream, a.x, a.hist,
                                a.taps_re, a.taps_im, a.chan, a.table, a.out, a.pitch, n_out, a.U, a.D, a.Tp, a.front, a.n0, a.levels);
         }
         FMRX_LAUNCH_CHECK("tuner_%s_kernel (format %d, %d/%d)", a.mfma ? "mfma" : "generic", a.format, a.U, a.D);

@@ -33,7 +33,7 @@
 // constant 128 (row sum of the taps) is a pair per PHASE, U pairs per channel.
 //
 // Launched by tuner_launch (kernels_tuner.hip) through tuner_rat_mfma_launch for every rate outside the integer tuner's
-// (U = 1, D <= 32), with the tiles and the output path tuner_plan chose.  The generic kernels and the history kernel, one set
+// (U = 1, D <= 32), with the tiles and the output path of tuner_plan_info (tuner_host.hpp).  The generic kernels and the history kernel, one set
 // for all rates, are in kernels_tuner.hip.
 #include "fmrx_internal.hpp"
 #include "tuner_host.hpp"
@@ -259,18 +259,20 @@ __global__ __launch_bounds__(256, 2) void tuner_rat_mfma_s16_kernel(
 
 }  // namespace
 
-int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, int n_steps, int steps_per_wg, dim3 grid, size_t lds, hipStream_t stream)
+int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, const TunerPlanInfo &plan, hipStream_t stream)
 {
     const i4 *img = reinterpret_cast<const i4 *>(a.a_img);
-    const int via = a.via_lds;
+    const int via = plan.via_lds, tiles = plan.tiles, n_steps = plan.n_steps, steps_per_wg = plan.steps_per_wg;
+    const dim3 grid(plan.grid_x, plan.grid_y);
+    const size_t lds = plan.lds_bytes;
     if (a.format == kTunerS16) {
-        const auto kernel = a.tiles == 2 ? tuner_rat_mfma_s16_kernel<2> : tuner_rat_mfma_s16_kernel<1>;
+        const auto kernel = tiles == 2 ? tuner_rat_mfma_s16_kernel<2> : tuner_rat_mfma_s16_kernel<1>;
         return tuner_launch_mfma(kernel, grid, lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.kconst, a.table, a.out, a.pitch, a.n_channels,
                                  n_out, a.U, a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, via, a.levels);
     }
     const auto kernel = a.format == kTunerS8
-                            ? (a.tiles == 4 ? tuner_rat_mfma_s8_kernel<4> : a.tiles == 2 ? tuner_rat_mfma_s8_kernel<2> : tuner_rat_mfma_s8_kernel<1>)
-                            : (a.tiles == 4 ? tuner_rat_mfma_kernel<4> : a.tiles == 2 ? tuner_rat_mfma_kernel<2> : tuner_rat_mfma_kernel<1>);
+                            ? (tiles == 4 ? tuner_rat_mfma_s8_kernel<4> : tiles == 2 ? tuner_rat_mfma_s8_kernel<2> : tuner_rat_mfma_s8_kernel<1>)
+                            : (tiles == 4 ? tuner_rat_mfma_kernel<4> : tiles == 2 ? tuner_rat_mfma_kernel<2> : tuner_rat_mfma_kernel<1>);
     return tuner_launch_mfma(kernel, grid, lds, stream, a.x, a.hist, a.n_bytes, img, a.chan, a.table, a.out, a.pitch, a.n_channels, n_out, a.U,
                              a.D, a.Tp, a.front, a.ks, a.ksp, a.n0, n_steps, steps_per_wg, via, a.levels);
 }

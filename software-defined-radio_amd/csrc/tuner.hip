@@ -23,8 +23,6 @@ struct fmrx_tuner {
     int device = 0, T = 0, n_channels = 0, format = kTunerU8;
     int U = 1, D = 0;                    // the rate: (1, R) for the integer tuner
     TunerShape sh;
-    int tiles = 0;                       // the matrix kernel's plan (tuner_plan)
-    bool via_lds = false;
     long max_wide = 0;
     bool mfma = true;
     size_t group_bytes = 0;
@@ -159,13 +157,9 @@ int create(fmrx_tuner **out, const char *fn, int U, int D, const float *h, int t
     t->format = format;
     t->max_wide = static_cast<long>(max_wide_samples);
     t->sh = tuner_shape(taps, U, D);
-    const TunerPlan plan = tuner_plan(U, D, t->sh.ks, format);
-    t->tiles = plan.tiles;
-    t->via_lds = plan.via_lds;
-    // The matrix kernels' range; outside it, and under tuner_variant = 1, the generic kernel runs.  The integer tuner
-    // (D <= 32, its plan fixed) is always inside: its largest window, D = 32, T = 250 .. 256, S16, takes 52,320 bytes of LDS.
-    t->mfma = options_snapshot().tuner_variant == 0 && U <= kTunerRatMfmaMaxU && D <= kTunerRatMfmaMaxD && t->sh.Tp <= kTunerMfmaMaxTaps &&
-              t->tiles > 0;
+    // The matrix kernels' range (tuner_plan_info); outside it, and under tuner_variant = 1, the generic kernel runs.  The integer
+    // tuner (D <= 32, its plan fixed) is always inside: its largest window, D = 32, T = 250 .. 256, S16, takes 52,320 bytes of LDS.
+    t->mfma = tuner_plan_info(U, D, taps, format, n_channels, 0, options_snapshot().tuner_variant == 0).matrix;
     t->group_bytes = tuner_group_image_bytes(t->sh);
     t->h.assign(h, h + taps);
     auto body = [&]() -> int {
@@ -295,6 +289,24 @@ int fmrx_tuner_set_channel(fmrx_tuner *t, int channel, double f_c_hz, double Fs_
     return design_channel(t, channel, f_c_hz, Fs_w, gain);
 }
 
+int fmrx_tuner_plan(const fmrx_tuner *t, size_t n_wide, fmrx_tuner_plan_info *out)
+{
+    if (!t || !out) return fail(FMRX_EINVAL, "tuner_plan: null argument");
+    if (n_wide == 0 || n_wide % t->D || n_wide > static_cast<size_t>(t->max_wide))
+        return fail(FMRX_EINVAL, "tuner_plan: n_wide = %zu wide samples: a non-zero multiple of the decimation %d, at most %ld", n_wide, t->D,
+                    t->max_wide);
+    const TunerPlanInfo p = tuner_plan_info(t->U, t->D, t->T, t->format, t->n_channels, static_cast<long>(n_wide), t->mfma);
+    out->matrix = p.matrix;
+    out->tiles = p.tiles;
+    out->via_lds = p.via_lds;
+    out->lds_bytes = p.lds_bytes;
+    out->n_steps = p.n_steps;
+    out->steps_per_wg = p.steps_per_wg;
+    out->grid_x = p.grid_x;
+    out->grid_y = p.grid_y;
+    return FMRX_OK;
+}
+
 int fmrx_tuner_format(const fmrx_tuner *t) { return t ? t->format : -1; }
 
 size_t fmrx_tuner_sample_bytes(const fmrx_tuner *t) { return t ? 2 * static_cast<size_t>(tuner_value_bytes(t->format)) : 0; }
@@ -320,8 +332,6 @@ int fmrx_tuner_process_dev(fmrx_tuner *t, const uint8_t *d_wide, size_t n_wide, 
     TunerLaunch a;
     a.mfma = t->mfma;
     a.format = t->format;
-    a.tiles = t->tiles;
-    a.via_lds = t->via_lds;
     a.kconst = t->d_kconst.p;
     a.x = d_wide;
     a.n_bytes = static_cast<long>(2 * n_wide);

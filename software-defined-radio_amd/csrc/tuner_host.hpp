@@ -181,6 +181,72 @@ inline size_t tuner_lds_bytes(int U, int D, int ks, int format, int tiles, bool 
            (via_lds ? static_cast<size_t>(4) * tiles * 4 * 256 * U : 0);
 }
 constexpr size_t kTwoPerCu = 64 * 1024;   // the most that leaves two workgroups on a CU, and what a kernel gets without asking for it
+constexpr size_t kOnePerCu = 160 * 1024;  // LDS of a workgroup that has a CU to itself
+constexpr int kTT = 4;                    // integer matrix kernels, 8-bit formats: tiles (of 16 columns x 8 outputs) per wave and step
+constexpr int kTT16 = 2;                  // integer matrix kernel, S16: two planes of accumulators per tile
+constexpr int kTunerWorkgroups = 2048;    // workgroups of a matrix kernel's launch: enough to fill the chip a few times over
+
+// Tiles per wave and step, and whether the outputs go through the LDS buffer.  The integer kernels are compiled for kTT / kTT16
+// tiles and store directly.  The rational ones, in order of preference: the buffer with the most tiles that keep two workgroups
+// on a CU; the buffer with one tile and one workgroup per CU; direct stores, by the same two rules.  tiles = 0: the window does
+// not fit the matrix kernel at all.
+struct TunerPlan {
+    int tiles;                           // 4, 2, 1, or 0 where the window does not fit the matrix kernel
+    bool via_lds;
+};
+inline TunerPlan tuner_plan(int U, int D, int ks, int format)
+{
+    if (tuner_integer_rate(U, D)) return {format == kTunerS16 ? kTT16 : kTT, false};
+    for (int via = 1; via >= 0; via--) {
+        for (int tiles = format == kTunerS16 ? 2 : 4; tiles >= 1; tiles >>= 1)
+            if (tuner_lds_bytes(U, D, ks, format, tiles, via) <= kTwoPerCu) return {tiles, via != 0};
+        if (tuner_lds_bytes(U, D, ks, format, 1, via) <= kOnePerCu) return {1, via != 0};
+    }
+    return {0, false};
+}
+
+// What a call of n_wide wide samples (a multiple of D; 0: the plan alone) launches: which kernel set, the matrix kernel's tiles,
+// output path and LDS, and the grid.  matrix: the shape lies in the matrix kernels' range (U <= 24, D <= 125, Tp <= 256, a window
+// that fits the LDS) and the caller allows them (allow_matrix: not under tuner_variant = 1).  A matrix launch walks n_steps steps
+// of 16 tiles columns (8 U outputs each) of every channel; its grid is grid_x workgroups of steps_per_wg consecutive steps each
+// times grid_y rows of 16 channels: as many steps per workgroup as kTunerWorkgroups workgroups leave (the rotation table is
+// loaded once per workgroup).  The generic kernel's grid is one channel times 256 outputs per workgroup; n_steps = 0 there.
+// fmrx_tuner_create, tuner_launch and fmrx_tuner_plan all read this one function (tests/cpp/tuner_plan_check.cpp walks it);
+// tuner_plan_of_shape is its body for a caller that holds tuner_shape(T, U, D)'s Tp and ks already.
+struct TunerPlanInfo {
+    bool matrix = false;
+    int tiles = 0;
+    bool via_lds = false;
+    size_t lds_bytes = 0;
+    int n_steps = 0, steps_per_wg = 0, grid_x = 0, grid_y = 0;
+};
+inline TunerPlanInfo tuner_plan_of_shape(int U, int D, int Tp, int ks, int format, int n_channels, long n_wide, bool allow_matrix)
+{
+    TunerPlanInfo p;
+    const long n_out = n_wide / D * U;
+    const TunerPlan plan = tuner_plan(U, D, ks, format);
+    p.matrix = allow_matrix && U <= kTunerRatMfmaMaxU && D <= kTunerRatMfmaMaxD && Tp <= kTunerMfmaMaxTaps && plan.tiles > 0;
+    if (!p.matrix) {
+        p.grid_x = n_channels;
+        p.grid_y = static_cast<int>((n_out + 255) / 256);
+        return p;
+    }
+    p.tiles = plan.tiles;
+    p.via_lds = plan.via_lds;
+    p.lds_bytes = tuner_lds_bytes(U, D, ks, format, p.tiles, p.via_lds);
+    const long cols = (n_out + kTunerPhases * U - 1) / (kTunerPhases * U);
+    p.n_steps = static_cast<int>((cols + 16 * p.tiles - 1) / (16 * p.tiles));
+    p.grid_y = (n_channels + 4 * kTunerGroup - 1) / (4 * kTunerGroup);
+    p.steps_per_wg = static_cast<int>((static_cast<long>(p.n_steps) * p.grid_y + kTunerWorkgroups - 1) / kTunerWorkgroups);
+    if (p.steps_per_wg < 1) p.steps_per_wg = 1;
+    p.grid_x = (p.n_steps + p.steps_per_wg - 1) / p.steps_per_wg;
+    return p;
+}
+inline TunerPlanInfo tuner_plan_info(int U, int D, int T, int format, int n_channels, long n_wide, bool allow_matrix = true)
+{
+    const TunerShape sh = tuner_shape(T, U, D);
+    return tuner_plan_of_shape(U, D, sh.Tp, sh.ks, format, n_channels, n_wide, allow_matrix);
+}
 inline size_t tuner_group_image_bytes(const TunerShape &s) { return static_cast<size_t>(kTunerPhases) * s.U * s.ksp * 64 * 16; }
 
 // One channel's rows of its group's A-operand image of v_mfma_i32_16x16x64_i8: [image q][K-step - j0[q]][lane][16 bytes],
