@@ -21,7 +21,9 @@ import math
 
 import numpy as np
 
+import _walk_events as we
 from _fir_model import fmaf
+from _walk_events import same  # noqa: F401
 
 F32 = np.float32
 FLT_MIN = F32(2.0 ** -126)
@@ -51,11 +53,6 @@ def step(x, x_prev, y_prev, p, b0):
         return np.where(np.abs(y) < FLT_MIN, F32(0.0), y).astype(F32)
 
 
-def same(a, b):
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
 def _rows(x, state):
     x = np.atleast_2d(np.asarray(x, F32))
     st = np.zeros((x.shape[0], 2), F32) if state is None else np.array(state, F32).reshape(x.shape[0], 2)
@@ -80,32 +77,36 @@ def parallel(x, p, b0, state=None, W=BUILTIN_W, L=BUILTIN_L):
     return y, st, int(missed.sum()), segs
 
 
-def parallel_rows(x, p, b0, state=None, W=BUILTIN_W, L=BUILTIN_L):
-    """parallel() with the misses per row (rows are independent: the first r rows of a result are the result of the first r rows)."""
+def speculate(x, p, b0, state=None, W=BUILTIN_W, L=BUILTIN_L):
+    """The lanes' half of the walk (_walk_events.lanes with this filter's step) -> (y [rows, n], start, end [rows, nseg])."""
+    x, st = _rows(x, state)
+    xpad = np.concatenate([st[:, :1], x], axis=1)           # xpad[:, g] = x[g - 1]; the carried x_prev in front
+    return we.lanes(lambda r, g, yp: step(x[r, g], xpad[r, g], yp, p, b0), st[:, 1], x.shape[1], W, L)
+
+
+def row_step(x, x_prev, p, b0):
+    """One row's step for _walk_events.verify: (g, y) -> y on Python floats.  v = b0 (x[g] + x[g-1]) does not depend on y."""
+    x = np.asarray(x, F32)
+    with np.errstate(all="ignore"):
+        v = (F32(b0) * (x + np.concatenate([[F32(x_prev)], x[:-1]])).astype(F32)).astype(F32).astype(np.float64).tolist()
+    pf, tiny = float(p), float(FLT_MIN)
+
+    def one(g, y):
+        r = we.fmaf1(pf, y, v[g])
+        return 0.0 if abs(r) < tiny else r
+    return one
+
+
+def parallel_rows(x, p, b0, state=None, W=BUILTIN_W, L=BUILTIN_L, spec=None):
+    """parallel() with the misses per row (rows are independent: the first r rows of a result are the result of the first r rows).
+    spec: what speculate() returned for these arguments, where the caller has it already."""
     x, st = _rows(x, state)
     rows, n = x.shape
     if n == 0:
         return x.copy(), st, np.zeros(rows, np.int64), 0
     nseg = (n + L - 1) // L
-    xpad = np.concatenate([st[:, :1], x], axis=1)           # xpad[:, g] = x[g - 1]; the carried x_prev in front
-    r = np.arange(rows)[:, None]
-    g0 = (np.arange(nseg) * L - W)[None, :].repeat(rows, 0)   # where each lane's warm-up would begin
-    # ---- lanes: one per (row, segment), all in step ----
-    yp = np.where(g0 <= 0, st[:, 1:2], F32(0.0)).astype(F32)
-    start = np.zeros((rows, nseg), F32)
-    y = np.zeros_like(x)
-    for j in range(W + L):
-        g = g0 + j
-        if j == W:
-            start[:] = yp
-        act = (g >= 0) & (g < n)
-        gc = np.clip(g, 0, n - 1)
-        ynew = step(x[r, gc], xpad[r, gc], yp, p, b0)
-        yp = np.where(act, ynew, yp)
-        if j >= W:
-            rr, cc = np.nonzero(act)
-            y[rr, g[rr, cc]] = yp[rr, cc]
-    end = yp.copy()
+    xpad = np.concatenate([st[:, :1], x], axis=1)
+    y, start, end = (v.copy() for v in (spec if spec is not None else speculate(x, p, b0, st, W, L)))
     # ---- verify, in order, and repair: vectorised over the rows that miss ----
     missed = np.zeros(rows, np.int64)
     for c in range(1, nseg):

@@ -34,6 +34,7 @@ import numpy as np
 import _blend_model as bm
 from _blend_model import DB_PER_OCTAVE, P_NOISE_HI, P_NOISE_LO, drive, interleave, ramp, smooth  # noqa: F401
 from _deemph_model import FLT_MIN, fixed_inputs, same  # noqa: F401
+import _walk_events as we
 from _fir_model import fmaf
 
 F32, F64 = np.float32, np.float64
@@ -166,31 +167,38 @@ def parallel(x, p0, p1, p_max, state=None, W=BUILTIN_W, L=BUILTIN_L):
     return y, st, int(missed.sum()), segs
 
 
-def parallel_rows(x, p0, p1, p_max, state=None, W=BUILTIN_W, L=BUILTIN_L):
-    """parallel() with the misses per row."""
+def speculate(x, p0, p1, p_max, state=None, W=BUILTIN_W, L=BUILTIN_L):
+    """The lanes' half of the walk (_walk_events.lanes with this filter's step) -> (y [rows, n], start, end [rows, nseg])."""
+    x, p0, p1, st = _rows(x, p0, p1, state)
+    P = poles(p0, p1, x.shape[1], p_max)
+    return we.lanes(lambda r, g, yp: filt(x[r, g], P[r, g], yp), st, x.shape[1], W, L)
+
+
+def row_step(x, p0, p1, p_max):
+    """One row's step for _walk_events.verify: (g, y) -> y on Python floats.  p[g], q and v = q x[g] do not depend on y."""
+    x = np.asarray(x, F32)
+    P = poles(p0, p1, len(x), p_max)[0]
+    with np.errstate(all="ignore"):
+        v = ((F32(1.0) - P).astype(F32) * x).astype(F32).astype(F64).tolist()
+    xs, Ps, tiny = x.astype(F64).tolist(), P.astype(F64).tolist(), float(FLT_MIN)
+
+    def one(g, y):
+        if Ps[g] == 0.0:
+            return xs[g]
+        r = we.fmaf1(Ps[g], y, v[g])
+        return 0.0 if abs(r) < tiny else r
+    return one
+
+
+def parallel_rows(x, p0, p1, p_max, state=None, W=BUILTIN_W, L=BUILTIN_L, spec=None):
+    """parallel() with the misses per row.  spec: what speculate() returned for these arguments, where the caller has it."""
     x, p0, p1, st = _rows(x, p0, p1, state)
     rows, n = x.shape
     if n == 0:
         return x.copy(), st, np.zeros(rows, np.int64), 0
     P = poles(p0, p1, n, p_max)
     nseg = (n + L - 1) // L
-    r = np.arange(rows)[:, None]
-    g0 = (np.arange(nseg) * L - W)[None, :].repeat(rows, 0)   # where each lane's warm-up would begin
-    yp = np.where(g0 <= 0, st[:, None], F32(0.0)).astype(F32)
-    start = np.zeros((rows, nseg), F32)
-    y = np.zeros_like(x)
-    for j in range(W + L):
-        g = g0 + j
-        if j == W:
-            start[:] = yp
-        act = (g >= 0) & (g < n)
-        gc = np.clip(g, 0, n - 1)
-        ynew = filt(x[r, gc], P[r, gc], yp)
-        yp = np.where(act, ynew, yp)
-        if j >= W:
-            rr, cc = np.nonzero(act)
-            y[rr, g[rr, cc]] = yp[rr, cc]
-    end = yp.copy()
+    y, start, end = (v.copy() for v in (spec if spec is not None else speculate(x, p0, p1, p_max, st, W, L)))
     missed = np.zeros(rows, np.int64)
     for c in range(1, nseg):
         miss = np.flatnonzero(~same(start[:, c], end[:, c - 1]))
