@@ -1177,6 +1177,123 @@ FMRX_API int fmrx_loudness_reset(fmrx_loudness *l, int channel);   /* channel < 
 FMRX_API int fmrx_loudness_push(fmrx_loudness *l, const fmrx_audio_meter *records, const double *bins, size_t max_bins);
 FMRX_API int fmrx_loudness_read(const fmrx_loudness *l, int channel, fmrx_loudness_levels *out);
 
+/* ------------------------------------------------------------------ */
+/* Loudness leveller and look-ahead peak limiter, driven by the audio meters */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  The stage that acts on what the audio meters measure: per channel of a receiver bank it
+ * brings the programme to one loudness target and bounds the output below full scale, so that the PCM it packs cannot wrap.
+ * capture -> tuner -> bank -> meters -> blend -> high-cut -> audio meters -> leveller on one stream, no host round trip.  A
+ * stage with a handle of its own; it changes nothing in front of it.  Defined by tests/_leveller_model.py (DESIGN.md section
+ * 4.15); host and device equal that model bit for bit.
+ *
+ * Parameters, linear values made once on the host with libm's pow: fs2 = full_scale^2; target_ms = 10^((target_lkfs + 0.691) /
+ * 10), gate_ms likewise; g_max = 10^(max_boost_db / 20), g_min = 10^(-max_cut_db / 20); the ceiling c = (float)(full_scale
+ * 10^(ceiling_dbfs / 20)).
+ * Control (float64, per channel and call, from the audio meters' record; every step one IEEE operation, no fused multiply-add,
+ * no sqrt, log or pow):
+ *   ms = ((sum_k2[0] + (stereo ? sum_k2[1] : 0)) / n) / fs2          the call's K-weighted mean square against full scale
+ *   gated = !(ms >= gate_ms && ms < infinity): dead air, a muted channel, n = 0, NaN -- the estimate loud_ms stands.
+ *   Otherwise the first such call sets loud_ms = ms, later ones loud_ms += k (ms - loud_ms), k = attack where ms > loud_ms,
+ *   else release.  Without an estimate the gain is 1.  With one, r = target_ms / loud_ms and gain = heron2(r) clamped to
+ *   [g_min, g_max] (g_min where r is not > 0, g_max where it is infinite).  heron2 is a square root in basic operations:
+ *   the seed pexp2(0.5 plog2(r)) -- plog2 the blend's pseudo-logarithm, pexp2(x) = ldexp(1 + (x - floor x), floor x) -- and two
+ *   steps y = 0.5 (y + r / y); within 1e-5 of sqrt r (DESIGN.md has the measured figure).
+ *   End points (float32): gain1 = (float)gain; gain0 = the previous call's gain1 (the first call: equal).
+ * Gain and limiter (float32 and integers; W the look-ahead, ONE = 2^24 = FMRX_LEVELLER_ONE; sample k of the call's n = n_audio,
+ * inv_n = (float)(1.0 / n)):
+ *   g[k] = fmaf((float)(k + 1), (gain1 - gain0) * inv_n, gain0);   u_r[k] = x_r[k] * g[k] for each row r
+ *   code(a) = a <= c ? ONE : (a < infinity ? (uint32)((c / a) * 16777216.0f) : 0)          NaN and infinity: 0
+ *   q[k] = min over the rows of code(|u_r[k]|)                      stereo is linked: one gain for both rows
+ *   m[k] = min(q[k-W+1 .. k]);   s[k] = (sum of m[k-W+1 .. k]) >> log2 W;   y_r[k] = u_r[k-(W-1)] * ((float)s[k] * 2^-24)
+ *   The output is the input delayed by W - 1 samples.  Every m that enters s[k] has q[k-W+1] in its window, so s[k] <=
+ *   q[k-W+1] and |y| <= c (1 + 2^-24)^2 < c (1 + 2^-22): no finite output exceeds the ceiling by more than two roundings.  With
+ *   gain 1 and nothing beyond c the output is the input delayed, bit for bit.  A NaN comes out as NaN, an infinity as NaN (the
+ *   product of infinity and the gain 0), and both fade their 2W - 1 neighbours to zero; neither stays in the state.
+ *   The state per channel, carried across calls: the last 2W - 2 codes and the last W - 1 values of u per row; fresh: ONE and 0.
+ *   Codes are integers and the float work is per sample, so any split of a row over lanes, workgroups or calls gives the
+ *   same bits; only the gain ramp is defined per call.
+ *   min_code: the smallest s of the call; limited: the number of k with s[k] < ONE.
+ *   PCM: the library's pack of y (pcm_policy), interleaved [n_channels][n_audio][audio_channels] as the banks write it.
+ *
+ * Defaults (fmrx_leveller_defaults) -- design choices: target -23 LKFS (EBU R 128); at most 12 dB up and 20 dB down; gate at
+ * -50 LKFS; attack 0.2 and release 0.02 per call; ceiling -1 dBFS; full_scale 2.0 (what the PCM pack maps to 32 768).
+ * max_boost_db = max_cut_db = 0 is a limiter alone.  fmrx_leveller_create / fmrx_leveller_control return FMRX_EINVAL unless
+ * everything is finite, max_boost_db >= 0, max_cut_db >= 0, gate_lkfs < target_lkfs, 0 < attack, release <= 1, ceiling_dbfs <
+ * 0, full_scale > 0, every linear value above is finite and > 0 and c is a normal float. */
+#define FMRX_LEVELLER_ONE 16777216u
+typedef struct fmrx_leveller_params {
+    double target_lkfs, max_boost_db, max_cut_db, gate_lkfs;
+    double attack, release;
+    double ceiling_dbfs, full_scale;
+} fmrx_leveller_params;
+/* Per channel: what the last call decided and did, and the state the next control step starts from. */
+typedef struct fmrx_leveller_status {
+    double loud_ms;             /* the loudness estimate as a mean square against full scale; 0: none yet */
+    double gain;
+    float gain0, gain1;         /* the last call's ramp */
+    uint32_t gated;
+    uint32_t min_code, limited; /* written by the pass over the audio */
+    uint32_t reserved;
+    uint64_t calls;             /* since create / reset; 0 = the next call is a first call */
+} fmrx_leveller_status;
+typedef struct fmrx_leveller_levels {
+    double loudness_lkfs;       /* -0.691 + 10 log10(loud_ms); -99 without an estimate */
+    double gain_db;             /* 20 log10(gain) */
+    double reduction_db;        /* 20 log10(min_code / 2^24) <= 0: the limiter's deepest reduction of the call; -99 for code 0 */
+} fmrx_leveller_levels;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_leveller_params) == 64, "fmrx_leveller_params layout");
+static_assert(sizeof(fmrx_leveller_status) == 48, "fmrx_leveller_status layout");
+static_assert(sizeof(fmrx_leveller_levels) == 24, "fmrx_leveller_levels layout");
+#else
+_Static_assert(sizeof(fmrx_leveller_params) == 64, "fmrx_leveller_params layout");
+_Static_assert(sizeof(fmrx_leveller_status) == 48, "fmrx_leveller_status layout");
+_Static_assert(sizeof(fmrx_leveller_levels) == 24, "fmrx_leveller_levels layout");
+#endif
+typedef struct fmrx_leveller fmrx_leveller;
+FMRX_API int fmrx_leveller_defaults(fmrx_leveller_params *p);
+/* Host code, no device needed.  control: one channel's control step on one record (n and sum_k2 are read); *state is read and
+ * replaced; a zeroed status is a fresh channel.  The function the control kernel runs (leveller_control.hpp).  ceiling: c.
+ * derive: a status in dB, with log10.  tile: the samples of a row one workgroup writes, 2048 - 2 lookahead (0 for a lookahead
+ * that is no power of two in 8 .. 128). */
+FMRX_API int fmrx_leveller_control(const fmrx_leveller_params *p, int audio_channels, const fmrx_audio_meter *rec,
+                                   fmrx_leveller_status *state_in_out);
+FMRX_API int fmrx_leveller_ceiling(const fmrx_leveller_params *p, float *ceiling);
+FMRX_API int fmrx_leveller_derive(const fmrx_leveller_status *st, fmrx_leveller_levels *out);
+FMRX_API size_t fmrx_leveller_tile(int lookahead);
+/* The host reference of one channel's gain and limiter, serial: rows [audio_channels][row_pitch] of which n >= 1 are walked
+ * with the ramp gain0 -> gain1 across them, out [audio_channels][out_pitch]; codes [2 lookahead - 2] and u
+ * [audio_channels][lookahead - 1] are the state, read and replaced (fresh: FMRX_LEVELLER_ONE and 0); *min_code and *limited
+ * (either may be NULL) as the status row's. */
+FMRX_API int fmrx_leveller_walk(int audio_channels, int lookahead, float ceiling, float gain0, float gain1, const float *rows,
+                                size_t row_pitch, size_t n, uint32_t *codes, float *u, float *out, size_t out_pitch, uint32_t *min_code,
+                                uint32_t *limited);
+/* n_audio: samples per row and call (fmrx_channels_n_audio); audio_channels 1 or 2; audio_Fs as the audio meters' (finite, 8 000
+ * .. 768 000; only the latency in seconds depends on it); lookahead: a power of two in 8 .. 128, 0 = 64 */
+FMRX_API int fmrx_leveller_create(fmrx_leveller **out, const fmrx_leveller_params *p, double audio_Fs, int n_channels, int audio_channels,
+                                  size_t n_audio, int lookahead, int device);
+FMRX_API int fmrx_leveller_destroy(fmrx_leveller *h);
+/* channel < 0: all.  Clears the status row and the limiter's state of the channel.  Waits for the handle's last call; the rows
+ * are clear when it returns, for a later call on any stream. */
+FMRX_API int fmrx_leveller_reset(fmrx_leveller *h, int channel);
+/* the delay of the stage in samples, lookahead - 1; 0 for a NULL handle */
+FMRX_API size_t fmrx_leveller_latency(const fmrx_leveller *h);
+/* Asynchronous on `stream`, after fmrx_audio_meters_process_dev on the same stream: reads the sums of am's last call where
+ * they lie on the device.  FMRX_EINVAL where am has made no call, where that call walked another n than this handle's n_audio,
+ * or where am has another channel count, audio_channels or device.  d_in [n_channels][audio_channels][n_audio]; d_out the same
+ * shape; d_pcm16 [n_channels][n_audio][audio_channels]; d_out or d_pcm16 may be NULL, not both.  d_out must not overlap d_in
+ * (FMRX_EINVAL): a workgroup reads 2 lookahead samples in front of the ones it writes.  Float rows 4-byte aligned, PCM 2-byte;
+ * stereo rows that are 16-byte aligned (every pointer given, n_audio a multiple of 4) move in 16-byte pieces, all others 4
+ * bytes at a time, the same arithmetic. */
+FMRX_API int fmrx_leveller_process_dev(fmrx_leveller *h, const fmrx_audio_meters *am, const float *d_in, float *d_out, int16_t *d_pcm16,
+                                       int pcm_policy, void *stream);
+/* Host rows and host records [n_channels] (fmrx_audio_meters_collect's), synchronous (it first waits for the handle's last
+ * call): the same kernels.  out must not overlap in; the device copies keep each host pointer's address modulo 16. */
+FMRX_API int fmrx_leveller_process(fmrx_leveller *h, const fmrx_audio_meter *recs, const float *in, float *out, int16_t *pcm16,
+                                   int pcm_policy);
+/* out [n_channels]; waits for the handle's last call (an event it recorded), not for the device */
+FMRX_API int fmrx_leveller_status_get(fmrx_leveller *h, fmrx_leveller_status *out);
+
 #ifdef __cplusplus
 }
 #endif

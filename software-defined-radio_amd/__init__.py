@@ -1684,6 +1684,136 @@ class Loudness:
                     blocks=int(out[0]["blocks"]), full=bool(out[0]["full"]))
 
 
+# --------------------------------------------------------------------------
+# Loudness leveller and look-ahead peak limiter behind the audio meters
+# --------------------------------------------------------------------------
+class LevellerParams(C.Structure):
+    """struct fmrx_leveller_params: target_lkfs / gate_lkfs in LKFS, max_boost_db / max_cut_db >= 0, attack / release per call in
+    (0, 1], ceiling_dbfs < 0, full_scale the float value of 0 dBFS.  LevellerParams() holds the library's defaults; keyword
+    arguments replace single fields.  max_boost_db = max_cut_db = 0 is a limiter alone."""
+    _fields_ = [(k, C.c_double) for k in ("target_lkfs", "max_boost_db", "max_cut_db", "gate_lkfs", "attack", "release", "ceiling_dbfs",
+                                          "full_scale")]
+
+    def __init__(self, **kw):
+        _params_init(self, lib.fmrx_leveller_defaults, kw)
+
+
+LEVELLER_STATUS_DTYPE = np.dtype([("loud_ms", "<f8"), ("gain", "<f8"), ("gain0", "<f4"), ("gain1", "<f4"), ("gated", "<u4"),
+                                  ("min_code", "<u4"), ("limited", "<u4"), ("reserved", "<u4"), ("calls", "<u8")])   # struct fmrx_leveller_status
+LEVELLER_LEVELS_DTYPE = np.dtype([("loudness_lkfs", "<f8"), ("gain_db", "<f8"), ("reduction_db", "<f8")])          # struct fmrx_leveller_levels
+LEVELLER_ONE = 1 << 24    # the gain code of "no reduction"
+assert LEVELLER_STATUS_DTYPE.itemsize == 48 and LEVELLER_LEVELS_DTYPE.itemsize == 24 and C.sizeof(LevellerParams) == 64
+_sig("fmrx_leveller_defaults", [C.POINTER(LevellerParams)])
+_sig("fmrx_leveller_control", [C.POINTER(LevellerParams), _int, _vp, _vp])
+_sig("fmrx_leveller_ceiling", [C.POINTER(LevellerParams), C.POINTER(C.c_float)])
+_sig("fmrx_leveller_derive", [_vp, _vp])
+_sig("fmrx_leveller_tile", [_int], _sz)
+_sig("fmrx_leveller_walk", [_int, _int, C.c_float, C.c_float, C.c_float, _vp, _sz, _sz, _vp, _vp, _vp, _sz, C.POINTER(C.c_uint32),
+                            C.POINTER(C.c_uint32)])
+_sig("fmrx_leveller_create", [C.POINTER(_vp), C.POINTER(LevellerParams), _dbl, _int, _int, _sz, _int, _int])
+_sig("fmrx_leveller_destroy", [_vp])
+_sig("fmrx_leveller_reset", [_vp, _int])
+_sig("fmrx_leveller_latency", [_vp], _sz)
+_sig("fmrx_leveller_process_dev", [_vp, _vp, _vp, _vp, _vp, _int, _vp])
+_sig("fmrx_leveller_process", [_vp, _vp, _vp, _vp, _vp, _int])
+_sig("fmrx_leveller_status_get", [_vp, _vp])
+
+
+def levellerControl(params, rec, state=None, audio_channels=2) -> np.ndarray:
+    """Host only: one channel's control step (fmrx_leveller_control) on one AUDIO_METER_DTYPE record; state: the
+    LEVELLER_STATUS_DTYPE record the last step returned (None or zeros: a fresh channel) -> the new one."""
+    r = np.array(rec, dtype=AUDIO_METER_DTYPE).reshape(1)
+    st = np.zeros(1, LEVELLER_STATUS_DTYPE) if state is None else np.array(state, dtype=LEVELLER_STATUS_DTYPE).reshape(1).copy()
+    p = params if params is not None else LevellerParams()
+    _check(lib.fmrx_leveller_control(C.byref(p), int(audio_channels), r.ctypes.data, st.ctypes.data))
+    return st[0]
+
+
+def levellerCeiling(params=None) -> np.float32:
+    """Host only: the limiter's ceiling as the float32 the kernels compare with."""
+    c = C.c_float()
+    _check(lib.fmrx_leveller_ceiling(C.byref(params if params is not None else LevellerParams()), C.byref(c)))
+    return np.float32(c.value)
+
+
+def levellerTile(lookahead=64) -> int:
+    """Host only: the samples of a row one workgroup of the apply kernel writes."""
+    return lib.fmrx_leveller_tile(int(lookahead))
+
+
+def levellerDerive(status) -> dict:
+    """Host only: loudness_lkfs, gain_db and reduction_db of one LEVELLER_STATUS_DTYPE record."""
+    st = np.array(status, dtype=LEVELLER_STATUS_DTYPE).reshape(1)
+    out = np.zeros(1, LEVELLER_LEVELS_DTYPE)
+    _check(lib.fmrx_leveller_derive(st.ctypes.data, out.ctypes.data))
+    return {k: float(out[0][k]) for k in LEVELLER_LEVELS_DTYPE.names}
+
+
+def levellerWalk(rows, gain0=1.0, gain1=1.0, lookahead=64, ceiling=None, state=None):
+    """Host only: the serial reference of one channel's gain and limiter (fmrx_leveller_walk) on rows float32
+    [audio_channels, n]; state: the (codes uint32 [2W-2], u float32 [audio_channels, W-1]) the last call returned (None: a fresh
+    channel) -> (out [audio_channels, n], state, min_code, limited)."""
+    x = _f32(rows)
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    ac, n, W = x.shape[0], x.shape[1], int(lookahead)
+    if state is None:
+        codes, u = np.full(max(2 * W - 2, 1), LEVELLER_ONE, np.uint32), np.zeros((ac, max(W - 1, 1)), np.float32)
+    else:
+        codes, u = np.array(state[0], dtype=np.uint32), np.array(state[1], dtype=np.float32).reshape(ac, -1)
+    out = np.zeros((ac, n), np.float32)
+    mn, cnt = C.c_uint32(), C.c_uint32()
+    c = levellerCeiling() if ceiling is None else ceiling
+    _check(lib.fmrx_leveller_walk(ac, W, float(c), float(gain0), float(gain1), x.ctypes.data, n, n, codes.ctypes.data, u.ctypes.data,
+                                  out.ctypes.data, n, C.byref(mn), C.byref(cnt)))
+    return out, (codes, u), mn.value, cnt.value
+
+
+class Leveller(_MeterStage):
+    """A gain towards a loudness target and a look-ahead peak limiter per channel of a receiver bank, decided from the audio
+    meters' K-weighted sums of the same call (fmrx_leveller_*).  The last stage of the chain, and the one
+    that packs the PCM: lv = Leveller.for_bank(bank, audio_meters); after audio_meters.process_bank(d_audio, stream=s):
+    lv.process_bank(d_audio, d_out, d_pcm, stream=s); lv.status().  The output is delayed by lv.latency samples; d_out must not
+    overlap d_audio."""
+
+    _prefix, _status_dtype = "leveller", LEVELLER_STATUS_DTYPE
+
+    def __init__(self, audio_Fs=48000.0, n_channels=1, audio_channels=2, n_audio=1920, params: LevellerParams | None = None, lookahead=64,
+                 device=0):
+        self.audio_Fs, self.n_channels, self.audio_channels, self.n_audio = float(audio_Fs), int(n_channels), int(audio_channels), int(n_audio)
+        self.params = params if params is not None else LevellerParams()
+        self.lookahead = int(lookahead)
+        self._meters = None
+        self._h = _vp()
+        _check(lib.fmrx_leveller_create(C.byref(self._h), C.byref(self.params), self.audio_Fs, self.n_channels, self.audio_channels,
+                                        self.n_audio, self.lookahead, device))
+        self.latency = lib.fmrx_leveller_latency(self._h)
+        self.tile = lib.fmrx_leveller_tile(self.latency + 1)
+        self.ceiling = levellerCeiling(self.params)
+
+    @classmethod
+    def for_bank(cls, bank, audio_meters, params: LevellerParams | None = None, lookahead=64):
+        """The leveller of a Channels bank and of the AudioMeters made for it, on the bank's device."""
+        lv = cls(bank.params.audio_Fs, bank.n_channels, bank.audio_channels, bank.n_audio, params, lookahead, bank.device)
+        lv._meters = audio_meters
+        return lv
+
+    def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True):
+        """Host records AUDIO_METER_DTYPE [n_channels] (AudioMeters.collect's) and host rows float32 [n_channels, audio_channels,
+        n_audio], synchronous -> dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]).  The rows keep their host address
+        modulo 16 on the device."""
+        r = np.ascontiguousarray(recs, dtype=AUDIO_METER_DTYPE).reshape(self.n_channels)
+        shape = (self.n_channels, self.audio_channels, self.n_audio)
+        x = _f32(audio).reshape(shape)
+        f = np.zeros(shape, np.float32) if want_f32 else None
+        s = np.zeros((self.n_channels, self.n_audio, self.audio_channels), np.int16) if want_pcm else None
+        self._call("process", r.ctypes.data, x.ctypes.data, None if f is None else f.ctypes.data, None if s is None else s.ctypes.data,
+                   PCM_WRAP if wrap else PCM_SATURATE)
+        return {"audio": f, "pcm16": s}
+
+    def derive(self, status) -> dict:
+        return levellerDerive(status)
+
+
 class FrontEndPlan:
     """Reusable device-side tap tables for the fused front-end kernel (fmrx_fe_plan)."""
 

@@ -83,6 +83,10 @@ void walk_channel(const audio_meters::Coefs &c, const float *rows, size_t pitch,
 
 }  // namespace
 
+namespace fmrx {
+AudioMetersSums audio_meters_sums(const fmrx_audio_meters *m) { return AudioMetersSums{m->d_sums.p, m->n, m->n_channels, m->ac, m->device, m->ran}; }
+}  // namespace fmrx
+
 extern "C" {
 
 int fmrx_audio_meters_design(double audio_Fs, double *coef)

@@ -462,5 +462,38 @@ struct AudioMetersArgs {
     double *bins = nullptr;              // [n_channels][2][max_bins], written
 };
 int audio_meters_launch(const AudioMetersArgs &a, hipStream_t s);
+// what an audio meters handle's last call left on the device, for a stage behind it on the same stream (leveller.hip): the sums
+// [kAudioMetersSumFields][n_channels] and that call's n (ran false: no call yet)
+struct AudioMetersSums {
+    const double *d_sums;
+    size_t n;
+    int n_channels, ac, device;
+    bool ran;
+};
+AudioMetersSums audio_meters_sums(const fmrx_audio_meters *m);
+
+// ---- loudness leveller and peak limiter (kernels_leveller.hip; control step in leveller_control.hpp; handle and C ABI in leveller.hip) -----------------
+namespace leveller {
+struct Control;
+}
+// one lane per channel: d_status[c] <- control_step on the channel's K-weighted sums d_k2a[c], d_k2b[c] (d_k2b is not read for
+// mono) and its n from d_n_each[c], or n_all where that is NULL
+int leveller_control_launch(const leveller::Control &c, int audio_channels, const double *d_k2a, const double *d_k2b,
+                            const unsigned long long *d_n_each, unsigned long long n_all, fmrx_leveller_status *d_status, int n_channels,
+                            hipStream_t s);
+// words of one channel's limiter state: 2W - 2 code deficits (2^24 - code) and W - 1 values of u per row; all zero is fresh
+inline size_t leveller_state_words(int audio_channels, int W) { return static_cast<size_t>(W - 1) * (2 + audio_channels); }
+struct LevellerArgs {
+    const float *x = nullptr;            // [n_channels][ac][n]
+    float *y = nullptr;                  // the same shape, or NULL; no overlap with x
+    int16_t *pcm = nullptr;              // [n_channels][n][ac], or NULL
+    fmrx_leveller_status *status = nullptr;   // [n_channels]: gain0, gain1 read; min_code lowered, limited added to
+    const uint32_t *state_in = nullptr;  // [n_channels][leveller_state_words]: read
+    uint32_t *state_out = nullptr;       // another buffer of that shape: written whole
+    int n_channels = 0, ac = 1, W = 64, wrap = 1;
+    size_t n = 0;
+    float inv_n = 0.0f, ceiling = 0.0f;
+};
+int leveller_apply_launch(const LevellerArgs &a, hipStream_t s);
 
 }  // namespace fmrx
