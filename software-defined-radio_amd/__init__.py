@@ -568,10 +568,26 @@ def modeParams(mode, rf_taps=101, base_audio_taps=101, stereo_taps=101) -> Param
 
 
 # --------------------------------------------------------------------------
+# what every class that owns a library handle derives from
+# --------------------------------------------------------------------------
+class _Handle:
+    """Owns self._h, a handle the library made; a subclass names the function that destroys it."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:  # lib is None during interpreter shutdown
+            getattr(lib, self._destroy)(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+# --------------------------------------------------------------------------
 # pipeline handle
 # --------------------------------------------------------------------------
-class Pipeline:
+class Pipeline(_Handle):
     """RF_FrontEnd + RF_MONO / RF_STEREO of src/project.cpp as one device-resident pipeline."""
+    _destroy = "fmrx_pipeline_destroy"
 
     def __init__(self, mode=0, channels=1, rf_taps=101, base_audio_taps=101, stereo_taps=101, max_block_bytes=None,
                  device=0, params: Params | None = None):
@@ -580,13 +596,6 @@ class Pipeline:
         self.max_block_bytes = int(max_block_bytes or self.params.block_bytes)
         self._h = _vp()
         _check(lib.fmrx_pipeline_create(C.byref(self._h), C.byref(self.params), channels, self.max_block_bytes, device))
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:  # lib is None during interpreter shutdown
-            lib.fmrx_pipeline_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def n_if(self, n_bytes):
         return lib.fmrx_pipeline_n_if(self._h, n_bytes)
@@ -684,13 +693,14 @@ class Pipeline:
         return dict(front_end_ms=float(t[0]), audio_ms=float(t[1]), rest_ms=float(t[2]), total_ms=float(t[3])), n.value
 
 
-class Channels:
+class Channels(_Handle):
     """N independent receivers (all four modes), the current block of all of them in one device call (fmrx_channels_*).
 
     audio_channels: 1 mono, 2 stereo (the reference's second command-line argument).  exact=True: every stage in the
     reference's float32 evaluation order, fmPLL as the serial recurrence with glibc's functions, one lane per channel --
     audio equals the compiled reference's bit for bit.  exact=False with audio_channels=2: the fast stereo bank (matrix-core
     front end, fma FIRs, the PLL's fast recurrence one lane per channel; the default stereo path's error envelope)."""
+    _destroy = "fmrx_channels_destroy"
 
     def __init__(self, mode=0, n_channels=1, rf_taps=101, base_audio_taps=101, block_bytes=None, device=0, params: Params | None = None,
                  audio_channels=1, exact=False, stereo_taps=101):
@@ -704,13 +714,6 @@ class Channels:
         _check(lib.fmrx_channels_create_ex(C.byref(self._h), C.byref(self.params), self.n_channels, self.audio_channels,
                                            int(self.exact), self.block_bytes, device))
         self.n_audio = lib.fmrx_channels_n_audio(self._h)
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_channels_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self, channel=-1):
         _check(lib.fmrx_channels_reset(self._h, channel))
@@ -818,9 +821,10 @@ def framesync(diff_data):
     return off.value.decode(), idx.value
 
 
-class Rds:
+class Rds(_Handle):
     """The RDS chain of model/fmMonoBlock.py:238-296 on fm_demod blocks (fmrx_rds_*): the device chain of RdsBank with one channel,
     any block of up to max_block samples per call, bits recovered on the host."""
+    _destroy = "fmrx_rds_destroy"
 
     def __init__(self, mode=0, max_block=9600, device=0, params: RdsParams | None = None):
         self.params = params if params is not None else RdsParams()
@@ -828,13 +832,6 @@ class Rds:
             _check(lib.fmrx_rds_mode_params(mode, C.byref(self.params)))
         self._h = _vp()
         _check(lib.fmrx_rds_create(C.byref(self._h), C.byref(self.params), max_block, device))
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_rds_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self):
         _check(lib.fmrx_rds_reset(self._h))
@@ -858,10 +855,11 @@ class Rds:
         return out
 
 
-class RdsBank:
+class RdsBank(_Handle):
     """The RDS chain of N channels per device call (fmrx_rds_bank_*), bits recovered on the device.  An Rds handle runs the same
     chain with one channel, so per channel this is, bit for bit, what an Rds handle reports for the same discriminator stream.
     block: IF samples per channel and call (9600 = the receiver banks' block_bytes 192000)."""
+    _destroy = "fmrx_rds_bank_destroy"
 
     def __init__(self, mode=0, n_channels=1, block=9600, device=0, params: RdsParams | None = None):
         self.params = params if params is not None else RdsParams()
@@ -872,13 +870,6 @@ class RdsBank:
         _check(lib.fmrx_rds_bank_create(C.byref(self._h), C.byref(self.params), self.n_channels, self.block, device))
         self.n_out = lib.fmrx_rds_bank_n_out(self._h)
         self.max_bits = lib.fmrx_rds_bank_max_bits(self._h)
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_rds_bank_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self, channel=-1):
         _check(lib.fmrx_rds_bank_reset(self._h, channel))
@@ -1010,12 +1001,13 @@ def rds_block_correct(word26: int, offset: int, max_burst: int):
     return rc, info.value, n.value
 
 
-class RdsStationDecoder:
+class RdsStationDecoder(_Handle):
     """The RDS station decoder on the host (fmrx_rds_station_*): PI, PTY, PS and RadioText from the in-phase matched-filter rows
     an Rds handle returns (feed_rrc), or from differentially decoded bits (feed_bits).  State carries across feeds.  Each feed
     returns (station dict, the groups it completed as an RDS_GROUP_DTYPE array); .record holds the raw station record and .ext
     the raw extension record (RDS_STATION_EXT_DTYPE [1]; rds_station_ext_dict).  max_burst: burst error correction, 0 (off)
     .. 5; 2 is recommended (one wrong chip pair per block is repaired; 5 % of random words pass for blocks, at 5: 36 %)."""
+    _destroy = "fmrx_rds_station_destroy"
 
     def __init__(self, mode=0, sps: int | None = None, max_burst=0):
         if sps is None:
@@ -1039,13 +1031,6 @@ class RdsStationDecoder:
         x = np.zeros(1, RDS_STATION_EXT_DTYPE)
         _check(lib.fmrx_rds_station_ext_get(self._h, x.ctypes.data))
         return x
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_rds_station_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self):
         _check(lib.fmrx_rds_station_reset(self._h))
@@ -1096,13 +1081,14 @@ TUNER_FORMATS = {"u8": 0, "s8": 1, "s16": 2}                       # FMRX_TUNER_
 _TUNER_DTYPES = {"u8": np.uint8, "s8": np.int8, "s16": np.int16}
 
 
-class Tuner:
+class Tuner(_Handle):
     """N channels of one wide I/Q capture (Fs_w = R * rf_Fs), each mixed to its own centre offset, low-pass filtered by
     the prototype h and decimated by R, as u8 I/Q rows: the input of a receiver bank (fmrx_tuner_*; exact integer
     arithmetic).  tuner.process_dev(d_wide, n_wide, *bank.input_layout(), stream) followed by
     bank.process_dev(..., stream=stream) runs capture -> audio without the samples leaving the device.
     fmt: the capture's format, "u8" (interleaved unsigned bytes), "s8" (int8) or "s16" (int16, 4 bytes per complex sample;
     a device with 12 or 14 bits in the low end of the short takes a gain of 16 or 4)."""
+    _destroy = "fmrx_tuner_destroy"
 
     def __init__(self, R, h, n_channels, max_wide_samples, device=0, fmt="u8"):
         self._open(lib.fmrx_tuner_create_ex, (int(R),), 1, int(R), h, n_channels, max_wide_samples, device, fmt)
@@ -1157,13 +1143,6 @@ class Tuner:
         c, s = np.zeros(n.value, np.int16), np.zeros(n.value, np.int16)
         _check(lib.fmrx_tuner_table(c.ctypes.data, s.ctypes.data, C.byref(n)))
         return c, s
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_tuner_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self):
         _check(lib.fmrx_tuner_reset(self._h))
@@ -1239,11 +1218,12 @@ def metersDerive(if_Fs, rec) -> dict:
     return {k: float(out[0][k]) for k in METER_LEVELS_DTYPE.names}
 
 
-class Meters:
+class Meters(_Handle):
     """Per channel of a receiver bank and call: RF level, CNR and clipping of the input slot, and frequency offset,
     deviation, pilot and RDS levels of the discriminator row (fmrx_meters_*).  One pass over what
     the bank's call left on the device: meters = Meters.for_bank(bank); after bank.process_dev(..., stream=s),
     meters.process_bank(stream=s); recs = meters.collect(); meters.derive(recs[c])."""
+    _destroy = "fmrx_meters_destroy"
 
     def __init__(self, if_Fs, n_channels=1, device=0):
         self.if_Fs, self.n_channels = float(if_Fs), int(n_channels)
@@ -1258,13 +1238,6 @@ class Meters:
         m = cls(bank.params.if_Fs, bank.n_channels, bank.device)
         m._bank = bank
         return m
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_meters_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def process_dev(self, d_iq_first, iq_pitch_bytes, n_iq_bytes, d_demod_row0, demod_pitch, n_if, stream=None):
         """Device rows as Channels.input_layout() / demod_layout() return them; either pointer may be None."""
@@ -1316,20 +1289,16 @@ def _params_init(self, defaults, kw):
         setattr(self, k, int(v) if kinds[k] is C.c_int32 else float(v))
 
 
-class _MeterStage:
-    """What Blend and HighCut share: a handle behind the meters on a bank's audio (csrc/meter_stage.hpp).  A subclass names its
-    fmrx_<_prefix>_* functions and its status dtype, and creates self._h."""
+class _MeterStage(_Handle):
+    """What Blend, HighCut and Leveller share: a handle behind a meters handle on a bank's audio (csrc/meter_stage.hpp).  A
+    subclass names its fmrx_<_prefix>_* functions, its status dtype and the dtype of the records its host call reads, and creates
+    self._h."""
     _prefix = _status_dtype = None
+    _rec_dtype = METER_DTYPE
+    _destroy = property(lambda self: f"fmrx_{self._prefix}_destroy")
 
     def _call(self, name, *args):
         _check(getattr(lib, f"fmrx_{self._prefix}_{name}")(self._h, *args))
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            getattr(lib, f"fmrx_{self._prefix}_destroy")(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self, channel=-1):
         self._call("reset", channel)
@@ -1344,10 +1313,11 @@ class _MeterStage:
         self.process_dev(self._meters, d_in, d_out, d_pcm, stream, wrap)
 
     def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True, in_place=False):
-        """Host records METER_DTYPE [n_channels] and host rows float32 [n_channels, audio_channels, n_audio], synchronous ->
-        dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]); in_place: the call writes over its input (audio is then an
-        array of its own, never the caller's).  The rows keep their host address modulo 16 on the device."""
-        r = np.ascontiguousarray(recs, dtype=METER_DTYPE).reshape(self.n_channels)
+        """Host records [n_channels] (METER_DTYPE; the leveller: AUDIO_METER_DTYPE, AudioMeters.collect's) and host rows float32
+        [n_channels, audio_channels, n_audio], synchronous -> dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]);
+        in_place: the call writes over its input (audio is then an array of its own, never the caller's; the leveller refuses
+        it, its output must not overlap its input).  The rows keep their host address modulo 16 on the device."""
+        r = np.ascontiguousarray(recs, dtype=self._rec_dtype).reshape(self.n_channels)
         shape = (self.n_channels, self.audio_channels, self.n_audio)
         x = _f32(audio).reshape(shape)
         f = s = None
@@ -1587,11 +1557,12 @@ def audioMetersDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dic
     return {k: (tuple(float(v) for v in out[0][k]) if out[0][k].ndim else float(out[0][k])) for k in AUDIO_LEVELS_DTYPE.names}
 
 
-class AudioMeters:
+class AudioMeters(_Handle):
     """Per channel of a receiver bank and call: overs, peak, sums, K-weighted energy, the stereo cross sum and the 100 ms bins of
     the audio rows (fmrx_audio_meters_*).  The last stage of the chain, behind whatever wrote the rows on
     stream s: am = AudioMeters.for_bank(bank); am.process_bank(d_audio, stream=s); recs, bins = am.collect(); am.derive(recs[c]).
     It needs no Meters, so it also works behind the fused mono bank."""
+    _destroy = "fmrx_audio_meters_destroy"
 
     def __init__(self, audio_Fs=48000.0, n_channels=1, audio_channels=2, n_audio=1920, device=0):
         self.audio_Fs, self.n_channels, self.audio_channels, self.n_audio = float(audio_Fs), int(n_channels), int(audio_channels), int(n_audio)
@@ -1604,13 +1575,6 @@ class AudioMeters:
     def for_bank(cls, bank):
         """The audio meters of a Channels bank, on the bank's device."""
         return cls(bank.params.audio_Fs, bank.n_channels, bank.audio_channels, bank.n_audio, bank.device)
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_audio_meters_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self, channel=-1):
         _check(lib.fmrx_audio_meters_reset(self._h, channel))
@@ -1648,9 +1612,10 @@ class AudioMeters:
         return audioMetersDerive(rec, self.audio_channels, full_scale)
 
 
-class Loudness:
+class Loudness(_Handle):
     """Gated loudness by ITU-R BS.1770-4 over the audio meters' bins (fmrx_loudness_*), host only: loud = Loudness.for_meters(am);
     loud.push(*am.collect()); loud.read(c) -> momentary, short_term, integrated (LKFS), blocks, full."""
+    _destroy = "fmrx_loudness_destroy"
 
     def __init__(self, n_channels, bin_len, max_blocks=36000, full_scale=AUDIO_FULL_SCALE):
         self.n_channels = int(n_channels)
@@ -1660,13 +1625,6 @@ class Loudness:
     @classmethod
     def for_meters(cls, am, max_blocks=36000, full_scale=AUDIO_FULL_SCALE):
         return cls(am.n_channels, am.bin_len, max_blocks, full_scale)
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_loudness_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def reset(self, channel=-1):
         _check(lib.fmrx_loudness_reset(self._h, channel))
@@ -1775,7 +1733,7 @@ class Leveller(_MeterStage):
     lv.process_bank(d_audio, d_out, d_pcm, stream=s); lv.status().  The output is delayed by lv.latency samples; d_out must not
     overlap d_audio."""
 
-    _prefix, _status_dtype = "leveller", LEVELLER_STATUS_DTYPE
+    _prefix, _status_dtype, _rec_dtype = "leveller", LEVELLER_STATUS_DTYPE, AUDIO_METER_DTYPE
 
     def __init__(self, audio_Fs=48000.0, n_channels=1, audio_channels=2, n_audio=1920, params: LevellerParams | None = None, lookahead=64,
                  device=0):
@@ -1797,38 +1755,19 @@ class Leveller(_MeterStage):
         lv._meters = audio_meters
         return lv
 
-    def process(self, recs, audio, want_f32=True, want_pcm=True, wrap=True):
-        """Host records AUDIO_METER_DTYPE [n_channels] (AudioMeters.collect's) and host rows float32 [n_channels, audio_channels,
-        n_audio], synchronous -> dict(audio=..., pcm16=[n_channels, n_audio, audio_channels]).  The rows keep their host address
-        modulo 16 on the device."""
-        r = np.ascontiguousarray(recs, dtype=AUDIO_METER_DTYPE).reshape(self.n_channels)
-        shape = (self.n_channels, self.audio_channels, self.n_audio)
-        x = _f32(audio).reshape(shape)
-        f = np.zeros(shape, np.float32) if want_f32 else None
-        s = np.zeros((self.n_channels, self.n_audio, self.audio_channels), np.int16) if want_pcm else None
-        self._call("process", r.ctypes.data, x.ctypes.data, None if f is None else f.ctypes.data, None if s is None else s.ctypes.data,
-                   PCM_WRAP if wrap else PCM_SATURATE)
-        return {"audio": f, "pcm16": s}
-
     def derive(self, status) -> dict:
         return levellerDerive(status)
 
 
-class FrontEndPlan:
+class FrontEndPlan(_Handle):
     """Reusable device-side tap tables for the fused front-end kernel (fmrx_fe_plan)."""
+    _destroy = "fmrx_fe_plan_destroy"
 
     def __init__(self, h, decim):
         h = _f32(h)
         self.taps, self.decim = len(h), int(decim)
         self._h = _vp()
         _check(lib.fmrx_fe_plan_create(C.byref(self._h), h, len(h), decim))
-
-    def close(self):
-        if getattr(self, "_h", None) and lib is not None:
-            lib.fmrx_fe_plan_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     @property
     def specialised(self) -> bool:

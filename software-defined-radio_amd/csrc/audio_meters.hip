@@ -3,18 +3,19 @@
 // kernels_audio_meters.hip; one channel's walk, shared with fmrx_audio_meters_walk below: audio_meters_core.hpp; definition:
 // tests/_audio_meters_model.py.
 //
-// A handle of the signal meters' kind (meters.hip), not meter_stage.hpp's: it reads no meters and writes no audio.  It keeps
-// the channels' state on the device (field-major, see fmrx_internal.hpp), the result arrays a call writes, their pinned host
-// copies, and the event the last call recorded behind the copies; collect waits on that event, not on the device.
+// A handle of the signal meters' kind (meters.hip), not a stage of meter_stage.hpp: it reads no meters and writes no audio.  It
+// keeps the channels' state on the device (field-major, see fmrx_internal.hpp), the result arrays a call writes, their pinned
+// host copies, and meter_stage.hpp's handle base: the event the last call recorded behind the copies; collect waits on that
+// event, not on the device.
 #include "audio_meters_core.hpp"
-#include "fmrx_internal.hpp"
+#include "meter_stage.hpp"
 
 #include <cmath>
 
 using namespace fmrx;
 
-struct fmrx_audio_meters {
-    int device = 0, n_channels = 0, ac = 1;
+struct fmrx_audio_meters : meter_stage::Handle {
+    int n_channels = 0, ac = 1;
     double audio_Fs = 0.0;
     size_t n_audio = 0, bin_len = 0, max_bins = 0;
     audio_meters::Coefs coef;
@@ -22,8 +23,6 @@ struct fmrx_audio_meters {
     DevBuf<unsigned> d_fill, d_counts;
     double *h_sums = nullptr, *h_bins = nullptr;   // pinned
     unsigned *h_counts = nullptr;                  // pinned
-    hipEvent_t done = nullptr;
-    bool ran = false;
     size_t n = 0;                                  // of the last call
     DevBuf<float> d_rows;                          // fmrx_audio_meters_process only
     ~fmrx_audio_meters()
@@ -31,23 +30,12 @@ struct fmrx_audio_meters {
         if (h_sums) (void)hipHostFree(h_sums);
         if (h_bins) (void)hipHostFree(h_bins);
         if (h_counts) (void)hipHostFree(h_counts);
-        if (done) (void)hipEventDestroy(done);
     }
 };
 
 namespace {
 
 bool good_fs(double Fs) { return std::isfinite(Fs) && Fs >= audio_meters::kMinFs && Fs <= audio_meters::kMaxFs; }
-
-// the signal meters' edge rule: offset + 10 log10(num / den) clamped to [-99, 99]; -99 where num is not positive (0 / 0 and NaN
-// included), 99 where only den is not
-double db(double num, double den, double offset = 0.0)
-{
-    if (!(num > 0.0)) return -99.0;
-    if (!(den > 0.0)) return 99.0;
-    const double v = offset + 10.0 * std::log10(num / den);
-    return v < -99.0 ? -99.0 : (v > 99.0 ? 99.0 : v);
-}
 
 template <int AC>
 void walk_channel(const audio_meters::Coefs &c, const float *rows, size_t pitch, size_t n, unsigned len, fmrx_audio_meter_state *st,
@@ -153,19 +141,15 @@ int fmrx_audio_meters_create(fmrx_audio_meters **out, double audio_Fs, int n_cha
     if (n_channels < 1) return fail(FMRX_EINVAL, "audio_meters_create: n_channels must be >= 1");
     if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "audio_meters_create: audio_channels must be 1 or 2");
     if (n_audio < 1 || n_audio > (size_t{1} << 26)) return fail(FMRX_EINVAL, "audio_meters_create: n_audio %zu (1 .. 2^26)", n_audio);
-    FMRX_TRY(require_device());
-    FMRX_HIP(hipSetDevice(device));
-    fmrx_audio_meters *m = new fmrx_audio_meters;
-    m->device = device;
-    m->n_channels = n_channels;
-    m->ac = audio_channels;
-    m->audio_Fs = audio_Fs;
-    m->n_audio = n_audio;
-    m->bin_len = audio_meters::bin_len(audio_Fs);
-    m->max_bins = n_audio / m->bin_len + 1;
-    audio_meters::design(audio_Fs, &m->coef);
-    auto body = [&]() -> int {
+    return meter_stage::make(out, device, [&](fmrx_audio_meters *m) -> int {
         const size_t N = n_channels;
+        m->n_channels = n_channels;
+        m->ac = audio_channels;
+        m->audio_Fs = audio_Fs;
+        m->n_audio = n_audio;
+        m->bin_len = audio_meters::bin_len(audio_Fs);
+        m->max_bins = n_audio / m->bin_len + 1;
+        audio_meters::design(audio_Fs, &m->coef);
         FMRX_TRY(m->d_state.alloc(N * kAudioMetersStateFields));
         FMRX_TRY(m->d_fill.alloc(N));
         FMRX_TRY(m->d_sums.alloc(N * kAudioMetersSumFields));
@@ -176,33 +160,17 @@ int fmrx_audio_meters_create(fmrx_audio_meters **out, double audio_Fs, int n_cha
         FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_sums), m->d_sums.bytes(), hipHostMallocDefault));
         FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_counts), m->d_counts.bytes(), hipHostMallocDefault));
         FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_bins), m->d_bins.bytes(), hipHostMallocDefault));
-        FMRX_HIP(hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
         return FMRX_OK;
-    };
-    const int rc = body();
-    if (rc != FMRX_OK) {
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return FMRX_OK;
+    });
 }
 
-int fmrx_audio_meters_destroy(fmrx_audio_meters *m)
-{
-    if (!m) return FMRX_OK;
-    (void)hipSetDevice(m->device);
-    if (m->ran) (void)hipEventSynchronize(m->done);
-    delete m;
-    return FMRX_OK;
-}
+int fmrx_audio_meters_destroy(fmrx_audio_meters *m) { return meter_stage::destroy(m); }
 
 int fmrx_audio_meters_reset(fmrx_audio_meters *m, int channel)
 {
     if (!m) return fail(FMRX_EINVAL, "audio_meters_reset: null handle");
     if (channel >= m->n_channels) return fail(FMRX_EINVAL, "audio_meters_reset: channel %d of %d", channel, m->n_channels);
-    FMRX_HIP(hipSetDevice(m->device));
-    if (m->ran) FMRX_HIP(hipEventSynchronize(m->done));
+    FMRX_TRY(m->wait());
     const size_t N = m->n_channels;
     if (channel < 0) {
         FMRX_HIP(hipMemset(m->d_state.p, 0, m->d_state.bytes()));
@@ -218,8 +186,7 @@ int fmrx_audio_meters_reset(fmrx_audio_meters *m, int channel)
 int fmrx_audio_meters_state_get(fmrx_audio_meters *m, fmrx_audio_meter_state *out)
 {
     if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_state_get: null argument");
-    FMRX_HIP(hipSetDevice(m->device));
-    if (m->ran) FMRX_HIP(hipEventSynchronize(m->done));
+    FMRX_TRY(m->wait());
     const size_t N = m->n_channels;
     std::vector<double> st(N * kAudioMetersStateFields);
     std::vector<unsigned> fill(N);
@@ -270,8 +237,7 @@ int fmrx_audio_meters_collect(fmrx_audio_meters *m, fmrx_audio_meter *out, doubl
 {
     if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_collect: null argument");
     if (!m->ran) return fail(FMRX_EINVAL, "audio_meters_collect: no call to collect");
-    FMRX_HIP(hipSetDevice(m->device));
-    FMRX_HIP(hipEventSynchronize(m->done));
+    FMRX_TRY(m->wait());
     const size_t N = m->n_channels;
     for (size_t c = 0; c < N; c++) {
         fmrx_audio_meter &r = out[c];

@@ -3,21 +3,21 @@
 // bank's audio.  Control step: blend_control.hpp; kernels: kernels_blend.hip; definition: tests/_blend_model.py (DESIGN.md
 // section 4.12).
 //
-// The handle is meter_stage.hpp's with the control structure: the stage owns no buffer of its own.
+// The handle is meter_stage.hpp's stage behind the signal meters with the control structure: the stage owns no buffer of its own.
 #include "blend_control.hpp"
 #include "meter_stage.hpp"
 
 using namespace fmrx;
 
-struct fmrx_blend : meter_stage::Stage<fmrx_blend_status> {
+struct fmrx_blend : meter_stage::MpxStage<fmrx_blend_status> {
     blend::Control control{};
 };
 
 namespace {
 
-int launch(fmrx_blend *b, const meter_stage::Call &c)
+int launch(fmrx_blend *b, const meter_stage::Call<meter_stage::Mpx> &c)
 {
-    FMRX_TRY(blend_control_launch(b->control, c.d_mpx, c.d_seg_each, c.seg_all, b->d_status.p, b->n_channels, c.s));
+    FMRX_TRY(blend_control_launch(b->control, c.src.d_mpx, c.src.d_seg_each, c.src.seg_all, b->d_status.p, b->n_channels, c.s));
     return blend_apply_launch(c.d_in, c.d_out, c.d_pcm, b->d_status.p, b->n_channels, b->audio_channels, b->n_audio, b->inv_n, c.wrap, c.s);
 }
 
@@ -61,7 +61,7 @@ int fmrx_blend_reset(fmrx_blend *b, int channel)
 
 int fmrx_blend_process_dev(fmrx_blend *b, const fmrx_meters *m, const float *d_in, float *d_out, int16_t *d_pcm16, int pcm_policy, void *stream)
 {
-    return meter_stage::process_dev("blend_process_dev", "the blend", b, launch, m, d_in, d_out, d_pcm16, pcm_policy, stream);
+    return meter_stage::process_dev("blend_process_dev", b, launch, m, d_in, d_out, d_pcm16, pcm_policy, stream);
 }
 
 int fmrx_blend_process(fmrx_blend *b, const fmrx_meter *recs, const float *in, float *out, int16_t *pcm16, int pcm_policy)

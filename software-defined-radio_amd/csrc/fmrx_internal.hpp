@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -386,6 +387,16 @@ int tuner_launch(const TunerLaunch &a, hipStream_t stream);
 // tuner_launch's matrix-kernel launch outside the integer rates (kernels_tuner_rational.hip)
 int tuner_rat_mfma_launch(const TunerLaunch &a, long n_out, const TunerPlanInfo &plan, hipStream_t stream);
 
+// ---- what the meters report in decibels (host only): offset + 10 log10(num / den) clamped to [-99, 99]; -99 where num is not
+// positive (0 / 0 and NaN included), 99 where only den is not
+inline double db(double num, double den, double offset = 0.0)
+{
+    if (!(num > 0.0)) return -99.0;
+    if (!(den > 0.0)) return 99.0;
+    const double v = offset + 10.0 * std::log10(num / den);
+    return v < -99.0 ? -99.0 : (v > 99.0 ? 99.0 : v);
+}
+
 // ---- signal meters (kernels_meters.hip; handle, host arithmetic and C ABI in meters.hip) -----------------
 constexpr int kMetersSegment = FMRX_METERS_SEGMENT, kMetersProbes = FMRX_METERS_PROBES;
 constexpr int kMetersRfFields = 5;    // per channel: sum_i, sum_q, m2, m4, clipped (64-bit integers)
@@ -396,7 +407,7 @@ int meters_rf_launch(const uint8_t *d_iq, size_t pitch, size_t n_bytes, int n_ch
 // d_table: re [5][1024] then im [5][1024]; at most max_blocks workgroups walk the channels
 int meters_mpx_launch(const float *d_x, size_t pitch, size_t n_if, int n_channels, const double *d_table, double *d_out, int max_blocks,
                       hipStream_t s);
-// what a meters handle's last call left on the device, for a stage behind it on the same stream (blend.hip): the MPX
+// what a meters handle's last call left on the device, for a stage behind it on the same stream (meter_stage.hpp's MpxStage): the MPX
 // results [n_channels][kMetersMpxFields], and that call's n_if (0: no discriminator rows were given; ran false: no call yet)
 struct MetersMpx {
     const double *d_mpx;

@@ -3,15 +3,15 @@
 // the audio behind the blend (or behind the bank).  Control step: highcut_control.hpp; kernels: kernels_highcut.hip;
 // definition: tests/_highcut_model.py.
 //
-// The handle is meter_stage.hpp's with the control structure, one filter state per audio row on the device, the scratch of the
-// parallel walk (the segments' start and end values, the miss counter), a copy of the input for calls that run in place and an
-// output for calls that take PCM only.
+// The handle is meter_stage.hpp's stage behind the signal meters with the control structure, one filter state per audio row on
+// the device, the scratch of the parallel walk (the segments' start and end values, the miss counter), a copy of the input for
+// calls that run in place and an output for calls that take PCM only.
 #include "highcut_control.hpp"
 #include "meter_stage.hpp"
 
 using namespace fmrx;
 
-struct fmrx_highcut : meter_stage::Stage<fmrx_highcut_status> {
+struct fmrx_highcut : meter_stage::MpxStage<fmrx_highcut_status> {
     int L = kHighcutSegment, W = kHighcutWarmup;
     bool force = false;
     highcut::Control control{};
@@ -23,7 +23,7 @@ struct fmrx_highcut : meter_stage::Stage<fmrx_highcut_status> {
 
 namespace {
 
-int launch(fmrx_highcut *h, const meter_stage::Call &c)
+int launch(fmrx_highcut *h, const meter_stage::Call<meter_stage::Mpx> &c)
 {
     const size_t total = h->rows() * h->n_audio;
     HighcutArgs a;
@@ -38,7 +38,7 @@ int launch(fmrx_highcut *h, const meter_stage::Call &c)
         FMRX_HIP(hipMemcpyAsync(h->d_copy.p, a.x, total * sizeof(float), hipMemcpyDeviceToDevice, c.s));
         a.x = h->d_copy.p;
     }
-    FMRX_TRY(highcut_control_launch(h->control, c.d_mpx, c.d_seg_each, c.seg_all, h->d_status.p, h->n_channels, c.s));
+    FMRX_TRY(highcut_control_launch(h->control, c.src.d_mpx, c.src.d_seg_each, c.src.seg_all, h->d_status.p, h->n_channels, c.s));
     a.pcm = c.d_pcm;
     a.status = h->d_status.p;
     a.ac = h->audio_channels;
@@ -119,14 +119,14 @@ int fmrx_highcut_reset(fmrx_highcut *h, int channel)
 int fmrx_highcut_set_force(fmrx_highcut *h, int on)
 {
     if (!h) return fail(FMRX_EINVAL, "highcut_set_force: null handle");
-    FMRX_TRY(meter_stage::wait(h));
+    FMRX_TRY(h->wait());
     h->force = on != 0;
     return FMRX_OK;
 }
 
 int fmrx_highcut_process_dev(fmrx_highcut *h, const fmrx_meters *m, const float *d_in, float *d_out, int16_t *d_pcm16, int pcm_policy, void *stream)
 {
-    return meter_stage::process_dev("highcut_process_dev", "the high-cut", h, launch, m, d_in, d_out, d_pcm16, pcm_policy, stream);
+    return meter_stage::process_dev("highcut_process_dev", h, launch, m, d_in, d_out, d_pcm16, pcm_policy, stream);
 }
 
 int fmrx_highcut_process(fmrx_highcut *h, const fmrx_meter *recs, const float *in, float *out, int16_t *pcm16, int pcm_policy)
@@ -139,7 +139,7 @@ int fmrx_highcut_status_get(fmrx_highcut *h, fmrx_highcut_status *out) { return 
 int fmrx_highcut_diagnostics(fmrx_highcut *h, unsigned long long *segments, unsigned long long *missed)
 {
     if (!h) return fail(FMRX_EINVAL, "highcut_diagnostics: null handle");
-    FMRX_TRY(meter_stage::wait(h));
+    FMRX_TRY(h->wait());
     if (segments) *segments = h->segments;
     if (missed) FMRX_HIP(hipMemcpy(missed, h->d_missed.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return FMRX_OK;

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void blend_apply_kernel(const float *in, 
 int blend_control_launch(const blend::Control &c, const double *d_mpx, const unsigned long long *d_seg_each, unsigned long long seg_all,
                          fmrx_blend_status *d_status, int n_channels, hipStream_t s)
 {
-    return meter_stage::control_launch("blend_control_kernel", blend_control_kernel, c, d_mpx, d_seg_each, seg_all, d_status, n_channels, s);
+    return meter_stage::control_launch("blend_control_kernel", blend_control_kernel, n_channels, s, c, d_mpx, d_seg_each, seg_all, d_status);
 }
 
 int blend_apply_launch(const float *d_in, float *d_out, int16_t *d_pcm, const fmrx_blend_status *d_status, int n_channels, int audio_channels,

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kLanes) void highcut_serial_kernel(const float *__r
 int highcut_control_launch(const highcut::Control &c, const double *d_mpx, const unsigned long long *d_seg_each, unsigned long long seg_all,
                            fmrx_highcut_status *d_status, int n_channels, hipStream_t s)
 {
-    return meter_stage::control_launch("highcut_control_kernel", highcut_control_kernel, c, d_mpx, d_seg_each, seg_all, d_status, n_channels, s);
+    return meter_stage::control_launch("highcut_control_kernel", highcut_control_kernel, n_channels, s, c, d_mpx, d_seg_each, seg_all, d_status);
 }
 
 long highcut_segments(size_t n, int L) { return walk::segments(n, L); }

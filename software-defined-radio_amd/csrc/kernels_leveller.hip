@@ -1,8 +1,8 @@
 // kernels_leveller.hip -- the two kernels of the loudness leveller / peak limiter stage (include/fmrx.h: fmrx_leveller_*;
 // DESIGN.md section 4.15; defined by tests/_leveller_model.py).
 //
-// leveller_control_kernel: one lane per channel runs control_step of leveller_control.hpp on the channel's K-weighted sums,
-// where the audio meters' pass left them, and its status row.
+// leveller_control_kernel: meter_stage.hpp's control kernel with control_step of leveller_control.hpp on the channel's K-weighted
+// sums, where the audio meters' pass left them.
 //
 // leveller_apply_kernel: the pass over the audio, 4 bytes in and 4 + 2 bytes out per sample.  The channel rides in the grid's x
 // (banks have more than 65 535 receivers), a tile of T = 2048 - 2W samples of its rows in y.  A workgroup holds kSpan = 2048
@@ -42,11 +42,9 @@ __global__ __launch_bounds__(meter_stage::kControlThreads) void leveller_control
                                                                                         unsigned long long n_all,
                                                                                         fmrx_leveller_status *__restrict__ st, unsigned n_channels)
 {
-    const unsigned i = blockIdx.x * meter_stage::kControlThreads + threadIdx.x;
-    if (i >= n_channels) return;
-    fmrx_leveller_status s = st[i];
-    leveller::control_step(c, ac, n_each ? n_each[i] : n_all, k2a[i], ac == 2 ? k2b[i] : 0.0, s);
-    st[i] = s;
+    meter_stage::control_body(st, n_channels, [&](unsigned i, fmrx_leveller_status &s) {
+        leveller::control_step(c, ac, n_each ? n_each[i] : n_all, k2a[i], ac == 2 ? k2b[i] : 0.0, s);
+    });
 }
 
 __device__ __forceinline__ u4 min4(u4 a, u4 b) { return u4{min(a[0], b[0]), min(a[1], b[1]), min(a[2], b[2]), min(a[3], b[3])}; }
@@ -258,11 +256,8 @@ int leveller_control_launch(const leveller::Control &c, int audio_channels, cons
                             const unsigned long long *d_n_each, unsigned long long n_all, fmrx_leveller_status *d_status, int n_channels,
                             hipStream_t s)
 {
-    const unsigned grid = (static_cast<unsigned>(n_channels) + meter_stage::kControlThreads - 1) / meter_stage::kControlThreads;
-    leveller_control_kernel<<<grid, meter_stage::kControlThreads, 0, s>>>(c, audio_channels, d_k2a, d_k2b, d_n_each, n_all, d_status,
-                                                                          static_cast<unsigned>(n_channels));
-    FMRX_LAUNCH_CHECK("leveller_control_kernel");
-    return FMRX_OK;
+    return meter_stage::control_launch("leveller_control_kernel", leveller_control_kernel, n_channels, s, c, audio_channels, d_k2a, d_k2b, d_n_each, n_all,
+                                       d_status);
 }
 
 int leveller_apply_launch(const LevellerArgs &a, hipStream_t s)

@@ -3,9 +3,9 @@
 // below full scale, applied to the audio behind the audio meters.  Control step and gain code: leveller_control.hpp; kernels:
 // kernels_leveller.hip; definition: tests/_leveller_model.py.
 //
-// The handle is meter_stage.hpp's common part (status rows, the `done` event, create / destroy / reset / status_get) with the
-// control structure and the limiter's state in two buffers, one read and one written by a call, swapped behind it.  The stage
-// reads an audio meters handle, not the signal meters, so its two process calls are its own.
+// The handle is meter_stage.hpp's stage with the control structure and the limiter's state in two buffers, one read and one
+// written by a call, swapped behind it.  Its source of control data is the audio meters: the K-weighted sums and sample counts
+// that an audio meters handle left on the device (from_handle), or those of the host's records (from_records).
 #include "leveller_control.hpp"
 #include "meter_stage.hpp"
 
@@ -14,6 +14,11 @@
 using namespace fmrx;
 
 struct fmrx_leveller : meter_stage::Stage<fmrx_leveller_status> {
+    struct Source {   // sum_k2[0] and sum_k2[1] of every channel, and their n (or n_all for all of them where d_n_each is NULL)
+        const double *d_k2a, *d_k2b;
+        const unsigned long long *d_n_each;
+        unsigned long long n_all;
+    };
     leveller::Control control{};
     int W = 64;
     double audio_Fs = 0.0;
@@ -21,37 +26,62 @@ struct fmrx_leveller : meter_stage::Stage<fmrx_leveller_status> {
     int cur = 0;                              // the buffer the next call reads
     DevBuf<double> d_k2;                      // the host call only: sum_k2[0] of every channel, then sum_k2[1]
     DevBuf<unsigned long long> d_n;
+
+    // what the audio meters' last call left on the device, if it fits the stage
+    static int from_handle(const char *who, const fmrx_leveller *h, const fmrx_audio_meters *am, Source *src)
+    {
+        const AudioMetersSums v = audio_meters_sums(am);
+        if (!v.ran) return fail(FMRX_EINVAL, "%s: the audio meters have made no call", who);
+        if (v.n_channels != h->n_channels || v.ac != h->audio_channels || v.device != h->device)
+            return fail(FMRX_EINVAL, "%s: the audio meters have %d channels of %d rows on device %d, the leveller %d of %d on %d", who, v.n_channels, v.ac,
+                        v.device, h->n_channels, h->audio_channels, h->device);
+        if (v.n != h->n_audio) return fail(FMRX_EINVAL, "%s: the audio meters' last call walked %zu samples per row, the leveller's rows have %zu", who, v.n, h->n_audio);
+        const size_t N = h->n_channels;
+        *src = Source{v.d_sums + 6 * N, v.d_sums + 7 * N, nullptr, v.n};   // sum_k2[0], sum_k2[1] of the field-major sums
+        return FMRX_OK;
+    }
+
+    static int from_records(fmrx_leveller *h, const fmrx_audio_meter *recs, Source *src)
+    {
+        const size_t N = h->n_channels;
+        std::vector<double> k2(2 * N);
+        std::vector<unsigned long long> n(N);
+        for (size_t c = 0; c < N; c++) {
+            k2[c] = recs[c].sum_k2[0];
+            k2[N + c] = recs[c].sum_k2[1];
+            n[c] = recs[c].n;
+        }
+        FMRX_TRY(h->d_k2.ensure(2 * N));
+        FMRX_TRY(h->d_n.ensure(N));
+        FMRX_HIP(hipMemcpy(h->d_k2.p, k2.data(), k2.size() * sizeof(double), hipMemcpyHostToDevice));
+        FMRX_HIP(hipMemcpy(h->d_n.p, n.data(), N * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        *src = Source{h->d_k2.p, h->d_k2.p + N, h->d_n.p, 0};
+        return FMRX_OK;
+    }
 };
 
 namespace {
 
-struct Sums {
-    const double *d_k2a, *d_k2b;
-    const unsigned long long *d_n_each;
-    unsigned long long n_all;
-};
-
-int launch(fmrx_leveller *h, const Sums &m, const float *d_in, float *d_out, int16_t *d_pcm, int wrap, hipStream_t s)
+int launch(fmrx_leveller *h, const meter_stage::Call<fmrx_leveller::Source> &c)
 {
-    FMRX_TRY(leveller_control_launch(h->control, h->audio_channels, m.d_k2a, m.d_k2b, m.d_n_each, m.n_all, h->d_status.p, h->n_channels, s));
+    FMRX_TRY(leveller_control_launch(h->control, h->audio_channels, c.src.d_k2a, c.src.d_k2b, c.src.d_n_each, c.src.n_all, h->d_status.p, h->n_channels,
+                                     c.s));
     LevellerArgs a;
-    a.x = d_in;
-    a.y = d_out;
-    a.pcm = d_pcm;
+    a.x = c.d_in;
+    a.y = c.d_out;
+    a.pcm = c.d_pcm;
     a.status = h->d_status.p;
     a.state_in = h->d_state[h->cur].p;
     a.state_out = h->d_state[h->cur ^ 1].p;
     a.n_channels = h->n_channels;
     a.ac = h->audio_channels;
     a.W = h->W;
-    a.wrap = wrap;
+    a.wrap = c.wrap;
     a.n = h->n_audio;
     a.inv_n = h->inv_n;
     a.ceiling = h->control.ceiling;
-    FMRX_TRY(leveller_apply_launch(a, s));
+    FMRX_TRY(leveller_apply_launch(a, c.s));
     h->cur ^= 1;
-    FMRX_HIP(hipEventRecord(h->done, s));
-    h->ran = true;
     return FMRX_OK;
 }
 
@@ -62,9 +92,10 @@ bool overlap(const void *a, size_t na, const void *b, size_t nb)
     return a && b && x < y + nb && y < x + na;
 }
 
-int check(const char *who, const fmrx_leveller *h, const float *in, const float *out, const int16_t *pcm, int pcm_policy)
+// the leveller's own refusal, in front of the shared call
+int apart(const char *who, const fmrx_leveller *h, const float *in, const float *out, const int16_t *pcm)
 {
-    FMRX_TRY(meter_stage::check_rows(who, in, out, pcm, pcm_policy));
+    if (!h) return fail(FMRX_EINVAL, "%s: null handle", who);
     const size_t bytes = h->rows() * h->n_audio * sizeof(float);
     if (overlap(in, bytes, out, bytes) || overlap(in, bytes, pcm, bytes / 2))
         return fail(FMRX_EINVAL, "%s: the output overlaps the input (a workgroup reads %d samples in front of the ones it writes)", who, 2 * h->W);
@@ -151,7 +182,7 @@ int fmrx_leveller_derive(const fmrx_leveller_status *st, fmrx_leveller_levels *o
 {
     if (!st || !out) return fail(FMRX_EINVAL, "leveller_derive: null argument");
     const auto clamp = [](double v) { return v < -99.0 ? -99.0 : (v > 99.0 ? 99.0 : v); };
-    out->loudness_lkfs = st->loud_ms > 0.0 ? clamp(-leveller::kLkfsOffset + 10.0 * std::log10(st->loud_ms)) : -99.0;
+    out->loudness_lkfs = db(st->loud_ms, 1.0, -leveller::kLkfsOffset);
     out->gain_db = st->gain > 0.0 ? clamp(20.0 * std::log10(st->gain)) : -99.0;
     out->reduction_db = st->min_code > 0 ? clamp(20.0 * std::log10(static_cast<double>(st->min_code) / 16777216.0)) : -99.0;
     return FMRX_OK;
@@ -212,60 +243,14 @@ size_t fmrx_leveller_latency(const fmrx_leveller *h) { return h ? static_cast<si
 int fmrx_leveller_process_dev(fmrx_leveller *h, const fmrx_audio_meters *am, const float *d_in, float *d_out, int16_t *d_pcm16, int pcm_policy,
                               void *stream)
 {
-    const char *who = "leveller_process_dev";
-    if (!h || !am) return fail(FMRX_EINVAL, "%s: null handle", who);
-    FMRX_TRY(check(who, h, d_in, d_out, d_pcm16, pcm_policy));
-    const AudioMetersSums v = audio_meters_sums(am);
-    if (!v.ran) return fail(FMRX_EINVAL, "%s: the audio meters have made no call", who);
-    if (v.n_channels != h->n_channels || v.ac != h->audio_channels || v.device != h->device)
-        return fail(FMRX_EINVAL, "%s: the audio meters have %d channels of %d rows on device %d, the leveller %d of %d on %d", who, v.n_channels, v.ac,
-                    v.device, h->n_channels, h->audio_channels, h->device);
-    if (v.n != h->n_audio) return fail(FMRX_EINVAL, "%s: the audio meters' last call walked %zu samples per row, the leveller's rows have %zu", who, v.n, h->n_audio);
-    FMRX_HIP(hipSetDevice(h->device));
-    const size_t N = h->n_channels;
-    const Sums m{v.d_sums + 6 * N, v.d_sums + 7 * N, nullptr, v.n};   // sum_k2[0], sum_k2[1] of the field-major sums
-    return launch(h, m, d_in, d_out, d_pcm16, pcm_policy == FMRX_PCM_WRAP ? 1 : 0, static_cast<hipStream_t>(stream));
+    FMRX_TRY(apart("leveller_process_dev", h, d_in, d_out, d_pcm16));
+    return meter_stage::process_dev("leveller_process_dev", h, launch, am, d_in, d_out, d_pcm16, pcm_policy, stream);
 }
 
 int fmrx_leveller_process(fmrx_leveller *h, const fmrx_audio_meter *recs, const float *in, float *out, int16_t *pcm16, int pcm_policy)
 {
-    const char *who = "leveller_process";
-    if (!h || !recs) return fail(FMRX_EINVAL, "%s: null argument", who);
-    FMRX_TRY(check(who, h, in, out, pcm16, pcm_policy));
-    FMRX_TRY(meter_stage::wait(h));   // this call runs on the null stream
-    const size_t N = h->n_channels, total = h->rows() * h->n_audio;
-    std::vector<double> k2(2 * N);
-    std::vector<unsigned long long> n(N);
-    for (size_t c = 0; c < N; c++) {
-        k2[c] = recs[c].sum_k2[0];
-        k2[N + c] = recs[c].sum_k2[1];
-        n[c] = recs[c].n;
-    }
-    FMRX_TRY(h->d_k2.ensure(2 * N));
-    FMRX_TRY(h->d_n.ensure(N));
-    FMRX_HIP(hipMemcpy(h->d_k2.p, k2.data(), k2.size() * sizeof(double), hipMemcpyHostToDevice));
-    FMRX_HIP(hipMemcpy(h->d_n.p, n.data(), N * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    // the device copies: at their host pointers' addresses modulo 16 (hipMalloc's are 256-byte aligned)
-    const auto at = [](auto *base, const void *host) { return reinterpret_cast<decltype(base)>(reinterpret_cast<char *>(base) + (reinterpret_cast<uintptr_t>(host) & 15)); };
-    const size_t slack = meter_stage::kSlack;
-    FMRX_TRY(h->d_in.ensure(total + slack / sizeof(float)));
-    float *d_in = at(h->d_in.p, in), *d_out = nullptr;
-    int16_t *d_pcm = nullptr;
-    FMRX_HIP(hipMemcpy(d_in, in, total * sizeof(float), hipMemcpyHostToDevice));
-    if (out) {
-        FMRX_TRY(h->d_out.ensure(total + slack / sizeof(float)));
-        d_out = at(h->d_out.p, out);
-    }
-    if (pcm16) {
-        FMRX_TRY(h->d_pcm.ensure(total + slack / sizeof(int16_t)));
-        d_pcm = at(h->d_pcm.p, pcm16);
-    }
-    const Sums m{h->d_k2.p, h->d_k2.p + N, h->d_n.p, 0};
-    FMRX_TRY(launch(h, m, d_in, d_out, d_pcm, pcm_policy == FMRX_PCM_WRAP ? 1 : 0, nullptr));
-    FMRX_HIP(hipEventSynchronize(h->done));
-    if (out) FMRX_HIP(hipMemcpy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost));
-    if (pcm16) FMRX_HIP(hipMemcpy(pcm16, d_pcm, total * sizeof(int16_t), hipMemcpyDeviceToHost));
-    return FMRX_OK;
+    FMRX_TRY(apart("leveller_process", h, in, out, pcm16));
+    return meter_stage::process("leveller_process", h, launch, recs, in, out, pcm16, pcm_policy);
 }
 
 int fmrx_leveller_status_get(fmrx_leveller *h, fmrx_leveller_status *out) { return meter_stage::status_get("leveller_status_get", h, out); }

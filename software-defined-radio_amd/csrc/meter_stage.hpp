@@ -1,7 +1,10 @@
-// meter_stage.hpp -- what the stages that sit behind the meters on a bank's audio share (blend.hip, highcut.hip and their
-// kernel files): the handle's common part, the argument checks, the ordering of a handle's calls, the validation of a meters
-// handle, the host call, status and reset, and the control kernel's body.  A stage adds its control structure, its kernels'
-// own buffers and its launch(handle, Call).
+// meter_stage.hpp -- what the handles of a bank's meter chain share.  Handle: the device, the event the last call recorded and
+// the wait on it, with make / destroy, for the meters (meters.hip, audio_meters.hip) and the stages alike.  Stage: what the stages
+// that sit behind a meters handle on a bank's audio share (blend.hip, highcut.hip, leveller.hip and their kernel files): the
+// argument checks, the device call, the host call, status and reset, and the control kernel's body.  A stage adds its control
+// structure, its kernels' own buffers, its launch(handle, Call) and its source of control data: the type Source that a call
+// hands to launch, from_handle (what the meters handle in front left on the device, if it fits the stage) and from_records (the
+// host's records, uploaded).  Mpx is that source for the stages behind the signal meters.
 //
 // Ordering: a call records the handle's `done` event on its stream; whatever touches the handle's rows from the host
 // (reset, status_get, the host call, a change of settings) waits for it first.
@@ -11,33 +14,72 @@
 namespace fmrx {
 namespace meter_stage {
 
-// one status row per channel on the device -- state and result at once --, the event the last call recorded, and, for the
-// host call only, device copies of the host's records and rows
-template <class Status>
-struct Stage {
-    int device = 0, n_channels = 0, audio_channels = 0;
-    size_t n_audio = 0;
-    float inv_n = 0.0f;
-    DevBuf<Status> d_status;
+struct Handle {
+    int device = 0;
     hipEvent_t done = nullptr;
     bool ran = false;
-    DevBuf<double> d_mpx;                     // the host call only
-    DevBuf<unsigned long long> d_segcount;
-    DevBuf<float> d_in, d_out;
-    DevBuf<int16_t> d_pcm;
-    size_t rows() const { return static_cast<size_t>(n_channels) * audio_channels; }
-    ~Stage()
+    // behind the handle's last call, whatever stream that was on
+    int wait()
+    {
+        FMRX_HIP(hipSetDevice(device));
+        if (ran) FMRX_HIP(hipEventSynchronize(done));
+        return FMRX_OK;
+    }
+    ~Handle()
     {
         if (done) (void)hipEventDestroy(done);
     }
 };
 
-// what a stage's launch gets: the meters' MPX results [n_channels][kMetersMpxFields], the segments of every channel (or
-// seg_all for all of them where d_seg_each is NULL), the rows, the stream
+// a new handle of type H (a Handle) on `device`: body(h) fills it, the event is made; nothing is left behind where either fails
+template <class H, class Body>
+int make(H **out, int device, Body body)
+{
+    FMRX_TRY(require_device());
+    FMRX_HIP(hipSetDevice(device));
+    H *h = new H;
+    h->device = device;
+    const auto all = [&]() -> int {
+        FMRX_TRY(body(h));
+        FMRX_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+        return FMRX_OK;
+    };
+    const int rc = all();
+    if (rc != FMRX_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return FMRX_OK;
+}
+
+template <class H>
+int destroy(H *h)
+{
+    if (!h) return FMRX_OK;
+    (void)hipSetDevice(h->device);
+    if (h->ran) (void)hipEventSynchronize(h->done);
+    delete h;
+    return FMRX_OK;
+}
+
+// one status row per channel on the device -- state and result at once --, and, for the host call only, device copies of the
+// host's rows
+template <class Status>
+struct Stage : Handle {
+    int n_channels = 0, audio_channels = 0;
+    size_t n_audio = 0;
+    float inv_n = 0.0f;
+    DevBuf<Status> d_status;
+    DevBuf<float> d_in, d_out;                // the host call only
+    DevBuf<int16_t> d_pcm;
+    size_t rows() const { return static_cast<size_t>(n_channels) * audio_channels; }
+};
+
+// what a stage's launch gets: its source of control data, the rows, the stream
+template <class Source>
 struct Call {
-    const double *d_mpx;
-    const unsigned long long *d_seg_each;
-    unsigned long long seg_all;
+    Source src;
     const float *d_in;
     float *d_out;
     int16_t *d_pcm;
@@ -57,15 +99,6 @@ inline int check_rows(const char *who, const float *in, const float *out, const 
     return FMRX_OK;
 }
 
-// behind the handle's last call, whatever stream that was on
-template <class Status>
-int wait(Stage<Status> *h)
-{
-    FMRX_HIP(hipSetDevice(h->device));
-    if (h->ran) FMRX_HIP(hipEventSynchronize(h->done));
-    return FMRX_OK;
-}
-
 // a new handle of type H (a Stage): the common checks, the status rows zeroed, then init(h) for the stage's own part
 template <class H, class Init>
 int create(const char *who, H **out, int n_channels, int audio_channels, size_t n_audio, int device, Init init)
@@ -73,39 +106,17 @@ int create(const char *who, H **out, int n_channels, int audio_channels, size_t 
     if (n_channels < 1) return fail(FMRX_EINVAL, "%s: n_channels must be >= 1", who);
     if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "%s: audio_channels %d: 1 or 2", who, audio_channels);
     if (n_audio < 1 || n_audio > (size_t{1} << 26)) return fail(FMRX_EINVAL, "%s: n_audio %zu: 1 .. 2^26", who, n_audio);
-    FMRX_TRY(require_device());
-    FMRX_HIP(hipSetDevice(device));
-    H *h = new H;
-    h->device = device;
-    h->n_channels = n_channels;
-    h->audio_channels = audio_channels;
-    h->n_audio = n_audio;
-    h->inv_n = static_cast<float>(1.0 / static_cast<double>(n_audio));
-    auto body = [&]() -> int {
+    return make(out, device, [&](H *h) -> int {
+        h->n_channels = n_channels;
+        h->audio_channels = audio_channels;
+        h->n_audio = n_audio;
+        h->inv_n = static_cast<float>(1.0 / static_cast<double>(n_audio));
         FMRX_TRY(h->d_status.alloc(n_channels));
         FMRX_HIP(hipMemset(h->d_status.p, 0, h->d_status.bytes()));
         FMRX_TRY(init(h));
         FMRX_HIP(hipStreamSynchronize(nullptr));
-        FMRX_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
         return FMRX_OK;
-    };
-    const int rc = body();
-    if (rc != FMRX_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return FMRX_OK;
-}
-
-template <class H>
-int destroy(H *h)
-{
-    if (!h) return FMRX_OK;
-    (void)hipSetDevice(h->device);
-    if (h->ran) (void)hipEventSynchronize(h->done);
-    delete h;
-    return FMRX_OK;
+    });
 }
 
 // channel < 0: all of them.  extra(): what else the stage clears
@@ -114,7 +125,7 @@ int reset(const char *who, Stage<Status> *h, int channel, Extra extra)
 {
     if (!h) return fail(FMRX_EINVAL, "%s: null handle", who);
     if (channel >= h->n_channels) return fail(FMRX_EINVAL, "%s: channel %d of %d", who, channel, h->n_channels);
-    FMRX_TRY(wait(h));
+    FMRX_TRY(h->wait());
     if (channel < 0) FMRX_HIP(hipMemset(h->d_status.p, 0, h->d_status.bytes()));
     else FMRX_HIP(hipMemset(h->d_status.p + channel, 0, sizeof(Status)));
     FMRX_TRY(extra());
@@ -126,13 +137,16 @@ template <class Status>
 int status_get(const char *who, Stage<Status> *h, Status *out)
 {
     if (!h || !out) return fail(FMRX_EINVAL, "%s: null argument", who);
-    FMRX_TRY(wait(h));
+    FMRX_TRY(h->wait());
     FMRX_HIP(hipMemcpy(out, h->d_status.p, static_cast<size_t>(h->n_channels) * sizeof(Status), hipMemcpyDeviceToHost));
     return FMRX_OK;
 }
 
 template <class H>
-int run(H *h, int (*launch)(H *, const Call &), const Call &c)
+using Launch = int (*)(H *, const Call<typename H::Source> &);
+
+template <class H>
+int run(H *h, Launch<H> launch, const Call<typename H::Source> &c)
 {
     FMRX_TRY(launch(h, c));
     FMRX_HIP(hipEventRecord(h->done, c.s));
@@ -140,57 +154,31 @@ int run(H *h, int (*launch)(H *, const Call &), const Call &c)
     return FMRX_OK;
 }
 
-// what the meters' last call left on the device, if it fits the stage (noun: "the blend")
-template <class Status>
-int meters_for(const char *who, const char *noun, const Stage<Status> *h, const fmrx_meters *m, MetersMpx *v)
-{
-    *v = meters_mpx(m);
-    if (!v->ran || v->n_if == 0) return fail(FMRX_EINVAL, "%s: the meters' last call measured no discriminator rows", who);
-    if (v->n_channels != h->n_channels || v->device != h->device)
-        return fail(FMRX_EINVAL, "%s: the meters have %d channels on device %d, %s %d on %d", who, v->n_channels, v->device, noun, h->n_channels,
-                    h->device);
-    return FMRX_OK;
-}
-
-// the device call: behind the meters' call on `stream`
-template <class H>
-int process_dev(const char *who, const char *noun, H *h, int (*launch)(H *, const Call &), const fmrx_meters *m, const float *d_in, float *d_out,
-                int16_t *d_pcm16, int pcm_policy, void *stream)
+// the device call: behind the call of the meters handle m on `stream`
+template <class H, class Meters>
+int process_dev(const char *who, H *h, Launch<H> launch, const Meters *m, const float *d_in, float *d_out, int16_t *d_pcm16, int pcm_policy,
+                void *stream)
 {
     if (!h || !m) return fail(FMRX_EINVAL, "%s: null handle", who);
     FMRX_TRY(check_rows(who, d_in, d_out, d_pcm16, pcm_policy));
-    MetersMpx v;
-    FMRX_TRY(meters_for(who, noun, h, m, &v));
+    typename H::Source src;
+    FMRX_TRY(H::from_handle(who, h, m, &src));
     FMRX_HIP(hipSetDevice(h->device));
-    return run(h, launch, Call{v.d_mpx, nullptr, v.n_if / kMetersSegment, d_in, d_out, d_pcm16, pcm_policy == FMRX_PCM_WRAP ? 1 : 0,
-                               static_cast<hipStream_t>(stream)});
+    return run(h, launch, {src, d_in, d_out, d_pcm16, pcm_policy == FMRX_PCM_WRAP ? 1 : 0, static_cast<hipStream_t>(stream)});
 }
 
 // the host call: records and rows go to the device, the stage runs on the null stream, the results come back
-template <class H>
-int process(const char *who, H *h, int (*launch)(H *, const Call &), const fmrx_meter *recs, const float *in, float *out, int16_t *pcm16,
-            int pcm_policy)
+template <class H, class Record>
+int process(const char *who, H *h, Launch<H> launch, const Record *recs, const float *in, float *out, int16_t *pcm16, int pcm_policy)
 {
     if (!h || !recs) return fail(FMRX_EINVAL, "%s: null argument", who);
     FMRX_TRY(check_rows(who, in, out, pcm16, pcm_policy));
-    FMRX_TRY(wait(h));   // this call runs on the null stream
-    const size_t N = h->n_channels, total = h->rows() * h->n_audio;
-    std::vector<double> mpx(N * kMetersMpxFields, 0.0);
-    std::vector<unsigned long long> seg(N);
-    for (size_t c = 0; c < N; c++) {
-        double *o = mpx.data() + c * kMetersMpxFields;
-        o[0] = recs[c].sum_x;
-        o[1] = recs[c].sum_x2;
-        o[2] = recs[c].max_abs;
-        for (int p = 0; p < kMetersProbes; p++) o[3 + p] = recs[c].probe[p];
-        seg[c] = recs[c].segments;
-    }
-    FMRX_TRY(h->d_mpx.ensure(mpx.size()));
-    FMRX_TRY(h->d_segcount.ensure(N));
-    FMRX_HIP(hipMemcpy(h->d_mpx.p, mpx.data(), mpx.size() * sizeof(double), hipMemcpyHostToDevice));
-    FMRX_HIP(hipMemcpy(h->d_segcount.p, seg.data(), N * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    FMRX_TRY(h->wait());   // this call runs on the null stream
+    typename H::Source src;
+    FMRX_TRY(H::from_records(h, recs, &src));
     // the device copies: at their host pointers' addresses modulo 16 (hipMalloc's are 256-byte aligned)
     const auto at = [](auto *base, const void *host) { return reinterpret_cast<decltype(base)>(reinterpret_cast<char *>(base) + (reinterpret_cast<uintptr_t>(host) & 15)); };
+    const size_t total = h->rows() * h->n_audio;
     FMRX_TRY(h->d_in.ensure(total + kSlack / sizeof(float)));
     float *d_in = at(h->d_in.p, in), *d_out = nullptr;
     int16_t *d_pcm = nullptr;
@@ -204,36 +192,92 @@ int process(const char *who, H *h, int (*launch)(H *, const Call &), const fmrx_
         FMRX_TRY(h->d_pcm.ensure(total + kSlack / sizeof(int16_t)));
         d_pcm = at(h->d_pcm.p, pcm16);
     }
-    FMRX_TRY(run(h, launch, Call{h->d_mpx.p, h->d_segcount.p, 0, d_in, d_out, d_pcm, pcm_policy == FMRX_PCM_WRAP ? 1 : 0, nullptr}));
+    FMRX_TRY(run(h, launch, {src, d_in, d_out, d_pcm, pcm_policy == FMRX_PCM_WRAP ? 1 : 0, nullptr}));
     FMRX_HIP(hipEventSynchronize(h->done));
     if (out) FMRX_HIP(hipMemcpy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost));
     if (pcm16) FMRX_HIP(hipMemcpy(pcm16, d_pcm, total * sizeof(int16_t), hipMemcpyDeviceToHost));
     return FMRX_OK;
 }
 
-// ---- the control kernel: one lane per channel runs the stage's control_step (found through the control structure's
-// namespace) on the channel's probe powers, where the meters' MPX pass left them, and its status row
+// ---- the signal meters as a stage's source: the MPX results [n_channels][kMetersMpxFields] and the segments of every channel
+// (or seg_all for all of them where d_seg_each is NULL)
+struct Mpx {
+    const double *d_mpx;
+    const unsigned long long *d_seg_each;
+    unsigned long long seg_all;
+};
+
+template <class Status>
+struct MpxStage : Stage<Status> {
+    using Source = Mpx;
+    DevBuf<double> d_mpx;                     // the host call only
+    DevBuf<unsigned long long> d_segcount;
+
+    // what the meters' last call left on the device, if it fits the stage
+    static int from_handle(const char *who, const MpxStage *h, const fmrx_meters *m, Mpx *src)
+    {
+        const MetersMpx v = meters_mpx(m);
+        if (!v.ran || v.n_if == 0) return fail(FMRX_EINVAL, "%s: the meters' last call measured no discriminator rows", who);
+        if (v.n_channels != h->n_channels || v.device != h->device)
+            return fail(FMRX_EINVAL, "%s: the meters have %d channels on device %d, the stage %d on %d", who, v.n_channels, v.device, h->n_channels,
+                        h->device);
+        *src = Mpx{v.d_mpx, nullptr, v.n_if / kMetersSegment};
+        return FMRX_OK;
+    }
+
+    static int from_records(MpxStage *h, const fmrx_meter *recs, Mpx *src)
+    {
+        const size_t N = h->n_channels;
+        std::vector<double> mpx(N * kMetersMpxFields, 0.0);
+        std::vector<unsigned long long> seg(N);
+        for (size_t c = 0; c < N; c++) {
+            double *o = mpx.data() + c * kMetersMpxFields;
+            o[0] = recs[c].sum_x;
+            o[1] = recs[c].sum_x2;
+            o[2] = recs[c].max_abs;
+            for (int p = 0; p < kMetersProbes; p++) o[3 + p] = recs[c].probe[p];
+            seg[c] = recs[c].segments;
+        }
+        FMRX_TRY(h->d_mpx.ensure(mpx.size()));
+        FMRX_TRY(h->d_segcount.ensure(N));
+        FMRX_HIP(hipMemcpy(h->d_mpx.p, mpx.data(), mpx.size() * sizeof(double), hipMemcpyHostToDevice));
+        FMRX_HIP(hipMemcpy(h->d_segcount.p, seg.data(), N * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        *src = Mpx{h->d_mpx.p, h->d_segcount.p, 0};
+        return FMRX_OK;
+    }
+};
+
+// ---- the control kernel: one lane per channel loads the channel's status row, runs step(channel, row) on it -- the stage's
+// control_step on what its source holds for the channel -- and stores it
 constexpr int kControlThreads = 256;
 
+template <class Status, class Step>
+__device__ __forceinline__ void control_body(Status *__restrict__ st, unsigned n_channels, Step step)
+{
+    const unsigned i = blockIdx.x * kControlThreads + threadIdx.x;
+    if (i >= n_channels) return;
+    Status s = st[i];
+    step(i, s);
+    st[i] = s;
+}
+
+// behind Mpx: control_step (found through the control structure's namespace) on the channel's probe powers, where the meters' MPX
+// pass left them
 template <class Control, class Status>
 __device__ __forceinline__ void control_body(const Control &c, const double *__restrict__ mpx, const unsigned long long *__restrict__ seg_each,
                                              unsigned long long seg_all, Status *__restrict__ st, unsigned n_channels)
 {
-    const unsigned i = blockIdx.x * kControlThreads + threadIdx.x;
-    if (i >= n_channels) return;
-    const double *probe = mpx + static_cast<size_t>(i) * kMetersMpxFields + 3;   // behind sum_x, sum_x2, max_abs
-    Status s = st[i];
-    control_step(c, probe, seg_each ? seg_each[i] : seg_all, s);
-    st[i] = s;
+    control_body(st, n_channels, [&](unsigned i, Status &s) {
+        control_step(c, mpx + static_cast<size_t>(i) * kMetersMpxFields + 3, seg_each ? seg_each[i] : seg_all, s);   // behind sum_x, sum_x2, max_abs
+    });
 }
 
-template <class Control, class Status>
-int control_launch(const char *name, void (*kernel)(Control, const double *, const unsigned long long *, unsigned long long, Status *, unsigned),
-                   const Control &c, const double *d_mpx, const unsigned long long *d_seg_each, unsigned long long seg_all, Status *d_status,
-                   int n_channels, hipStream_t s)
+// kernel(args..., n_channels) on a grid of one lane per channel
+template <class... Params, class... Args>
+int control_launch(const char *name, void (*kernel)(Params...), int n_channels, hipStream_t s, const Args &...args)
 {
     const unsigned grid = (static_cast<unsigned>(n_channels) + kControlThreads - 1) / kControlThreads;
-    kernel<<<grid, kControlThreads, 0, s>>>(c, d_mpx, d_seg_each, seg_all, d_status, static_cast<unsigned>(n_channels));
+    kernel<<<grid, kControlThreads, 0, s>>>(args..., static_cast<unsigned>(n_channels));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FMRX_EHIP, "launch %s: %s", name, hipGetErrorString(e));
     return FMRX_OK;

@@ -4,22 +4,20 @@
 //
 // The handle keeps no signal state: the tone table on the device, the two result arrays a call writes ([n_channels][5]
 // 64-bit integers, zeroed on the stream and added to by the RF pass; [n_channels][8] doubles written by the MPX pass), their
-// pinned host copies, and the event the last call recorded behind the copies.
-#include "fmrx_internal.hpp"
+// pinned host copies, and meter_stage.hpp's handle base: the event the last call recorded behind the copies.
+#include "meter_stage.hpp"
 
 #include <cmath>
 
 using namespace fmrx;
 
-struct fmrx_meters {
-    int device = 0, n_channels = 0, max_blocks = 1;
+struct fmrx_meters : meter_stage::Handle {
+    int n_channels = 0, max_blocks = 1;
     double if_Fs = 0.0;
     DevBuf<double> d_table, d_mpx;
     DevBuf<unsigned long long> d_rf;
     unsigned long long *h_rf = nullptr;   // pinned
     double *h_mpx = nullptr;              // pinned
-    hipEvent_t done = nullptr;
-    bool ran = false;
     size_t n_iq = 0, n_if = 0;            // of the last call; 0 = that group was not measured
     DevBuf<uint8_t> d_iq;                 // fmrx_meters_process only
     DevBuf<float> d_demod;
@@ -27,7 +25,6 @@ struct fmrx_meters {
     {
         if (h_rf) (void)hipHostFree(h_rf);
         if (h_mpx) (void)hipHostFree(h_mpx);
-        if (done) (void)hipEventDestroy(done);
     }
 };
 
@@ -47,15 +44,6 @@ void meters_table(double if_Fs, double *re, double *im)
             re[p * kMetersSegment + k] = w * std::cos(th);
             im[p * kMetersSegment + k] = -(w * std::sin(th));
         }
-}
-
-// 10 log10(num / den) clamped to [-99, 99]; -99 where num is not positive (0 / 0 included), 99 where only den is not
-double db(double num, double den)
-{
-    if (!(num > 0.0)) return -99.0;
-    if (!(den > 0.0)) return 99.0;
-    const double v = 10.0 * std::log10(num / den);
-    return v < -99.0 ? -99.0 : (v > 99.0 ? 99.0 : v);
 }
 
 double mean(double a, double n) { return n > 0.0 ? a / n : 0.0; }
@@ -110,14 +98,10 @@ int fmrx_meters_create(fmrx_meters **out, double if_Fs, int n_channels, int devi
     if (!(if_Fs >= kMinIfFs) || !std::isfinite(if_Fs))
         return fail(FMRX_EINVAL, "meters_create: if_Fs %g (at least %g: the top probe stays below Nyquist)", if_Fs, kMinIfFs);
     if (n_channels < 1) return fail(FMRX_EINVAL, "meters_create: n_channels must be >= 1");
-    FMRX_TRY(require_device());
-    FMRX_HIP(hipSetDevice(device));
-    fmrx_meters *m = new fmrx_meters;
-    m->device = device;
-    m->n_channels = n_channels;
-    m->if_Fs = if_Fs;
-    auto body = [&]() -> int {
+    return meter_stage::make(out, device, [&](fmrx_meters *m) -> int {
         const size_t N = n_channels;
+        m->n_channels = n_channels;
+        m->if_Fs = if_Fs;
         int cus = 0;
         FMRX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         m->max_blocks = kMpxBlocksPerCu * (cus > 0 ? cus : 1);
@@ -129,26 +113,11 @@ int fmrx_meters_create(fmrx_meters **out, double if_Fs, int n_channels, int devi
         FMRX_TRY(m->d_mpx.alloc(N * kMetersMpxFields));
         FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_rf), m->d_rf.bytes(), hipHostMallocDefault));
         FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_mpx), m->d_mpx.bytes(), hipHostMallocDefault));
-        FMRX_HIP(hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
         return FMRX_OK;
-    };
-    const int rc = body();
-    if (rc != FMRX_OK) {
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return FMRX_OK;
+    });
 }
 
-int fmrx_meters_destroy(fmrx_meters *m)
-{
-    if (!m) return FMRX_OK;
-    (void)hipSetDevice(m->device);
-    if (m->ran) (void)hipEventSynchronize(m->done);
-    delete m;
-    return FMRX_OK;
-}
+int fmrx_meters_destroy(fmrx_meters *m) { return meter_stage::destroy(m); }
 
 int fmrx_meters_process_dev(fmrx_meters *m, const uint8_t *d_iq_first, size_t iq_pitch_bytes, size_t n_iq_bytes, const float *d_demod_row0,
                             size_t demod_pitch, size_t n_if, void *stream)
@@ -189,8 +158,7 @@ int fmrx_meters_collect(fmrx_meters *m, fmrx_meter *out)
 {
     if (!m || !out) return fail(FMRX_EINVAL, "meters_collect: null argument");
     if (!m->ran) return fail(FMRX_EINVAL, "meters_collect: no call to collect");
-    FMRX_HIP(hipSetDevice(m->device));
-    FMRX_HIP(hipEventSynchronize(m->done));
+    FMRX_TRY(m->wait());
     for (size_t c = 0; c < static_cast<size_t>(m->n_channels); c++) {
         const unsigned long long *rf = m->h_rf + c * kMetersRfFields;
         const double *mpx = m->h_mpx + c * kMetersMpxFields;

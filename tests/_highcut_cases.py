@@ -4,6 +4,7 @@ import numpy as np
 
 import _highcut_model as hm
 import _meters_model as mm
+from _stage_cases import same_pcm, same_status
 
 IF_FS, AUDIO_FS = 240000.0, 48000.0
 CALLS = 6
@@ -50,17 +51,6 @@ def inputs(kind, rng, N, ac, n, calls=CALLS):
     return [np.ascontiguousarray(rows[pick, k * n:(k + 1) * n]).reshape(N, ac, n) for k in range(calls)]
 
 
-def same_status(got, want):
-    for k in hm.STATUS_DTYPE.names:
-        x, y = got[k], want[k]
-        if x.dtype.kind == "f":
-            u = np.uint64 if x.dtype.itemsize == 8 else np.uint32
-            ok = (x.view(u) == y.view(u)) | (np.isnan(x) & np.isnan(y))
-        else:
-            ok = x == y
-        assert ok.all(), (k, np.flatnonzero(~ok)[:5], x[~ok][:5], y[~ok][:5])
-
-
 class Model:
     """the model's side of a handle: status rows, filter state, the diagnostics' counts"""
 
@@ -81,11 +71,10 @@ class Model:
 
 
 def check_call(oracle, out, hc, model, want, wrap, f32, pcm):
-    same_status(hc.status(), model.status)
+    same_status(hc.status(), model.status, hm.STATUS_DTYPE.names)
     if f32:
         ok = hm.same(out["audio"], want)
         assert ok.all(), (np.argwhere(~ok)[:5], out["audio"][~ok][:5], want[~ok][:5])
     if pcm:
-        want_pcm = oracle.pcm16(hm.interleave(want).reshape(-1), wrap).reshape(out["pcm16"].shape)
-        assert np.array_equal(out["pcm16"], want_pcm)
+        same_pcm(oracle, out["pcm16"], want, wrap)
     assert hc.diagnostics() == {"segments": model.segments, "missed": model.missed}

@@ -9,59 +9,39 @@ import pytest
 
 import _audio_meters_model as am
 import _meters_capture as MC
-import _tuner_capture as TC
+from _bank_chain import N, bank_chain
 
 pytestmark = pytest.mark.gpu
 
-N = 8
-
 
 def run_chain(fmrx, oracle, fused_mono=False):
-    import torch
-    c = TC.RDS
-    R, bb = c["R"], MC.BYTES_PER_CALL
-    wide = MC.capture()
-    h = oracle.impulse_response_lpf(c["Fs_w"], c["cutoff"], c["T"])
-    n_wide = bb // 2 * R
-    tuner = fmrx.Tuner(R, h, N, n_wide)
-    for k, (f, g) in enumerate(MC.channels()):
-        tuner.set_channel(k, f, c["Fs_w"], g)
-    bank = fmrx.Channels(0, N, block_bytes=bb) if fused_mono else fmrx.Channels(0, N, audio_channels=2, exact=False, block_bytes=bb)
-    ac, n = bank.audio_channels, bank.n_audio
-    meters = blend = hc = None
-    if not fused_mono:
-        meters = fmrx.Meters.for_bank(bank)
-        blend = fmrx.Blend.for_bank(bank, meters)
-        hc = fmrx.HighCut.for_bank(bank, meters)
-    audio_meters = fmrx.AudioMeters.for_bank(bank)
-    loud = fmrx.Loudness.for_meters(audio_meters)
-    d_wide = torch.from_numpy(wide).cuda()
-    d_audio = torch.zeros((N, ac, n), dtype=torch.float32, device="cuda")
-    d_out = torch.full((N, ac, n), 7.0, dtype=torch.float32, device="cuda") if not fused_mono else d_audio
-    d_bank_pcm = torch.zeros((N, n, ac), dtype=torch.int16, device="cuda")
-    stream = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    first, pitch = bank.input_layout()
-    calls = []
-    for i in range(MC.CALLS):
-        s = stream.cuda_stream
-        tuner.process_dev(d_wide.data_ptr() + 2 * n_wide * i, n_wide, first, pitch, stream=s)
-        bank.process_dev(d_audio.data_ptr(), d_bank_pcm.data_ptr(), stream=s)
+    with bank_chain(fmrx, oracle, fused_mono) as ch:
+        torch, bank, ac, n, d_audio = ch.torch, ch.bank, ch.ac, ch.n, ch.d_audio
+        meters = blend = hc = None
         if not fused_mono:
-            meters.process_bank(stream=s)
-            blend.process_bank(d_audio.data_ptr(), d_audio.data_ptr(), None, stream=s)
-            hc.process_bank(d_audio.data_ptr(), d_out.data_ptr(), None, stream=s)
-        audio_meters.process_bank(d_out.data_ptr(), stream=s)
-        recs, bins = audio_meters.collect()
-        loud.push(recs, bins)
-        stream.synchronize()
-        calls.append(dict(recs=recs, bins=bins, state=audio_meters.state(), out=d_out.cpu().numpy(),
-                          levels=[audio_meters.derive(r) for r in recs]))
-    audio_Fs = float(bank.params.audio_Fs)
-    gated = [loud.read(k) for k in range(N)]
-    for x in (loud, audio_meters, hc, blend, meters, tuner, bank):
-        if x is not None:
-            x.close()
+            meters = fmrx.Meters.for_bank(bank)
+            blend = fmrx.Blend.for_bank(bank, meters)
+            hc = fmrx.HighCut.for_bank(bank, meters)
+        audio_meters = fmrx.AudioMeters.for_bank(bank)
+        loud = fmrx.Loudness.for_meters(audio_meters)
+        d_out = torch.full((N, ac, n), 7.0, dtype=torch.float32, device="cuda") if not fused_mono else d_audio
+        calls = []
+        for i in ch.calls():
+            if not fused_mono:
+                meters.process_bank(stream=ch.s)
+                blend.process_bank(d_audio.data_ptr(), d_audio.data_ptr(), None, stream=ch.s)
+                hc.process_bank(d_audio.data_ptr(), d_out.data_ptr(), None, stream=ch.s)
+            audio_meters.process_bank(d_out.data_ptr(), stream=ch.s)
+            recs, bins = audio_meters.collect()
+            loud.push(recs, bins)
+            ch.stream.synchronize()
+            calls.append(dict(recs=recs, bins=bins, state=audio_meters.state(), out=d_out.cpu().numpy(),
+                              levels=[audio_meters.derive(r) for r in recs]))
+        audio_Fs = float(bank.params.audio_Fs)
+        gated = [loud.read(k) for k in range(N)]
+        for x in (loud, audio_meters, hc, blend, meters):
+            if x is not None:
+                x.close()
     return dict(calls=calls, audio_Fs=audio_Fs, ac=ac, n=n, gated=gated)
 
 

@@ -8,6 +8,7 @@ import pytest
 
 import _blend_model as bm
 import _meters_model as mm
+from _stage_cases import offset_rows, same_pcm, same_status
 
 pytestmark = pytest.mark.gpu
 
@@ -51,26 +52,14 @@ def records(c, N, calls=CALLS):
     return out
 
 
-def same_status(got, want):
-    for k in bm.STATUS_DTYPE.names:
-        x, y = got[k], want[k]
-        if x.dtype.kind == "f":
-            u = np.uint64 if x.dtype.itemsize == 8 else np.uint32
-            ok = (x.view(u) == y.view(u)) | (np.isnan(x) & np.isnan(y))
-        else:
-            ok = x == y
-        assert ok.all(), (k, np.flatnonzero(~ok)[:5], x[~ok][:5], y[~ok][:5])
-
-
 def check_call(oracle, out, status, want_status, audio, wrap, f32, pcm):
-    same_status(status, want_status)
+    same_status(status, want_status, bm.STATUS_DTYPE.names)
     want = bm.apply(want_status, audio)
     if f32:
         ok = bm.same(out["audio"], want)
         assert ok.all(), (np.argwhere(~ok)[:5], out["audio"][~ok][:5], want[~ok][:5])
     if pcm:
-        want_pcm = oracle.pcm16(bm.interleave(want).reshape(-1), wrap).reshape(out["pcm16"].shape)
-        assert np.array_equal(out["pcm16"], want_pcm)
+        same_pcm(oracle, out["pcm16"], want, wrap)
     return want
 
 
@@ -136,16 +125,6 @@ def test_66000_channels(fmrx, oracle):
     out = blend.process(recs, audio)
     check_call(oracle, out, blend.status(), want_status, audio, True, True, True)
     blend.close()
-
-
-def offset_rows(x, byte_offset):
-    """a copy of x whose address is byte_offset modulo 16"""
-    pad = np.zeros(x.size + 8, np.float32)
-    o = ((byte_offset - pad.ctypes.data) % 16) // 4
-    v = pad[o:o + x.size].reshape(x.shape)
-    v[...] = x
-    assert v.ctypes.data % 16 == byte_offset
-    return v
 
 
 @pytest.mark.parametrize("n", [1024, 1920])

@@ -11,56 +11,33 @@ import pytest
 
 import _blend_model as bm
 import _meters_capture as MC
-import _tuner_capture as TC
+from _bank_chain import N, bank_chain
 
 pytestmark = pytest.mark.gpu
 
-N = 8
-
 
 def run_chain(fmrx, oracle, p, audio_channels=2, exact=False, fused_mono=False):
-    import torch
-    c = TC.RDS
-    R, bb = c["R"], MC.BYTES_PER_CALL
-    wide = MC.capture()
-    h = oracle.impulse_response_lpf(c["Fs_w"], c["cutoff"], c["T"])
-    n_wide = bb // 2 * R
-    tuner = fmrx.Tuner(R, h, N, n_wide)
-    for k, (f, g) in enumerate(MC.channels()):
-        tuner.set_channel(k, f, c["Fs_w"], g)
-    if fused_mono:
-        bank = fmrx.Channels(0, N, block_bytes=bb)
-    else:
-        bank = fmrx.Channels(0, N, audio_channels=audio_channels, exact=exact, block_bytes=bb)
-    ac, n = bank.audio_channels, bank.n_audio
-    meters = fmrx.Meters.for_bank(bank)
-    blend = fmrx.Blend.for_bank(bank, meters, fmrx.BlendParams(**p))
-    d_wide = torch.from_numpy(wide).cuda()
-    d_audio = torch.zeros((N, ac, n), dtype=torch.float32, device="cuda")
-    d_out = torch.full((N, ac, n), 7.0, dtype=torch.float32, device="cuda")
-    d_pcm = torch.full((N, n, ac), 7, dtype=torch.int16, device="cuda")
-    d_bank_pcm = torch.zeros((N, n, ac), dtype=torch.int16, device="cuda")
-    stream = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    first, pitch = bank.input_layout()
-    calls, refused = [], None
-    for i in range(MC.CALLS):
-        s = stream.cuda_stream
-        tuner.process_dev(d_wide.data_ptr() + 2 * n_wide * i, n_wide, first, pitch, stream=s)
-        bank.process_dev(d_audio.data_ptr(), d_bank_pcm.data_ptr(), stream=s)
-        meters.process_bank(stream=s)
-        try:
-            blend.process_bank(d_audio.data_ptr(), d_out.data_ptr(), d_pcm.data_ptr(), stream=s)
-        except fmrx.FmrxError as e:
-            refused = e.code
-            break
-        recs, status = meters.collect(), blend.status()
-        stream.synchronize()
-        calls.append(dict(recs=recs, status=status, audio=d_audio.cpu().numpy(), out=d_out.cpu().numpy(), pcm=d_pcm.cpu().numpy()))
-    stream.synchronize()
-    if_Fs = float(bank.params.if_Fs)
-    for x in (blend, meters, tuner, bank):
-        x.close()
+    with bank_chain(fmrx, oracle, fused_mono, audio_channels, exact) as ch:
+        torch, bank, ac, n, d_audio = ch.torch, ch.bank, ch.ac, ch.n, ch.d_audio
+        meters = fmrx.Meters.for_bank(bank)
+        blend = fmrx.Blend.for_bank(bank, meters, fmrx.BlendParams(**p))
+        d_out = torch.full((N, ac, n), 7.0, dtype=torch.float32, device="cuda")
+        d_pcm = torch.full((N, n, ac), 7, dtype=torch.int16, device="cuda")
+        calls, refused = [], None
+        for i in ch.calls():
+            meters.process_bank(stream=ch.s)
+            try:
+                blend.process_bank(d_audio.data_ptr(), d_out.data_ptr(), d_pcm.data_ptr(), stream=ch.s)
+            except fmrx.FmrxError as e:
+                refused = e.code
+                break
+            recs, status = meters.collect(), blend.status()
+            ch.stream.synchronize()
+            calls.append(dict(recs=recs, status=status, audio=d_audio.cpu().numpy(), out=d_out.cpu().numpy(), pcm=d_pcm.cpu().numpy()))
+        ch.stream.synchronize()
+        if_Fs = float(bank.params.if_Fs)
+        for x in (blend, meters):
+            x.close()
     return dict(calls=calls, refused=refused, if_Fs=if_Fs, ac=ac, n=n)
 
 

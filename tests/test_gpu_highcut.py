@@ -10,6 +10,7 @@ import pytest
 
 import _highcut_model as hm
 from _highcut_cases import AUDIO_FS, BUILTIN, CALLS, IF_FS, Model, check_call, inputs, make, records
+from _stage_cases import offset_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -119,16 +120,6 @@ def test_66000_channels(fmrx, oracle):
     assert len(set(model.status["p1"].tolist())) > 2
     check_call(oracle, out, hc, model, want, True, True, True)
     hc.close()
-
-
-def offset_rows(x, byte_offset):
-    """a copy of x whose address is byte_offset modulo 16"""
-    pad = np.zeros(x.size + 8, np.float32)
-    o = ((byte_offset - pad.ctypes.data) % 16) // 4
-    v = pad[o:o + x.size].reshape(x.shape)
-    v[...] = x
-    assert v.ctypes.data % 16 == byte_offset
-    return v
 
 
 def test_a_row_4_bytes_off_gives_the_aligned_rows_bits(fmrx, oracle):

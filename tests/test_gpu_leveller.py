@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import _leveller_model as lm
+from _stage_cases import offset_rows, same_pcm, same_status
 
 pytestmark = pytest.mark.gpu
 
@@ -61,29 +62,8 @@ def reference(W, n, ac, N, pset):
     return p, calls
 
 
-def same_status(got, want):
-    for k in lm.STATUS_DTYPE.names:
-        x, y = got[k], want[k]
-        if x.dtype.kind == "f":
-            u = np.uint64 if x.dtype.itemsize == 8 else np.uint32
-            ok = (x.view(u) == y.view(u)) | (np.isnan(x) & np.isnan(y))
-        else:
-            ok = x == y
-        assert ok.all(), (k, np.flatnonzero(~ok)[:5], x[~ok][:5], y[~ok][:5])
-
-
-def offset_rows(x, byte_offset):
-    """a copy of x whose address is byte_offset modulo 16"""
-    pad = np.zeros(x.size + 8, F32)
-    o = ((byte_offset - pad.ctypes.data) % 16) // 4
-    v = pad[o:o + x.size].reshape(x.shape)
-    v[...] = x
-    assert v.ctypes.data % 16 == byte_offset
-    return v
-
-
 def check_call(oracle, out, status, call, wrap, outputs):
-    same_status(status, call["status"])
+    same_status(status, call["status"], lm.STATUS_DTYPE.names)
     want = call["want"]
     if outputs != "pcm":
         ok = lm.same(out["audio"], want)
@@ -91,8 +71,7 @@ def check_call(oracle, out, status, call, wrap, outputs):
     else:
         assert out["audio"] is None
     if outputs != "f32":
-        want_pcm = oracle.pcm16(lm.interleave(want).reshape(-1), wrap).reshape(out["pcm16"].shape)
-        assert np.array_equal(out["pcm16"], want_pcm)
+        same_pcm(oracle, out["pcm16"], want, wrap)
     else:
         assert out["pcm16"] is None
 
@@ -280,6 +259,9 @@ def test_process_dev_behind_the_audio_meters_and_its_refusals(fmrx, oracle):
     x = np.zeros((N, ac, n), F32)
     with pytest.raises(fmrx.FmrxError) as e:                                          # the host call: out over in
         fmrx._check(fmrx.lib.fmrx_leveller_process(lv._h, recs.ctypes.data, x.ctypes.data, x.ctypes.data, None, fmrx.PCM_WRAP))
+    assert e.value.code == fmrx.EINVAL
+    with pytest.raises(fmrx.FmrxError) as e:                                          # the same through the class: in place
+        lv.process(recs, x, in_place=True)
     assert e.value.code == fmrx.EINVAL
     for f in (lambda: fmrx.Leveller(48000.0, 0, 2, 4), lambda: fmrx.Leveller(48000.0, 1, 3, 4), lambda: fmrx.Leveller(48000.0, 1, 2, 0),
               lambda: fmrx.Leveller(48000.0, 1, 2, 4, lookahead=12), lambda: fmrx.Leveller(48000.0, 1, 2, 4, lookahead=256),

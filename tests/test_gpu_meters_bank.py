@@ -9,13 +9,12 @@ import pytest
 
 import _meters_capture as MC
 import _meters_model as mm
-import _tuner_capture as TC
+from _bank_chain import N, bank_chain
 
 pytestmark = pytest.mark.gpu
 
 REL, RF_FIELDS = mm.REL, mm.RF_FIELDS
 
-N = 8
 DB_LEVELS = ("level_dbfs", "cnr_db", "pilot_db", "rds_db")
 PILOT_MARGIN = 0.056   # (d): the CPU models read 3.5 - 3.6 % below the generator's 0.1 rad on the last call; that + 2 %
 
@@ -32,34 +31,17 @@ def slot_bytes(torch, first, pitch, n_bytes):
 
 
 def run_chain(fmrx, oracle, stereo):
-    import torch
-    c = TC.RDS
-    R, bb = c["R"], MC.BYTES_PER_CALL
-    wide = MC.capture()
-    h = oracle.impulse_response_lpf(c["Fs_w"], c["cutoff"], c["T"])
-    n_wide = bb // 2 * R
-    tuner = fmrx.Tuner(R, h, N, n_wide)
-    for k, (f, g) in enumerate(MC.channels()):
-        tuner.set_channel(k, f, c["Fs_w"], g)
-    bank = fmrx.Channels(0, N, audio_channels=2, exact=False, block_bytes=bb) if stereo else fmrx.Channels(0, N, block_bytes=bb)
-    meters = fmrx.Meters.for_bank(bank)
-    ac = 2 if stereo else 1
-    d_wide = torch.from_numpy(wide).cuda()
-    d_audio = torch.zeros(N * ac * bank.n_audio, dtype=torch.float32, device="cuda")
-    d_pcm = torch.zeros(N * ac * bank.n_audio, dtype=torch.int16, device="cuda")
-    stream = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    first, pitch = bank.input_layout()
-    for i in range(MC.CALLS):
-        tuner.process_dev(d_wide.data_ptr() + 2 * n_wide * i, n_wide, first, pitch, stream=stream.cuda_stream)
-        bank.process_dev(d_audio.data_ptr(), d_pcm.data_ptr(), stream=stream.cuda_stream)
-        meters.process_bank(stream=stream.cuda_stream)
-        recs = meters.collect()
-    stream.synchronize()
-    out = dict(recs=recs, levels=[meters.derive(r) for r in recs], slots=slot_bytes(torch, first, pitch, bb), power=tuner.levels()[1],
-               rows=[bank.read_tap(k, "demod") for k in range(N)] if stereo else None, if_Fs=float(bank.params.if_Fs))
-    for x in (meters, tuner, bank):
-        x.close()
+    with bank_chain(fmrx, oracle, fused_mono=not stereo) as ch:
+        bank, bb = ch.bank, MC.BYTES_PER_CALL
+        meters = fmrx.Meters.for_bank(bank)
+        for i in ch.calls():
+            meters.process_bank(stream=ch.s)
+            recs = meters.collect()
+        ch.stream.synchronize()
+        out = dict(recs=recs, levels=[meters.derive(r) for r in recs], slots=slot_bytes(ch.torch, ch.first, ch.pitch, bb),
+                   power=ch.tuner.levels()[1], rows=[bank.read_tap(k, "demod") for k in range(N)] if stereo else None,
+                   if_Fs=float(bank.params.if_Fs))
+        meters.close()
     return out
 
 
