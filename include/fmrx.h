@@ -1294,6 +1294,90 @@ FMRX_API int fmrx_leveller_process(fmrx_leveller *h, const fmrx_audio_meter *rec
 /* out [n_channels]; waits for the handle's last call (an event it recorded), not for the device */
 FMRX_API int fmrx_leveller_status_get(fmrx_leveller *h, fmrx_leveller_status *out);
 
+/* ------------------------------------------------------------------ */
+/* True-peak meter: the 4x oversampled peak (dBTP) of every audio row   */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  What EBU R 128 asks of programme that is monitored, recorded or restreamed: the maximum
+ * true-peak level, the peak of the reconstructed waveform between the samples, which a DAC, a resampler or a codec downstream
+ * overloads on and which a sample-peak reading (the audio meters' peak, the leveller's ceiling) misses by up to 3 dB at fs/4.
+ * ... -> audio meters -> leveller -> true peak on one stream; it serves any rows of the banks' shape, the limiter's output
+ * first.  A handle of the audio meters' kind that only reads the rows.  Defined by tests/_true_peak_model.py (DESIGN.md section
+ * 4.16); host and device equal that model bit for bit (a NaN's sign and payload are the machine's).
+ *
+ * Interpolator: 4x oversampling, as ITU-R BS.1770-4 Annex 2 prescribes at 44.1 / 48 kHz, at whatever rate the row has.  Four
+ * phases p of 12 taps over the samples x[k-5 .. k+6] give the waveform at k + p/4.  Phase 0 is the sample itself and no filter,
+ * so a true peak is never below the sample peak of the same positions, exactly.  Phases 1 .. 3 are a Kaiser-windowed sinc
+ * (beta = 5): H[p][j] = sinc(t) I0(5 sqrt(1 - (t/6)^2)) / I0(5), t = (j - 5) - p/4, computed in float64 and rounded once to
+ * float32.  The float32 table (fmrx_true_peak_taps; literals in true_peak_core.hpp) is the definition; H[3] is H[1] reversed,
+ * H[2] is symmetric.  Phase gain error 0.03 dB up to 0.36 fs; the only systematic under-read is the 4x grid's own, -0.44 dB at
+ * 0.4 fs.
+ * Groups: the row is a stream across calls with zeros in front of it.  When sample i arrives, group k = i - 6 is evaluated:
+ *   v0 = |x[k]|;   for p = 1, 2, 3:  acc = +0;  for j = 0 .. 11 ascending: acc = fmaf(H[p][j], x[k-5+j], acc);  v_p = |acc|
+ * every step rounded once, float32 denormals kept.  A call of n samples evaluates exactly n groups, negative k on a fresh stream
+ * included; there is no special case at a stream's start.  The carried state per row is the last 11 samples (fresh: zeros); a
+ * call with n < 11 shifts it.  The reading lags the audio by fmrx_true_peak_latency() = 6 samples.
+ * Record per channel and call (fmrx_true_peak_record; arrays of 2 for the rows L and R, mono fills index 0 only):
+ *   n             the call's samples per row
+ *   over[r]       groups in which any of the four values v has !(v <= limit); NaN counts
+ *   true_peak[r]  the maximum over all v of all groups, taken with v > m: it skips NaN and reads infinity for an infinity
+ *   peak[r]       the maximum of v0 alone
+ * limit is a finite positive float fixed at create, in the row's units (the library calls no pow; -1 dBTP at full scale 2.0 is
+ * (float)(2.0 * 10^(-1/20))).  Records of successive calls add n and over and take the maximum of the peaks.  Nothing depends on
+ * the order of evaluation: any split of a row over lanes, workgroups and calls gives the same merged record.
+ * Levels (fmrx_true_peak_levels; fmrx_true_peak_derive, host arithmetic in double; full_scale as the audio meters'), every dB
+ * value by the signal meters' edge rule:
+ *   true_peak_dbtp[r]  10 log10(true_peak^2 / fs2)      peak_dbfs[r]  10 log10(peak^2 / fs2)      (-99 for a row a mono channel lacks)
+ *   max_dbtp           the larger of the rows' true_peak_dbtp      over_fraction  (over[0] + over[1]) / (n audio_channels)
+ *
+ * The device pass: parallel in time -- the channel in the grid's x, a tile of fmrx_true_peak_tile() = 2048 samples in y -- so a
+ * single long stream is as fast as a bank.  About 36 fused multiply-adds and 4 bytes per sample. */
+typedef struct fmrx_true_peak_record {
+    uint64_t n, over[2];
+    double true_peak[2], peak[2];
+} fmrx_true_peak_record;
+typedef struct fmrx_true_peak_levels {
+    double true_peak_dbtp[2], peak_dbfs[2], max_dbtp, over_fraction;
+} fmrx_true_peak_levels;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_true_peak_record) == 56, "fmrx_true_peak_record layout");
+static_assert(sizeof(fmrx_true_peak_levels) == 48, "fmrx_true_peak_levels layout");
+#else
+_Static_assert(sizeof(fmrx_true_peak_record) == 56, "fmrx_true_peak_record layout");
+_Static_assert(sizeof(fmrx_true_peak_levels) == 48, "fmrx_true_peak_levels layout");
+#endif
+typedef struct fmrx_true_peak fmrx_true_peak;
+/* Host code, no device needed.  taps: h36 [3][12] = H[1], H[2], H[3].  latency: 6 samples.  tile: the samples of a row one
+ * workgroup walks. */
+FMRX_API int fmrx_true_peak_taps(float *h36);
+FMRX_API size_t fmrx_true_peak_latency(void);
+FMRX_API size_t fmrx_true_peak_tile(void);
+/* The host reference of one channel: rows [audio_channels][row_pitch] floats of which n (1 .. 2^26) are walked; state_in_out
+ * [2][11] floats, the rows' last 11 samples, is read and replaced (a mono channel's second row is left alone); *rec is written.
+ * limit finite and > 0, else FMRX_EINVAL.  The body the kernel runs (true_peak_core.hpp). */
+FMRX_API int fmrx_true_peak_walk(int audio_channels, const float *rows, size_t row_pitch, size_t n, float limit, float *state_in_out,
+                                 fmrx_true_peak_record *rec);
+FMRX_API int fmrx_true_peak_derive(const fmrx_true_peak_record *rec, int audio_channels, double full_scale, fmrx_true_peak_levels *out);
+/* n_audio: the most samples per row and call (fmrx_channels_n_audio), 1 .. 2^26; audio_channels 1 or 2; limit finite and > 0 */
+FMRX_API int fmrx_true_peak_create(fmrx_true_peak **out, int n_channels, int audio_channels, size_t n_audio, float limit, int device);
+FMRX_API int fmrx_true_peak_destroy(fmrx_true_peak *m);
+/* channel < 0: all.  Clears the channel's carried samples.  Waits for the handle's last call; the state is clear when it returns,
+ * for a later call on any stream. */
+FMRX_API int fmrx_true_peak_reset(fmrx_true_peak *m, int channel);
+/* out [n_channels][2][11] floats: every channel's carried samples (a mono channel's second row 0); waits for the handle's last
+ * call */
+FMRX_API int fmrx_true_peak_state_get(fmrx_true_peak *m, float *out);
+/* Asynchronous on `stream`, behind whatever wrote the rows on the same stream: d_audio [n_channels][audio_channels][row_pitch]
+ * floats, as the banks and every later stage write them (row_pitch = n_audio there), of which the first n <= n_audio of every
+ * row are walked; 4-byte aligned.  Rows that are 16-byte aligned (d_audio is, and row_pitch is a multiple of 4) are fetched in
+ * 16-byte pieces, all others 4 bytes at a time, the same arithmetic.  The rows are only read.  A clear of the results and one
+ * kernel launch; a second call before fmrx_true_peak_collect replaces the results (the state has then advanced by both). */
+FMRX_API int fmrx_true_peak_process_dev(fmrx_true_peak *m, const float *d_audio, size_t row_pitch, size_t n, void *stream);
+/* records [n_channels]; waits for the last call (an event it recorded), not for the device */
+FMRX_API int fmrx_true_peak_collect(fmrx_true_peak *m, fmrx_true_peak_record *records);
+/* host rows [n_channels][audio_channels][row_pitch], synchronous (it first waits for the handle's last call): the single-stream
+ * use is n_channels = 1 with the audio fmrx_pipeline_process returns */
+FMRX_API int fmrx_true_peak_process(fmrx_true_peak *m, const float *audio, size_t row_pitch, size_t n, fmrx_true_peak_record *records);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1759,6 +1759,110 @@ class Leveller(_MeterStage):
         return levellerDerive(status)
 
 
+# --------------------------------------------------------------------------
+# True-peak meter: the 4x oversampled peak (dBTP) of every audio row of a bank
+# --------------------------------------------------------------------------
+TRUE_PEAK_DTYPE = np.dtype([("n", "<u8"), ("over", "<u8", (2,)), ("true_peak", "<f8", (2,)), ("peak", "<f8", (2,))])    # struct fmrx_true_peak_record
+TRUE_PEAK_LEVELS_DTYPE = np.dtype([("true_peak_dbtp", "<f8", (2,)), ("peak_dbfs", "<f8", (2,)), ("max_dbtp", "<f8"),
+                                   ("over_fraction", "<f8")])                                                        # struct fmrx_true_peak_levels
+assert TRUE_PEAK_DTYPE.itemsize == 56 and TRUE_PEAK_LEVELS_DTYPE.itemsize == 48
+TRUE_PEAK_CARRY = 11                                                   # samples of a row carried from call to call
+TRUE_PEAK_LIMIT = np.float32(AUDIO_FULL_SCALE * 10.0 ** (-1.0 / 20.0))   # -1 dBTP
+_sig("fmrx_true_peak_taps", [_f32p])
+_sig("fmrx_true_peak_latency", [], _sz)
+_sig("fmrx_true_peak_tile", [], _sz)
+_sig("fmrx_true_peak_walk", [_int, _vp, _sz, _sz, _flt, _vp, _vp])
+_sig("fmrx_true_peak_derive", [_vp, _int, _dbl, _vp])
+_sig("fmrx_true_peak_create", [C.POINTER(_vp), _int, _int, _sz, _flt, _int])
+_sig("fmrx_true_peak_destroy", [_vp])
+_sig("fmrx_true_peak_reset", [_vp, _int])
+_sig("fmrx_true_peak_state_get", [_vp, _vp])
+_sig("fmrx_true_peak_process_dev", [_vp, _vp, _sz, _sz, _vp])
+_sig("fmrx_true_peak_collect", [_vp, _vp])
+_sig("fmrx_true_peak_process", [_vp, _vp, _sz, _sz, _vp])
+
+
+def truePeakTaps() -> np.ndarray:
+    """Host only: the interpolator's table, float32 [3, 12]: phases 1, 2, 3 (phase 0 is the sample itself)."""
+    h = np.zeros(36, np.float32)
+    _check(lib.fmrx_true_peak_taps(h))
+    return h.reshape(3, 12)
+
+
+def truePeakWalk(rows, state=None, limit=TRUE_PEAK_LIMIT):
+    """Host only: the reference walk of one channel (fmrx_true_peak_walk) on rows float32 [audio_channels, n]; state: float32
+    [2, 11], what the last call returned (None or zeros: a fresh channel) -> (record, state)."""
+    x = _f32(rows)
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    st = np.zeros((2, TRUE_PEAK_CARRY), np.float32) if state is None else np.array(state, dtype=np.float32).reshape(2, TRUE_PEAK_CARRY).copy()
+    rec = np.zeros(1, TRUE_PEAK_DTYPE)
+    _check(lib.fmrx_true_peak_walk(x.shape[0], x.ctypes.data, x.shape[1], x.shape[1], float(limit), st.ctypes.data, rec.ctypes.data))
+    return rec[0], st
+
+
+def truePeakDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dict:
+    """Host only: the levels (fmrx_true_peak_levels, as a dict; the arrays of 2 as tuples) of one TRUE_PEAK_DTYPE record."""
+    r = np.array(rec, dtype=TRUE_PEAK_DTYPE).reshape(1)
+    out = np.zeros(1, TRUE_PEAK_LEVELS_DTYPE)
+    _check(lib.fmrx_true_peak_derive(r.ctypes.data, int(audio_channels), float(full_scale), out.ctypes.data))
+    return {k: (tuple(float(v) for v in out[0][k]) if out[0][k].ndim else float(out[0][k])) for k in TRUE_PEAK_LEVELS_DTYPE.names}
+
+
+class TruePeak(_Handle):
+    """Per channel of a receiver bank and call: the peak of the 4x oversampled waveform, the sample peak and the groups beyond
+    `limit` of the audio rows (fmrx_true_peak_*).  Behind the last audio stage on stream s: tp =
+    TruePeak.for_bank(bank); tp.process_bank(d_out, stream=s); recs = tp.collect(); tp.derive(recs[c]).  The reading lags the
+    audio by tp.latency samples."""
+    _destroy = "fmrx_true_peak_destroy"
+
+    def __init__(self, n_channels=1, audio_channels=2, n_audio=1920, limit=TRUE_PEAK_LIMIT, device=0):
+        self.n_channels, self.audio_channels, self.n_audio, self.limit = int(n_channels), int(audio_channels), int(n_audio), np.float32(limit)
+        self._h = _vp()
+        _check(lib.fmrx_true_peak_create(C.byref(self._h), self.n_channels, self.audio_channels, self.n_audio, float(self.limit), device))
+        self.latency = lib.fmrx_true_peak_latency()
+        self.tile = lib.fmrx_true_peak_tile()
+
+    @classmethod
+    def for_bank(cls, bank, limit=TRUE_PEAK_LIMIT):
+        """The true-peak meter of a Channels bank, on the bank's device."""
+        return cls(bank.n_channels, bank.audio_channels, bank.n_audio, limit, bank.device)
+
+    def reset(self, channel=-1):
+        _check(lib.fmrx_true_peak_reset(self._h, channel))
+
+    def state(self) -> np.ndarray:
+        """Waits for the last call; every channel's carried samples, float32 [n_channels, 2, 11]."""
+        out = np.zeros((self.n_channels, 2, TRUE_PEAK_CARRY), np.float32)
+        _check(lib.fmrx_true_peak_state_get(self._h, out.ctypes.data))
+        return out
+
+    def process_dev(self, d_audio, row_pitch=None, n=None, stream=None):
+        """Device rows float32 [n_channels, audio_channels, row_pitch] of which the first n samples are walked (defaults: n_audio),
+        asynchronous on `stream`; the rows are only read."""
+        n = self.n_audio if n is None else int(n)
+        _check(lib.fmrx_true_peak_process_dev(self._h, d_audio, n if row_pitch is None else int(row_pitch), n, stream))
+
+    def process_bank(self, d_audio, stream=None):
+        """process_dev on rows as the bank or any later stage wrote them: [n_channels, audio_channels, n_audio]."""
+        self.process_dev(d_audio, self.n_audio, self.n_audio, stream)
+
+    def collect(self) -> np.ndarray:
+        """Waits for the last call; TRUE_PEAK_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, TRUE_PEAK_DTYPE)
+        _check(lib.fmrx_true_peak_collect(self._h, out.ctypes.data))
+        return out
+
+    def process(self, audio) -> np.ndarray:
+        """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
+        x = _f32(audio).reshape(self.n_channels, self.audio_channels, -1)
+        out = np.zeros(self.n_channels, TRUE_PEAK_DTYPE)
+        _check(lib.fmrx_true_peak_process(self._h, x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data))
+        return out
+
+    def derive(self, rec, full_scale=AUDIO_FULL_SCALE) -> dict:
+        return truePeakDerive(rec, self.audio_channels, full_scale)
+
+
 class FrontEndPlan(_Handle):
     """Reusable device-side tap tables for the fused front-end kernel (fmrx_fe_plan)."""
     _destroy = "fmrx_fe_plan_destroy"

@@ -507,4 +507,19 @@ struct LevellerArgs {
 };
 int leveller_apply_launch(const LevellerArgs &a, hipStream_t s);
 
+// ---- true-peak meter (kernels_true_peak.hip; the interpolator in true_peak_core.hpp; handle and C ABI in true_peak.hip) -----------------
+constexpr int kTruePeakStateFields = 22;   // per channel: the last 11 samples of row L, then of row R (floats)
+constexpr int kTruePeakFields = 6;         // per channel: true_peak[2], peak[2] (the bits of floats >= +0), over[2] (32-bit)
+struct TruePeakArgs {
+    const float *x = nullptr;            // [n_channels][ac][pitch]; only read
+    size_t pitch = 0, n = 0;             // floats per row; samples of every row to walk
+    int n_channels = 0, ac = 1;
+    float limit = 0.0f;
+    // field-major [field][n_channels]
+    const float *state_in = nullptr;     // [kTruePeakStateFields][n_channels]: read
+    float *state_out = nullptr;          // another buffer of that shape: the rows' fields written whole
+    unsigned *res = nullptr;             // [kTruePeakFields][n_channels]: cleared on the stream, then raised by the kernel's atomics
+};
+int true_peak_launch(const TruePeakArgs &a, hipStream_t s);
+
 }  // namespace fmrx
