@@ -571,8 +571,13 @@ def modeParams(mode, rf_taps=101, base_audio_taps=101, stereo_taps=101) -> Param
 # what every class that owns a library handle derives from
 # --------------------------------------------------------------------------
 class _Handle:
-    """Owns self._h, a handle the library made; a subclass names the function that destroys it."""
-    _destroy = None
+    """Owns self._h, a handle the library made; a subclass names the function that destroys it, or the _prefix of its
+    fmrx_<_prefix>_* functions, which _call then finds by name."""
+    _prefix = None
+    _destroy = property(lambda self: f"fmrx_{self._prefix}_destroy")
+
+    def _call(self, name, *args):
+        _check(getattr(lib, f"fmrx_{self._prefix}_{name}")(self._h, *args))
 
     def close(self):
         if getattr(self, "_h", None) and lib is not None:  # lib is None during interpreter shutdown
@@ -1293,12 +1298,8 @@ class _MeterStage(_Handle):
     """What Blend, HighCut and Leveller share: a handle behind a meters handle on a bank's audio (csrc/meter_stage.hpp).  A
     subclass names its fmrx_<_prefix>_* functions, its status dtype and the dtype of the records its host call reads, and creates
     self._h."""
-    _prefix = _status_dtype = None
+    _status_dtype = None
     _rec_dtype = METER_DTYPE
-    _destroy = property(lambda self: f"fmrx_{self._prefix}_destroy")
-
-    def _call(self, name, *args):
-        _check(getattr(lib, f"fmrx_{self._prefix}_{name}")(self._h, *args))
 
     def reset(self, channel=-1):
         self._call("reset", channel)
@@ -1523,6 +1524,17 @@ _sig("fmrx_loudness_push", [_vp, _vp, _vp, _sz])
 _sig("fmrx_loudness_read", [_vp, _int, _vp])
 
 
+def _walk_rows(rows) -> np.ndarray:
+    """One channel's rows for a host walk: float32 [audio_channels, n]; a single row may come flat."""
+    x = _f32(rows)
+    return x.reshape(1, -1) if x.ndim == 1 else x
+
+
+def _levels_dict(out, dtype) -> dict:
+    """One levels record as a dict, its arrays of 2 as tuples."""
+    return {k: (tuple(float(v) for v in out[0][k]) if out[0][k].ndim else float(out[0][k])) for k in dtype.names}
+
+
 def audioMetersDesign(audio_Fs) -> np.ndarray:
     """Host only: the K-weighting biquads for audio_Fs, float64 [2, 5]: (b0, b1, b2, a1, a2) of the shelf, then of the high-pass."""
     c = np.zeros(10)
@@ -1538,8 +1550,7 @@ def audioMetersBinLen(audio_Fs) -> int:
 def audioMetersWalk(audio_Fs, rows, state=None):
     """Host only: the reference walk of one channel (fmrx_audio_meters_walk) on rows float32 [audio_channels, n]; state: the
     AUDIO_METER_STATE_DTYPE record the last call returned (None or zeros: a fresh channel) -> (record, bins [2, max_bins], state)."""
-    x = _f32(rows)
-    x = x.reshape(1, -1) if x.ndim == 1 else x
+    x = _walk_rows(rows)
     st = np.zeros(1, AUDIO_METER_STATE_DTYPE) if state is None else np.array(state, dtype=AUDIO_METER_STATE_DTYPE).reshape(1).copy()
     rec = np.zeros(1, AUDIO_METER_DTYPE)
     nb = lib.fmrx_audio_meters_max_bins(float(audio_Fs), x.shape[1])
@@ -1554,15 +1565,47 @@ def audioMetersDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dic
     r = np.array(rec, dtype=AUDIO_METER_DTYPE).reshape(1)
     out = np.zeros(1, AUDIO_LEVELS_DTYPE)
     _check(lib.fmrx_audio_meters_derive(r.ctypes.data, int(audio_channels), float(full_scale), out.ctypes.data))
-    return {k: (tuple(float(v) for v in out[0][k]) if out[0][k].ndim else float(out[0][k])) for k in AUDIO_LEVELS_DTYPE.names}
+    return _levels_dict(out, AUDIO_LEVELS_DTYPE)
 
 
-class AudioMeters(_Handle):
+class _AudioReader(_Handle):
+    """What AudioMeters and TruePeak share: a handle that only reads a bank's audio rows (csrc/meter_stage.hpp's Reader).  A
+    subclass names its fmrx_<_prefix>_* functions and its module-level derive function, creates self._h, and says in _bank_extra
+    what its constructor takes beyond n_channels, audio_channels, n_audio and device."""
+
+    @classmethod
+    def for_bank(cls, bank, *args, **kw):
+        """The reader of a Channels bank, on the bank's device; further arguments as the class's _bank_extra takes them."""
+        return cls(n_channels=bank.n_channels, audio_channels=bank.audio_channels, n_audio=bank.n_audio, device=bank.device,
+                   **cls._bank_extra(bank, *args, **kw))
+
+    def reset(self, channel=-1):
+        self._call("reset", channel)
+
+    def process_dev(self, d_audio, row_pitch=None, n=None, stream=None):
+        """Device rows float32 [n_channels, audio_channels, row_pitch] of which the first n samples are walked (defaults: n_audio),
+        asynchronous on `stream`; the rows are only read."""
+        n = self.n_audio if n is None else int(n)
+        self._call("process_dev", d_audio, n if row_pitch is None else int(row_pitch), n, stream)
+
+    def process_bank(self, d_audio, stream=None):
+        """process_dev on rows as the bank or any later stage wrote them: [n_channels, audio_channels, n_audio]."""
+        self.process_dev(d_audio, self.n_audio, self.n_audio, stream)
+
+    def _rows(self, audio) -> np.ndarray:    # the host call's rows
+        return _f32(audio).reshape(self.n_channels, self.audio_channels, -1)
+
+    def derive(self, rec, full_scale=AUDIO_FULL_SCALE) -> dict:
+        return self._derive(rec, self.audio_channels, full_scale)
+
+
+class AudioMeters(_AudioReader):
     """Per channel of a receiver bank and call: overs, peak, sums, K-weighted energy, the stereo cross sum and the 100 ms bins of
     the audio rows (fmrx_audio_meters_*).  The last stage of the chain, behind whatever wrote the rows on
     stream s: am = AudioMeters.for_bank(bank); am.process_bank(d_audio, stream=s); recs, bins = am.collect(); am.derive(recs[c]).
     It needs no Meters, so it also works behind the fused mono bank."""
-    _destroy = "fmrx_audio_meters_destroy"
+    _prefix, _derive = "audio_meters", staticmethod(audioMetersDerive)
+    _bank_extra = staticmethod(lambda bank: {"audio_Fs": bank.params.audio_Fs})
 
     def __init__(self, audio_Fs=48000.0, n_channels=1, audio_channels=2, n_audio=1920, device=0):
         self.audio_Fs, self.n_channels, self.audio_channels, self.n_audio = float(audio_Fs), int(n_channels), int(audio_channels), int(n_audio)
@@ -1571,45 +1614,24 @@ class AudioMeters(_Handle):
         self.bin_len = lib.fmrx_audio_meters_bin_len(self.audio_Fs)
         self.max_bins = lib.fmrx_audio_meters_max_bins(self.audio_Fs, self.n_audio)
 
-    @classmethod
-    def for_bank(cls, bank):
-        """The audio meters of a Channels bank, on the bank's device."""
-        return cls(bank.params.audio_Fs, bank.n_channels, bank.audio_channels, bank.n_audio, bank.device)
-
-    def reset(self, channel=-1):
-        _check(lib.fmrx_audio_meters_reset(self._h, channel))
-
     def state(self) -> np.ndarray:
         """Waits for the last call; every channel's carried state, AUDIO_METER_STATE_DTYPE [n_channels]."""
         out = np.zeros(self.n_channels, AUDIO_METER_STATE_DTYPE)
-        _check(lib.fmrx_audio_meters_state_get(self._h, out.ctypes.data))
+        self._call("state_get", out.ctypes.data)
         return out
-
-    def process_dev(self, d_audio, row_pitch=None, n=None, stream=None):
-        """Device rows float32 [n_channels, audio_channels, row_pitch] of which the first n samples are walked (defaults: n_audio),
-        asynchronous on `stream`; the rows are only read."""
-        n = self.n_audio if n is None else int(n)
-        _check(lib.fmrx_audio_meters_process_dev(self._h, d_audio, n if row_pitch is None else int(row_pitch), n, stream))
-
-    def process_bank(self, d_audio, stream=None):
-        """process_dev on rows as the bank, the blend or the high-cut wrote them: [n_channels, audio_channels, n_audio]."""
-        self.process_dev(d_audio, self.n_audio, self.n_audio, stream)
 
     def collect(self):
         """Waits for the last call; (AUDIO_METER_DTYPE [n_channels], bins float64 [n_channels, 2, max_bins])."""
         out, bins = np.zeros(self.n_channels, AUDIO_METER_DTYPE), np.zeros((self.n_channels, 2, self.max_bins))
-        _check(lib.fmrx_audio_meters_collect(self._h, out.ctypes.data, bins.ctypes.data))
+        self._call("collect", out.ctypes.data, bins.ctypes.data)
         return out, bins
 
     def process(self, audio):
         """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
-        x = _f32(audio).reshape(self.n_channels, self.audio_channels, -1)
+        x = self._rows(audio)
         out, bins = np.zeros(self.n_channels, AUDIO_METER_DTYPE), np.zeros((self.n_channels, 2, self.max_bins))
-        _check(lib.fmrx_audio_meters_process(self._h, x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data, bins.ctypes.data))
+        self._call("process", x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data, bins.ctypes.data)
         return out, bins
-
-    def derive(self, rec, full_scale=AUDIO_FULL_SCALE) -> dict:
-        return audioMetersDerive(rec, self.audio_channels, full_scale)
 
 
 class Loudness(_Handle):
@@ -1711,8 +1733,7 @@ def levellerWalk(rows, gain0=1.0, gain1=1.0, lookahead=64, ceiling=None, state=N
     """Host only: the serial reference of one channel's gain and limiter (fmrx_leveller_walk) on rows float32
     [audio_channels, n]; state: the (codes uint32 [2W-2], u float32 [audio_channels, W-1]) the last call returned (None: a fresh
     channel) -> (out [audio_channels, n], state, min_code, limited)."""
-    x = _f32(rows)
-    x = x.reshape(1, -1) if x.ndim == 1 else x
+    x = _walk_rows(rows)
     ac, n, W = x.shape[0], x.shape[1], int(lookahead)
     if state is None:
         codes, u = np.full(max(2 * W - 2, 1), LEVELLER_ONE, np.uint32), np.zeros((ac, max(W - 1, 1)), np.float32)
@@ -1792,8 +1813,7 @@ def truePeakTaps() -> np.ndarray:
 def truePeakWalk(rows, state=None, limit=TRUE_PEAK_LIMIT):
     """Host only: the reference walk of one channel (fmrx_true_peak_walk) on rows float32 [audio_channels, n]; state: float32
     [2, 11], what the last call returned (None or zeros: a fresh channel) -> (record, state)."""
-    x = _f32(rows)
-    x = x.reshape(1, -1) if x.ndim == 1 else x
+    x = _walk_rows(rows)
     st = np.zeros((2, TRUE_PEAK_CARRY), np.float32) if state is None else np.array(state, dtype=np.float32).reshape(2, TRUE_PEAK_CARRY).copy()
     rec = np.zeros(1, TRUE_PEAK_DTYPE)
     _check(lib.fmrx_true_peak_walk(x.shape[0], x.ctypes.data, x.shape[1], x.shape[1], float(limit), st.ctypes.data, rec.ctypes.data))
@@ -1805,15 +1825,16 @@ def truePeakDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dict:
     r = np.array(rec, dtype=TRUE_PEAK_DTYPE).reshape(1)
     out = np.zeros(1, TRUE_PEAK_LEVELS_DTYPE)
     _check(lib.fmrx_true_peak_derive(r.ctypes.data, int(audio_channels), float(full_scale), out.ctypes.data))
-    return {k: (tuple(float(v) for v in out[0][k]) if out[0][k].ndim else float(out[0][k])) for k in TRUE_PEAK_LEVELS_DTYPE.names}
+    return _levels_dict(out, TRUE_PEAK_LEVELS_DTYPE)
 
 
-class TruePeak(_Handle):
+class TruePeak(_AudioReader):
     """Per channel of a receiver bank and call: the peak of the 4x oversampled waveform, the sample peak and the groups beyond
     `limit` of the audio rows (fmrx_true_peak_*).  Behind the last audio stage on stream s: tp =
     TruePeak.for_bank(bank); tp.process_bank(d_out, stream=s); recs = tp.collect(); tp.derive(recs[c]).  The reading lags the
     audio by tp.latency samples."""
-    _destroy = "fmrx_true_peak_destroy"
+    _prefix, _derive = "true_peak", staticmethod(truePeakDerive)
+    _bank_extra = staticmethod(lambda bank, limit=TRUE_PEAK_LIMIT: {"limit": limit})
 
     def __init__(self, n_channels=1, audio_channels=2, n_audio=1920, limit=TRUE_PEAK_LIMIT, device=0):
         self.n_channels, self.audio_channels, self.n_audio, self.limit = int(n_channels), int(audio_channels), int(n_audio), np.float32(limit)
@@ -1822,45 +1843,24 @@ class TruePeak(_Handle):
         self.latency = lib.fmrx_true_peak_latency()
         self.tile = lib.fmrx_true_peak_tile()
 
-    @classmethod
-    def for_bank(cls, bank, limit=TRUE_PEAK_LIMIT):
-        """The true-peak meter of a Channels bank, on the bank's device."""
-        return cls(bank.n_channels, bank.audio_channels, bank.n_audio, limit, bank.device)
-
-    def reset(self, channel=-1):
-        _check(lib.fmrx_true_peak_reset(self._h, channel))
-
     def state(self) -> np.ndarray:
         """Waits for the last call; every channel's carried samples, float32 [n_channels, 2, 11]."""
         out = np.zeros((self.n_channels, 2, TRUE_PEAK_CARRY), np.float32)
-        _check(lib.fmrx_true_peak_state_get(self._h, out.ctypes.data))
+        self._call("state_get", out.ctypes.data)
         return out
-
-    def process_dev(self, d_audio, row_pitch=None, n=None, stream=None):
-        """Device rows float32 [n_channels, audio_channels, row_pitch] of which the first n samples are walked (defaults: n_audio),
-        asynchronous on `stream`; the rows are only read."""
-        n = self.n_audio if n is None else int(n)
-        _check(lib.fmrx_true_peak_process_dev(self._h, d_audio, n if row_pitch is None else int(row_pitch), n, stream))
-
-    def process_bank(self, d_audio, stream=None):
-        """process_dev on rows as the bank or any later stage wrote them: [n_channels, audio_channels, n_audio]."""
-        self.process_dev(d_audio, self.n_audio, self.n_audio, stream)
 
     def collect(self) -> np.ndarray:
         """Waits for the last call; TRUE_PEAK_DTYPE [n_channels]."""
         out = np.zeros(self.n_channels, TRUE_PEAK_DTYPE)
-        _check(lib.fmrx_true_peak_collect(self._h, out.ctypes.data))
+        self._call("collect", out.ctypes.data)
         return out
 
     def process(self, audio) -> np.ndarray:
         """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
-        x = _f32(audio).reshape(self.n_channels, self.audio_channels, -1)
+        x = self._rows(audio)
         out = np.zeros(self.n_channels, TRUE_PEAK_DTYPE)
-        _check(lib.fmrx_true_peak_process(self._h, x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data))
+        self._call("process", x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data)
         return out
-
-    def derive(self, rec, full_scale=AUDIO_FULL_SCALE) -> dict:
-        return truePeakDerive(rec, self.audio_channels, full_scale)
 
 
 class FrontEndPlan(_Handle):

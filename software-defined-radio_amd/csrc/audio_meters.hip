@@ -3,34 +3,25 @@
 // kernels_audio_meters.hip; one channel's walk, shared with fmrx_audio_meters_walk below: audio_meters_core.hpp; definition:
 // tests/_audio_meters_model.py.
 //
-// A handle of the signal meters' kind (meters.hip), not a stage of meter_stage.hpp: it reads no meters and writes no audio.  It
-// keeps the channels' state on the device (field-major, see fmrx_internal.hpp), the result arrays a call writes, their pinned
-// host copies, and meter_stage.hpp's handle base: the event the last call recorded behind the copies; collect waits on that
-// event, not on the device.
+// A reader of meter_stage.hpp: it reads no meters and writes no audio.  Its own part is the channels' state on the device
+// (field-major), the result arrays a call writes and their pinned host copies, the launch that fills them, the records' layout
+// and the host arithmetic.
 #include "audio_meters_core.hpp"
 #include "meter_stage.hpp"
 
 #include <cmath>
 
 using namespace fmrx;
+using meter_stage::field;
 
-struct fmrx_audio_meters : meter_stage::Handle {
-    int n_channels = 0, ac = 1;
+struct fmrx_audio_meters : meter_stage::Reader {
     double audio_Fs = 0.0;
-    size_t n_audio = 0, bin_len = 0, max_bins = 0;
+    size_t bin_len = 0, max_bins = 0;
     audio_meters::Coefs coef;
     DevBuf<double> d_state, d_sums, d_bins;
     DevBuf<unsigned> d_fill, d_counts;
-    double *h_sums = nullptr, *h_bins = nullptr;   // pinned
-    unsigned *h_counts = nullptr;                  // pinned
-    size_t n = 0;                                  // of the last call
-    DevBuf<float> d_rows;                          // fmrx_audio_meters_process only
-    ~fmrx_audio_meters()
-    {
-        if (h_sums) (void)hipHostFree(h_sums);
-        if (h_bins) (void)hipHostFree(h_bins);
-        if (h_counts) (void)hipHostFree(h_counts);
-    }
+    HostBuf<double> h_sums, h_bins;
+    HostBuf<unsigned> h_counts;
 };
 
 namespace {
@@ -69,10 +60,33 @@ void walk_channel(const audio_meters::Coefs &c, const float *rows, size_t pitch,
     rec->bins_done = w.bins_done;
 }
 
+int launch(fmrx_audio_meters *m, const float *d_audio, size_t pitch, size_t n, hipStream_t s)
+{
+    AudioMetersArgs a;
+    a.x = d_audio;
+    a.pitch = pitch;
+    a.n = n;
+    a.n_channels = m->n_channels;
+    a.ac = m->audio_channels;
+    std::memcpy(a.coef, m->coef.q, sizeof a.coef);
+    a.bin_len = static_cast<unsigned>(m->bin_len);
+    a.max_bins = m->max_bins;
+    a.state = m->d_state.p;
+    a.fill = m->d_fill.p;
+    a.sums = m->d_sums.p;
+    a.counts = m->d_counts.p;
+    a.bins = m->d_bins.p;
+    FMRX_TRY(audio_meters_launch(a, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_sums.p, m->d_sums.p, m->d_sums.bytes(), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_counts.p, m->d_counts.p, m->d_counts.bytes(), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_bins.p, m->d_bins.p, m->d_bins.bytes(), hipMemcpyDeviceToHost, s));
+    return FMRX_OK;
+}
+
 }  // namespace
 
 namespace fmrx {
-AudioMetersSums audio_meters_sums(const fmrx_audio_meters *m) { return AudioMetersSums{m->d_sums.p, m->n, m->n_channels, m->ac, m->device, m->ran}; }
+AudioMetersSums audio_meters_sums(const fmrx_audio_meters *m) { return AudioMetersSums{m->d_sums.p, m->n, m->n_channels, m->audio_channels, m->device, m->ran}; }
 }  // namespace fmrx
 
 extern "C" {
@@ -112,9 +126,7 @@ int fmrx_audio_meters_walk(double audio_Fs, int audio_channels, const float *row
 
 int fmrx_audio_meters_derive(const fmrx_audio_meter *m, int audio_channels, double full_scale, fmrx_audio_levels *out)
 {
-    if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_derive: null argument");
-    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "audio_meters_derive: audio_channels must be 1 or 2");
-    if (!(full_scale > 0.0) || !std::isfinite(full_scale)) return fail(FMRX_EINVAL, "audio_meters_derive: full_scale %g", full_scale);
+    FMRX_TRY(meter_stage::check_derive("audio_meters_derive", m, out, audio_channels, full_scale));
     const double n = static_cast<double>(m->n), fs2 = full_scale * full_scale;
     std::memset(out, 0, sizeof *out);
     for (int r = 0; r < 2; r++) {
@@ -130,23 +142,16 @@ int fmrx_audio_meters_derive(const fmrx_audio_meter *m, int audio_channels, doub
         out->correlation = den > 0.0 && std::isfinite(den) ? m->sum_lr / den : 0.0;
         out->balance_db = db(m->sum_x2[0], m->sum_x2[1]);
     }
-    out->over_fraction = n > 0.0 ? (static_cast<double>(m->over[0]) + static_cast<double>(m->over[1])) / (n * audio_channels) : 0.0;
+    out->over_fraction = meter_stage::over_fraction(m->over, m->n, audio_channels);
     return FMRX_OK;
 }
 
 int fmrx_audio_meters_create(fmrx_audio_meters **out, double audio_Fs, int n_channels, int audio_channels, size_t n_audio, int device)
 {
-    if (!out) return fail(FMRX_EINVAL, "audio_meters_create: null argument");
     if (!good_fs(audio_Fs)) return fail(FMRX_EINVAL, "audio_meters_create: audio_Fs %g (finite, %g .. %g)", audio_Fs, audio_meters::kMinFs, audio_meters::kMaxFs);
-    if (n_channels < 1) return fail(FMRX_EINVAL, "audio_meters_create: n_channels must be >= 1");
-    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "audio_meters_create: audio_channels must be 1 or 2");
-    if (n_audio < 1 || n_audio > (size_t{1} << 26)) return fail(FMRX_EINVAL, "audio_meters_create: n_audio %zu (1 .. 2^26)", n_audio);
-    return meter_stage::make(out, device, [&](fmrx_audio_meters *m) -> int {
+    return meter_stage::create_on_audio("audio_meters_create", out, n_channels, audio_channels, n_audio, device, [&](fmrx_audio_meters *m) -> int {
         const size_t N = n_channels;
-        m->n_channels = n_channels;
-        m->ac = audio_channels;
         m->audio_Fs = audio_Fs;
-        m->n_audio = n_audio;
         m->bin_len = audio_meters::bin_len(audio_Fs);
         m->max_bins = n_audio / m->bin_len + 1;
         audio_meters::design(audio_Fs, &m->coef);
@@ -155,12 +160,11 @@ int fmrx_audio_meters_create(fmrx_audio_meters **out, double audio_Fs, int n_cha
         FMRX_TRY(m->d_sums.alloc(N * kAudioMetersSumFields));
         FMRX_TRY(m->d_counts.alloc(N * kAudioMetersCountFields));
         FMRX_TRY(m->d_bins.alloc(N * 2 * m->max_bins));
-        FMRX_HIP(hipMemset(m->d_state.p, 0, m->d_state.bytes()));
-        FMRX_HIP(hipMemset(m->d_fill.p, 0, m->d_fill.bytes()));
-        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_sums), m->d_sums.bytes(), hipHostMallocDefault));
-        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_counts), m->d_counts.bytes(), hipHostMallocDefault));
-        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_bins), m->d_bins.bytes(), hipHostMallocDefault));
-        return FMRX_OK;
+        FMRX_TRY(m->h_sums.alloc(m->d_sums.n));
+        FMRX_TRY(m->h_counts.alloc(m->d_counts.n));
+        FMRX_TRY(m->h_bins.alloc(m->d_bins.n));
+        FMRX_TRY(meter_stage::clear_fields(m->d_state.p, kAudioMetersStateFields, n_channels, -1));
+        return meter_stage::clear_fields(m->d_fill.p, 1, n_channels, -1);
     });
 }
 
@@ -168,34 +172,25 @@ int fmrx_audio_meters_destroy(fmrx_audio_meters *m) { return meter_stage::destro
 
 int fmrx_audio_meters_reset(fmrx_audio_meters *m, int channel)
 {
-    if (!m) return fail(FMRX_EINVAL, "audio_meters_reset: null handle");
-    if (channel >= m->n_channels) return fail(FMRX_EINVAL, "audio_meters_reset: channel %d of %d", channel, m->n_channels);
-    FMRX_TRY(m->wait());
-    const size_t N = m->n_channels;
-    if (channel < 0) {
-        FMRX_HIP(hipMemset(m->d_state.p, 0, m->d_state.bytes()));
-        FMRX_HIP(hipMemset(m->d_fill.p, 0, m->d_fill.bytes()));
-    } else {   // the channel's column of the field-major state
-        FMRX_HIP(hipMemset2D(m->d_state.p + channel, N * sizeof(double), 0, sizeof(double), kAudioMetersStateFields));
-        FMRX_HIP(hipMemset(m->d_fill.p + channel, 0, sizeof(unsigned)));
-    }
-    FMRX_HIP(hipStreamSynchronize(nullptr));   // clear before this returns: a call on any stream, non-blocking ones included, finds it so
-    return FMRX_OK;
+    return meter_stage::reset_on_audio("audio_meters_reset", m, channel, [&]() -> int {
+        FMRX_TRY(meter_stage::clear_fields(m->d_state.p, kAudioMetersStateFields, m->n_channels, channel));
+        return meter_stage::clear_fields(m->d_fill.p, 1, m->n_channels, channel);
+    });
 }
 
 int fmrx_audio_meters_state_get(fmrx_audio_meters *m, fmrx_audio_meter_state *out)
 {
     if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_state_get: null argument");
     FMRX_TRY(m->wait());
-    const size_t N = m->n_channels;
-    std::vector<double> st(N * kAudioMetersStateFields);
-    std::vector<unsigned> fill(N);
-    FMRX_HIP(hipMemcpy(st.data(), m->d_state.p, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-    FMRX_HIP(hipMemcpy(fill.data(), m->d_fill.p, fill.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < N; c++) {
+    const int N = m->n_channels;
+    std::vector<double> st(m->d_state.n);
+    std::vector<unsigned> fill(m->d_fill.n);
+    FMRX_HIP(hipMemcpy(st.data(), m->d_state.p, m->d_state.bytes(), hipMemcpyDeviceToHost));
+    FMRX_HIP(hipMemcpy(fill.data(), m->d_fill.p, m->d_fill.bytes(), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < static_cast<size_t>(N); c++) {
         for (int r = 0; r < 2; r++) {
-            for (int i = 0; i < 4; i++) out[c].z[r][i] = st[(r * 4 + i) * N + c];
-            out[c].bin_acc[r] = st[(8 + r) * N + c];
+            for (int i = 0; i < 4; i++) out[c].z[r][i] = field(st.data(), N, r * 4 + i, c);
+            out[c].bin_acc[r] = field(st.data(), N, 8 + r, c);
         }
         out[c].bin_fill = fill[c];
     }
@@ -204,69 +199,33 @@ int fmrx_audio_meters_state_get(fmrx_audio_meters *m, fmrx_audio_meter_state *ou
 
 int fmrx_audio_meters_process_dev(fmrx_audio_meters *m, const float *d_audio, size_t row_pitch, size_t n, void *stream)
 {
-    if (!m || !d_audio) return fail(FMRX_EINVAL, "audio_meters_process_dev: null argument");
-    if (n < 1 || n > m->n_audio) return fail(FMRX_EINVAL, "audio_meters_process_dev: %zu samples per row (1 .. the handle's n_audio %zu)", n, m->n_audio);
-    if (row_pitch < n) return fail(FMRX_EINVAL, "audio_meters_process_dev: pitch of %zu floats is shorter than a row's %zu samples", row_pitch, n);
-    FMRX_HIP(hipSetDevice(m->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    AudioMetersArgs a;
-    a.x = d_audio;
-    a.pitch = row_pitch;
-    a.n = n;
-    a.n_channels = m->n_channels;
-    a.ac = m->ac;
-    std::memcpy(a.coef, m->coef.q, sizeof a.coef);
-    a.bin_len = static_cast<unsigned>(m->bin_len);
-    a.max_bins = m->max_bins;
-    a.state = m->d_state.p;
-    a.fill = m->d_fill.p;
-    a.sums = m->d_sums.p;
-    a.counts = m->d_counts.p;
-    a.bins = m->d_bins.p;
-    FMRX_TRY(audio_meters_launch(a, s));
-    FMRX_HIP(hipMemcpyAsync(m->h_sums, m->d_sums.p, m->d_sums.bytes(), hipMemcpyDeviceToHost, s));
-    FMRX_HIP(hipMemcpyAsync(m->h_counts, m->d_counts.p, m->d_counts.bytes(), hipMemcpyDeviceToHost, s));
-    FMRX_HIP(hipMemcpyAsync(m->h_bins, m->d_bins.p, m->d_bins.bytes(), hipMemcpyDeviceToHost, s));
-    FMRX_HIP(hipEventRecord(m->done, s));
-    m->n = n;
-    m->ran = true;
-    return FMRX_OK;
+    return meter_stage::read_dev("audio_meters_process_dev", m, launch, d_audio, row_pitch, n, stream);
 }
 
 int fmrx_audio_meters_collect(fmrx_audio_meters *m, fmrx_audio_meter *out, double *bins)
 {
-    if (!m || !out) return fail(FMRX_EINVAL, "audio_meters_collect: null argument");
-    if (!m->ran) return fail(FMRX_EINVAL, "audio_meters_collect: no call to collect");
-    FMRX_TRY(m->wait());
-    const size_t N = m->n_channels;
-    for (size_t c = 0; c < N; c++) {
+    FMRX_TRY(meter_stage::collected("audio_meters_collect", m, out));
+    const int N = m->n_channels;
+    for (size_t c = 0; c < static_cast<size_t>(N); c++) {
         fmrx_audio_meter &r = out[c];
         r.n = m->n;
         for (int k = 0; k < 2; k++) {
-            r.peak[k] = m->h_sums[(0 + k) * N + c];
-            r.sum_x[k] = m->h_sums[(2 + k) * N + c];
-            r.sum_x2[k] = m->h_sums[(4 + k) * N + c];
-            r.sum_k2[k] = m->h_sums[(6 + k) * N + c];
-            r.over[k] = m->h_counts[k * N + c];
+            r.peak[k] = field(m->h_sums.p, N, 0 + k, c);
+            r.sum_x[k] = field(m->h_sums.p, N, 2 + k, c);
+            r.sum_x2[k] = field(m->h_sums.p, N, 4 + k, c);
+            r.sum_k2[k] = field(m->h_sums.p, N, 6 + k, c);
+            r.over[k] = field(m->h_counts.p, N, k, c);
         }
-        r.sum_lr = m->h_sums[8 * N + c];
-        r.bins_done = m->h_counts[2 * N + c];
+        r.sum_lr = field(m->h_sums.p, N, 8, c);
+        r.bins_done = field(m->h_counts.p, N, 2, c);
     }
-    if (bins) std::memcpy(bins, m->h_bins, N * 2 * m->max_bins * sizeof(double));
+    if (bins) std::memcpy(bins, m->h_bins.p, m->h_bins.bytes());
     return FMRX_OK;
 }
 
 int fmrx_audio_meters_process(fmrx_audio_meters *m, const float *audio, size_t row_pitch, size_t n, fmrx_audio_meter *out, double *bins)
 {
-    if (!m || !audio || !out) return fail(FMRX_EINVAL, "audio_meters_process: null argument");
-    if (n < 1 || n > m->n_audio) return fail(FMRX_EINVAL, "audio_meters_process: %zu samples per row (1 .. the handle's n_audio %zu)", n, m->n_audio);
-    if (row_pitch < n) return fail(FMRX_EINVAL, "audio_meters_process: a pitch shorter than its row");
-    FMRX_HIP(hipSetDevice(m->device));
-    const size_t rows = static_cast<size_t>(m->n_channels) * m->ac, dp = (n + 3) / 4 * 4;   // the device copy's rows are 16-byte aligned
-    FMRX_TRY(m->d_rows.ensure(dp * rows));
-    FMRX_HIP(hipMemcpy2D(m->d_rows.p, dp * sizeof(float), audio, row_pitch * sizeof(float), n * sizeof(float), rows, hipMemcpyHostToDevice));
-    FMRX_TRY(fmrx_audio_meters_process_dev(m, m->d_rows.p, dp, n, nullptr));
-    return fmrx_audio_meters_collect(m, out, bins);
+    return meter_stage::read_host("audio_meters_process", m, launch, audio, row_pitch, n, out, [&] { return fmrx_audio_meters_collect(m, out, bins); });
 }
 
 }  // extern "C"

@@ -92,6 +92,24 @@ struct DevBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// ---- and its pinned host counterpart: where a call's asynchronous copies land ----------
+template <typename T>
+struct HostBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    ~HostBuf() { if (p) (void)hipHostFree(p); }
+    int alloc(size_t count)   // once per buffer
+    {
+        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), count * sizeof(T), hipHostMallocDefault));
+        n = count;
+        return FMRX_OK;
+    }
+    size_t bytes() const { return n * sizeof(T); }
+};
+
 // ---- front-end fast path (kernels_fe.hip) -----------------------------------
 // Device-side tap table for the register-window FIR: phase-major, padded,
 // pre-scaled.  See kernels_fe.hip for the layout.

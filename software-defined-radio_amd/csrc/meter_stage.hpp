@@ -1,13 +1,19 @@
 // meter_stage.hpp -- what the handles of a bank's meter chain share.  Handle: the device, the event the last call recorded and
-// the wait on it, with make / destroy, for the meters (meters.hip, audio_meters.hip) and the stages alike.  Stage: what the stages
-// that sit behind a meters handle on a bank's audio share (blend.hip, highcut.hip, leveller.hip and their kernel files): the
-// argument checks, the device call, the host call, status and reset, and the control kernel's body.  A stage adds its control
-// structure, its kernels' own buffers, its launch(handle, Call) and its source of control data: the type Source that a call
-// hands to launch, from_handle (what the meters handle in front left on the device, if it fits the stage) and from_records (the
-// host's records, uploaded).  Mpx is that source for the stages behind the signal meters.
+// the wait on it, with make / destroy and the guard of a collect, for the signal meters (meters.hip) and all below.  OnAudio: a
+// handle on a bank's audio rows, with the checks of a create and of a reset, each closed by a synchronise.  On it, two kinds.
+// Stage: what the stages that sit behind a meters handle on a bank's audio share (blend.hip, highcut.hip, leveller.hip and their
+// kernel files): the argument checks, the device call, the host call, status and reset, and the control kernel's body.  A stage
+// adds its control structure, its kernels' own buffers, its launch(handle, Call) and its source of control data: the type Source
+// that a call hands to launch, from_handle (what the meters handle in front left on the device, if it fits the stage) and
+// from_records (the host's records, uploaded).  Mpx is that source for the stages behind the signal meters.
+// Reader: what the meters that only read the audio rows share (audio_meters.hip, true_peak.hip): the checks of a call, the device
+// call, the host call and its staging, their field-major arrays [fields][n_channels], the checks of a derive.  A reader adds its
+// buffers, its launch(handle, rows, pitch, n, stream) (the kernel and the asynchronous copies of its results), the unpacking of
+// its records and its host arithmetic.
 //
 // Ordering: a call records the handle's `done` event on its stream; whatever touches the handle's rows from the host
-// (reset, status_get, the host call, a change of settings) waits for it first.
+// (reset, status_get, state_get, collect, the host call, a change of settings) waits for it first.  What a create or a reset clears
+// on the null stream is clear before it returns, so that a call on any stream, non-blocking ones included, finds it so.
 #pragma once
 #include "fmrx_internal.hpp"
 
@@ -63,17 +69,60 @@ int destroy(H *h)
     return FMRX_OK;
 }
 
+// in front of a collect: there is a call, and it is done
+inline int collected(const char *who, Handle *h, const void *out)
+{
+    if (!h || !out) return fail(FMRX_EINVAL, "%s: null argument", who);
+    if (!h->ran) return fail(FMRX_EINVAL, "%s: no call to collect", who);
+    return h->wait();
+}
+
+// a handle on a bank's audio rows [n_channels][audio_channels][n_audio]
+struct OnAudio : Handle {
+    int n_channels = 0, audio_channels = 0;
+    size_t n_audio = 0;
+    size_t rows() const { return static_cast<size_t>(n_channels) * audio_channels; }
+};
+
+// a new handle of type H (an OnAudio): the common checks, then init(h) for the type's own part; what that clears on the null
+// stream is clear before this returns
+template <class H, class Init>
+int create_on_audio(const char *who, H **out, int n_channels, int audio_channels, size_t n_audio, int device, Init init)
+{
+    if (!out) return fail(FMRX_EINVAL, "%s: null argument", who);
+    if (n_channels < 1) return fail(FMRX_EINVAL, "%s: n_channels must be >= 1", who);
+    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "%s: audio_channels %d: 1 or 2", who, audio_channels);
+    if (n_audio < 1 || n_audio > (size_t{1} << 26)) return fail(FMRX_EINVAL, "%s: n_audio %zu: 1 .. 2^26", who, n_audio);
+    return make(out, device, [&](H *h) -> int {
+        h->n_channels = n_channels;
+        h->audio_channels = audio_channels;
+        h->n_audio = n_audio;
+        FMRX_TRY(init(h));
+        FMRX_HIP(hipStreamSynchronize(nullptr));
+        return FMRX_OK;
+    });
+}
+
+// channel < 0: all of them.  clear(): the memsets of the type's carried state
+template <class Clear>
+int reset_on_audio(const char *who, OnAudio *h, int channel, Clear clear)
+{
+    if (!h) return fail(FMRX_EINVAL, "%s: null handle", who);
+    if (channel >= h->n_channels) return fail(FMRX_EINVAL, "%s: channel %d of %d", who, channel, h->n_channels);
+    FMRX_TRY(h->wait());
+    FMRX_TRY(clear());
+    FMRX_HIP(hipStreamSynchronize(nullptr));   // the rows are clear before this returns: a call on any stream, non-blocking ones included, finds them so
+    return FMRX_OK;
+}
+
 // one status row per channel on the device -- state and result at once --, and, for the host call only, device copies of the
 // host's rows
 template <class Status>
-struct Stage : Handle {
-    int n_channels = 0, audio_channels = 0;
-    size_t n_audio = 0;
+struct Stage : OnAudio {
     float inv_n = 0.0f;
     DevBuf<Status> d_status;
     DevBuf<float> d_in, d_out;                // the host call only
     DevBuf<int16_t> d_pcm;
-    size_t rows() const { return static_cast<size_t>(n_channels) * audio_channels; }
 };
 
 // what a stage's launch gets: its source of control data, the rows, the stream
@@ -103,19 +152,11 @@ inline int check_rows(const char *who, const float *in, const float *out, const 
 template <class H, class Init>
 int create(const char *who, H **out, int n_channels, int audio_channels, size_t n_audio, int device, Init init)
 {
-    if (n_channels < 1) return fail(FMRX_EINVAL, "%s: n_channels must be >= 1", who);
-    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "%s: audio_channels %d: 1 or 2", who, audio_channels);
-    if (n_audio < 1 || n_audio > (size_t{1} << 26)) return fail(FMRX_EINVAL, "%s: n_audio %zu: 1 .. 2^26", who, n_audio);
-    return make(out, device, [&](H *h) -> int {
-        h->n_channels = n_channels;
-        h->audio_channels = audio_channels;
-        h->n_audio = n_audio;
+    return create_on_audio(who, out, n_channels, audio_channels, n_audio, device, [&](H *h) -> int {
         h->inv_n = static_cast<float>(1.0 / static_cast<double>(n_audio));
         FMRX_TRY(h->d_status.alloc(n_channels));
         FMRX_HIP(hipMemset(h->d_status.p, 0, h->d_status.bytes()));
-        FMRX_TRY(init(h));
-        FMRX_HIP(hipStreamSynchronize(nullptr));
-        return FMRX_OK;
+        return init(h);
     });
 }
 
@@ -123,14 +164,11 @@ int create(const char *who, H **out, int n_channels, int audio_channels, size_t 
 template <class Status, class Extra>
 int reset(const char *who, Stage<Status> *h, int channel, Extra extra)
 {
-    if (!h) return fail(FMRX_EINVAL, "%s: null handle", who);
-    if (channel >= h->n_channels) return fail(FMRX_EINVAL, "%s: channel %d of %d", who, channel, h->n_channels);
-    FMRX_TRY(h->wait());
-    if (channel < 0) FMRX_HIP(hipMemset(h->d_status.p, 0, h->d_status.bytes()));
-    else FMRX_HIP(hipMemset(h->d_status.p + channel, 0, sizeof(Status)));
-    FMRX_TRY(extra());
-    FMRX_HIP(hipStreamSynchronize(nullptr));   // the rows are clear before this returns: a call on any stream, non-blocking ones included, finds them so
-    return FMRX_OK;
+    return reset_on_audio(who, h, channel, [&]() -> int {
+        if (channel < 0) FMRX_HIP(hipMemset(h->d_status.p, 0, h->d_status.bytes()));
+        else FMRX_HIP(hipMemset(h->d_status.p + channel, 0, sizeof(Status)));
+        return extra();
+    });
 }
 
 template <class Status>
@@ -197,6 +235,79 @@ int process(const char *who, H *h, Launch<H> launch, const Record *recs, const f
     if (out) FMRX_HIP(hipMemcpy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost));
     if (pcm16) FMRX_HIP(hipMemcpy(pcm16, d_pcm, total * sizeof(int16_t), hipMemcpyDeviceToHost));
     return FMRX_OK;
+}
+
+// ---- the readers: meters of a bank's audio rows that keep their state and results field-major on the device
+struct Reader : OnAudio {
+    size_t n = 0;            // samples per row of the last call
+    DevBuf<float> d_rows;    // the host call only
+};
+
+// a reader's launch: its kernel on rows [n_channels][audio_channels][pitch] of n samples, then the asynchronous copies of its results
+template <class H>
+using Read = int (*)(H *, const float *d_audio, size_t pitch, size_t n, hipStream_t s);
+
+inline int check_read(const char *who, const Reader *h, const float *audio, size_t row_pitch, size_t n)
+{
+    if (!h || !audio) return fail(FMRX_EINVAL, "%s: null argument", who);
+    if (n < 1 || n > h->n_audio) return fail(FMRX_EINVAL, "%s: %zu samples per row (1 .. the handle's n_audio %zu)", who, n, h->n_audio);
+    if (row_pitch < n) return fail(FMRX_EINVAL, "%s: pitch of %zu floats is shorter than a row's %zu samples", who, row_pitch, n);
+    return FMRX_OK;
+}
+
+// the device call, asynchronous on `stream`
+template <class H>
+int read_dev(const char *who, H *h, Read<H> launch, const float *d_audio, size_t row_pitch, size_t n, void *stream)
+{
+    FMRX_TRY(check_read(who, h, d_audio, row_pitch, n));
+    FMRX_HIP(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FMRX_TRY(launch(h, d_audio, row_pitch, n, s));
+    FMRX_HIP(hipEventRecord(h->done, s));
+    h->n = n;
+    h->ran = true;
+    return FMRX_OK;
+}
+
+// the host call: the rows go to the device, the reader runs on the null stream, collect() unpacks into `out`
+template <class H, class Collect>
+int read_host(const char *who, H *h, Read<H> launch, const float *audio, size_t row_pitch, size_t n, const void *out, Collect collect)
+{
+    FMRX_TRY(check_read(who, h, audio, row_pitch, n));
+    if (!out) return fail(FMRX_EINVAL, "%s: null argument", who);
+    FMRX_TRY(h->wait());   // this call runs on the null stream
+    const size_t dp = (n + 3) / 4 * 4;   // the device copy's rows are 16-byte aligned
+    FMRX_TRY(h->d_rows.ensure(dp * h->rows()));
+    FMRX_HIP(hipMemcpy2D(h->d_rows.p, dp * sizeof(float), audio, row_pitch * sizeof(float), n * sizeof(float), h->rows(), hipMemcpyHostToDevice));
+    FMRX_TRY(read_dev(who, h, launch, h->d_rows.p, dp, n, nullptr));
+    return collect();
+}
+
+// field-major arrays [fields][n_channels]: all of it (channel < 0) or one channel's column cleared, on the null stream
+template <class T>
+int clear_fields(T *d, int fields, int n_channels, int channel)
+{
+    const size_t N = n_channels;
+    if (channel < 0) FMRX_HIP(hipMemset(d, 0, fields * N * sizeof(T)));
+    else FMRX_HIP(hipMemset2D(d + channel, N * sizeof(T), 0, sizeof(T), fields));
+    return FMRX_OK;
+}
+
+template <class T>
+T field(const T *a, int n_channels, int k, size_t c) { return a[static_cast<size_t>(k) * n_channels + c]; }   // field k of channel c
+
+// what the readers' derive functions share (host only)
+inline int check_derive(const char *who, const void *m, const void *out, int audio_channels, double full_scale)
+{
+    if (!m || !out) return fail(FMRX_EINVAL, "%s: null argument", who);
+    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "%s: audio_channels must be 1 or 2", who);
+    if (!(full_scale > 0.0) || !std::isfinite(full_scale)) return fail(FMRX_EINVAL, "%s: full_scale %g", who, full_scale);
+    return FMRX_OK;
+}
+
+inline double over_fraction(const uint64_t over[2], uint64_t n, int audio_channels)
+{
+    return n > 0 ? (static_cast<double>(over[0]) + static_cast<double>(over[1])) / (static_cast<double>(n) * audio_channels) : 0.0;
 }
 
 // ---- the signal meters as a stage's source: the MPX results [n_channels][kMetersMpxFields] and the segments of every channel

@@ -16,16 +16,11 @@ struct fmrx_meters : meter_stage::Handle {
     double if_Fs = 0.0;
     DevBuf<double> d_table, d_mpx;
     DevBuf<unsigned long long> d_rf;
-    unsigned long long *h_rf = nullptr;   // pinned
-    double *h_mpx = nullptr;              // pinned
+    HostBuf<unsigned long long> h_rf;
+    HostBuf<double> h_mpx;
     size_t n_iq = 0, n_if = 0;            // of the last call; 0 = that group was not measured
     DevBuf<uint8_t> d_iq;                 // fmrx_meters_process only
     DevBuf<float> d_demod;
-    ~fmrx_meters()
-    {
-        if (h_rf) (void)hipHostFree(h_rf);
-        if (h_mpx) (void)hipHostFree(h_mpx);
-    }
 };
 
 namespace {
@@ -111,9 +106,8 @@ int fmrx_meters_create(fmrx_meters **out, double if_Fs, int n_channels, int devi
         FMRX_HIP(hipMemcpy(m->d_table.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
         FMRX_TRY(m->d_rf.alloc(N * kMetersRfFields));
         FMRX_TRY(m->d_mpx.alloc(N * kMetersMpxFields));
-        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_rf), m->d_rf.bytes(), hipHostMallocDefault));
-        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_mpx), m->d_mpx.bytes(), hipHostMallocDefault));
-        return FMRX_OK;
+        FMRX_TRY(m->h_rf.alloc(m->d_rf.n));
+        return m->h_mpx.alloc(m->d_mpx.n);
     });
 }
 
@@ -145,8 +139,8 @@ int fmrx_meters_process_dev(fmrx_meters *m, const uint8_t *d_iq_first, size_t iq
     } else {
         FMRX_HIP(hipMemsetAsync(m->d_mpx.p, 0, m->d_mpx.bytes(), s));
     }
-    FMRX_HIP(hipMemcpyAsync(m->h_rf, m->d_rf.p, m->d_rf.bytes(), hipMemcpyDeviceToHost, s));
-    FMRX_HIP(hipMemcpyAsync(m->h_mpx, m->d_mpx.p, m->d_mpx.bytes(), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_rf.p, m->d_rf.p, m->d_rf.bytes(), hipMemcpyDeviceToHost, s));
+    FMRX_HIP(hipMemcpyAsync(m->h_mpx.p, m->d_mpx.p, m->d_mpx.bytes(), hipMemcpyDeviceToHost, s));
     FMRX_HIP(hipEventRecord(m->done, s));
     m->n_iq = d_iq_first ? n_iq_bytes / 2 : 0;
     m->n_if = d_demod_row0 ? n_if : 0;
@@ -156,12 +150,10 @@ int fmrx_meters_process_dev(fmrx_meters *m, const uint8_t *d_iq_first, size_t iq
 
 int fmrx_meters_collect(fmrx_meters *m, fmrx_meter *out)
 {
-    if (!m || !out) return fail(FMRX_EINVAL, "meters_collect: null argument");
-    if (!m->ran) return fail(FMRX_EINVAL, "meters_collect: no call to collect");
-    FMRX_TRY(m->wait());
+    FMRX_TRY(meter_stage::collected("meters_collect", m, out));
     for (size_t c = 0; c < static_cast<size_t>(m->n_channels); c++) {
-        const unsigned long long *rf = m->h_rf + c * kMetersRfFields;
-        const double *mpx = m->h_mpx + c * kMetersMpxFields;
+        const unsigned long long *rf = m->h_rf.p + c * kMetersRfFields;
+        const double *mpx = m->h_mpx.p + c * kMetersMpxFields;
         fmrx_meter &r = out[c];
         std::memset(&r, 0, sizeof r);
         r.n_iq = m->n_iq;

@@ -3,31 +3,23 @@
 // kernels_true_peak.hip; the interpolator, shared with fmrx_true_peak_walk below: true_peak_core.hpp; definition:
 // tests/_true_peak_model.py.
 //
-// A handle of the audio meters' kind (audio_meters.hip): it only reads the rows.  It keeps the rows' carried samples on the
-// device in two buffers, one read and one written per call (field-major, see fmrx_internal.hpp), the result array a call
-// writes, its pinned host copy, and meter_stage.hpp's handle base: the event the last call recorded behind the copy; collect
-// waits on that event, not on the device.
+// A reader of meter_stage.hpp: it only reads the rows.  Its own part is the rows' carried samples on the device in two buffers,
+// one read and one written per call (field-major), the result array a call writes and its pinned host copy, the launch that
+// fills them, the records' layout and the host arithmetic.
 #include "meter_stage.hpp"
 #include "true_peak_core.hpp"
 
 #include <cmath>
 
 using namespace fmrx;
+using meter_stage::field;
 
-struct fmrx_true_peak : meter_stage::Handle {
-    int n_channels = 0, ac = 1;
-    size_t n_audio = 0;
+struct fmrx_true_peak : meter_stage::Reader {
     float limit = 0.0f;
     DevBuf<float> d_state[2];
     int cur = 0;                 // the buffer the next call reads
     DevBuf<unsigned> d_res;
-    unsigned *h_res = nullptr;   // pinned
-    size_t n = 0;                // of the last call
-    DevBuf<float> d_rows;        // fmrx_true_peak_process only
-    ~fmrx_true_peak()
-    {
-        if (h_res) (void)hipHostFree(h_res);
-    }
+    HostBuf<unsigned> h_res;
 };
 
 namespace {
@@ -56,6 +48,24 @@ void walk_row(const float *row, size_t n, float limit, float *carry, true_peak::
         true_peak::run<kRun>(w, n - i < static_cast<size_t>(kRun) ? static_cast<int>(n - i) : kRun, limit, acc);
     }
     std::memcpy(carry, e.data() + n, kCarry * sizeof(float));
+}
+
+int launch(fmrx_true_peak *m, const float *d_audio, size_t pitch, size_t n, hipStream_t s)
+{
+    TruePeakArgs a;
+    a.x = d_audio;
+    a.pitch = pitch;
+    a.n = n;
+    a.n_channels = m->n_channels;
+    a.ac = m->audio_channels;
+    a.limit = m->limit;
+    a.state_in = m->d_state[m->cur].p;
+    a.state_out = m->d_state[m->cur ^ 1].p;
+    a.res = m->d_res.p;
+    FMRX_TRY(true_peak_launch(a, s));
+    m->cur ^= 1;
+    FMRX_HIP(hipMemcpyAsync(m->h_res.p, m->d_res.p, m->d_res.bytes(), hipMemcpyDeviceToHost, s));
+    return FMRX_OK;
 }
 
 }  // namespace
@@ -94,10 +104,8 @@ int fmrx_true_peak_walk(int audio_channels, const float *rows, size_t row_pitch,
 
 int fmrx_true_peak_derive(const fmrx_true_peak_record *m, int audio_channels, double full_scale, fmrx_true_peak_levels *out)
 {
-    if (!m || !out) return fail(FMRX_EINVAL, "true_peak_derive: null argument");
-    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "true_peak_derive: audio_channels must be 1 or 2");
-    if (!(full_scale > 0.0) || !std::isfinite(full_scale)) return fail(FMRX_EINVAL, "true_peak_derive: full_scale %g", full_scale);
-    const double n = static_cast<double>(m->n), fs2 = full_scale * full_scale;
+    FMRX_TRY(meter_stage::check_derive("true_peak_derive", m, out, audio_channels, full_scale));
+    const double fs2 = full_scale * full_scale;
     std::memset(out, 0, sizeof *out);
     out->max_dbtp = -99.0;
     for (int r = 0; r < 2; r++) {
@@ -106,31 +114,22 @@ int fmrx_true_peak_derive(const fmrx_true_peak_record *m, int audio_channels, do
         out->peak_dbfs[r] = has ? db(m->peak[r] * m->peak[r], fs2) : -99.0;
         if (out->true_peak_dbtp[r] > out->max_dbtp) out->max_dbtp = out->true_peak_dbtp[r];
     }
-    out->over_fraction = n > 0.0 ? (static_cast<double>(m->over[0]) + static_cast<double>(m->over[1])) / (n * audio_channels) : 0.0;
+    out->over_fraction = meter_stage::over_fraction(m->over, m->n, audio_channels);
     return FMRX_OK;
 }
 
 int fmrx_true_peak_create(fmrx_true_peak **out, int n_channels, int audio_channels, size_t n_audio, float limit, int device)
 {
-    if (!out) return fail(FMRX_EINVAL, "true_peak_create: null argument");
-    if (n_channels < 1) return fail(FMRX_EINVAL, "true_peak_create: n_channels must be >= 1");
-    if (audio_channels != 1 && audio_channels != 2) return fail(FMRX_EINVAL, "true_peak_create: audio_channels must be 1 or 2");
-    if (n_audio < 1 || n_audio > (size_t{1} << 26)) return fail(FMRX_EINVAL, "true_peak_create: n_audio %zu (1 .. 2^26)", n_audio);
     if (!good_limit(limit)) return fail(FMRX_EINVAL, "true_peak_create: limit %g (finite, > 0)", limit);
-    return meter_stage::make(out, device, [&](fmrx_true_peak *m) -> int {
+    return meter_stage::create_on_audio("true_peak_create", out, n_channels, audio_channels, n_audio, device, [&](fmrx_true_peak *m) -> int {
         const size_t N = n_channels;
-        m->n_channels = n_channels;
-        m->ac = audio_channels;
-        m->n_audio = n_audio;
         m->limit = limit;
         for (auto &b : m->d_state) {
             FMRX_TRY(b.alloc(N * kTruePeakStateFields));
-            FMRX_HIP(hipMemset(b.p, 0, b.bytes()));
+            FMRX_TRY(meter_stage::clear_fields(b.p, kTruePeakStateFields, n_channels, -1));
         }
         FMRX_TRY(m->d_res.alloc(N * kTruePeakFields));
-        FMRX_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->h_res), m->d_res.bytes(), hipHostMallocDefault));
-        FMRX_HIP(hipStreamSynchronize(nullptr));
-        return FMRX_OK;
+        return m->h_res.alloc(m->d_res.n);
     });
 }
 
@@ -138,67 +137,39 @@ int fmrx_true_peak_destroy(fmrx_true_peak *m) { return meter_stage::destroy(m); 
 
 int fmrx_true_peak_reset(fmrx_true_peak *m, int channel)
 {
-    if (!m) return fail(FMRX_EINVAL, "true_peak_reset: null handle");
-    if (channel >= m->n_channels) return fail(FMRX_EINVAL, "true_peak_reset: channel %d of %d", channel, m->n_channels);
-    FMRX_TRY(m->wait());
-    DevBuf<float> &b = m->d_state[m->cur];
-    if (channel < 0) FMRX_HIP(hipMemset(b.p, 0, b.bytes()));
-    else FMRX_HIP(hipMemset2D(b.p + channel, m->n_channels * sizeof(float), 0, sizeof(float), kTruePeakStateFields));   // the channel's column
-    FMRX_HIP(hipStreamSynchronize(nullptr));   // clear before this returns: a call on any stream, non-blocking ones included, finds it so
-    return FMRX_OK;
+    return meter_stage::reset_on_audio("true_peak_reset", m, channel,
+                                       [&] { return meter_stage::clear_fields(m->d_state[m->cur].p, kTruePeakStateFields, m->n_channels, channel); });
 }
 
 int fmrx_true_peak_state_get(fmrx_true_peak *m, float *out)
 {
     if (!m || !out) return fail(FMRX_EINVAL, "true_peak_state_get: null argument");
     FMRX_TRY(m->wait());
-    const size_t N = m->n_channels;
-    std::vector<float> st(N * kTruePeakStateFields);
-    FMRX_HIP(hipMemcpy(st.data(), m->d_state[m->cur].p, st.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < N; c++)
-        for (int f = 0; f < kTruePeakStateFields; f++) out[c * kTruePeakStateFields + f] = f < m->ac * kCarry ? st[f * N + c] : 0.0f;
+    const DevBuf<float> &b = m->d_state[m->cur];
+    std::vector<float> st(b.n);
+    FMRX_HIP(hipMemcpy(st.data(), b.p, b.bytes(), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < static_cast<size_t>(m->n_channels); c++)
+        for (int f = 0; f < kTruePeakStateFields; f++)
+            out[c * kTruePeakStateFields + f] = f < m->audio_channels * kCarry ? field(st.data(), m->n_channels, f, c) : 0.0f;
     return FMRX_OK;
 }
 
 int fmrx_true_peak_process_dev(fmrx_true_peak *m, const float *d_audio, size_t row_pitch, size_t n, void *stream)
 {
-    if (!m || !d_audio) return fail(FMRX_EINVAL, "true_peak_process_dev: null argument");
-    if (n < 1 || n > m->n_audio) return fail(FMRX_EINVAL, "true_peak_process_dev: %zu samples per row (1 .. the handle's n_audio %zu)", n, m->n_audio);
-    if (row_pitch < n) return fail(FMRX_EINVAL, "true_peak_process_dev: pitch of %zu floats is shorter than a row's %zu samples", row_pitch, n);
-    FMRX_HIP(hipSetDevice(m->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TruePeakArgs a;
-    a.x = d_audio;
-    a.pitch = row_pitch;
-    a.n = n;
-    a.n_channels = m->n_channels;
-    a.ac = m->ac;
-    a.limit = m->limit;
-    a.state_in = m->d_state[m->cur].p;
-    a.state_out = m->d_state[m->cur ^ 1].p;
-    a.res = m->d_res.p;
-    FMRX_TRY(true_peak_launch(a, s));
-    m->cur ^= 1;
-    FMRX_HIP(hipMemcpyAsync(m->h_res, m->d_res.p, m->d_res.bytes(), hipMemcpyDeviceToHost, s));
-    FMRX_HIP(hipEventRecord(m->done, s));
-    m->n = n;
-    m->ran = true;
-    return FMRX_OK;
+    return meter_stage::read_dev("true_peak_process_dev", m, launch, d_audio, row_pitch, n, stream);
 }
 
 int fmrx_true_peak_collect(fmrx_true_peak *m, fmrx_true_peak_record *out)
 {
-    if (!m || !out) return fail(FMRX_EINVAL, "true_peak_collect: null argument");
-    if (!m->ran) return fail(FMRX_EINVAL, "true_peak_collect: no call to collect");
-    FMRX_TRY(m->wait());
-    const size_t N = m->n_channels;
-    for (size_t c = 0; c < N; c++) {
+    FMRX_TRY(meter_stage::collected("true_peak_collect", m, out));
+    const int N = m->n_channels;
+    for (size_t c = 0; c < static_cast<size_t>(N); c++) {
         fmrx_true_peak_record &r = out[c];
         r.n = m->n;
         for (int k = 0; k < 2; k++) {
-            r.true_peak[k] = static_cast<double>(bits_float(m->h_res[(0 + k) * N + c]));
-            r.peak[k] = static_cast<double>(bits_float(m->h_res[(2 + k) * N + c]));
-            r.over[k] = m->h_res[(4 + k) * N + c];
+            r.true_peak[k] = static_cast<double>(bits_float(field(m->h_res.p, N, 0 + k, c)));
+            r.peak[k] = static_cast<double>(bits_float(field(m->h_res.p, N, 2 + k, c)));
+            r.over[k] = field(m->h_res.p, N, 4 + k, c);
         }
     }
     return FMRX_OK;
@@ -206,15 +177,7 @@ int fmrx_true_peak_collect(fmrx_true_peak *m, fmrx_true_peak_record *out)
 
 int fmrx_true_peak_process(fmrx_true_peak *m, const float *audio, size_t row_pitch, size_t n, fmrx_true_peak_record *out)
 {
-    if (!m || !audio || !out) return fail(FMRX_EINVAL, "true_peak_process: null argument");
-    if (n < 1 || n > m->n_audio) return fail(FMRX_EINVAL, "true_peak_process: %zu samples per row (1 .. the handle's n_audio %zu)", n, m->n_audio);
-    if (row_pitch < n) return fail(FMRX_EINVAL, "true_peak_process: a pitch shorter than its row");
-    FMRX_TRY(m->wait());   // this call runs on the null stream
-    const size_t rows = static_cast<size_t>(m->n_channels) * m->ac, dp = (n + 3) / 4 * 4;   // the device copy's rows are 16-byte aligned
-    FMRX_TRY(m->d_rows.ensure(dp * rows));
-    FMRX_HIP(hipMemcpy2D(m->d_rows.p, dp * sizeof(float), audio, row_pitch * sizeof(float), n * sizeof(float), rows, hipMemcpyHostToDevice));
-    FMRX_TRY(fmrx_true_peak_process_dev(m, m->d_rows.p, dp, n, nullptr));
-    return fmrx_true_peak_collect(m, out);
+    return meter_stage::read_host("true_peak_process", m, launch, audio, row_pitch, n, out, [&] { return fmrx_true_peak_collect(m, out); });
 }
 
 }  // extern "C"

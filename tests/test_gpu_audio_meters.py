@@ -209,6 +209,30 @@ def test_7_a_second_call_before_collect_replaces_the_results(fmrx):
     m.close()
 
 
+def test_8_the_host_call_runs_behind_a_device_call_on_another_stream(fmrx):
+    """process_dev on a non-blocking stream, then at once the host call, which runs on the null stream: its results are those of
+    the two calls in that order.  (A race need not lose: this pins the sequence's result; that the host call waits for the
+    handle's last call first is read in meter_stage.hpp's read_host.)"""
+    import torch
+    N, ac = 3, 2
+    n = am.bin_len(FS) + 3                                 # a bin closes within each call
+    assert n == 4803
+    rng = np.random.default_rng(8)
+    x0, x1 = ((0.7 * rng.standard_normal((N, ac, n))).astype(np.float32) for _ in range(2))
+    _, _, state0 = am.walk(FS, x0, am.fresh(N), am.max_bins(FS, n))
+    rec1, bins1, state1 = am.walk(FS, x1, state0, am.max_bins(FS, n))
+    m = fmrx.AudioMeters(FS, N, ac, n)
+    stream = torch.cuda.Stream()
+    t0 = torch.from_numpy(x0).cuda()
+    torch.cuda.synchronize()
+    m.process_dev(t0.data_ptr(), stream=stream.cuda_stream)
+    got_rec, got_bins = m.process(x1)
+    assert am.same(got_rec, rec1) and am.same(got_bins, bins1) and (got_rec["bins_done"] == 1).all()
+    check_state(m.state(), state1, N, ac)
+    stream.synchronize()
+    m.close()
+
+
 def test_arguments_are_checked(fmrx):
     import torch
     t = torch.zeros(64, dtype=torch.float32, device="cuda")

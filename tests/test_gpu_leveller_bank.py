@@ -1,24 +1,20 @@
-"""The leveller at the end of the chain, on one stream: a fast stereo bank of mode 0 with 8 channels on the same synthetic
-programme -> a gain per channel (0.1, 1, 4, 0 = an empty channel, 30, and 0.1, 1, 4 again) -> AudioMeters.for_bank ->
-Leveller.for_bank, 50 calls of 1 920 samples (2 s).  (1) the device chain equals the host chain (collect ->
+"""The leveller at the end of the chain of tests/_gain_chain.py (bank -> a gain per channel -> AudioMeters.for_bank ->
+Leveller.for_bank, on one stream), 50 calls of 1 920 samples (2 s).  (1) the device chain equals the host chain (collect ->
 fmrx_leveller_process) bit for bit, and the control rows equal the model's on the collected records; (2) the ungated channels
 end at the target, or at their clamp on its far side, within a tolerance the model gives on the same records; (3) the empty
 channel stays gated at gain 1 and silent; (4) no PCM sample of the output wraps, though the loud channels' input lies beyond
 what the pack holds."""
-import importlib
 import math
 
 import numpy as np
 import pytest
 
 import _leveller_model as lm
+from _gain_chain import EMPTY, GAINS, HOT, N, gain_chain
 
 pytestmark = pytest.mark.gpu
 
-N, CALLS, W = 8, 50, 64
-GAINS = (0.1, 1.0, 4.0, 0.0, 30.0, 0.1, 1.0, 4.0)
-BYTES_PER_CALL = 192000             # 96 000 I/Q samples at 2.4 MS/s: 1 920 audio samples at 48 kHz
-EMPTY, HOT = 3, 4
+CALLS, W = 50, 64
 
 
 def lkfs(ms):
@@ -27,43 +23,25 @@ def lkfs(ms):
 
 @pytest.fixture(scope="module")
 def chain(fmrx, oracle):
-    import torch
-    synth = importlib.import_module(fmrx.__name__ + ".synth")
-    iq = synth.synth_fm_u8(CALLS * BYTES_PER_CALL // 2)
-    bank = fmrx.Channels(0, N, audio_channels=2, exact=False, block_bytes=BYTES_PER_CALL)
-    ac, n = bank.audio_channels, bank.n_audio
-    am, am_out = fmrx.AudioMeters.for_bank(bank), fmrx.AudioMeters.for_bank(bank)
-    lv = fmrx.Leveller.for_bank(bank, am, lookahead=W)
-    host = fmrx.Leveller(bank.params.audio_Fs, N, ac, n, lookahead=W)
-    d_iq = torch.from_numpy(iq.reshape(CALLS, BYTES_PER_CALL)).cuda()
-    d_gain = torch.tensor(GAINS, dtype=torch.float32, device="cuda").reshape(N, 1, 1)
-    d_audio = torch.zeros((N, ac, n), dtype=torch.float32, device="cuda")
-    d_out = torch.full((N, ac, n), 7.0, dtype=torch.float32, device="cuda")
-    d_pcm = torch.zeros((N, n, ac), dtype=torch.int16, device="cuda")
-    stream = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    calls = []
-    with torch.cuda.stream(stream):
-        s = stream.cuda_stream
-        for i in range(CALLS):
-            d_block = d_iq[i].expand(N, BYTES_PER_CALL).contiguous()
-            bank.load_dev(d_block.data_ptr(), stream=s)
-            bank.process_dev(d_audio.data_ptr(), None, stream=s)
-            d_audio.mul_(d_gain)                                           # the stations differ in level
-            am.process_bank(d_audio.data_ptr(), stream=s)
-            lv.process_bank(d_audio.data_ptr(), d_out.data_ptr(), d_pcm.data_ptr(), stream=s)
-            am_out.process_bank(d_out.data_ptr(), stream=s)
+    with gain_chain(fmrx, CALLS, lookahead=W) as ch:
+        am, lv, d_audio, d_out, d_pcm = ch.am, ch.lv, ch.d_audio, ch.d_out, ch.d_pcm
+        am_out = fmrx.AudioMeters.for_bank(ch.bank)
+        host = fmrx.Leveller(ch.bank.params.audio_Fs, N, ch.ac, ch.n, lookahead=W)
+        calls = []
+        for i in ch.calls():
+            lv.process_bank(d_audio.data_ptr(), d_out.data_ptr(), d_pcm.data_ptr(), stream=ch.s)
+            am_out.process_bank(d_out.data_ptr(), stream=ch.s)
             recs, _ = am.collect()
             out_recs, _ = am_out.collect()
-            stream.synchronize()
+            ch.stream.synchronize()
             calls.append(dict(recs=recs, out_recs=out_recs, status=lv.status(), audio=d_audio.cpu().numpy(), out=d_out.cpu().numpy(),
                               pcm=d_pcm.cpu().numpy()))
-    for c in calls:                                                        # the host chain, from the collected records
-        o = host.process(c["recs"], c["audio"])
-        c["host_out"], c["host_pcm"], c["host_status"] = o["audio"], o["pcm16"], host.status()
-    info = dict(calls=calls, ac=ac, n=n, audio_Fs=float(bank.params.audio_Fs), ceiling=lv.ceiling, latency=lv.latency)
-    for x in (host, lv, am_out, am, bank):
-        x.close()
+        for c in calls:                                                        # the host chain, from the collected records
+            o = host.process(c["recs"], c["audio"])
+            c["host_out"], c["host_pcm"], c["host_status"] = o["audio"], o["pcm16"], host.status()
+        info = dict(calls=calls, ac=ch.ac, n=ch.n, audio_Fs=float(ch.bank.params.audio_Fs), ceiling=lv.ceiling, latency=lv.latency)
+        host.close()
+        am_out.close()
     return info
 
 

@@ -1,62 +1,39 @@
-"""The true-peak meter at both ends of the audio stages, on one stream: the chain of tests/test_gpu_leveller_bank.py -- a fast
-stereo bank of mode 0 with 8 channels on the same synthetic programme -> a gain per channel (0.1, 1, 4, 0 = an empty channel,
-30, and 0.1, 1, 4 again) -> AudioMeters.for_bank -> Leveller.for_bank --, with one TruePeak on the audio meters' input and one on
-the leveller's float output, 12 calls of 1 920 samples.  (1) every device record equals truePeakWalk of the collected rows bit
+"""The true-peak meter at both ends of the audio stages, on one stream: the chain of tests/_gain_chain.py (bank -> a gain per
+channel -> AudioMeters.for_bank -> Leveller.for_bank) with one TruePeak on the audio meters' input and one on the leveller's float
+output, 12 calls of 1 920 samples.  (1) every device record equals truePeakWalk of the collected rows bit
 for bit; (2) true_peak >= peak everywhere; (3) the empty channel reads the floor; (4) how far the limited channel's output true
 peak lies above the leveller's ceiling is printed for DESIGN.md section 4.16: the limiter bounds samples, not the waveform
 between them, so nothing beyond finiteness is asserted of it."""
-import importlib
 import math
 
 import numpy as np
 import pytest
 
 import _true_peak_model as tp
+from _gain_chain import EMPTY, GAINS, HOT, N, gain_chain
 
 pytestmark = pytest.mark.gpu
 
-N, CALLS, W = 8, 12, 64
-GAINS = (0.1, 1.0, 4.0, 0.0, 30.0, 0.1, 1.0, 4.0)
-BYTES_PER_CALL = 192000             # 96 000 I/Q samples at 2.4 MS/s: 1 920 audio samples at 48 kHz
-EMPTY, HOT = 3, 4
+CALLS, W = 12, 64
 
 
 @pytest.fixture(scope="module")
 def chain(fmrx):
-    import torch
-    synth = importlib.import_module(fmrx.__name__ + ".synth")
-    iq = synth.synth_fm_u8(CALLS * BYTES_PER_CALL // 2)
-    bank = fmrx.Channels(0, N, audio_channels=2, exact=False, block_bytes=BYTES_PER_CALL)
-    ac, n = bank.audio_channels, bank.n_audio
-    am = fmrx.AudioMeters.for_bank(bank)
-    lv = fmrx.Leveller.for_bank(bank, am, lookahead=W)
-    tp_in, tp_out = fmrx.TruePeak.for_bank(bank), fmrx.TruePeak.for_bank(bank, limit=lv.ceiling)
-    assert (tp_in.n_channels, tp_in.audio_channels, tp_in.n_audio, tp_in.limit) == (N, ac, n, fmrx.TRUE_PEAK_LIMIT)
-    d_iq = torch.from_numpy(iq.reshape(CALLS, BYTES_PER_CALL)).cuda()
-    d_gain = torch.tensor(GAINS, dtype=torch.float32, device="cuda").reshape(N, 1, 1)
-    d_audio = torch.zeros((N, ac, n), dtype=torch.float32, device="cuda")
-    d_out = torch.full((N, ac, n), 7.0, dtype=torch.float32, device="cuda")
-    d_pcm = torch.zeros((N, n, ac), dtype=torch.int16, device="cuda")
-    stream = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    calls = []
-    with torch.cuda.stream(stream):
-        s = stream.cuda_stream
-        for i in range(CALLS):
-            d_block = d_iq[i].expand(N, BYTES_PER_CALL).contiguous()
-            bank.load_dev(d_block.data_ptr(), stream=s)
-            bank.process_dev(d_audio.data_ptr(), None, stream=s)
-            d_audio.mul_(d_gain)                                           # the stations differ in level
-            am.process_bank(d_audio.data_ptr(), stream=s)
-            tp_in.process_bank(d_audio.data_ptr(), stream=s)
-            lv.process_bank(d_audio.data_ptr(), d_out.data_ptr(), d_pcm.data_ptr(), stream=s)
-            tp_out.process_bank(d_out.data_ptr(), stream=s)
+    with gain_chain(fmrx, CALLS, lookahead=W) as ch:
+        lv, d_audio, d_out = ch.lv, ch.d_audio, ch.d_out
+        tp_in, tp_out = fmrx.TruePeak.for_bank(ch.bank), fmrx.TruePeak.for_bank(ch.bank, limit=lv.ceiling)
+        assert (tp_in.n_channels, tp_in.audio_channels, tp_in.n_audio, tp_in.limit) == (N, ch.ac, ch.n, fmrx.TRUE_PEAK_LIMIT)
+        calls = []
+        for i in ch.calls():
+            tp_in.process_bank(d_audio.data_ptr(), stream=ch.s)
+            lv.process_bank(d_audio.data_ptr(), d_out.data_ptr(), ch.d_pcm.data_ptr(), stream=ch.s)
+            tp_out.process_bank(d_out.data_ptr(), stream=ch.s)
             rec_in, rec_out = tp_in.collect(), tp_out.collect()
-            stream.synchronize()
+            ch.stream.synchronize()
             calls.append(dict(rec_in=rec_in, rec_out=rec_out, status=lv.status(), audio=d_audio.cpu().numpy(), out=d_out.cpu().numpy()))
-    info = dict(calls=calls, ac=ac, n=n, ceiling=np.float32(lv.ceiling), state_in=tp_in.state(), state_out=tp_out.state())
-    for x in (tp_out, tp_in, lv, am, bank):
-        x.close()
+        info = dict(calls=calls, ac=ch.ac, n=ch.n, ceiling=np.float32(lv.ceiling), state_in=tp_in.state(), state_out=tp_out.state())
+        tp_out.close()
+        tp_in.close()
     return info
 
 

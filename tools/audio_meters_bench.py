@@ -14,7 +14,6 @@ The high-cut stage at the same shapes is tools/highcut_bench.py --channels ... -
 from __future__ import annotations
 
 import argparse
-import ctypes
 import importlib
 import json
 import os
@@ -24,7 +23,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
 
-from blend_bench import loaded_hip_runtime, median_ms  # noqa: E402
+from _bench_util import copy_call, median_ms  # noqa: E402
 
 
 def time_config(fmrx, torch, N, n, calls, warmup):
@@ -43,14 +42,7 @@ def time_config(fmrx, torch, N, n, calls, warmup):
     collect_ms = (time.perf_counter() - t0) * 1e3
     odd = median_ms(torch, stream, lambda: am.process_dev(a + 4, n, n, stream=s), calls, warmup)
     mo = median_ms(torch, stream, lambda: mono.process_dev(a, 2 * n, n, stream=s), calls, warmup)
-    hip = loaded_hip_runtime()
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-
-    def run_copy():
-        if hip.hipMemcpyAsync(d_dst.data_ptr(), a, read, 3, s) != 0:      # 3: hipMemcpyDeviceToDevice
-            raise RuntimeError("hipMemcpyAsync failed")
-
-    copy = median_ms(torch, stream, run_copy, calls, warmup)
+    copy = median_ms(torch, stream, copy_call(d_dst.data_ptr(), a, read, s), calls, warmup)
     lv = am.derive(recs[0])
     res = dict(channels=N, n_audio=n, calls=calls, audio_ms=both[0], audio_ms_min=both[1], audio_ms_max=both[2], odd_ms=odd[0], mono_ms=mo[0],
                collect_ms=collect_ms, copy_ms=copy[0], read_bytes=float(read), GB_s=read / (both[0] * 1e-3) / 1e9,

@@ -16,46 +16,17 @@ run in front of every timed blend call, outside its pair of events, as in the lo
 from __future__ import annotations
 
 import argparse
-import ctypes
 import importlib
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
+
+from _bench_util import copy_call, median_ms  # noqa: E402
 
 BLOCK_BYTES = 192000
-
-
-def median_ms(torch, stream, call, calls, warmup, before=None):
-    """before: enqueued in front of every call, outside its pair of events"""
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
-    with torch.cuda.stream(stream):
-        for _ in range(warmup):
-            if before:
-                before()
-            call()
-        for a, b in ev:
-            if before:
-                before()
-            a.record(stream)
-            call()
-            b.record(stream)
-    stream.synchronize()
-    ms = sorted(a.elapsed_time(b) for a, b in ev)
-    return statistics.median(ms), ms[0], ms[-1]
-
-
-def loaded_hip_runtime():
-    """The HIP runtime this process has already mapped (torch's and the library's one), opened by the path it was loaded
-    from: the same handle, never a second copy under another name."""
-    with open("/proc/self/maps") as f:
-        paths = {line.split()[-1] for line in f if "libamdhip64" in line}
-    if len(paths) != 1:
-        raise RuntimeError(f"expected one HIP runtime in the process, found {sorted(paths)}")
-    return ctypes.CDLL(paths.pop())
 
 
 def time_config(fmrx, torch, N, calls, warmup):
@@ -89,14 +60,7 @@ def time_config(fmrx, torch, N, calls, warmup):
     inplace = median_ms(torch, stream, lambda: blend.process_bank(a, a, p, stream=s), calls, warmup, front)
     f32 = median_ms(torch, stream, lambda: blend.process_bank(a, o, None, stream=s), calls, warmup, front)
     pcm = median_ms(torch, stream, lambda: blend.process_bank(a, None, p, stream=s), calls, warmup, front)
-    hip = loaded_hip_runtime()
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-
-    def run_copy():
-        if hip.hipMemcpyAsync(d_dst.data_ptr(), d_src.data_ptr(), moved // 2, 3, s) != 0:      # 3: hipMemcpyDeviceToDevice
-            raise RuntimeError("hipMemcpyAsync failed")
-
-    copy = median_ms(torch, stream, run_copy, calls, warmup, front)
+    copy = median_ms(torch, stream, copy_call(d_dst.data_ptr(), d_src.data_ptr(), moved // 2, s), calls, warmup, front)
     status = blend.status()
     res = dict(channels=N, block_bytes=BLOCK_BYTES, n_audio=n, calls=calls, blend_ms=both[0], blend_ms_min=both[1], blend_ms_max=both[2],
                inplace_ms=inplace[0], f32_ms=f32[0], pcm_ms=pcm[0], copy_ms=copy[0], copy_ms_min=copy[1], moved_bytes=float(moved),

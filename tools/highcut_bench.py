@@ -27,11 +27,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
 
-from blend_bench import BLOCK_BYTES, loaded_hip_runtime, median_ms  # noqa: E402
+from _bench_util import copy_call, median_ms  # noqa: E402
+from blend_bench import BLOCK_BYTES  # noqa: E402
 
 
 def time_config(fmrx, torch, N, calls, warmup):
-    import ctypes
     bank = fmrx.Channels(0, N, audio_channels=2, exact=False, block_bytes=BLOCK_BYTES)
     meters = fmrx.Meters.for_bank(bank)
     blend = fmrx.Blend.for_bank(bank, meters)
@@ -68,14 +68,7 @@ def time_config(fmrx, torch, N, calls, warmup):
     serial = median_ms(torch, stream, lambda: hc.process_bank(a, o, p, stream=s), calls, warmup, front)
     hc.force_serial(False)
     bl = median_ms(torch, stream, lambda: blend.process_bank(a, o, p, stream=s), calls, warmup, front)
-    hip = loaded_hip_runtime()
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-
-    def run_copy():
-        if hip.hipMemcpyAsync(d_dst.data_ptr(), d_src.data_ptr(), moved // 2, 3, s) != 0:      # 3: hipMemcpyDeviceToDevice
-            raise RuntimeError("hipMemcpyAsync failed")
-
-    copy = median_ms(torch, stream, run_copy, calls, warmup, front)
+    copy = median_ms(torch, stream, copy_call(d_dst.data_ptr(), d_src.data_ptr(), moved // 2, s), calls, warmup, front)
     status = hc.status()
     res = dict(channels=N, block_bytes=BLOCK_BYTES, n_audio=n, calls=calls, highcut_ms=both[0], highcut_ms_min=both[1], highcut_ms_max=both[2],
                inplace_ms=inplace[0], f32_ms=f32[0], pcm_ms=pcm[0], serial_ms=serial[0], serial_over_highcut=serial[0] / both[0],

@@ -19,41 +19,17 @@ tools/blend_bench.py at the same channel counts gives the blend's apply pass, wh
 from __future__ import annotations
 
 import argparse
-import ctypes
 import importlib
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
+
+from _bench_util import copy_call, median_ms  # noqa: E402
 
 N_AUDIO = 1920
-
-
-def median_ms(torch, stream, call, calls, warmup):
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
-    with torch.cuda.stream(stream):
-        for _ in range(warmup):
-            call()
-        for a, b in ev:
-            a.record(stream)
-            call()
-            b.record(stream)
-    stream.synchronize()
-    ms = sorted(a.elapsed_time(b) for a, b in ev)
-    return statistics.median(ms), ms[0], ms[-1]
-
-
-def loaded_hip_runtime():
-    """The HIP runtime this process has already mapped (torch's and the library's one), opened by the path it was loaded
-    from: the same handle, never a second copy under another name."""
-    with open("/proc/self/maps") as f:
-        paths = {line.split()[-1] for line in f if "libamdhip64" in line}
-    if len(paths) != 1:
-        raise RuntimeError(f"expected one HIP runtime in the process, found {sorted(paths)}")
-    return ctypes.CDLL(paths.pop())
 
 
 def time_config(fmrx, torch, N, W, calls, warmup):
@@ -75,14 +51,8 @@ def time_config(fmrx, torch, N, W, calls, warmup):
     a, o, p = d_audio.data_ptr(), d_out.data_ptr(), d_pcm.data_ptr()
     both = median_ms(torch, stream, lambda: lv.process_dev(am, a, o, p, stream=s), calls, warmup)
     pcm = median_ms(torch, stream, lambda: lv.process_dev(am, a, None, p, stream=s), calls, warmup)
-    hip = loaded_hip_runtime()
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-
     def copy_of(nbytes):
-        def run():
-            if hip.hipMemcpyAsync(d_dst.data_ptr(), d_src.data_ptr(), nbytes // 2, 3, s) != 0:      # 3: hipMemcpyDeviceToDevice
-                raise RuntimeError("hipMemcpyAsync failed")
-        return median_ms(torch, stream, run, calls, warmup)
+        return median_ms(torch, stream, copy_call(d_dst.data_ptr(), d_src.data_ptr(), nbytes // 2, s), calls, warmup)
 
     copy_both, copy_pcm = copy_of(moved["both"]), copy_of(moved["pcm"])
     status = lv.status()

@@ -18,33 +18,15 @@ import argparse
 import importlib
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
+
+from _bench_util import median_ms  # noqa: E402
 
 STREAM_PROBE = 6.2e12        # bytes / s
 BLOCK_BYTES = 192000
-
-
-def median_ms(torch, stream, call, calls, warmup, before=None):
-    """before: enqueued in front of every call, outside its pair of events"""
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
-    with torch.cuda.stream(stream):
-        for _ in range(warmup):
-            if before:
-                before()
-            call()
-        for a, b in ev:
-            if before:
-                before()
-            a.record(stream)
-            call()
-            b.record(stream)
-    stream.synchronize()
-    ms = sorted(a.elapsed_time(b) for a, b in ev)
-    return statistics.median(ms), ms[0], ms[-1]
 
 
 def time_config(fmrx, torch, N, calls, warmup):

@@ -16,7 +16,6 @@ The audio meters at the same shapes are tools/audio_meters_bench.py --channels .
 from __future__ import annotations
 
 import argparse
-import ctypes
 import importlib
 import json
 import os
@@ -26,18 +25,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
 
-from blend_bench import loaded_hip_runtime, median_ms  # noqa: E402
-
-
-def copy_call(d_dst, src, nbytes, s):
-    hip = loaded_hip_runtime()
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-
-    def run_copy():
-        if hip.hipMemcpyAsync(d_dst.data_ptr(), src, nbytes, 3, s) != 0:      # 3: hipMemcpyDeviceToDevice
-            raise RuntimeError("hipMemcpyAsync failed")
-
-    return run_copy
+from _bench_util import copy_call, median_ms  # noqa: E402
 
 
 def time_config(fmrx, torch, N, n, calls, warmup):
@@ -56,7 +44,7 @@ def time_config(fmrx, torch, N, n, calls, warmup):
     collect_ms = (time.perf_counter() - t0) * 1e3
     odd = median_ms(torch, stream, lambda: tp.process_dev(a + 4, n, n, stream=s), calls, warmup)
     mo = median_ms(torch, stream, lambda: mono.process_dev(a, 2 * n, n, stream=s), calls, warmup)
-    copy = median_ms(torch, stream, copy_call(d_dst, a, read, s), calls, warmup)
+    copy = median_ms(torch, stream, copy_call(d_dst.data_ptr(), a, read, s), calls, warmup)
     lv = tp.derive(recs[0])
     res = dict(channels=N, n_audio=n, calls=calls, peak_ms=both[0], peak_ms_min=both[1], peak_ms_max=both[2], odd_ms=odd[0], mono_ms=mo[0],
                collect_ms=collect_ms, copy_ms=copy[0], read_bytes=float(read), GB_s=read / (both[0] * 1e-3) / 1e9,
@@ -79,7 +67,7 @@ def time_long(fmrx, torch, n, calls, warmup):
     s, a = stream.cuda_stream, d_audio.data_ptr()
     one = median_ms(torch, stream, lambda: tp.process_dev(a, n, n, stream=s), calls, warmup)
     odd = median_ms(torch, stream, lambda: tp.process_dev(a + 4, n, n, stream=s), calls, warmup)
-    copy = median_ms(torch, stream, copy_call(d_dst, a, 4 * n, s), calls, warmup)
+    copy = median_ms(torch, stream, copy_call(d_dst.data_ptr(), a, 4 * n, s), calls, warmup)
     lv = tp.derive(tp.collect()[0])
     tp.close()
     return dict(channels=1, audio_channels=1, n_audio=n, calls=calls, peak_ms=one[0], peak_ms_min=one[1], peak_ms_max=one[2], odd_ms=odd[0],
