@@ -1378,6 +1378,113 @@ FMRX_API int fmrx_true_peak_collect(fmrx_true_peak *m, fmrx_true_peak_record *re
  * use is n_channels = 1 with the audio fmrx_pipeline_process returns */
 FMRX_API int fmrx_true_peak_process(fmrx_true_peak *m, const float *audio, size_t row_pitch, size_t n, fmrx_true_peak_record *records);
 
+/* ------------------------------------------------------------------ */
+/* Audio spectrum meter: band powers of every audio row of a bank       */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  What the audio consists of: the power in up to 32 frequency bands of each audio row, from
+ * which a monitor reads a band-limited relay, mains hum, pilot leakage, speech against music, or the flat hiss of an empty
+ * channel.  ... -> audio meters -> leveller -> true peak / audio spectrum on one stream; a handle of the audio meters' kind that
+ * only reads the rows.  Defined by tests/_audio_spectrum_model.py; host and device equal that model bit
+ * for bit (a NaN's sign and payload are the machine's).
+ *
+ * Frames: a row is a stream across calls.  Frame f covers stream samples 256 f .. 256 f + 255; no overlap, nothing in front of a
+ * fresh stream.  The carried state per channel (fmrx_audio_spectrum_state) is fill (0 .. 255, one value for both rows) and the
+ * fill samples of the open frame per row.  A call of n samples completes F = (fill + n) div 256 frames and leaves (fill + n) mod
+ * 256 samples; a call may complete no frame (frames = 0, every band +0).
+ * Tables (float32, fmrx_audio_spectrum_tables; literals in audio_spectrum_core.hpp; they are the definition):
+ *   w[j] = (float)(0.5 - 0.5 cos(2 pi j / 256)), the periodic Hann window, w[0] = +0
+ *   C[m] = (float)cos(2 pi m / 256), m = 0 .. 255, built from the quarter m = 0 .. 64 by symmetry, C[64] = C[192] = +0 exactly
+ * Per frame and row: xw[j] = x[j] w[j], one float32 multiply; for bins k = 0 .. 127
+ *   re_k = acc = +0;  for j = 0 .. 255 ascending: acc = fmaf(C[(k j) mod 256], xw[j], acc)
+ *   im_k = the same chain with C[(k j - 64) mod 256]
+ *   p_k  = fmaf(im_k, im_k, fl(re_k re_k))
+ * every step rounded once, float32 denormals kept; NaN and infinity propagate as the arithmetic has them: a NaN sample
+ * makes every bin of its frame NaN, an infinite one NaN or infinity (NaN where it meets one of the zeros w[0], C[64], C[192]).
+ * Bands: edges[0 .. B] strictly ascending within 1 .. 128, 1 <= B <= 32; band b covers bins edges[b] .. edges[b+1] - 1; bin 0 is
+ * computed and belongs to no band.  A frame's band power is the float32 sum of its p_k, ascending from +0.  The default
+ * (fmrx_audio_spectrum_default_edges) has 23 bands, edges 1 2 3 4 5 6 7 8 10 12 14 16 20 24 28 32 40 48 56 64 80 96 112 128: at
+ * 48 kHz a bin is 187.5 Hz and the 19 kHz pilot falls in band 21.
+ * Record per channel and call (fmrx_audio_spectrum_record; mono fills row 0; bands >= B are +0): n, frames, and
+ *   band[r][b]  a two-level float64 sum: the call's completed frames q = 0 .. F - 1 form tiles of fmrx_audio_spectrum_tile() = 16
+ *               consecutive frames; a tile's sum runs over its frames ascending from +0.0, the call's over its tiles ascending
+ *               from +0.0
+ * The per-frame band powers do not depend on how the stream is cut into calls.  The sums DO, through this grouping: the same
+ * stream cut into other calls groups other frames into tiles, and the records' sum over the calls can differ in its last bits.
+ * Records of successive calls add.
+ * Levels (fmrx_audio_spectrum_levels; fmrx_audio_spectrum_derive, host arithmetic in double), every dB value by the signal
+ * meters' edge rule, clamped to +-99:
+ *   band_dbfs[r][b]  10 log10((band / frames) / (6144 full_scale^2)); 6144 = 256 sum(w^2) / 4, so that a full-scale sine whose
+ *                    main lobe lies inside a band reads 0 dBFS there
+ *   total_dbfs[r]    the same over the sum of the bands
+ *   centroid_hz[r]   sum_b fc_b band_b / sum_b band_b, fc_b = (edges[b] + edges[b+1] - 1) / 2 audio_Fs / 256; 0 where the total is
+ *                    not positive
+ * With frames = 0, for the row a mono channel lacks and for bands >= B every level reads -99 and the centroid 0.
+ *
+ * The device pass: a frame's 2 x 128 chains are a matrix product on the f32 matrix cores (v_mfma_f32_16x16x4_f32: 16 outputs x 4
+ * window positions x 16 frames), which rounds as the chain above does.  Rows of at most 2 048 samples -- every bank row -- take
+ * one workgroup per two rows and one launch; longer rows one workgroup per 16 frames and a second small launch for the tiles'
+ * sum. */
+typedef struct fmrx_audio_spectrum_record {
+    uint64_t n, frames;
+    double band[2][32];
+} fmrx_audio_spectrum_record;
+typedef struct fmrx_audio_spectrum_state {
+    uint32_t fill;
+    float carry[2][255];    /* entries at and beyond fill read 0, and so does a mono channel's second row */
+} fmrx_audio_spectrum_state;
+typedef struct fmrx_audio_spectrum_levels {
+    double band_dbfs[2][32], total_dbfs[2], centroid_hz[2];
+} fmrx_audio_spectrum_levels;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_audio_spectrum_record) == 528, "fmrx_audio_spectrum_record layout");
+static_assert(sizeof(fmrx_audio_spectrum_state) == 2044, "fmrx_audio_spectrum_state layout");
+static_assert(sizeof(fmrx_audio_spectrum_levels) == 544, "fmrx_audio_spectrum_levels layout");
+#else
+_Static_assert(sizeof(fmrx_audio_spectrum_record) == 528, "fmrx_audio_spectrum_record layout");
+_Static_assert(sizeof(fmrx_audio_spectrum_state) == 2044, "fmrx_audio_spectrum_state layout");
+_Static_assert(sizeof(fmrx_audio_spectrum_levels) == 544, "fmrx_audio_spectrum_levels layout");
+#endif
+typedef struct fmrx_audio_spectrum fmrx_audio_spectrum;
+/* Host code, no device needed.  tables: window256 [256] = w, cos256 [256] = C.  frame 256, bins 128, tile 16, max_bands 32.
+ * default_edges: edges [24], *n_bands = 23. */
+FMRX_API int fmrx_audio_spectrum_tables(float *window256, float *cos256);
+FMRX_API size_t fmrx_audio_spectrum_frame(void);
+FMRX_API size_t fmrx_audio_spectrum_bins(void);
+FMRX_API size_t fmrx_audio_spectrum_tile(void);
+FMRX_API size_t fmrx_audio_spectrum_max_bands(void);
+FMRX_API int fmrx_audio_spectrum_default_edges(int *edges, int *n_bands);
+/* The host reference of one channel: rows [audio_channels][row_pitch] floats of which n (1 .. 2^26) are walked; edges [n_bands + 1]
+ * (NULL: the default, n_bands ignored); *state_in_out is read and replaced (a mono channel's second row is left alone); *rec is
+ * written.  Edges that do not ascend strictly within 1 .. 128, n_bands outside 1 .. 32 or a fill beyond 255: FMRX_EINVAL.  The body
+ * the kernel's arithmetic is checked against (audio_spectrum_core.hpp). */
+FMRX_API int fmrx_audio_spectrum_walk(int audio_channels, const float *rows, size_t row_pitch, size_t n, const int *edges, int n_bands,
+                                      fmrx_audio_spectrum_state *state_in_out, fmrx_audio_spectrum_record *rec);
+/* edges, n_bands: those the record was made with (NULL: the default); audio_Fs finite and > 0, for the centroid */
+FMRX_API int fmrx_audio_spectrum_derive(const fmrx_audio_spectrum_record *rec, int audio_channels, const int *edges, int n_bands, double audio_Fs,
+                                        double full_scale, fmrx_audio_spectrum_levels *out);
+/* n_audio: the most samples per row and call (fmrx_channels_n_audio), 1 .. 2^26; audio_channels 1 or 2; edges [n_bands + 1], NULL:
+ * the default */
+FMRX_API int fmrx_audio_spectrum_create(fmrx_audio_spectrum **out, int n_channels, int audio_channels, size_t n_audio, const int *edges, int n_bands,
+                                        int device);
+FMRX_API int fmrx_audio_spectrum_destroy(fmrx_audio_spectrum *m);
+/* channel < 0: all.  Clears the channel's open frame (fill = 0).  Waits for the handle's last call; the state is clear when it
+ * returns, for a later call on any stream. */
+FMRX_API int fmrx_audio_spectrum_reset(fmrx_audio_spectrum *m, int channel);
+/* out [n_channels]: every channel's carried state; waits for the handle's last call */
+FMRX_API int fmrx_audio_spectrum_state_get(fmrx_audio_spectrum *m, fmrx_audio_spectrum_state *out);
+/* Asynchronous on `stream`, behind whatever wrote the rows on the same stream: d_audio [n_channels][audio_channels][row_pitch]
+ * floats, as the banks and every later stage write them (row_pitch = n_audio there), of which the first n <= n_audio of every
+ * row are walked; 4-byte aligned, at any pitch.  A frame starts wherever the open frame's fill puts it, so the rows are fetched
+ * 4 bytes per lane, consecutive lanes consecutive samples, whatever their alignment; the pass is bound by the matrix cores.  The
+ * rows are only read.  One kernel launch (two for n > 2048); a second call before fmrx_audio_spectrum_collect replaces the results
+ * (the state has then advanced by both). */
+FMRX_API int fmrx_audio_spectrum_process_dev(fmrx_audio_spectrum *m, const float *d_audio, size_t row_pitch, size_t n, void *stream);
+/* records [n_channels]; waits for the last call (an event it recorded), not for the device */
+FMRX_API int fmrx_audio_spectrum_collect(fmrx_audio_spectrum *m, fmrx_audio_spectrum_record *records);
+/* host rows [n_channels][audio_channels][row_pitch], synchronous (it first waits for the handle's last call): the single-stream
+ * use is n_channels = 1 with the audio fmrx_pipeline_process returns */
+FMRX_API int fmrx_audio_spectrum_process(fmrx_audio_spectrum *m, const float *audio, size_t row_pitch, size_t n, fmrx_audio_spectrum_record *records);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1569,7 +1569,7 @@ def audioMetersDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dic
 
 
 class _AudioReader(_Handle):
-    """What AudioMeters and TruePeak share: a handle that only reads a bank's audio rows (csrc/meter_stage.hpp's Reader).  A
+    """What AudioMeters, TruePeak and AudioSpectrum share: a handle that only reads a bank's audio rows (csrc/meter_stage.hpp's Reader).  A
     subclass names its fmrx_<_prefix>_* functions and its module-level derive function, creates self._h, and says in _bank_extra
     what its constructor takes beyond n_channels, audio_channels, n_audio and device."""
 
@@ -1859,6 +1859,120 @@ class TruePeak(_AudioReader):
         """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
         x = self._rows(audio)
         out = np.zeros(self.n_channels, TRUE_PEAK_DTYPE)
+        self._call("process", x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data)
+        return out
+
+
+# --------------------------------------------------------------------------
+# Audio spectrum meter: the band powers of every audio row of a bank
+# --------------------------------------------------------------------------
+AUDIO_SPECTRUM_DTYPE = np.dtype([("n", "<u8"), ("frames", "<u8"), ("band", "<f8", (2, 32))])                      # struct fmrx_audio_spectrum_record
+AUDIO_SPECTRUM_STATE_DTYPE = np.dtype([("fill", "<u4"), ("carry", "<f4", (2, 255))])                              # struct fmrx_audio_spectrum_state
+AUDIO_SPECTRUM_LEVELS_DTYPE = np.dtype([("band_dbfs", "<f8", (2, 32)), ("total_dbfs", "<f8", (2,)), ("centroid_hz", "<f8", (2,))])   # struct fmrx_audio_spectrum_levels
+assert AUDIO_SPECTRUM_DTYPE.itemsize == 528 and AUDIO_SPECTRUM_STATE_DTYPE.itemsize == 2044 and AUDIO_SPECTRUM_LEVELS_DTYPE.itemsize == 544
+_sig("fmrx_audio_spectrum_tables", [_f32p, _f32p])
+_sig("fmrx_audio_spectrum_frame", [], _sz)
+_sig("fmrx_audio_spectrum_bins", [], _sz)
+_sig("fmrx_audio_spectrum_tile", [], _sz)
+_sig("fmrx_audio_spectrum_max_bands", [], _sz)
+_sig("fmrx_audio_spectrum_default_edges", [_vp, C.POINTER(_int)])
+_sig("fmrx_audio_spectrum_walk", [_int, _vp, _sz, _sz, _vp, _int, _vp, _vp])
+_sig("fmrx_audio_spectrum_derive", [_vp, _int, _vp, _int, _dbl, _dbl, _vp])
+_sig("fmrx_audio_spectrum_create", [C.POINTER(_vp), _int, _int, _sz, _vp, _int, _int])
+_sig("fmrx_audio_spectrum_destroy", [_vp])
+_sig("fmrx_audio_spectrum_reset", [_vp, _int])
+_sig("fmrx_audio_spectrum_state_get", [_vp, _vp])
+_sig("fmrx_audio_spectrum_process_dev", [_vp, _vp, _sz, _sz, _vp])
+_sig("fmrx_audio_spectrum_collect", [_vp, _vp])
+_sig("fmrx_audio_spectrum_process", [_vp, _vp, _sz, _sz, _vp])
+
+
+def audioSpectrumTables():
+    """Host only: (w float32 [256], the periodic Hann window; C float32 [256], cos(2 pi m / 256)), the tables that define the meter."""
+    w, c = np.zeros(256, np.float32), np.zeros(256, np.float32)
+    _check(lib.fmrx_audio_spectrum_tables(w, c))
+    return w, c
+
+
+def audioSpectrumDefaultEdges() -> np.ndarray:
+    """Host only: the default band edges, int32 [24]: 23 bands."""
+    e, nb = np.zeros(33, np.int32), _int()
+    _check(lib.fmrx_audio_spectrum_default_edges(e.ctypes.data, C.byref(nb)))
+    return e[:nb.value + 1].copy()
+
+
+def _spectrum_edges(edges):
+    """-> (int32 array or None, its pointer or None, n_bands) as the library's edges / n_bands arguments take them"""
+    if edges is None:
+        return None, None, 0
+    e = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+    return e, e.ctypes.data, len(e) - 1
+
+
+def audioSpectrumWalk(rows, state=None, edges=None):
+    """Host only: the reference walk of one channel (fmrx_audio_spectrum_walk) on rows float32 [audio_channels, n]; state: the
+    AUDIO_SPECTRUM_STATE_DTYPE record the last call returned (None or zeros: a fresh channel); edges: None for the default bands
+    -> (record, state)."""
+    x = _walk_rows(rows)
+    st = np.zeros(1, AUDIO_SPECTRUM_STATE_DTYPE) if state is None else np.array(state, dtype=AUDIO_SPECTRUM_STATE_DTYPE).reshape(1).copy()
+    rec = np.zeros(1, AUDIO_SPECTRUM_DTYPE)
+    e, ep, nb = _spectrum_edges(edges)
+    _check(lib.fmrx_audio_spectrum_walk(x.shape[0], x.ctypes.data, x.shape[1], x.shape[1], ep, nb, st.ctypes.data, rec.ctypes.data))
+    return rec[0], st[0]
+
+
+def audioSpectrumDerive(rec, audio_channels=2, edges=None, audio_Fs=48000.0, full_scale=AUDIO_FULL_SCALE) -> dict:
+    """Host only: the levels (fmrx_audio_spectrum_levels) of one AUDIO_SPECTRUM_DTYPE record, as a dict of float64 arrays:
+    band_dbfs [2, 32], total_dbfs [2], centroid_hz [2]."""
+    r = np.array(rec, dtype=AUDIO_SPECTRUM_DTYPE).reshape(1)
+    out = np.zeros(1, AUDIO_SPECTRUM_LEVELS_DTYPE)
+    e, ep, nb = _spectrum_edges(edges)
+    _check(lib.fmrx_audio_spectrum_derive(r.ctypes.data, int(audio_channels), ep, nb, float(audio_Fs), float(full_scale), out.ctypes.data))
+    return {k: out[0][k].copy() for k in AUDIO_SPECTRUM_LEVELS_DTYPE.names}
+
+
+class AudioSpectrum(_AudioReader):
+    """Per channel of a receiver bank and call: the power in up to 32 frequency bands of each audio row, summed over the
+    256-sample frames the call completed (fmrx_audio_spectrum_*).  Behind the last audio stage on stream s:
+    sp = AudioSpectrum.for_bank(bank); sp.process_bank(d_out, stream=s); recs = sp.collect(); sp.derive(recs[c]).  edges: None
+    for the 23 default bands, or B + 1 bin numbers ascending within 1 .. 128."""
+    _prefix = "audio_spectrum"
+    _bank_extra = staticmethod(lambda bank, edges=None: {"edges": edges, "audio_Fs": bank.params.audio_Fs})
+
+    def __init__(self, n_channels=1, audio_channels=2, n_audio=1920, edges=None, audio_Fs=48000.0, device=0):
+        self.n_channels, self.audio_channels, self.n_audio, self.audio_Fs = int(n_channels), int(audio_channels), int(n_audio), float(audio_Fs)
+        e, ep, nb = _spectrum_edges(edges)
+        self._h = _vp()
+        _check(lib.fmrx_audio_spectrum_create(C.byref(self._h), self.n_channels, self.audio_channels, self.n_audio, ep, nb, device))
+        self.edges = audioSpectrumDefaultEdges() if e is None else e.copy()
+        self.n_bands = len(self.edges) - 1
+        self.frame = lib.fmrx_audio_spectrum_frame()
+        self.tile = lib.fmrx_audio_spectrum_tile()
+
+    def band_hz(self) -> np.ndarray:
+        """The centre frequency of every band, float64 [n_bands]: what the centroid weighs the bands with."""
+        e = self.edges.astype(np.float64)
+        return (e[:-1] + e[1:] - 1.0) / 2.0 * (self.audio_Fs / self.frame)
+
+    def derive(self, rec, full_scale=AUDIO_FULL_SCALE) -> dict:
+        return audioSpectrumDerive(rec, self.audio_channels, self.edges, self.audio_Fs, full_scale)
+
+    def state(self) -> np.ndarray:
+        """Waits for the last call; every channel's carried state, AUDIO_SPECTRUM_STATE_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, AUDIO_SPECTRUM_STATE_DTYPE)
+        self._call("state_get", out.ctypes.data)
+        return out
+
+    def collect(self) -> np.ndarray:
+        """Waits for the last call; AUDIO_SPECTRUM_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, AUDIO_SPECTRUM_DTYPE)
+        self._call("collect", out.ctypes.data)
+        return out
+
+    def process(self, audio) -> np.ndarray:
+        """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
+        x = self._rows(audio)
+        out = np.zeros(self.n_channels, AUDIO_SPECTRUM_DTYPE)
         self._call("process", x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data)
         return out
 

@@ -540,4 +540,25 @@ struct TruePeakArgs {
 };
 int true_peak_launch(const TruePeakArgs &a, hipStream_t s);
 
+// ---- audio spectrum meter (kernels_audio_spectrum.hip; tables and frame arithmetic in audio_spectrum_core.hpp; handle and C ABI in
+// audio_spectrum.hip) --------------------------------------------------------------------------------------------------------------
+constexpr size_t kAudioSpectrumPairMax = 2048;   // a row of at most this many samples completes at most 8 frames: two rows share a tile
+struct AudioSpectrumArgs {
+    const float *x = nullptr;            // [n_channels][ac][pitch]; only read
+    size_t pitch = 0, n = 0;             // floats per row; samples of every row to walk
+    int n_channels = 0, ac = 1;
+    int n_bands = 0;
+    const int *edges = nullptr;          // device, [n_bands + 1]
+    // the carried state, channel-major: fill [n_channels], carry [n_channels][ac][256] floats of which the first fill count
+    const unsigned *fill_in = nullptr;
+    const float *carry_in = nullptr;
+    unsigned *fill_out = nullptr;        // another pair of buffers of those shapes
+    float *carry_out = nullptr;
+    unsigned *frames = nullptr;          // [n_channels]: the frames the call completed
+    double *res = nullptr;               // field-major [ac * n_bands][n_channels]: field r * n_bands + b
+    double *tiles = nullptr;             // rows longer than 2048 samples only: [audio_spectrum_tiles(n)][n_channels * ac][n_bands]
+};
+size_t audio_spectrum_tiles(size_t n);   // the tiles of 16 frames a row of n samples can complete, whatever its fill
+int audio_spectrum_launch(const AudioSpectrumArgs &a, hipStream_t s);
+
 }  // namespace fmrx
