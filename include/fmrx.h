@@ -814,9 +814,17 @@ FMRX_API int fmrx_tuner_levels(fmrx_tuner *t, uint64_t *clipped, uint64_t *power
  *   The samples past the last whole segment take part in sum_x, sum_x2 and max_abs only.
  * The raw sums of successive calls add and max_abs takes the maximum: integration over longer periods is the caller's, by
  * adding records field by field before fmrx_meters_derive.
- * A row that is not finite: NaN or infinity goes into sum_x, sum_x2 and the probes of its segment as IEEE arithmetic takes it
- * (the fields read NaN or infinity); max_abs skips NaN and reads infinity for an infinity.  The library's discriminators write
- * 0 where I^2 + Q^2 = 0 (a noise-only channel can get there), so the rows of a bank are finite.
+ * The order of the float64 additions is part of the contract (tests/_meters_order_model.py restates it; the device is compared
+ * with it bit for bit).  Thread t of 256 owns samples 4t .. 4t+3 of every 1024-sample segment.  Per segment and table row (5
+ * real, 5 imaginary) it runs a = fma(x[4t+j], tab[4t+j], a) for j = 0 .. 3 from 0.0; the 256 values are added within each wave
+ * of 64 lanes by halving (lanes l and l + 32, then l and l + 16, ... l and l + 1), the four waves as ((w0 + w1) + w2) + w3; the
+ * power re * re + im * im (two rounded products, one add) is added to probe[p] in rising segment order.  sum_x and sum_x2: per
+ * thread sx += x and sx2 = fma(x, x, sx2) over its samples, segment by segment, then over samples 1024 M + t, + 256, ... of the
+ * tail; then the same halving and the same ((w0 + w1) + w2) + w3.  max_abs is an fmax chain from 0.0.
+ * A row that is not finite: NaN or infinity goes into sum_x, sum_x2 and the probes -- all five, when it lies in a whole segment;
+ * none, when it lies in the tail -- as IEEE arithmetic takes it in that order (the fields read NaN or infinity).  max_abs is the
+ * largest |x| among the samples that are not NaN (infinity for an infinity; fmax skips NaN), 0 if there is none.  The
+ * library's discriminators write 0 where I^2 + Q^2 = 0 (a noise-only channel can get there), so the rows of a bank are finite.
  *
  * Levels (fmrx_meter_levels; fmrx_meters_derive, host arithmetic in double).  Every dB value is clamped to [-99, 99]: -99
  * where the numerator is not positive (0 / 0 included), 99 where only the denominator is not; the other fields read 0 where

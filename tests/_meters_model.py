@@ -12,7 +12,10 @@ MPX group, from the float32 discriminator row x[0 .. n_if) (radians per IF sampl
                  powers, averaged incoherently; the phase restarts in every segment because only powers are used
   f_p            17 kHz, 21 kHz (noise, the guard bands beside the pilot), 19 kHz (pilot), 57 kHz -+ 1187.5 Hz (RDS: the
                  biphase spectrum's maxima; it has a null at 57 kHz itself)
-The model is defined for finite rows.
+mpx_group below is defined for finite rows and adds in numpy's order.  The order in which the device adds, and with it the value
+of every float64 bit for bit, is stated by tests/_meters_order_model.py, which also extends the definition to rows that are not
+finite: sums and probes follow IEEE arithmetic in that order and may read NaN or infinity; max_abs is the largest |x| among the
+samples that are not NaN, 0 if there is none.
 
 Limits of the definition: cnr_db is over the slot's whole bandwidth (rf_Fs), not over the 200 kHz of a channel; and the
 noise probes sit 2 kHz = about 8.5 bins from the pilot, so the Hann window's leakage of the pilot into them caps pilot_db
