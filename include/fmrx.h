@@ -403,7 +403,7 @@ FMRX_API int fmrx_pipeline_deemph_diagnostics(fmrx_pipeline *pl, unsigned long l
  * receivers is N processes.  fmrx_channels processes the current block of N independent channels in one call
  * (fmrx_channels_create: mono, modes 0 and 1, ONE kernel launch; fmrx_channels_create_ex below: mono or stereo, exact or fast): what a live multi-channel receiver needs, where one 51 200-sample block per
  * channel and launch would leave the chip idle.  A channel's whole carried state is its last ~1 200 input
- * samples, kept as raw bytes in front of its block (csrc/channels.hip); results equal fmrx_pipeline's for the
+ * samples, kept as raw bytes in front of its block (csrc/bank.hip); results equal fmrx_pipeline's for the
  * same stream (audio to within float32 summation order, <= 2e-6; PCM +-1 LSB).
  *   block_bytes: bytes per channel and call (a multiple of 16 and of 2*rf_decim*audio_decim; the reference's
  *   p->block_bytes qualifies).  Input: either host memory, channel-major [n_channels][block_bytes]

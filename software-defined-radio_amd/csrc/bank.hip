@@ -1,8 +1,7 @@
 // bank.hip -- a bank of N independent receivers per device call, host side (include/fmrx.h: fmrx_channels_create_ex): the handle's
-// buffers, the two-stream chunk schedule of a stereo call, reset and tap read-back.  The kernels, their tables and launchers are
-// kernels_bank.hip's, which also says which banks these are, what they compute and how their rows are laid out.
-#include <memory>
-
+// buffers, the two-stream chunk schedule of a stereo call, reset and tap read-back, for every kind of bank.  The kernels, their
+// tables and launchers are kernels_bank.hip's, which also says what the banks with rows compute and how the rows are laid out; the
+// fast mono bank of modes 0/1 keeps no rows (below: plan_fused) and runs the fused mono kernel of kernels_fe_mfma.hip.
 #include "bank_kernels.hpp"
 
 namespace fmrx {
@@ -125,62 +124,114 @@ int process_mono(Bank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStream_t 
     return b->k.out(*b, d_audio, d_pcm, wrap, 0, b->n_audio, b->n_if, s);
 }
 
+// the slots of all channels as one pseudo-stream that starts in silence; the audio / PCM of whole slots, for the finish kernel to compact
+int process_fused(Bank *b, float *d_audio, int wrap, hipStream_t s)
+{
+    const float *zend = b->zeros.p + b->p.audio_taps + 32;     // "one past the previous block's last discriminator sample": zeros
+    return mono_fused_launch(b->fe, b->audio, b->slots.p, b->slot_bytes * b->n_channels / 2, b->fe.silence.p, b->zeros.p, zend, nullptr, 0,
+                             nullptr, d_audio ? b->audio_all.p : nullptr, b->pcm_all.p, wrap, nullptr, b->opt, s);
+}
+
+// The fused kind (mono, fast, modes 0/1).  The mono chain of modes 0/1 is a sliding-window map of its input
+// (SURVEY A.4): audio sample k depends on the rf_decim*(audio_taps) + rf_taps - 1 complex input samples in front of it (1 110 at
+// 101/101 taps) and on nothing else, so a channel's whole carried state (I/Q FIR state, prev_i/prev_q, state_mono) is its last
+// 1 110 input samples: the history in front of its slot.  Audio samples whose window reaches back into the previous slot (the
+// first junk_audio of every slot: 28 at 101/101 taps, 2.3 % extra work at the reference's block size) are computed and thrown
+// away; all others see exactly the samples the streaming pipeline would have seen: IF and discriminator values bit-identical to
+// fmrx_pipeline's, audio equal to within the float32 summation order of the fused kernel's MFMA tiles (<= 2e-6).
+int plan_fused(Bank &b, const Filters &f)
+{
+    const fmrx_params &p = b.p;
+    FMRX_TRY(fe_plan_init(b.fe, f.rf.data(), p.rf_taps, p.rf_decim));
+    FMRX_TRY(audio_plan_init(b.audio, f.audio.data(), p.audio_taps, p.audio_decim));
+    // samples an audio output reaches back: rf_decim*audio_taps + rf_taps - 1, plus what the kernel's tiles read in
+    // front of a run (one IF sample for the discriminator, 16-byte rounding): rounded up to whole audio samples
+    // and 16-byte multiples
+    const size_t unit = static_cast<size_t>(2) * p.rf_decim * p.audio_decim;   // bytes per audio sample
+    const size_t reach = static_cast<size_t>(p.rf_decim) * (p.audio_taps + 1) + p.rf_taps + 8 * p.rf_decim;
+    size_t hs = (reach * 2 + unit - 1) / unit * unit;
+    while (hs % 16) hs += unit;
+    b.hist_bytes = hs;
+    b.junk_audio = hs / unit;
+    return FMRX_OK;
+}
+
+// Every other kind: the tables of its stages, and the histories in front of a channel's slot and rows.
+int plan_rows(Bank &b, const Filters &f)
+{
+    const fmrx_params &p = b.p;
+    const bool stereo = b.audio_channels == 2;
+    FMRX_TRY(b.k.fe_table(b, f.rf.data()));
+    b.hist_bytes = b.k.hist_bytes;
+    if (!b.exact) {   // the matrix-core front end (int8 MFMA on the raw bytes): its tap image, and the history its windows reach
+        FMRX_TRY(fe_plan_init(b.fe, f.rf.data(), p.rf_taps, p.rf_decim));
+        const int lead = fe_mfma_bank_lead(b.fe);
+        if (!b.fe.mfma || lead < 0) return fail(FMRX_EINVAL, "channels: no matrix-core front end for rf %d taps / decim %d", p.rf_taps, p.rf_decim);
+        const size_t need = (static_cast<size_t>(lead) + 15) / 16 * 16;
+        if (need > b.hist_bytes) b.hist_bytes = need;
+    }
+    FMRX_TRY(b.k.out_table(b, f.audio.data()));
+    b.Ha = b.resample ? (p.audio_taps - 1) / p.audio_upsamp : p.audio_taps - 1;
+    b.delay = stereo ? (p.stereo_taps - 1) / 2 : 0;                        // allPass, src/filter.cpp:14-29
+    b.Hd = b.Ha + b.delay;
+    if (stereo && p.stereo_taps - 1 + 3 > b.Hd) b.Hd = p.stereo_taps - 1 + 3;
+    const int more = b.res_hist > b.Ha ? b.res_hist - b.Ha : 0;   // (the lane-per-channel resampler rounds its windows up to whole iterations)
+    if (b.Ha + b.delay + more > b.Hd) b.Hd = b.Ha + b.delay + more;
+    b.Hd = (b.Hd + 3) / 4 * 4 + 4;
+    b.Hm = (b.Ha + more + 3) / 4 * 4 + 4;
+    b.dpitch = (b.Hd + b.n_if + 16 + 3) / 4 * 4;
+    b.ypitch = (b.n_if + 16 + 3) / 4 * 4;
+    plan_chunks(b);
+    return FMRX_OK;
+}
+
 }  // namespace
 
-void bank_destroy(Bank *b) { delete b; }
-
-int bank_create(Bank **out, const fmrx_params &p, int n_channels, int audio_channels, int exact, size_t block_bytes)
+int bank_create(std::unique_ptr<Bank> &out, const fmrx_params &p, int n_channels, int audio_channels, int exact, size_t block_bytes,
+                const Options &opt)
 {
     const bool stereo = audio_channels == 2;
-    if (!exact && !stereo && p.audio_upsamp == 0)
-        return fail(FMRX_EINVAL, "channels: the fast mono bank of the integer-decimation modes is fmrx_channels_create's");
     if (p.audio_upsamp > 0 && p.audio_taps % p.audio_upsamp != 0)   // as fmrx_pipeline_create: the reference is a stream only then
         return fail(FMRX_EINVAL, "channels: audio_taps %d is not a multiple of audio_upsamp %d", p.audio_taps, p.audio_upsamp);
     std::unique_ptr<Bank> b(new Bank);   // (a failure below frees what was built so far)
     if (!bank_resolve(p, audio_channels, exact, b->k))
         return fail(FMRX_EINVAL, "channels (exact): no reference-order kernels for rf %d/%d, audio %d/%d, stereo %d taps (modes 0 and 1 of the "
                     "reference's tap sets are covered)", p.rf_taps, p.rf_decim, p.audio_taps, p.audio_decim, p.stereo_taps);
+    const bool fused = b->k.fused;
     b->p = p;
     b->n_channels = n_channels;
     b->audio_channels = audio_channels;
     b->exact = exact ? 1 : 0;
-    const Filters f = design_filters(p, stereo);
-    FMRX_TRY(b->k.fe_table(*b, f.rf.data()));
-    b->hist_bytes = b->k.hist_bytes;
-    if (!b->exact) {   // the matrix-core front end (int8 MFMA on the raw bytes): its tap image, and the history its windows reach
-        FMRX_TRY(fe_plan_init(b->fe, f.rf.data(), p.rf_taps, p.rf_decim));
-        const int lead = fe_mfma_bank_lead(b->fe);
-        if (!b->fe.mfma || lead < 0) return fail(FMRX_EINVAL, "channels: no matrix-core front end for rf %d taps / decim %d", p.rf_taps, p.rf_decim);
-        const size_t need = (static_cast<size_t>(lead) + 15) / 16 * 16;
-        if (need > b->hist_bytes) b->hist_bytes = need;
-    }
+    b->opt = opt;
     b->resample = p.audio_upsamp > 0;
-    FMRX_TRY(b->k.out_table(*b, f.audio.data()));
     b->n_if = static_cast<long>(block_bytes / 2) / p.rf_decim;
     b->n_audio = b->resample ? b->n_if * p.audio_upsamp / p.audio_decim : b->n_if / p.audio_decim;
+    const Filters f = design_filters(p, stereo);
+    FMRX_TRY(fused ? plan_fused(*b, f) : plan_rows(*b, f));
     if (b->resample && (b->n_if * p.audio_upsamp) % p.audio_decim)
         return fail(FMRX_EINVAL, "channels: n_if * upsamp = %ld is not a multiple of audio_decim %d (a block must end on an output boundary)",
                     b->n_if * p.audio_upsamp, p.audio_decim);
-    b->Ha = b->resample ? (p.audio_taps - 1) / p.audio_upsamp : p.audio_taps - 1;
-    b->delay = stereo ? (p.stereo_taps - 1) / 2 : 0;                        // allPass, src/filter.cpp:14-29
-    b->Hd = b->Ha + b->delay;
-    if (stereo && p.stereo_taps - 1 + 3 > b->Hd) b->Hd = p.stereo_taps - 1 + 3;
-    const int more = b->res_hist > b->Ha ? b->res_hist - b->Ha : 0;   // (the lane-per-channel resampler rounds its windows up to whole iterations)
-    if (b->Ha + b->delay + more > b->Hd) b->Hd = b->Ha + b->delay + more;
-    b->Hd = (b->Hd + 3) / 4 * 4 + 4;
-    b->Hm = (b->Ha + more + 3) / 4 * 4 + 4;
+    // (the finish kernels copy the tail of a slot and of a row to its front: the two must not overlap)
     if (block_bytes < b->hist_bytes || b->n_if < b->Hd)
-        return fail(FMRX_EINVAL, "channels (exact): block of %zu bytes is shorter than the history a channel carries (%zu bytes, %d IF samples)",
-                    block_bytes, b->hist_bytes, b->Hd);
+        return fused ? fail(FMRX_EINVAL, "channels_create: block_bytes %zu < the %zu bytes of history a channel carries", block_bytes, b->hist_bytes)
+                     : fail(FMRX_EINVAL, "channels (exact): block of %zu bytes is shorter than the history a channel carries (%zu bytes, %d IF samples)",
+                            block_bytes, b->hist_bytes, b->Hd);
     b->slot_bytes = b->hist_bytes + block_bytes;
-    b->dpitch = (b->Hd + b->n_if + 16 + 3) / 4 * 4;
-    b->ypitch = (b->n_if + 16 + 3) / 4 * 4;
-    plan_chunks(*b);
-    const size_t N = static_cast<size_t>(n_channels);
-    // the last tile's lanes past the block read on (results discarded): 63*R outputs' worth of bytes behind the last slot
-    FMRX_TRY(b->slots.alloc(b->slot_bytes * N + 2 * 64 * kR * p.rf_decim + 64));
+    const size_t N = static_cast<size_t>(n_channels), total = b->slot_bytes * N;
+    if (fused && !mono_fused_available(b->fe, b->audio, reinterpret_cast<const uint8_t *>(16), total / 2, reinterpret_cast<const uint8_t *>(16)))
+        return fail(FMRX_EINVAL, "channels_create: no fused mono kernel for rf_taps %d / decim %d / audio_taps %d / decim %d",
+                    p.rf_taps, p.rf_decim, p.audio_taps, p.audio_decim);
+    // the kernels' last loads run on behind the last slot (results discarded): the exact front end's last tile by 63*R outputs' worth of bytes
+    FMRX_TRY(b->slots.alloc(total + 64 + (fused ? 0 : 2 * 64 * kR * p.rf_decim)));
     FMRX_TRY(k_fill_u8(b->slots.p, b->slots.n, 128, nullptr));                            // silence: a stream that starts here
-    FMRX_TRY(zeroed(b->demod, b->dpitch * N + 64));
+    if (fused) {
+        FMRX_TRY(zeroed(b->zeros, p.audio_taps + 64));
+        const size_t all = N * (b->junk_audio + b->n_audio);   // the audio of whole slots, junk included
+        FMRX_TRY(b->audio_all.alloc(all + 16));
+        FMRX_TRY(b->pcm_all.alloc(all + 16));
+    } else {
+        FMRX_TRY(zeroed(b->demod, b->dpitch * N + 64));
+    }
     if (stereo) {
         FMRX_TRY(b->k.bpf_table(*b, f.stereo.data(), f.pilot.data()));
         if (b->exact) {
@@ -205,7 +256,7 @@ int bank_create(Bank **out, const fmrx_params &p, int n_channels, int audio_chan
         for (hipEvent_t *e : {&b->ev_fork, &b->ev_join}) FMRX_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     FMRX_HIP(hipDeviceSynchronize());
-    *out = b.release();
+    out = std::move(b);
     return FMRX_OK;
 }
 
@@ -215,21 +266,24 @@ void bank_input_layout(const Bank *b, uint8_t **d_first_block, size_t *pitch_byt
     *d_first_block = b->slots.p + b->hist_bytes;
     *pitch_bytes = b->slot_bytes;
 }
-void bank_demod_layout(const Bank *b, const float **d_row0, size_t *pitch, size_t *n_if)
+int bank_demod_layout(const Bank *b, const float **d_row0, size_t *pitch, size_t *n_if)
 {
+    if (b->k.fused) return fail(FMRX_EINVAL, "channels_demod_layout: the fused mono bank of modes 0/1 keeps no discriminator rows");
     *d_row0 = b->demod.p + b->Hd;   // the finish kernel rewrites only the history in front of each row
     *pitch = static_cast<size_t>(b->dpitch);
     *n_if = static_cast<size_t>(b->n_if);
+    return FMRX_OK;
 }
 
 // back to the start-of-stream state (src/project.cpp:61-65, 446-458): one channel, or all of them (channel < 0).  One channel:
-// the history in front of each of its rows; the whole bank: the same buffers whole, one fill each.
+// the history in front of its slot and of each of its rows; the whole bank: the same buffers whole, one fill each.
 int bank_reset(Bank *b, int channel)
 {
     FMRX_HIP(hipDeviceSynchronize());
     const bool all = channel < 0;
     const size_t c = all ? 0 : channel, nc = all ? b->n_channels : 1;
     auto zero = [&](DevBuf<float> &buf, long pitch, int hist) {
+        if (!buf.p) return hipSuccess;   // rows this bank does not keep
         return all ? hipMemsetAsync(buf.p, 0, buf.bytes(), nullptr) : hipMemsetAsync(buf.p + c * pitch, 0, hist * sizeof(float), nullptr);
     };
     FMRX_TRY(k_fill_u8(b->slots.p + c * b->slot_bytes, all ? b->slot_bytes * nc : b->hist_bytes, 128, nullptr));
@@ -246,8 +300,9 @@ int bank_reset(Bank *b, int channel)
 // d_audio: [n_channels][audio_channels][n_audio] (stereo: left, then right); d_pcm: [n_channels][n_audio][audio_channels]
 int bank_process_dev(Bank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStream_t s)
 {
-    FMRX_TRY(b->audio_channels == 2 ? process_stereo(b, d_audio, d_pcm, wrap, s) : process_mono(b, d_audio, d_pcm, wrap, s));
-    return bank_launch_finish(*b, s);
+    FMRX_TRY(b->k.fused ? process_fused(b, d_audio, wrap, s)
+                        : b->audio_channels == 2 ? process_stereo(b, d_audio, d_pcm, wrap, s) : process_mono(b, d_audio, d_pcm, wrap, s));
+    return bank_launch_finish(*b, d_audio, d_pcm, s);
 }
 
 // diagnostics / tests: one channel's row of an intermediate of the last call.  which: FMRX_TAP_DEMOD, _CARRIER (fast banks: the
@@ -256,6 +311,9 @@ int bank_process_dev(Bank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStrea
 // the row stays raw; the other banks' NCO pass overwrites it in place)
 int bank_read_tap(Bank *b, int channel, int which, float *out, size_t *n)
 {
+    if (b->k.fused)
+        return fail(FMRX_EINVAL, "channels_read_tap: the fused mono bank of modes 0/1 keeps no intermediates in memory (stereo, exact and "
+                    "resampling-mode banks do)");
     if (channel < 0 || channel >= b->n_channels) return fail(FMRX_EINVAL, "channels_read_tap: channel %d of %d", channel, b->n_channels);
     FMRX_HIP(hipDeviceSynchronize());
     const size_t n_if = static_cast<size_t>(b->n_if);

@@ -15,6 +15,9 @@ constexpr float kPilotHz = 19e3f, kNcoScale = 2.0f, kPhaseAdjust = 0.0f, kPllBan
 // The kernels of one bank: its shapes, exact / fast and mono / stereo resolved to template instances once, when the bank is
 // created.  A table builder fills the bank's device table of that stage; a launcher covers a range of every channel's block.
 struct BankKernels {
+    // the fast mono bank of modes 0/1: the slots of all channels, back to back, are ONE pseudo-stream through the fused mono kernel
+    // (kernels_fe_mfma.hip: mono_fused_launch), which keeps nothing but the audio in memory: no rows, and none of the stages below
+    bool fused = false;
     size_t hist_bytes = 0;   // bytes of history the exact front end reads in front of a block
     int (*fe_table)(Bank &b, const float *h) = nullptr;
     int (*fe)(const Bank &b, long k_lo, long k_hi, hipStream_t s) = nullptr;                      // IF outputs [k_lo, k_hi)
@@ -30,7 +33,8 @@ bool bank_resolve(const fmrx_params &p, int audio_channels, int exact, BankKerne
 // chs_nco_kernel over [k_lo, k_hi) of n_rows rows of raw trigArg, in place; mixer != nullptr: the mixer rows too
 int bank_launch_nco(bool exact, float *trig, long ypitch, int n_rows, long k_lo, long k_hi, const float *bpf, const float *nco0,
                     float *mixer, long mpitch, int hm, hipStream_t s);
-int bank_launch_finish(const Bank &b, hipStream_t s);               // carried state: every row's tail -> its history
+// carried state: every slot's and row's tail -> its history; the fused kind: and its audio / PCM -> the caller's arrays
+int bank_launch_finish(const Bank &b, float *d_audio, int16_t *d_pcm, hipStream_t s);
 int bank_launch_fill_state(float *pll, long n, hipStream_t s);      // state_PLL of n / 8 channels at the start of a stream
 
 struct Bank {
@@ -44,6 +48,13 @@ struct Bank {
     DevBuf<uint8_t> slots;
     DevBuf<float> fe_table, bpf_table, out_table;
     FePlan fe;                      // fast banks: the matrix-core front end's tap image
+    // the fused kind: the audio taps' image, the options its launch takes, the audio samples per slot that the history region yields
+    // (computed and discarded), zeros for the discriminator history of the pseudo-stream, and the audio / PCM of whole slots
+    AudioPlan audio;
+    Options opt;
+    size_t junk_audio = 0;
+    DevBuf<float> zeros, audio_all;
+    DevBuf<int16_t> pcm_all;
     DevBuf<float> demod, carrier, bpf, trig, pll, nco0, mixtail[2];
     DevBuf<int8_t> carrier8;        // fast banks: the sign of the pilot band-pass output, one byte per IF sample
     // resampling modes (2, 3): the plain audio taps and, stereo, the mixer rows [Hm | n_if]

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -357,13 +358,13 @@ int k_stream_read(const void *d_buf, size_t bytes, int method, unsigned *d_sink,
 // d_seg_db: (n/nfft)*(nfft/2) floats of scratch; d_freq, d_psd: nfft/2 floats
 int k_estimate_psd(const float *d_x, size_t n, float Fs, int nfft, float *d_seg_db, float *d_freq, float *d_psd, hipStream_t s);
 
-// ---- banks of receivers: every stereo bank, the exact mono banks, the fast mono banks of modes 2 / 3 (bank.hip, kernels_bank.hip) ----
+// ---- banks of receivers, every kind (bank.hip, kernels_bank.hip; struct Bank: bank_kernels.hpp) ----
 struct Bank;
-int bank_create(Bank **out, const fmrx_params &p, int n_channels, int audio_channels, int exact, size_t block_bytes);
-void bank_destroy(Bank *b);
+int bank_create(std::unique_ptr<Bank> &out, const fmrx_params &p, int n_channels, int audio_channels, int exact, size_t block_bytes,
+                const Options &opt);
 size_t bank_n_audio(const Bank *b);
 void bank_input_layout(const Bank *b, uint8_t **d_first_block, size_t *pitch_bytes);
-void bank_demod_layout(const Bank *b, const float **d_row0, size_t *pitch, size_t *n_if);
+int bank_demod_layout(const Bank *b, const float **d_row0, size_t *pitch, size_t *n_if);   // FMRX_EINVAL: the bank keeps no rows
 int bank_reset(Bank *b, int channel);
 int bank_process_dev(Bank *b, float *d_audio, int16_t *d_pcm, int wrap, hipStream_t s);
 int bank_read_tap(Bank *b, int channel, int which, float *out, size_t *n);

@@ -1,5 +1,6 @@
 // kernels_bank.hip -- the kernels of a receiver bank (bank.hip: every stereo bank, the bit-exact mono banks and the fast mono banks of
 // modes 2 and 3), the host-side builders of their tap tables, their launchers, and the resolver from a bank's shapes to those.
+// Of the fast mono bank of modes 0/1 (the fused kind: one kernel of kernels_fe_mfma.hip for the whole chain) only the finish is here.
 //
 // The reference runs one receiver per process (one PARAMS / STATES set, src/project.cpp:455-468); its stereo
 // thread body RF_STEREO (src/project.cpp:154-309) is, per block of fm_demod:
@@ -833,6 +834,43 @@ __global__ void chs_finish_kernel(uint8_t *__restrict__ slots, long slot_bytes, 
     }
 }
 
+// the fused kind's finish.  Per channel: history <- the slot's last hist_bytes bytes; audio / PCM of the slot, minus the junk in front,
+// -> the caller's contiguous per-channel arrays.  Workgroups [c * gx, (c + 1) * gx) serve channel c: the channel rides in the
+// grid's x, which has room for any bank (y and z end at 65 535, and a bank may have more receivers than that)
+__global__ void channels_finish_kernel(uint8_t *__restrict__ slots, long slot_bytes, long hist_bytes, const float *__restrict__ audio_all,
+                                       const int16_t *__restrict__ pcm_all, long slot_audio, long junk_audio, long n_audio,
+                                       float *__restrict__ audio_out, int16_t *__restrict__ pcm_out, unsigned gx)
+{
+    const long c = blockIdx.x / gx;
+    const unsigned bx = blockIdx.x - static_cast<unsigned>(c) * gx;
+    uint8_t *slot = slots + c * slot_bytes;
+    const long t = static_cast<long>(bx) * blockDim.x + threadIdx.x, nt = static_cast<long>(gx) * blockDim.x;
+    const long so = c * slot_audio + junk_audio, dof = c * n_audio;   // first element of this channel: source, destination
+    // four outputs per access where source and destination allow it (8-byte s16 / 16-byte f32 pieces): true for every reference
+    // shape (52 600 / 1 024 elements per slot / channel, 28 in front)
+    if (n_audio % 4 == 0 && so % 4 == 0 && dof % 4 == 0 && (!pcm_out || (reinterpret_cast<uintptr_t>(pcm_out) % 8 == 0 &&
+        reinterpret_cast<uintptr_t>(pcm_all) % 8 == 0)) && (!audio_out || (reinterpret_cast<uintptr_t>(audio_out) % 16 == 0 &&
+        reinterpret_cast<uintptr_t>(audio_all) % 16 == 0))) {
+        typedef short s4v __attribute__((ext_vector_type(4)));
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        for (long k = t; k < n_audio / 4; k += nt) {
+            if (audio_out) reinterpret_cast<f4v *>(audio_out + dof)[k] = reinterpret_cast<const f4v *>(audio_all + so)[k];
+            if (pcm_out) reinterpret_cast<s4v *>(pcm_out + dof)[k] = reinterpret_cast<const s4v *>(pcm_all + so)[k];
+        }
+    } else {
+        for (long k = t; k < n_audio; k += nt) {
+            if (audio_out) audio_out[dof + k] = audio_all[so + k];
+            if (pcm_out) pcm_out[dof + k] = pcm_all[so + k];
+        }
+    }
+    // history: 16-byte pieces; source and destination overlap only if the block is shorter than the history, which
+    // create() rejects, so a plain copy is safe whatever the order
+    const u4 *src = reinterpret_cast<const u4 *>(slot + slot_bytes - hist_bytes);
+    u4 *dst = reinterpret_cast<u4 *>(slot);
+    if (bx == 0)
+        for (long i = threadIdx.x; i < hist_bytes / 16; i += blockDim.x) dst[i] = src[i];
+}
+
 __global__ void chs_fill_state_kernel(float *__restrict__ pll, long n)
 {
     const long i = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1032,12 +1070,14 @@ int launch_resample(Bank &b, float *d_audio, int16_t *d_pcm, int wrap, long a_lo
 }  // namespace
 
 // The one place the shape lists are expanded.  Fast banks keep the exact front end's table and history (its tap-range check
-// and slot layout hold for them too) and launch the matrix-core front end; the fast mono bank of modes 0/1 has no output
-// stage here (it is the fused-kernel bank of channels.hip).
+// and slot layout hold for them too) and launch the matrix-core front end.  The fast mono bank of modes 0/1 is the fused kind:
+// decided here and nowhere else; whether the fused mono kernel has its shapes is asked when its plans exist (bank_create).
 bool bank_resolve(const fmrx_params &p, int audio_channels, int exact, BankKernels &k)
 {
     const bool stereo = audio_channels == 2;
     k = BankKernels{};
+    k.fused = !stereo && !exact && p.audio_upsamp == 0;
+    if (k.fused) return true;
 #define X(T_, D_) \
     if (p.rf_taps == T_ && p.rf_decim == D_) { k.hist_bytes = FeX<T_, D_>::HIST; k.fe_table = fe_table_init<T_, D_>; k.fe = exact ? launch_fe<T_, D_> : launch_fe_mfma; }
     CHS_FE_CASES(X)
@@ -1048,7 +1088,7 @@ bool bank_resolve(const fmrx_params &p, int audio_channels, int exact, BankKerne
 #define X(T_, D_)                                                                                                        \
     if (p.audio_upsamp == 0 && p.audio_taps == T_ && p.audio_decim == D_) {                                              \
         k.out_table = [](Bank &b, const float *h) { return upload(b.out_table, step_major_table<OutX, T_, D_>(h, 1.0f)); };  \
-        k.out = stereo ? (exact ? launch_out<T_, D_, true, true> : launch_out<T_, D_, true, false>) : (exact ? launch_out<T_, D_, false, true> : nullptr); \
+        k.out = stereo ? (exact ? launch_out<T_, D_, true, true> : launch_out<T_, D_, true, false>) : launch_out<T_, D_, false, true>; \
     }
     CHS_OUT_CASES(X)
 #undef X
@@ -1073,8 +1113,19 @@ int bank_launch_nco(bool exact, float *trig, long ypitch, int n_rows, long k_lo,
     return FMRX_OK;
 }
 
-int bank_launch_finish(const Bank &b, hipStream_t s)
+int bank_launch_finish(const Bank &b, float *d_audio, int16_t *d_pcm, hipStream_t s)
 {
+    if (b.k.fused) {
+        // workgroups per channel: four outputs per thread where the shapes allow it (see the kernel), 8 at the most -- times
+        // n_channels they fit the grid's x (2^31 - 1) for every bank whose slots fit a device's memory
+        const long g = ((b.n_audio + 3) / 4 + 255) / 256;
+        const unsigned gx = static_cast<unsigned>(g < 1 ? 1 : g < 8 ? g : 8);
+        hipLaunchKernelGGL(channels_finish_kernel, dim3(gx * static_cast<unsigned>(b.n_channels)), dim3(256), 0, s, b.slots.p,
+                           static_cast<long>(b.slot_bytes), static_cast<long>(b.hist_bytes), b.audio_all.p, b.pcm_all.p,
+                           static_cast<long>(b.junk_audio) + b.n_audio, static_cast<long>(b.junk_audio), b.n_audio, d_audio, d_pcm, gx);
+        FMRX_LAUNCH_CHECK("channels_finish_kernel");
+        return FMRX_OK;
+    }
     hipLaunchKernelGGL(chs_finish_kernel, dim3(static_cast<unsigned>(b.n_channels)), dim3(64), 0, s, b.slots.p,
                        static_cast<long>(b.slot_bytes), static_cast<long>(b.hist_bytes), b.demod.p, b.dpitch, b.Hd, b.n_if,
                        b.resample && b.audio_channels == 2 ? b.mixer.p : nullptr, b.mpitch, b.Hm);

@@ -1,7 +1,7 @@
 // rds_bank.hip -- the RDS chain of N channels per device call: the chain itself (rds_chain.hpp), which the single-stream handle
 // (rds.hip: include/fmrx.h fmrx_rds_*) runs with one channel, and the bank around it (fmrx_rds_bank_*).
 //
-// A receiver bank (channels.hip, bank.hip) demodulates 10^4 - 10^5 stations per call; the chain gives each of them the float64
+// A receiver bank (bank.hip) demodulates 10^4 - 10^5 stations per call; the chain gives each of them the float64
 // arithmetic of the reference's model (rds.hip lists the stages) in a FIXED number of launches, whatever the number of channels
 // (tests/_rds_stage_model.py is the model of every stage's order of operations):
 //   rdsb_cvt_kernel         f32 demod rows (caller's pitch) -> f64 rows behind their histories

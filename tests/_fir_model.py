@@ -248,7 +248,7 @@ def fused_audio(x, h, decim, k0=0, n_out=None, kq_order=MFMA_K_ORDER, row0=0):
     chain from +0 over j ascending, kq in `kq_order` inside each MFMA, padding K-steps included; y = y0 + y1 (one f32
     add).  x: the discriminator stream from its start (samples before it are 0).
 
-    row0: the row of output k0 where the block does not start a launch -- the fused mono bank (channels.hip) runs all
+    row0: the row of output k0 where the block does not start a launch -- the fused mono bank (bank.hip) runs all
     slots as one launch, so channel c's first kept output sits at row (c * slot_audio + junk_audio) mod 16.  The row
     decides which K-steps carry an output's taps, hence which products land in the even and which in the odd chain.  It
     is the block that starts row0 outputs earlier, those outputs dropped (16 DA zeros in front keep them in the

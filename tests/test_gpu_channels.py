@@ -337,3 +337,77 @@ def test_eight_pipelines_on_eight_streams(fmrx, oracle):
     assert len({hashlib.sha256(a[0].tobytes()).digest() for a in alone}) == nch
     for pl in pls:
         pl.close()
+
+
+def fused_block(fmrx, oracle, mode, N=3):
+    """(the smallest block the fused mono bank of this mode takes at 101/101 taps, one such block of N receivers' streams)"""
+    from test_gpu_mono_banks_exact import smallest_fused_block
+    bb = smallest_fused_block(fmrx, mode, 101, 101)
+    rf_Fs = fmrx.modeParams(mode, 101, 101).rf_Fs
+    return bb, np.stack([channel_stream(oracle, c, bb // 2, rf_Fs) for c in range(N)])
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_fused_mono_bank_refusals(fmrx, oracle, mode):
+    """The fast mono bank of modes 0/1 keeps no rows: the tap read-back and the rows' layout are FMRX_EINVAL in the bank's own
+    words; a channel index past the bank is refused by the reset every bank goes through (an exact mono bank too).  None of
+    the refusals disturbs the handle: one block through it equals a fresh handle's bit for bit."""
+    bb, iq = fused_block(fmrx, oracle, mode)
+    ch = fmrx.Channels(mode, 3, block_bytes=bb)
+    for refused in (lambda: ch.read_tap(0, "demod"), ch.demod_layout):
+        with pytest.raises(fmrx.FmrxError) as e:
+            refused()
+        assert e.value.code == fmrx.EINVAL and "fused mono bank" in str(e.value)
+    exact = fmrx.Channels(mode, 3, exact=True)
+    for bank in (ch, exact):
+        with pytest.raises(fmrx.FmrxError):
+            bank.reset(3)
+    got, want = ch.process(iq), fmrx.Channels(mode, 3, block_bytes=bb).process(iq)
+    assert np.any(want["pcm16"] != 0)
+    bits_equal(got["audio"], want["audio"], f"mode {mode}: audio after the refusals")
+    bits_equal(got["pcm16"], want["pcm16"], f"mode {mode}: pcm after the refusals")
+
+
+@pytest.mark.parametrize("mode, taps, unit, hist", [(0, 101, 100, 2800), (1, 101, 60, 1440), (0, 13, 100, 800)])
+def test_fused_mono_bank_geometry(fmrx, mode, taps, unit, hist):
+    """The history in front of a fused mono bank's slot, by hand from reach = rf_decim (audio_taps + 1) + rf_taps + 8 rf_decim
+    complex samples, two bytes each, rounded up to whole audio samples (unit = 2 rf_decim audio_decim bytes) and then, unit by
+    unit, to a multiple of 16:
+        mode 0, 101/101 taps: reach 1 201 -> 2 402 bytes -> 2 500 -> 2 800 (28 discarded audio samples per slot)
+        mode 1, 101/101 taps: reach   651 -> 1 302       -> 1 320 -> 1 440 (24)
+        mode 0,  13/13  taps: reach   233 ->   466       ->   500 ->   800 (8)
+    The bit-exact tests read the geometry from the handle; a history that grew would pass them and cost memory and time."""
+    from test_gpu_mono_banks_exact import bank_of, smallest_fused_block
+    bb = smallest_fused_block(fmrx, mode, taps, taps)
+    ch = bank_of(fmrx, mode, taps, taps, 2, bb)
+    assert ch.input_layout()[1] - bb == hist
+    assert ch.n_audio == bb // unit
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_close_behind_a_call_on_another_stream(fmrx, oracle, mode):
+    """close() right behind load_dev / process_dev on a stream of the caller's, nothing waited for in between: the call's
+    kernels run on that stream, not the handle's, and close() must let them finish before it frees what they use.  The PCM
+    and the audio equal those of a second handle that was waited for before its close()."""
+    import torch
+    bb, iq = fused_block(fmrx, oracle, mode)
+    d_iq = torch.from_numpy(iq).cuda()
+    stream = torch.cuda.Stream()
+
+    def run(wait_before_close):
+        ch = fmrx.Channels(mode, 3, block_bytes=bb)
+        d_pcm = torch.zeros(3, ch.n_audio, dtype=torch.int16, device="cuda")
+        d_f32 = torch.zeros(3, ch.n_audio, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        ch.load_dev(d_iq.data_ptr(), stream=stream.cuda_stream)
+        ch.process_dev(d_f32.data_ptr(), d_pcm.data_ptr(), stream=stream.cuda_stream)
+        if wait_before_close:
+            stream.synchronize()
+        ch.close()
+        stream.synchronize()
+        return d_pcm.cpu().numpy(), d_f32.cpu().numpy()
+
+    (pcm, f32), (want_pcm, want_f32) = run(False), run(True)
+    assert np.any(want_pcm != 0)
+    bits_equal(pcm, want_pcm, f"mode {mode}: pcm")
+    bits_equal(f32, want_f32, f"mode {mode}: audio")

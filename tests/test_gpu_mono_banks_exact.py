@@ -1,7 +1,7 @@
 """The two fast MONO banks checked BIT FOR BIT against the fma-chain models of tests/_fir_model.py: no tolerance anywhere,
 float outputs compared as uint32, PCM as integers.
 
-  the fused mono bank of modes 0/1 (channels.hip: mono_fused_kernel over all slots as one pseudo-stream, then
+  the fused mono bank of modes 0/1 (bank.hip: mono_fused_kernel over all slots as one pseudo-stream, then
   channels_finish_kernel) = fused_audio(row0 = the row of the channel's first kept output in the launch), fed the
   discriminator stream of a twin single-stream pipeline that saw this channel's samples alone, in the same cuts.  A
   neighbour's sample in a window, a wrong history byte at the seam between calls, a junk count off by one, a wrong
