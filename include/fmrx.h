@@ -1493,6 +1493,102 @@ FMRX_API int fmrx_audio_spectrum_collect(fmrx_audio_spectrum *m, fmrx_audio_spec
  * use is n_channels = 1 with the audio fmrx_pipeline_process returns */
 FMRX_API int fmrx_audio_spectrum_process(fmrx_audio_spectrum *m, const float *audio, size_t row_pitch, size_t n, fmrx_audio_spectrum_record *records);
 
+/* ------------------------------------------------------------------ */
+/* Audio feature frames: a mel-band spectrogram of every channel        */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference.  Every stage above reduces a channel and call to one record; what a monitor does next --
+ * speech against music, speech-to-text, jingle and advert detection, programme fingerprinting -- starts from a time series: a
+ * mel-band spectrogram at a 10 ms hop.  This stage leaves it on the device as a tensor [n_channels][frames][n_mels] that a
+ * model reads by pointer, without the samples leaving the card.  ... -> leveller -> true peak / audio spectrum / audio features
+ * on one stream; a handle of the audio meters' kind that only reads the rows.  Defined by tests/_audio_features_model.py
+ * (DESIGN.md section 4.18); the host walk and the device equal that model bit for bit (a NaN's sign and payload are the machine's).
+ *
+ * Geometry (fmrx_audio_features_params, set at create): win, the frame length in samples, a multiple of 4 within 16 .. 1280; hop
+ * 1 .. win; n_bins 1 .. min(256, win / 2), bins 0 .. n_bins - 1 of a DFT of period win; n_mels 1 .. 128; 0 <= f_lo < f_hi <=
+ * audio_Fs / 2, all finite.  Anything else: FMRX_EINVAL.  fmrx_audio_features_preset fills in the speech-model geometry:
+ *   audio_Fs 48 000: win 1200 (25 ms), hop 480 (10 ms), 201 bins, 80 mels, 0 .. 8 kHz: bin k sits at 40 k Hz, the bins of a 400-point
+ *                    DFT of the signal at 16 kHz, with no resampler and no aliasing
+ *   audio_Fs 44 100: win 1104, hop 441, 201 bins (39.95 Hz apart), 80 mels, 0 .. 8 kHz
+ * and refuses any other rate.
+ * Tables (float32, made on the host in double and rounded once; what fmrx_audio_features_tables returns is the definition):
+ *   w[j] = 0.5 - 0.5 cos(2 pi j / win), the periodic Hann window, w[0] = +0, w[win - j] = w[j]
+ *   C[m] = cos(2 pi m / win), m = 0 .. win - 1, unfolded from the quarter m = 0 .. win / 4 by symmetry (C[win/2 - m] = -C[m],
+ *          C[win - m] = C[m]); C[win/4] = C[3 win/4] = +0 exactly
+ *   mel filters on the Slaney scale (linear at 200/3 Hz per mel below 1 kHz, logarithmic with step ln(6.4)/27 above): n_mels + 2
+ *          points f[i] equally spaced in mel from f_lo to f_hi; mel_w[b][k] = the triangle over f[b], f[b+1], f[b+2] at k audio_Fs /
+ *          win, times the Slaney norm 2 / (f[b+2] - f[b]); mel_lo[b] .. mel_hi[b] - 1 are the contiguous bins whose weight is
+ *          positive, lo = hi = 0 where there are none (that feature reads +0)
+ * Per frame: samples m[j], j < win, of the mono mix: m = 0.5f (L + R) for a stereo channel (one float32 add, then an exact
+ * halving), row 0 for a mono one.  xw[j] = m[j] w[j]; for bins k = 0 .. n_bins - 1
+ *   re_k = acc = +0;  for j = 0 .. win - 1 ascending: acc = fmaf(C[(k j) mod win], xw[j], acc)
+ *   im_k = the same chain with C[(k j - win/4) mod win]
+ *   p_k  = fmaf(im_k, im_k, fl(re_k re_k))
+ *   feat[b] = acc = +0;  for k = mel_lo[b] .. mel_hi[b] - 1 ascending: acc = fmaf(mel_w[b][k], p_k, acc)
+ * every step rounded once, float32 denormals kept; NaN and infinity propagate as the arithmetic has them.  The output is linear
+ * mel power; the logarithm is the caller's.
+ * Frames: a row is a stream across calls.  Frame f covers stream samples f hop .. f hop + win - 1; nothing stands in front of a
+ * fresh stream (no centre padding).  The carried state per channel (fmrx_audio_features_state) is fill (0 .. win - 1) and the fill
+ * samples of the mono mix.  A call of n samples has T = fill + n; it completes F = 0 frames if T < win, else (T - win) div hop + 1,
+ * and carries T - F hop samples.  At most F_max = (n_audio - 1) div hop + 1 frames complete per call
+ * (fmrx_audio_features_max_frames; 4 for a bank row of 1 920 at the preset).  The frames do not depend on how a stream is cut
+ * into calls: the same stream cut differently gives the same frames, byte for byte.
+ * Results per call: feat [n_channels][F_max][n_mels] float32, frames >= F of a channel +0, and frames [n_channels] uint32, on
+ * the device (fmrx_audio_features_result_dev) and, on request, on the host (fmrx_audio_features_collect).
+ *
+ * The device pass: a frame's 2 n_bins chains are a matrix product on the f32 matrix cores (v_mfma_f32_16x16x4_f32: 16 outputs x 4
+ * window positions x 16 frames), which rounds as the chains above do.  The 16 columns of a workgroup are consecutive entries of
+ * the flattened (channel, frame < F_max) list, so a tile spans several channels and a long row many tiles; one launch. */
+typedef struct fmrx_audio_features_params {
+    uint32_t win, hop, n_bins, n_mels;
+    double f_lo, f_hi, audio_Fs;
+} fmrx_audio_features_params;
+typedef struct fmrx_audio_features_state {
+    uint32_t fill;
+    float carry[1279];      /* the mono mix; entries at and beyond fill read 0 */
+} fmrx_audio_features_state;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_audio_features_params) == 40, "fmrx_audio_features_params layout");
+static_assert(sizeof(fmrx_audio_features_state) == 5120, "fmrx_audio_features_state layout");
+#else
+_Static_assert(sizeof(fmrx_audio_features_params) == 40, "fmrx_audio_features_params layout");
+_Static_assert(sizeof(fmrx_audio_features_state) == 5120, "fmrx_audio_features_state layout");
+#endif
+typedef struct fmrx_audio_features fmrx_audio_features;
+/* Host code, no device needed.  preset: audio_Fs 48000 or 44100.  tables: window [win], cosine [win], mel_lo [n_mels], mel_hi
+ * [n_mels], mel_w [n_mels][n_bins].  max_frames: F_max of a call of n_audio samples; 0 for a refused geometry or n_audio = 0. */
+FMRX_API int fmrx_audio_features_preset(double audio_Fs, fmrx_audio_features_params *params);
+FMRX_API int fmrx_audio_features_tables(const fmrx_audio_features_params *params, float *window, float *cosine, int32_t *mel_lo, int32_t *mel_hi,
+                                        float *mel_w);
+FMRX_API size_t fmrx_audio_features_max_frames(const fmrx_audio_features_params *params, size_t n_audio);
+/* The host reference of one channel: rows [audio_channels][row_pitch] floats of which n (1 .. 2^26) are walked; *state_in_out is
+ * read and replaced (a fill of win or more: FMRX_EINVAL); feat [max_frames(params, n)][n_mels] is written whole, frames the call
+ * did not complete +0; *frames is the count F.  The body the kernel's arithmetic is checked against (audio_features_core.hpp). */
+FMRX_API int fmrx_audio_features_walk(const fmrx_audio_features_params *params, int audio_channels, const float *rows, size_t row_pitch, size_t n,
+                                      fmrx_audio_features_state *state_in_out, float *feat, uint32_t *frames);
+/* n_audio: the most samples per row and call (fmrx_channels_n_audio), 1 .. 2^26; audio_channels 1 or 2 */
+FMRX_API int fmrx_audio_features_create(fmrx_audio_features **out, const fmrx_audio_features_params *params, int n_channels, int audio_channels,
+                                        size_t n_audio, int device);
+FMRX_API int fmrx_audio_features_destroy(fmrx_audio_features *m);
+/* channel < 0: all.  Clears the channel's carried samples (fill = 0): its stream starts anew.  Waits for the handle's last call;
+ * the state is clear when it returns, for a later call on any stream. */
+FMRX_API int fmrx_audio_features_reset(fmrx_audio_features *m, int channel);
+/* out [n_channels]: every channel's carried state; waits for the handle's last call */
+FMRX_API int fmrx_audio_features_state_get(fmrx_audio_features *m, fmrx_audio_features_state *out);
+/* Asynchronous on `stream`, behind whatever wrote the rows on the same stream: d_audio [n_channels][audio_channels][row_pitch]
+ * floats, as the banks and every later stage write them (row_pitch = n_audio there), of which the first n <= n_audio of every
+ * row are walked; 4-byte aligned, at any pitch.  The rows are only read.  One kernel launch and no copy; a second call before
+ * fmrx_audio_features_collect replaces the results (the state has then advanced by both). */
+FMRX_API int fmrx_audio_features_process_dev(fmrx_audio_features *m, const float *d_audio, size_t row_pitch, size_t n, void *stream);
+/* The last call's results where the kernel left them: *d_feat [n_channels][F_max][n_mels] floats, *d_frames [n_channels].  The
+ * pointers are the handle's and hold until it is destroyed; their contents are the last call's, ordered behind it on its stream,
+ * until the handle's next call.  This is the tensor a torch consumer wraps. */
+FMRX_API int fmrx_audio_features_result_dev(fmrx_audio_features *m, const float **d_feat, const uint32_t **d_frames);
+/* feat [n_channels][F_max][n_mels], frames [n_channels], to the host; waits for the last call (an event it recorded), not for
+ * the device */
+FMRX_API int fmrx_audio_features_collect(fmrx_audio_features *m, float *feat, uint32_t *frames);
+/* host rows [n_channels][audio_channels][row_pitch], synchronous (it first waits for the handle's last call), then as collect */
+FMRX_API int fmrx_audio_features_process(fmrx_audio_features *m, const float *audio, size_t row_pitch, size_t n, float *feat, uint32_t *frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1569,7 +1569,7 @@ def audioMetersDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dic
 
 
 class _AudioReader(_Handle):
-    """What AudioMeters, TruePeak and AudioSpectrum share: a handle that only reads a bank's audio rows (csrc/meter_stage.hpp's Reader).  A
+    """What AudioMeters, TruePeak, AudioSpectrum and AudioFeatures share: a handle that only reads a bank's audio rows (csrc/meter_stage.hpp's Reader).  A
     subclass names its fmrx_<_prefix>_* functions and its module-level derive function, creates self._h, and says in _bank_extra
     what its constructor takes beyond n_channels, audio_channels, n_audio and device."""
 
@@ -1975,6 +1975,123 @@ class AudioSpectrum(_AudioReader):
         out = np.zeros(self.n_channels, AUDIO_SPECTRUM_DTYPE)
         self._call("process", x.ctypes.data, x.shape[2], x.shape[2], out.ctypes.data)
         return out
+
+
+# --------------------------------------------------------------------------
+# Audio feature frames: a mel-band spectrogram of every channel of a bank
+# --------------------------------------------------------------------------
+class AudioFeaturesParams(C.Structure):
+    """struct fmrx_audio_features_params (include/fmrx.h): the geometry of the feature frames."""
+    _fields_ = [("win", C.c_uint32), ("hop", C.c_uint32), ("n_bins", C.c_uint32), ("n_mels", C.c_uint32), ("f_lo", _dbl), ("f_hi", _dbl),
+                ("audio_Fs", _dbl)]
+
+
+AUDIO_FEATURES_STATE_DTYPE = np.dtype([("fill", "<u4"), ("carry", "<f4", (1279,))])                                # struct fmrx_audio_features_state
+assert C.sizeof(AudioFeaturesParams) == 40 and AUDIO_FEATURES_STATE_DTYPE.itemsize == 5120
+_afp = C.POINTER(AudioFeaturesParams)
+_sig("fmrx_audio_features_preset", [_dbl, _afp])
+_sig("fmrx_audio_features_tables", [_afp, _vp, _vp, _vp, _vp, _vp])
+_sig("fmrx_audio_features_max_frames", [_afp, _sz], _sz)
+_sig("fmrx_audio_features_walk", [_afp, _int, _vp, _sz, _sz, _vp, _vp, _vp])
+_sig("fmrx_audio_features_create", [C.POINTER(_vp), _afp, _int, _int, _sz, _int])
+_sig("fmrx_audio_features_destroy", [_vp])
+_sig("fmrx_audio_features_reset", [_vp, _int])
+_sig("fmrx_audio_features_state_get", [_vp, _vp])
+_sig("fmrx_audio_features_process_dev", [_vp, _vp, _sz, _sz, _vp])
+_sig("fmrx_audio_features_result_dev", [_vp, C.POINTER(_vp), C.POINTER(_vp)])
+_sig("fmrx_audio_features_collect", [_vp, _vp, _vp])
+_sig("fmrx_audio_features_process", [_vp, _vp, _sz, _sz, _vp, _vp])
+
+
+def _features_params(params) -> AudioFeaturesParams:
+    """An AudioFeaturesParams from one, from a dict of its fields, or from (win, hop, n_bins, n_mels, f_lo, f_hi, audio_Fs)."""
+    if isinstance(params, AudioFeaturesParams):
+        return params
+    if isinstance(params, dict):
+        return AudioFeaturesParams(**params)
+    return AudioFeaturesParams(*params)
+
+
+def audioFeaturesPreset(audio_Fs=48000.0) -> AudioFeaturesParams:
+    """Host only: the speech-model geometry for an audio rate of 48 000 or 44 100 Hz (fmrx_audio_features_preset)."""
+    p = AudioFeaturesParams()
+    _check(lib.fmrx_audio_features_preset(float(audio_Fs), C.byref(p)))
+    return p
+
+
+def audioFeaturesTables(params) -> dict:
+    """Host only: the float32 tables that define the stage for a geometry (fmrx_audio_features_tables): window [win], cosine [win],
+    mel_lo and mel_hi int32 [n_mels], mel_w [n_mels, n_bins]."""
+    p = _features_params(params)
+    shape = (max(int(p.n_mels), 1), max(int(p.n_bins), 1))
+    t = dict(window=np.zeros(max(int(p.win), 1), np.float32), cosine=np.zeros(max(int(p.win), 1), np.float32), mel_lo=np.zeros(shape[0], np.int32),
+             mel_hi=np.zeros(shape[0], np.int32), mel_w=np.zeros(shape, np.float32))
+    _check(lib.fmrx_audio_features_tables(C.byref(p), *(t[k].ctypes.data for k in ("window", "cosine", "mel_lo", "mel_hi", "mel_w"))))
+    return t
+
+
+def audioFeaturesMaxFrames(params, n_audio) -> int:
+    """Host only: the most frames a call of n_audio samples completes, (n_audio - 1) // hop + 1; 0 for a refused geometry."""
+    return int(lib.fmrx_audio_features_max_frames(C.byref(_features_params(params)), int(n_audio)))
+
+
+def audioFeaturesWalk(rows, params, state=None):
+    """Host only: the reference walk of one channel (fmrx_audio_features_walk) on rows float32 [audio_channels, n]; state: the
+    AUDIO_FEATURES_STATE_DTYPE record the last call returned (None or zeros: a fresh channel) -> (feat float32 [F_max(n), n_mels],
+    frames, state)."""
+    p = _features_params(params)
+    x = _walk_rows(rows)
+    st = np.zeros(1, AUDIO_FEATURES_STATE_DTYPE) if state is None else np.array(state, dtype=AUDIO_FEATURES_STATE_DTYPE).reshape(1).copy()
+    feat = np.zeros((max(audioFeaturesMaxFrames(p, x.shape[1]), 1), max(int(p.n_mels), 1)), np.float32)
+    frames = np.zeros(1, np.uint32)
+    _check(lib.fmrx_audio_features_walk(C.byref(p), x.shape[0], x.ctypes.data, x.shape[1], x.shape[1], st.ctypes.data, feat.ctypes.data, frames.ctypes.data))
+    return feat, int(frames[0]), st[0]
+
+
+class AudioFeatures(_AudioReader):
+    """Per channel of a receiver bank: a mel-band spectrogram of the channel's mono mix, n_mels linear powers per frame of win
+    samples every hop samples, across calls (fmrx_audio_features_*).  Behind the last audio stage on stream
+    s: af = AudioFeatures.for_bank(bank); af.process_bank(d_out, stream=s); ptr, frames_ptr, shape = af.result_dev() for a
+    consumer on the device, or feat, frames = af.collect().  params: None for the preset of the audio rate."""
+    _prefix = "audio_features"
+    _bank_extra = staticmethod(lambda bank, params=None: {"params": audioFeaturesPreset(bank.params.audio_Fs) if params is None else params})
+
+    def __init__(self, n_channels=1, audio_channels=2, n_audio=1920, params=None, device=0):
+        self.n_channels, self.audio_channels, self.n_audio = int(n_channels), int(audio_channels), int(n_audio)
+        self.params = audioFeaturesPreset(48000.0) if params is None else _features_params(params)
+        self._h = _vp()
+        _check(lib.fmrx_audio_features_create(C.byref(self._h), C.byref(self.params), self.n_channels, self.audio_channels, self.n_audio, device))
+        self.n_mels = int(self.params.n_mels)
+        self.max_frames = audioFeaturesMaxFrames(self.params, self.n_audio)
+
+    def _results(self):
+        return np.zeros((self.n_channels, self.max_frames, self.n_mels), np.float32), np.zeros(self.n_channels, np.uint32)
+
+    def state(self) -> np.ndarray:
+        """Waits for the last call; every channel's carried state, AUDIO_FEATURES_STATE_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, AUDIO_FEATURES_STATE_DTYPE)
+        self._call("state_get", out.ctypes.data)
+        return out
+
+    def result_dev(self):
+        """(feat_ptr, frames_ptr, (n_channels, F_max, n_mels)): the last call's float32 features and uint32 frame counts on the
+        device, ordered behind the call on its stream and valid until the handle's next call."""
+        feat, frames = _vp(), _vp()
+        self._call("result_dev", C.byref(feat), C.byref(frames))
+        return feat.value, frames.value, (self.n_channels, self.max_frames, self.n_mels)
+
+    def collect(self):
+        """Waits for the last call; (feat float32 [n_channels, F_max, n_mels], frames uint32 [n_channels])."""
+        feat, frames = self._results()
+        self._call("collect", feat.ctypes.data, frames.ctypes.data)
+        return feat, frames
+
+    def process(self, audio):
+        """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
+        x = self._rows(audio)
+        feat, frames = self._results()
+        self._call("process", x.ctypes.data, x.shape[2], x.shape[2], feat.ctypes.data, frames.ctypes.data)
+        return feat, frames
 
 
 class FrontEndPlan(_Handle):

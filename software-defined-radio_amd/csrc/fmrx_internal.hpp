@@ -562,4 +562,26 @@ struct AudioSpectrumArgs {
 size_t audio_spectrum_tiles(size_t n);   // the tiles of 16 frames a row of n samples can complete, whatever its fill
 int audio_spectrum_launch(const AudioSpectrumArgs &a, hipStream_t s);
 
+// ---- audio feature frames (kernels_audio_features.hip; tables and frame arithmetic in audio_features_core.hpp; handle and C ABI in
+// audio_features.hip) --------------------------------------------------------------------------------------------------------------
+struct AudioFeaturesArgs {
+    const float *x = nullptr;            // [n_channels][ac][pitch]; only read
+    size_t pitch = 0, n = 0;             // floats per row; samples of every row to walk
+    int n_channels = 0, ac = 1;
+    int win = 0, hop = 0, n_bins = 0, n_mels = 0;
+    size_t f_max = 0;                    // frames per channel in feat
+    // device tables: w [win], c [win], mel_lo / mel_hi [n_mels], mel_w [n_mels][n_bins]
+    const float *w = nullptr, *c = nullptr, *mel_w = nullptr;
+    const int *mel_lo = nullptr, *mel_hi = nullptr;
+    // the carried state, channel-major: fill [n_channels], carry [n_channels][win] floats of the mono mix of which the first fill count
+    const unsigned *fill_in = nullptr;
+    const float *carry_in = nullptr;
+    unsigned *fill_out = nullptr;        // another pair of buffers of those shapes
+    float *carry_out = nullptr;
+    unsigned *frames = nullptr;          // [n_channels]: the frames the call completed
+    float *feat = nullptr;               // [n_channels][f_max][n_mels]; frames the call did not complete read +0
+};
+size_t audio_features_tiles(size_t n_channels, size_t f_max);   // the workgroups of a call: 16 columns of the (channel, frame) list each
+int audio_features_launch(const AudioFeaturesArgs &a, hipStream_t s);
+
 }  // namespace fmrx
