@@ -1589,6 +1589,102 @@ FMRX_API int fmrx_audio_features_collect(fmrx_audio_features *m, float *feat, ui
 /* host rows [n_channels][audio_channels][row_pitch], synchronous (it first waits for the handle's last call), then as collect */
 FMRX_API int fmrx_audio_features_process(fmrx_audio_features *m, const float *audio, size_t row_pitch, size_t n, float *feat, uint32_t *frames);
 
+/* ------------------------------------------------------------------ */
+/* Audio rate converter: a bank's audio at 16 kHz mono or any rate U/D  */
+/* ------------------------------------------------------------------ */
+/* No counterpart in the reference (its resampler is the IF-to-audio stage inside the pipeline).  A bank writes 48 or 44.1 kHz;
+ * speech models, voice-activity detectors and loggers take 16 kHz mono, fingerprinters 8 .. 11 kHz, a restream 32 or 44.1 kHz.
+ * This stage converts every channel's audio, the mono mix or each row, by a polyphase FIR at a rational rate up / down, carries
+ * its history and phase from call to call and leaves the samples on the device as [n_channels][R][M_max] float32 and / or s16
+ * that a model reads by pointer.  ... -> leveller -> true peak / audio spectrum / audio features / audio resample on one stream; a
+ * handle of the audio meters' kind that only reads the rows.  Defined by tests/_audio_resample_model.py;
+ * the host walk and the device equal that model bit for bit (a NaN's sign and payload are the machine's).
+ *
+ * Geometry (fmrx_audio_resample_params, set at create): up 1 .. 160, down 1 .. 1024, gcd(up, down) = 1; taps T, the input samples
+ * an output reads, a multiple of 4 within 8 .. 256 with up taps <= 16 384; mix 0 or 1; 0 < cutoff <= 1; 0 <= beta <= 20.  Anything
+ * else, or a double that is not finite: FMRX_EINVAL.  fmrx_audio_resample_preset(audio_Fs, out_Fs, mix) fills it in for two integer
+ * rates within 8 000 .. 48 000: up / down = out_Fs / audio_Fs reduced, taps = 4 ceil(24 / min(1, up / down) / 4) (twelve zero
+ * crossings a side), cutoff 0.9, beta 8; it refuses other rates and ratios beyond the limits.
+ *   48 000 -> 16 000: 1/3, T 72     -> 8 000: 1/6, T 144      -> 24 000: 1/2, T 48     -> 32 000: 2/3, T 36     -> 44 100: 147/160, T 28
+ *   44 100 -> 16 000: 160/441, T 68      -> 22 050: 1/2, T 48      -> 48 000: 160/147, T 24
+ * Taps (float32, made on the host in double and rounded once; what fmrx_audio_resample_taps returns, [up][taps] phase-major, is
+ * the definition): with L = up T, c = (L - 1) / 2, w = cutoff min(1, up / down), for k < L
+ *   g[k] = w sinc(w (k - c) / up) I0(beta sqrt(1 - ((k - c) / (L / 2))^2)) / I0(beta),   h[p][j] = g[j up + p]
+ * Input: with mix = 1 one row per channel is converted: 0.5f (L + R) for a stereo channel (one float32 add, then an exact
+ * halving), row 0 for a mono one.  With mix = 0 every row is converted by itself.  R is 1 with mix, else audio_channels.
+ * An output: a row is a stream across calls, x[s], s >= 0, with x[s < 0] = +0.  Output m reads the newest input i = (m down) div up
+ * at phase p = (m down) mod up:
+ *   y[m] = acc = +0;  for j = 0 .. T - 1 ascending: acc = fmaf(h[p][j], x[i - j], acc)
+ * every step rounded once, float32 denormals kept; NaN and infinity propagate as this arithmetic has them and no further: a
+ * sample that is not finite reaches the outputs whose T-sample window holds it.  The group delay is
+ * fmrx_audio_resample_latency() = (L - 1) / (2 up) input samples.
+ * Calls and state: a call brings n inputs.  pos (0 .. down - 1) is the carried position of the next output in units of 1 / up input
+ * sample from the call's first sample; output q of the call has t = pos + q down, i = t div up, p = t mod up.  The call completes
+ * M = ceil((n up - pos) / down) outputs if n up > pos, else 0, and leaves pos' = pos + M down - n up; at most M_max = ceil(n_audio
+ * up / down) complete (fmrx_audio_resample_max_out).  All of this is 64-bit arithmetic.  The state (fmrx_audio_resample_state) is
+ * pos and, per converted row, the last T - 1 samples (the mixed ones with mix), oldest first, zeros in front of a fresh stream;
+ * entries from T - 1 on and the rows a channel does not convert read 0.  A call shorter than T - 1 shifts it.  The same stream cut
+ * differently into calls gives the same samples, byte for byte.
+ * Results per call: out_f32 and / or out_pcm [n_channels][R][M_max], entries at and beyond a channel's count +0 / 0, and counts
+ * [n_channels] uint32.  The PCM is the pipeline's pack of the float value (FMRX_PCM_WRAP / FMRX_PCM_SATURATE), the policy given
+ * per call.  Which of the two a handle keeps is chosen at create (want_f32, want_pcm; at least one).
+ *
+ * The device pass: parallel in time, the channel in the grid's x and a tile of up to 1 024 outputs in y; a workgroup stages the
+ * tile's input window and the tap table in LDS and every lane runs two outputs' chains in the halves of packed fmas. */
+typedef struct fmrx_audio_resample_params {
+    uint32_t up, down, taps, mix;
+    double cutoff, beta;
+} fmrx_audio_resample_params;
+typedef struct fmrx_audio_resample_state {
+    uint32_t pos, reserved;
+    float carry[2][255];    /* per converted row the last taps - 1 samples, oldest first; the rest reads 0 */
+} fmrx_audio_resample_state;
+#ifdef __cplusplus
+static_assert(sizeof(fmrx_audio_resample_params) == 32, "fmrx_audio_resample_params layout");
+static_assert(sizeof(fmrx_audio_resample_state) == 2048, "fmrx_audio_resample_state layout");
+#else
+_Static_assert(sizeof(fmrx_audio_resample_params) == 32, "fmrx_audio_resample_params layout");
+_Static_assert(sizeof(fmrx_audio_resample_state) == 2048, "fmrx_audio_resample_state layout");
+#endif
+typedef struct fmrx_audio_resample fmrx_audio_resample;
+/* Host code, no device needed.  preset: see above.  taps: h [up][taps].  max_out: M_max of a call of n_audio samples; 0 for a refused
+ * geometry or n_audio = 0.  latency: (up taps - 1) / (2 up) input samples; a NaN for a refused geometry. */
+FMRX_API int fmrx_audio_resample_preset(double audio_Fs, double out_Fs, int mix, fmrx_audio_resample_params *params);
+FMRX_API int fmrx_audio_resample_taps(const fmrx_audio_resample_params *params, float *h);
+FMRX_API size_t fmrx_audio_resample_max_out(const fmrx_audio_resample_params *params, size_t n_audio);
+FMRX_API double fmrx_audio_resample_latency(const fmrx_audio_resample_params *params);
+/* The host reference of one channel: rows [audio_channels][row_pitch] floats of which n (1 .. 2^26) are walked; *state_in_out is
+ * read and replaced (a pos of down or more: FMRX_EINVAL); out [R][max_out(params, n)] is written whole, entries the call did not
+ * complete +0; *count is M.  The bodies the kernel runs (audio_resample_core.hpp). */
+FMRX_API int fmrx_audio_resample_walk(const fmrx_audio_resample_params *params, int audio_channels, const float *rows, size_t row_pitch, size_t n,
+                                      fmrx_audio_resample_state *state_in_out, float *out, uint32_t *count);
+/* n_audio: the most samples per row and call (fmrx_channels_n_audio), 1 .. 2^26; audio_channels 1 or 2; want_f32, want_pcm: the
+ * results the handle keeps, at least one.  A geometry and n_audio whose M_max needs more than 65 535 tiles per row: FMRX_EINVAL. */
+FMRX_API int fmrx_audio_resample_create(fmrx_audio_resample **out, const fmrx_audio_resample_params *params, int n_channels, int audio_channels,
+                                        size_t n_audio, int want_f32, int want_pcm, int device);
+FMRX_API int fmrx_audio_resample_destroy(fmrx_audio_resample *m);
+/* channel < 0: all.  Clears the channel's carried samples and position: its stream starts anew.  Waits for the handle's last call;
+ * the state is clear when it returns, for a later call on any stream. */
+FMRX_API int fmrx_audio_resample_reset(fmrx_audio_resample *m, int channel);
+/* out [n_channels]: every channel's carried state; waits for the handle's last call */
+FMRX_API int fmrx_audio_resample_state_get(fmrx_audio_resample *m, fmrx_audio_resample_state *out);
+/* Asynchronous on `stream`, behind whatever wrote the rows on the same stream: d_audio [n_channels][audio_channels][row_pitch]
+ * floats, as the banks and every later stage write them (row_pitch = n_audio there), of which the first n <= n_audio of every
+ * row are walked; 4-byte aligned, at any pitch.  Rows that are 16-byte aligned (d_audio is, and row_pitch is a multiple of 4) are
+ * fetched in 16-byte pieces, all others 4 bytes per lane, the same arithmetic.  The rows are only read.  One kernel launch and no
+ * copy; a second call before fmrx_audio_resample_collect replaces the results (the state has then advanced by both). */
+FMRX_API int fmrx_audio_resample_process_dev(fmrx_audio_resample *m, const float *d_audio, size_t row_pitch, size_t n, int pcm_policy, void *stream);
+/* The last call's results where the kernel left them: *d_f32 and *d_pcm [n_channels][R][M_max] (NULL for the one the handle does
+ * not keep), *d_counts [n_channels].  The pointers are the handle's and hold until it is destroyed; their contents are the last
+ * call's, ordered behind it on its stream, until the handle's next call.  These are the tensors a torch consumer wraps. */
+FMRX_API int fmrx_audio_resample_result_dev(fmrx_audio_resample *m, const float **d_f32, const int16_t **d_pcm, const uint32_t **d_counts);
+/* out_f32 and out_pcm [n_channels][R][M_max] (either may be NULL; one the handle does not keep must be), counts [n_channels], to the
+ * host; waits for the last call (an event it recorded), not for the device */
+FMRX_API int fmrx_audio_resample_collect(fmrx_audio_resample *m, float *out_f32, int16_t *out_pcm, uint32_t *counts);
+/* host rows [n_channels][audio_channels][row_pitch], synchronous (it first waits for the handle's last call), then as collect */
+FMRX_API int fmrx_audio_resample_process(fmrx_audio_resample *m, const float *audio, size_t row_pitch, size_t n, int pcm_policy, float *out_f32,
+                                         int16_t *out_pcm, uint32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

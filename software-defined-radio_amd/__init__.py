@@ -1569,7 +1569,7 @@ def audioMetersDerive(rec, audio_channels=2, full_scale=AUDIO_FULL_SCALE) -> dic
 
 
 class _AudioReader(_Handle):
-    """What AudioMeters, TruePeak, AudioSpectrum and AudioFeatures share: a handle that only reads a bank's audio rows (csrc/meter_stage.hpp's Reader).  A
+    """What AudioMeters, TruePeak, AudioSpectrum, AudioFeatures and AudioResample share: a handle that only reads a bank's audio rows (csrc/meter_stage.hpp's Reader).  A
     subclass names its fmrx_<_prefix>_* functions and its module-level derive function, creates self._h, and says in _bank_extra
     what its constructor takes beyond n_channels, audio_channels, n_audio and device."""
 
@@ -2092,6 +2092,155 @@ class AudioFeatures(_AudioReader):
         feat, frames = self._results()
         self._call("process", x.ctypes.data, x.shape[2], x.shape[2], feat.ctypes.data, frames.ctypes.data)
         return feat, frames
+
+
+# --------------------------------------------------------------------------
+# Audio rate converter: a bank's audio at 16 kHz mono or any rate up / down
+# --------------------------------------------------------------------------
+class AudioResampleParams(C.Structure):
+    """struct fmrx_audio_resample_params (include/fmrx.h): the geometry of the rate converter."""
+    _fields_ = [("up", C.c_uint32), ("down", C.c_uint32), ("taps", C.c_uint32), ("mix", C.c_uint32), ("cutoff", _dbl), ("beta", _dbl)]
+
+    @classmethod
+    def preset(cls, audio_Fs, out_Fs, mix=True):
+        """Host only: the geometry that takes audio_Fs to out_Fs, two integer rates within 8 000 .. 48 000 (fmrx_audio_resample_preset)."""
+        p = cls()
+        _check(lib.fmrx_audio_resample_preset(float(audio_Fs), float(out_Fs), int(bool(mix)), C.byref(p)))
+        return p
+
+
+AUDIO_RESAMPLE_STATE_DTYPE = np.dtype([("pos", "<u4"), ("reserved", "<u4"), ("carry", "<f4", (2, 255))])          # struct fmrx_audio_resample_state
+assert C.sizeof(AudioResampleParams) == 32 and AUDIO_RESAMPLE_STATE_DTYPE.itemsize == 2048
+_arp = C.POINTER(AudioResampleParams)
+_sig("fmrx_audio_resample_preset", [_dbl, _dbl, _int, _arp])
+_sig("fmrx_audio_resample_taps", [_arp, _vp])
+_sig("fmrx_audio_resample_max_out", [_arp, _sz], _sz)
+_sig("fmrx_audio_resample_latency", [_arp], _dbl)
+_sig("fmrx_audio_resample_walk", [_arp, _int, _vp, _sz, _sz, _vp, _vp, _vp])
+_sig("fmrx_audio_resample_create", [C.POINTER(_vp), _arp, _int, _int, _sz, _int, _int, _int])
+_sig("fmrx_audio_resample_destroy", [_vp])
+_sig("fmrx_audio_resample_reset", [_vp, _int])
+_sig("fmrx_audio_resample_state_get", [_vp, _vp])
+_sig("fmrx_audio_resample_process_dev", [_vp, _vp, _sz, _sz, _int, _vp])
+_sig("fmrx_audio_resample_result_dev", [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)])
+_sig("fmrx_audio_resample_collect", [_vp, _vp, _vp, _vp])
+_sig("fmrx_audio_resample_process", [_vp, _vp, _sz, _sz, _int, _vp, _vp, _vp])
+
+
+def _resample_params(params) -> AudioResampleParams:
+    """An AudioResampleParams from one, from a dict of its fields, or from (up, down, taps, mix, cutoff, beta)."""
+    if isinstance(params, AudioResampleParams):
+        return params
+    if isinstance(params, dict):
+        return AudioResampleParams(**params)
+    return AudioResampleParams(*params)
+
+
+def audioResamplePreset(audio_Fs=48000.0, out_Fs=16000.0, mix=True) -> AudioResampleParams:
+    """Host only: AudioResampleParams.preset."""
+    return AudioResampleParams.preset(audio_Fs, out_Fs, mix)
+
+
+def audioResampleTaps(params) -> np.ndarray:
+    """Host only: the float32 taps that define the converter for a geometry, [up, taps] phase-major (fmrx_audio_resample_taps)."""
+    p = _resample_params(params)
+    h = np.zeros((max(int(p.up), 1), max(int(p.taps), 1)), np.float32)
+    _check(lib.fmrx_audio_resample_taps(C.byref(p), h.ctypes.data))
+    return h
+
+
+def audioResampleMaxOut(params, n_audio) -> int:
+    """Host only: the most outputs a call of n_audio samples completes, ceil(n_audio up / down); 0 for a refused geometry."""
+    return int(lib.fmrx_audio_resample_max_out(C.byref(_resample_params(params)), int(n_audio)))
+
+
+def audioResampleLatency(params) -> float:
+    """Host only: the group delay (up taps - 1) / (2 up) in input samples; NaN for a refused geometry."""
+    return float(lib.fmrx_audio_resample_latency(C.byref(_resample_params(params))))
+
+
+def audioResampleWalk(rows, params, state=None):
+    """Host only: the reference walk of one channel (fmrx_audio_resample_walk) on rows float32 [audio_channels, n]; state: the
+    AUDIO_RESAMPLE_STATE_DTYPE record the last call returned (None or zeros: a fresh channel) -> (out float32 [R, M_max(n)], count,
+    state)."""
+    p = _resample_params(params)
+    x = _walk_rows(rows)
+    st = np.zeros(1, AUDIO_RESAMPLE_STATE_DTYPE) if state is None else np.array(state, dtype=AUDIO_RESAMPLE_STATE_DTYPE).reshape(1).copy()
+    out = np.zeros((1 if p.mix else x.shape[0], max(audioResampleMaxOut(p, x.shape[1]), 1)), np.float32)
+    count = np.zeros(1, np.uint32)
+    _check(lib.fmrx_audio_resample_walk(C.byref(p), x.shape[0], x.ctypes.data, x.shape[1], x.shape[1], st.ctypes.data, out.ctypes.data, count.ctypes.data))
+    return out, int(count[0]), st[0]
+
+
+class AudioResample(_AudioReader):
+    """Per channel of a receiver bank: the channel's mono mix (params.mix) or each of its rows at the rate up / down, history and
+    phase carried across calls (fmrx_audio_resample_*).  Behind the last audio stage on stream s:
+    ar = AudioResample.for_bank(bank, AudioResampleParams.preset(48000, 16000)); ar.process_bank(d_out, stream=s);
+    f32_ptr, pcm_ptr, counts_ptr, shape = ar.result_dev() for a consumer on the device, or out = ar.collect().  params: None for
+    the preset that takes the audio rate to 16 kHz mono."""
+    _prefix = "audio_resample"
+    _bank_extra = staticmethod(lambda bank, params=None, want_f32=True, want_pcm=False: {
+        "params": AudioResampleParams.preset(bank.params.audio_Fs, 16000.0) if params is None else params, "want_f32": want_f32, "want_pcm": want_pcm})
+
+    def __init__(self, n_channels=1, audio_channels=2, n_audio=1920, params=None, want_f32=True, want_pcm=False, device=0):
+        self.n_channels, self.audio_channels, self.n_audio = int(n_channels), int(audio_channels), int(n_audio)
+        self.params = AudioResampleParams.preset(48000.0, 16000.0) if params is None else _resample_params(params)
+        self.want_f32, self.want_pcm = bool(want_f32), bool(want_pcm)
+        self._h = _vp()
+        _check(lib.fmrx_audio_resample_create(C.byref(self._h), C.byref(self.params), self.n_channels, self.audio_channels, self.n_audio,
+                                              int(self.want_f32), int(self.want_pcm), device))
+        self.rows = 1 if self.params.mix else self.audio_channels
+        self.max_out = audioResampleMaxOut(self.params, self.n_audio)
+        self.latency = audioResampleLatency(self.params)
+
+    @property
+    def shape(self):
+        return (self.n_channels, self.rows, self.max_out)
+
+    def _results(self):
+        return dict(audio=np.zeros(self.shape, np.float32) if self.want_f32 else None, pcm16=np.zeros(self.shape, np.int16) if self.want_pcm else None,
+                    counts=np.zeros(self.n_channels, np.uint32))
+
+    @staticmethod
+    def _ptrs(out):
+        return tuple(None if out[k] is None else out[k].ctypes.data for k in ("audio", "pcm16", "counts"))
+
+    def process_dev(self, d_audio, row_pitch=None, n=None, stream=None, wrap=True):
+        """Device rows float32 [n_channels, audio_channels, row_pitch] of which the first n samples are walked (defaults: n_audio),
+        asynchronous on `stream`; the rows are only read.  wrap: the PCM pack's policy."""
+        n = self.n_audio if n is None else int(n)
+        self._call("process_dev", d_audio, n if row_pitch is None else int(row_pitch), n, PCM_WRAP if wrap else PCM_SATURATE, stream)
+
+    def process_bank(self, d_audio, stream=None, wrap=True):
+        """process_dev on rows as the bank or any later stage wrote them: [n_channels, audio_channels, n_audio]."""
+        self.process_dev(d_audio, self.n_audio, self.n_audio, stream, wrap)
+
+    def state(self) -> np.ndarray:
+        """Waits for the last call; every channel's carried state, AUDIO_RESAMPLE_STATE_DTYPE [n_channels]."""
+        out = np.zeros(self.n_channels, AUDIO_RESAMPLE_STATE_DTYPE)
+        self._call("state_get", out.ctypes.data)
+        return out
+
+    def result_dev(self):
+        """(f32_ptr, pcm_ptr, counts_ptr, (n_channels, R, M_max)): the last call's float32 and int16 rows (None for the one the handle
+        does not keep) and uint32 counts on the device, ordered behind the call on its stream and valid until the handle's next call."""
+        f32, pcm, counts = _vp(), _vp(), _vp()
+        self._call("result_dev", C.byref(f32), C.byref(pcm), C.byref(counts))
+        return f32.value, pcm.value, counts.value, self.shape
+
+    def collect(self) -> dict:
+        """Waits for the last call; dict(audio float32 [n_channels, R, M_max] or None, pcm16 int16 of that shape or None, counts uint32
+        [n_channels])."""
+        out = self._results()
+        self._call("collect", *self._ptrs(out))
+        return out
+
+    def process(self, audio, wrap=True) -> dict:
+        """Host rows float32 [n_channels, audio_channels, n], n <= n_audio, synchronous -> what collect() returns."""
+        x = self._rows(audio)
+        out = self._results()
+        self._call("process", x.ctypes.data, x.shape[2], x.shape[2], PCM_WRAP if wrap else PCM_SATURATE, *self._ptrs(out))
+        return out
 
 
 class FrontEndPlan(_Handle):

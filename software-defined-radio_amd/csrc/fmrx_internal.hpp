@@ -584,4 +584,27 @@ struct AudioFeaturesArgs {
 size_t audio_features_tiles(size_t n_channels, size_t f_max);   // the workgroups of a call: 16 columns of the (channel, frame) list each
 int audio_features_launch(const AudioFeaturesArgs &a, hipStream_t s);
 
+// ---- audio rate converter (kernels_audio_resample.hip; taps, positions and chains in audio_resample_core.hpp; handle and C ABI in
+// audio_resample.hip) ---------------------------------------------------------------------------------------------------------------
+struct AudioResampleArgs {
+    const float *x = nullptr;            // [n_channels][ac][pitch]; only read
+    size_t pitch = 0, n = 0;             // floats per row; samples of every row to walk
+    int n_channels = 0, ac = 1, rows = 1;    // rows: the rows a channel converts, 1 (the mono mix of ac) or ac
+    unsigned up = 1, down = 1, taps = 8;
+    const float *h = nullptr;            // device, [up][taps]
+    // the carried state, channel-major: pos [n_channels], carry [n_channels][rows][taps - 1]
+    const unsigned *pos_in = nullptr;
+    const float *carry_in = nullptr;
+    unsigned *pos_out = nullptr;         // another pair of buffers of those shapes
+    float *carry_out = nullptr;
+    size_t m_max = 0;                    // outputs per row in out_f32 / out_pcm
+    unsigned tile_out = 0;               // outputs per workgroup, from audio_resample_tile_out
+    float *out_f32 = nullptr;            // [n_channels][rows][m_max], or NULL; entries the call did not complete read +0
+    int16_t *out_pcm = nullptr;          // the same shape, or NULL
+    int wrap = 1;
+    unsigned *counts = nullptr;          // [n_channels]: the outputs the call completed
+};
+unsigned audio_resample_tile_out(unsigned up, unsigned down, unsigned taps);   // the outputs of a workgroup's tile, 1 .. 1024
+int audio_resample_launch(const AudioResampleArgs &a, hipStream_t s);
+
 }  // namespace fmrx

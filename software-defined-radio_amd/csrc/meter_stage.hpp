@@ -6,7 +6,7 @@
 // adds its control structure, its kernels' own buffers, its launch(handle, Call) and its source of control data: the type Source
 // that a call hands to launch, from_handle (what the meters handle in front left on the device, if it fits the stage) and
 // from_records (the host's records, uploaded).  Mpx is that source for the stages behind the signal meters.
-// Reader: what the meters that only read the audio rows share (audio_meters.hip, true_peak.hip, audio_spectrum.hip, audio_features.hip): the checks
+// Reader: what the meters that only read the audio rows share (audio_meters.hip, true_peak.hip, audio_spectrum.hip, audio_features.hip, audio_resample.hip): the checks
 // of a call, the device call, the host call and its staging, their field-major arrays [fields][n_channels], the checks of a derive.
 // A reader adds its
 // buffers, its launch(handle, rows, pitch, n, stream) (the kernel and the asynchronous copies of its results), the unpacking of
